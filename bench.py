@@ -18,6 +18,12 @@ Clips shard across ranks with no data-path collective (decoder instances share n
 MobiclipDecoder.cs:15-39); torch.distributed (a gloo group: nothing travels over RCCL) is used only for the barrier /
 max-over-ranks timing.
 
+A plain run sets up, warms up, times the steps, writes the last step's planes if --dump-outputs is given, and prints the line;
+everything beside the headline -- the check of every clip against the oracle, `cpu_baseline` and the other legs below -- runs with --full:
+
+  python bench.py --full               # the headline and every leg beside it
+  python bench.py --dump-outputs DIR   # also DIR/*.npy: the planes of a fixed sample of clips after the last timed step (float32)
+
 Prints ONE JSON line (rank 0).  `roofline` = algorithmic bytes of the dominant kernel
 (mobi_recon_inter8: the inter macroblocks' pixels and commands only) per launch / its average duration from HIP events
 recorded on the launch stream inside the timed region; `roofline.whole_step_frac` = the same for the whole step (both
@@ -467,6 +473,30 @@ def verify_clips(b, streams, distinct, clips, frame, W, H):
             "against": "CPU oracle (Y and UV planes of ring slot 0 of the distinct source clips); every other clip byte for byte against its source clip"}
 
 
+DUMP_BYTES = 60 << 20  # --dump-outputs: at most this many bytes of .npy data
+DUMP_SEED = 20240601   # the sample of clips --dump-outputs writes: the same for every run with the same --clips
+
+
+def dump_outputs(b, out_dir, clips, W, H):
+    """--dump-outputs: what a caller of the timed path receives after its last step -- the Y and UV planes of ring slot 0
+    (mobi_batch_get_planes) -- for a fixed, seeded sample of the batch's clips, as float32 arrays:
+      y.npy (n, H, W), uv.npy (n, H/2, stride), clips.npy (n,) the clip indices (float64).
+    Y is cut to the picture's width (the columns beyond it are padding no caller reads); the UV rows are returned whole."""
+    S = b.Stride
+    n = int(max(1, min(clips, 32, DUMP_BYTES // (4 * (H * W + H // 2 * S)))))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(clips, size=n, replace=False))
+    ys, uvs = np.empty((n, H, W), np.float32), np.empty((n, H // 2, S), np.float32)
+    for k, c in enumerate(idx):
+        got = b.planes(int(c))
+        if got is None:
+            raise SystemExit(f"bench.py: clip {c} has no decoded frame to dump")
+        ys[k], uvs[k] = got[0][:, :W], got[1]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "y.npy"), ys)
+    np.save(os.path.join(out_dir, "uv.npy"), uvs)
+    np.save(os.path.join(out_dir, "clips.npy"), idx.astype(np.float64))
+
+
 def content_leg(m, sharding, config, rank, local, clips, distinct, overrides, chains=2):
     """The same batch on OTHER content: generator overrides (e.g. lowfreq_prob=700: 70 % of the coded blocks carry one or two levels within
     the three lowest scan positions -- what DC-dominated video looks like, and what the reference's IDCT1P / IDCT3P classes take,
@@ -573,7 +603,12 @@ def main():
     ap.add_argument("--no-kernel-events", action="store_true", help="skip per-launch HIP events (roofline becomes null)")
     ap.add_argument("--content-lowfreq", type=int, default=700, help="second content profile beside the headline: per mille of coded blocks that carry only 1..2 levels in the three lowest scan positions; 0 = skip")
     ap.add_argument("--dry-run", action="store_true", help="rank plumbing only: streams, sharding, barrier, reduction, the one line; no HIP call")
+    ap.add_argument("--full", action="store_true", help="also the check of every clip against the oracle, cpu_baseline and the legs beside the headline "
+                                                        "(end-to-end, config 4, single stream, Bitmap, second content profile); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps: write the planes of a fixed sample of clips as the last step left them to DIR/*.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # not under a launcher: be one (the driver's 1-GPU command is `python3 bench.py --gpus 1 ...`; its N-GPU one may have that shape too)
@@ -716,15 +751,17 @@ def main():
     elapsed = sharding.max_over_ranks(dist, elapsed)
     per_rank = [my_elapsed]
     steps = args.steps
-    # every rank checks its own clips (all of them: verify_clips) and says how many it ran: a rank that silently ran half the batch, or the
+    # --full: every rank checks its own clips (all of them: verify_clips) and says how many it ran: a rank that silently ran half the batch, or the
     # wrong pictures, shows in the one line
-    verified = verify_clips(b, streams, distinct, args.clips, timed_frames[-1], W, H) if timed_frames else None
-    rank_report = [{"rank": rank, "device": local, "clips_per_gpu": int(args.clips), "verified_ok": bool(verified and verified["ok"]), "ms_per_step": round(my_elapsed * 1e3 / steps, 4), "host": host_info}]
+    verified = verify_clips(b, streams, distinct, args.clips, timed_frames[-1], W, H) if args.full else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(b, args.dump_outputs, args.clips, W, H)
+    rank_report = [{"rank": rank, "device": local, "clips_per_gpu": int(args.clips), "verified_ok": bool(verified["ok"]) if verified else None, "ms_per_step": round(my_elapsed * 1e3 / steps, 4), "host": host_info}]
     if dist is not None:
         per_rank = [None] * world
         dist.all_gather_object(per_rank, my_elapsed)
         rank_report = [None] * world
-        dist.all_gather_object(rank_report, {"rank": rank, "device": local, "clips_per_gpu": int(args.clips), "verified_ok": bool(verified and verified["ok"]),
+        dist.all_gather_object(rank_report, {"rank": rank, "device": local, "clips_per_gpu": int(args.clips), "verified_ok": bool(verified["ok"]) if verified else None,
                                              "ms_per_step": round(my_elapsed * 1e3 / steps, 4), "host": host_info})
     cmd_bytes = sum(b.cmd_bytes(f) for f in timed_frames) / steps          # per step, all clips of this GPU
     stats = [b.intra_stats(f) for f in timed_frames]
@@ -733,7 +770,7 @@ def main():
     b.close()
     e2e = e2e_large = c4 = single = None
     e2e_all = None
-    if world > 1 and args.e2e_clips > 0 and args.config == "B":
+    if args.full and world > 1 and args.e2e_clips > 0 and args.config == "B":
         # N > 1: the PRODUCT path on every rank at once (the legs above only run at N = 1, so host staging x N ranks, N x PCIe and
         # N parse pools on one host went unmeasured): frame-parallel groups at the headline batch, each rank on its own streams and cpus,
         # behind the timed region's last barrier; per rank in ranks[], and the slowest rank's time for the whole job's rate.
@@ -756,11 +793,11 @@ def main():
                            "how": "every rank at once: mobi_batch_decode_gop / gop_begin + gop_finish on its own clips (bench.py gop_leg); the whole job's pixels per step / the slowest rank's ms per step"}
             else:
                 e2e_all = {"error": [g.get("error") for g in every]}
-    if world == 1 and args.single_stream and args.config == "B":
+    if args.full and world == 1 and args.single_stream and args.config == "B":
         single = single_stream_leg(m, streams[0], W, H, p0.version, local)
-    if world == 1 and args.e2e_clips > 0 and args.config == "B":
+    if args.full and world == 1 and args.e2e_clips > 0 and args.config == "B":
         e2e = end_to_end(m, streams, W, H, p0.version, local, args.e2e_clips, args.e2e_steps)
-    if world == 1 and args.e2e_clips > 0 and min(args.e2e_large_clips, args.clips) >= 8192 and args.config == "B":  # (--e2e-clips 0 skips both legs)
+    if args.full and world == 1 and args.e2e_clips > 0 and min(args.e2e_large_clips, args.clips) >= 8192 and args.config == "B":  # (--e2e-clips 0 skips both legs)
         try:
             # The lock-step parser's lanes (32 clips per wave) run until the slowest is done and every round costs what the lanes' different states need:
             # a wave of 4 x 16 copies is a quarter as diverse as a wave of 64 clips.  r04 measured 24.3 ms per step with 16 distinct streams
@@ -787,16 +824,16 @@ def main():
                 break
             except Exception as e:
                 e2e_xl = {"error": f"{type(e).__name__}: {e}"}
-    if world == 1 and args.config4_clips > 0 and args.config == "B":
+    if args.full and world == 1 and args.config4_clips > 0 and args.config == "B":
         c4 = config4_leg(m, streams, W, H, p0.version, local, args.config4_clips, 24)
     bitmap = None
-    if world == 1 and args.bitmap_clips > 0 and args.config == "B":
+    if args.full and world == 1 and args.bitmap_clips > 0 and args.config == "B":
         try:
             bitmap = bitmap_leg(m, streams, W, H, p0.version, local, args.bitmap_clips)
         except Exception as e:
             bitmap = {"error": f"{type(e).__name__}: {e}"}
     content = None
-    if world == 1 and args.content_lowfreq > 0 and not gen_over:
+    if args.full and world == 1 and args.content_lowfreq > 0 and not gen_over:
         try:
             content = content_leg(m, sharding, args.config, rank, local, args.clips, distinct, {"lowfreq_prob": args.content_lowfreq})
         except Exception as e:
@@ -859,7 +896,7 @@ def main():
                 except Exception:
                     pass
         base = None
-        if args.cpu_seconds > 0:  # rank 0, after the timed region's last barrier (the other ranks are done and idle)
+        if args.full and args.cpu_seconds > 0:  # rank 0, after the timed region's last barrier (the other ranks are done and idle)
             base = cpu_baseline(*streams[0], args.cpu_seconds)
         out = {
             "metric": "decoded Mpixels/s @ 640x480 P-frames" if args.config == "B" else f"decoded Mpixels/s P-frames (config {args.config})",

@@ -60,10 +60,31 @@ def intra_cases():
     return cases
 
 
-def main():
-    if not os.path.isdir("/root/reference"):
-        sys.exit("needs /root/reference (build container only)")
-    L = lib()
+# what generate() draws from its seeded generator (the rest of the file is what the library computes from these)
+INPUT_KEYS = ("intra_plane", "intra_cases", "plane_cases", "idct8_coef", "idct8_pred", "idct4_coef", "idct4_pred", "copy_src", "copy_cases",
+              "copy_offset", "dct8_in", "dct4_in")
+
+
+class InputsOnly:
+    """Stands in for the library where it cannot be built: no call writes anything and every call returns 0 except the decoder's
+    predictor, which "throws" (so generate() compares no two statements), so that generate() draws exactly the inputs it draws with the
+    library."""
+    def __getattr__(self, name):
+        rc = 1 if name == "csref_dec_predict" else 0
+        return lambda *args: rc
+
+
+def reference_present():
+    sys.path.insert(0, os.path.join(ROOT, "oracle", "tools"))
+    try:
+        import cs2cpp
+    finally:
+        sys.path.pop(0)
+    return os.path.isdir(cs2cpp.REF)
+
+
+def generate(L):
+    """the file's arrays, computed with the library L; returns (arrays, number of intra cases stated twice and equal)"""
     rng = np.random.default_rng(0x4D4F4249)
     dec = L.csref_create(256, 192, 2)
     out = {}
@@ -159,6 +180,14 @@ def main():
         assert L.csref_enc_dct(64, f8[k].ctypes.data, o8[k].ctypes.data) == 0
         assert L.csref_enc_dct(16, f4[k].ctypes.data, o4[k].ctypes.data) == 0
     out.update(dct8_in=f8, dct8_out=o8, dct4_in=f4, dct4_out=o4)
+    return out, n_both
+
+
+def main():
+    if not reference_present():
+        sys.exit("needs the reference sources (oracle/tools/cs2cpp.py)")
+    out, n_both = generate(lib())
+    cases, rc = out["intra_cases"], out["intra_rc"]
     np.savez_compressed(OUT, **out)
     print(OUT, os.path.getsize(OUT), "bytes;", len(cases), "intra cases,", n_both, "of them stated twice (decoder + encoder) and equal;",
           int((rc != 0).sum()), "throw in the decoder")

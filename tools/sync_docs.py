@@ -73,7 +73,7 @@ text = f'''Results, MI355X, {RND} build (`profiles/{RND}_{{A,B,C}}_bench.json`; 
 {row("B 640×480 Moflex3DS", B, "B")}
 {row("C 848×480 Moflex3DS", C, "C")}
 
-After the timed region `bench.py` checks EVERY clip's newest frame: the {ver.get('sources_against_oracle', '?')} distinct source clips against the oracle's frame at that
+After the timed region `bench.py --full` checks EVERY clip's newest frame: the {ver.get('sources_against_oracle', '?')} distinct source clips against the oracle's frame at that
 stream position, the other {ver.get('copies_against_their_source_on_device', '?')} byte for byte against their source clip on the device: `verified.ok` = {str(ver.get('ok')).lower()}
 ({ver.get('copies_that_differ', '?')} copies differ); the same in both end-to-end legs. `mobi_recon_intra` on its own bytes (`roofline.intra`): {((B['roofline'].get('intra') or {{}}).get('frac') or 0):.3f} by
 SURVEY's formula, {((B['roofline'].get('intra') or {{}}).get('frac_without_reference_read') or 0):.3f} without the reference read an intra macroblock does not make; whole step without it: {(B['roofline'].get('whole_step_frac_intra_without_reference_read') or 0):.3f};
