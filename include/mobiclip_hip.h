@@ -199,6 +199,37 @@ int mobi_batch_get_argb(mobi_batch *b, int clip, uint32_t *out);
 /* ... of the frame at ring index ring_idx (0 = the newest; MOBI_E_NULLREF for a slot never produced): the Bitmap DecodeFrame() returned
  * ring_idx calls ago.  For callers that decode in groups and want every frame's Bitmap: frame k of a group of K is ring index K - 1 - k. */
 int mobi_batch_get_argb_at(mobi_batch *b, int clip, int ring_idx, uint32_t *out);
+/* ---- export of decoded pictures to host memory (the callers' decode -> AddFrame loop, MobiConverter/Program.cs:69-76) ----------------
+ * The getters above move one clip's frame per call and wait for everything enqueued; these move many clips x frames per call, through a
+ * copy pipeline of their own, and do not wait for anything the caller has enqueued. */
+#define MOBI_EXPORT_I420 0 /* per picture: Y width*height, then U, then V, (width/2)*(height/2) each; rows packed, no stride padding.
+                              = the reference's Y[0] / UV[0] (MD.cs:107-108, 414-415) restricted to the picture area */
+#define MOBI_EXPORT_ARGB 1 /* per picture: width*height uint32 words, byte for byte what mobi_batch_get_argb_at returns */
+/* Pinned, portable host memory for export destinations (plain C callers cannot reach hipHostMalloc).  NULL without a device.
+ * mobi_host_free takes only what mobi_host_alloc returned (anything else is ignored). */
+void *mobi_host_alloc(size_t bytes);
+void mobi_host_free(void *p);
+/* n_frames pictures of clips [clip0, clip0 + n_clips): picture j is ring index ring_idx - j (j = 0 .. n_frames - 1, oldest first), written to
+ * dst + (j * n_clips + (c - clip0)) * picture_bytes.  After gop_finish reported a part of P frames, (ring_idx = P - 1, n_frames = P) gives
+ * them in the order of its rc / offsets arrays.  Returns at once with *ticket_out when dst lies inside one mobi_host_alloc block; for any
+ * other dst it returns when the data is in dst (the ticket is then already complete).  ticket_out may be NULL.
+ *   SNAPSHOT: what lands in dst is the pictures as they are when the call returns.  Later decode / submit / gop_finish / replay calls turn
+ *             the ring and write those slots; a step that will write a slot an export has not finished reading waits for it on the GPU
+ *             (so a decode that outruns the copy engine runs at the export's pace; with no export outstanding nothing waits).
+ *   NO DRAIN: the export waits for no step or group in flight (on the host); it goes behind the reconstruction already enqueued.
+ *   REFUSED:  MOBI_E_NULLREF for ring_idx >= frames started.  MOBI_E_ARG for a bad format or clip range, ring_idx > 5 or
+ *             ring_idx - n_frames + 1 < 0, dst NULL or dst_bytes too small, a poisoned batch, and ring indices below
+ *             mobi_batch_in_flight(b): frames of submitted steps not waited for yet (mobi_batch_wait may still repair them).
+ *             A refused or failed export changes nothing and issues no ticket.
+ *   LIFETIME: dst stays valid until mobi_batch_export_wait for its ticket (or a later one) returned, or until mobi_batch_destroy, which waits
+ *             for the exports outstanding before it frees anything.
+ * The getters (mobi_batch_get_planes, convert_argb, get_argb, get_argb_at) are not affected: the export has buffers of its own (a few
+ * staging chunks in HBM, allocated at the batch's first export). */
+int mobi_batch_export(mobi_batch *b, int format, int ring_idx, int n_frames, int clip0, int n_clips, void *dst, size_t dst_bytes,
+                      uint64_t *ticket_out);
+int mobi_batch_export_wait(mobi_batch *b, uint64_t ticket);  /* this export and all earlier ones are in dst; MOBI_OK or MOBI_E_DEVICE
+                                                                (MOBI_E_ARG: a ticket this batch never issued) */
+int mobi_batch_export_query(mobi_batch *b, uint64_t ticket); /* 1 done, 0 not yet, < 0 error */
 /* Encoder-side analysis: Analyzer.InterPredict2x2 (Analyzer.cs:608-681) for every 2x2 luma block of
  * every macroblock of every clip, as SolveInterPredictionPuzzle calls it (:683-693): three-step search (6, 3, 1 pels) in up
  * to five past frames = ring slots 0..4 of this batch (the encoder's PastFramesY, MobiEncoder.cs:138-144).

@@ -9,6 +9,8 @@ from .decoder import (  # noqa: F401
     MobiclipBatch,
     MobiclipVersion,
     MobiclipError,
+    host_empty,
+    split_i420,
     load_library,
     unpack_motion_search,
 )

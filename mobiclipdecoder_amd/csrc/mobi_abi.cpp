@@ -20,6 +20,7 @@
 #include "../../include/mobiclip_hip.h"
 #include "mobi_cmd.h"
 #include "mobi_dparse.h"
+#include "mobi_exporter.h"
 #define MOBI_GOP_DEVICE_DECLS
 #include "mobi_gop.h"
 #include "mobi_kernels.h"
@@ -367,6 +368,13 @@ struct mobi_batch {
   std::vector<hipEvent_t> ev_pool;
   float acc_ms[2] = {0, 0};
   int acc_launches[2] = {0, 0};
+  // export to host memory (mobi_batch_export, mobi_export.cpp): created at the first export; its staging chunks with it
+  MobiExporter *exporter = nullptr;
+
+  // The ring-slot guard, called by every step that writes a ring slot, right after the ring has turned and before anything of the step is
+  // enqueued: the slot the step writes (ring_base) may still be read by the pack of an export; the batch's stream then waits for it.  With no
+  // export outstanding (or none ever) it does nothing.
+  int guard_slot() { return exporter ? mobi_exporter_guard(exporter, ring_base, stream) : MOBI_OK; }
 
   MobiReconArgs args(const uint8_t *desc, const uint8_t *payload) const {
     MobiReconArgs a;
@@ -438,6 +446,8 @@ struct mobi_batch {
     evs.clear();
   }
   ~mobi_batch() {
+    if (exporter) mobi_exporter_delete(exporter); // (waits for the exports outstanding: they read the ring and write the callers' memory)
+    exporter = nullptr;
     if (stream2) (void)hipStreamSynchronize(stream2); // an upload of a submitted step may still be reading pinned memory we are about to free
     if (stream_p) (void)hipStreamSynchronize(stream_p);
     if (stream) (void)hipStreamSynchronize(stream);
@@ -504,6 +514,7 @@ int mobi_debug_write_planes(mobi_batch *b, int clip, int ring_idx, const uint8_t
   if (!b || clip < 0 || clip >= b->n || ring_idx < 0 || ring_idx > 5 || !y || !uv) return MOBI_E_ARG;
   if (ring_idx >= b->frames_started) return MOBI_E_NULLREF;
   HIP_TRY(hipSetDevice(b->device));
+  if (b->exporter && mobi_exporter_guard(b->exporter, (b->ring_base + 6 - ring_idx) % 6, b->stream) != MOBI_OK) return MOBI_E_DEVICE;
   HIP_TRY(hipStreamSynchronize(b->stream));
   const uint32_t ysz = (uint32_t)b->g.stride * (uint32_t)b->g.height;
   std::vector<uint8_t> t(b->slot_bytes);
@@ -535,7 +546,7 @@ long long mobi_debug_read_parse(mobi_batch *b, uint32_t *desc_out, uint32_t *ite
 #pragma GCC visibility pop
 #endif // MOBI_PROFILING
 
-const char *mobi_build_info(void) { return "libmobiclip_hip 0.6 (gfx950, macroblock-tiled planes; HIP kernels: mobi_recon_inter8, mobi_recon_intra, mobi_recon_step, mobi_recon_intra_cl, mobi_recon_intra_walk, mobi_parse_frames, mobi_parse_frames_ls, mobi_ls_deps, mobi_parse_tail, mobi_gop_prepare, mobi_gop_chain, mobi_gop_fronts, mobi_gop_front_starts, mobi_gop_scatter, mobi_untile, mobi_yuv_to_argb, mobi_motion_search_2x2, mobi_fwd_dct8, mobi_fwd_dct4; no CPU reconstruction path)"; }
+const char *mobi_build_info(void) { return "libmobiclip_hip 0.6 (gfx950, macroblock-tiled planes; HIP kernels: mobi_recon_inter8, mobi_recon_intra, mobi_recon_step, mobi_recon_intra_cl, mobi_recon_intra_walk, mobi_parse_frames, mobi_parse_frames_ls, mobi_ls_deps, mobi_parse_tail, mobi_gop_prepare, mobi_gop_chain, mobi_gop_fronts, mobi_gop_front_starts, mobi_gop_scatter, mobi_untile, mobi_yuv_to_argb, mobi_export_i420, mobi_motion_search_2x2, mobi_fwd_dct8, mobi_fwd_dct4; no CPU reconstruction path)"; }
 
 const char *mobi_error_string(int rc) {
   switch (rc) {
@@ -1037,6 +1048,7 @@ static int decode_device_parse(mobi_batch *b, const uint8_t *const *data, const 
   b->argb_all_valid = false;
   b->frames_started++;
   FailAll fail_all{rc, n, b->stream}; // rc[], Offset, the ring and the decoder state have advanced: the launches below must complete
+  if (int e = b->guard_slot()) return e;
   MobiReconArgs a = b->args(b->d_pdesc.p, b->d_ppay.p);
   a.pay_clip_words = b->pay_clip_words;
   a.done = b->d_done;
@@ -1217,6 +1229,7 @@ int mobi_batch_submit(mobi_batch *b, const uint8_t *const *data, const size_t *l
   b->argb_all_valid = false;
   b->frames_started++;
   S.ring_base = b->ring_base;
+  if (int e = b->guard_slot()) return e;
   MobiReconArgs a = b->args(S.d_pdesc.p, S.d_ppay.p);
   a.pay_clip_words = b->pay_clip_words;
   a.done = b->d_done;
@@ -1673,6 +1686,7 @@ int mobi_batch_gop_finish(mobi_batch *b, int32_t *offsets_out, int *rc) {
     b->step_tag = b->step_tag + 1 ? b->step_tag + 1 : 1;
     b->argb_all_valid = false;
     b->frames_started++;
+    if (int e = b->guard_slot()) return e;
     MobiReconArgs a = b->args(S.d_desc.p + kn * desc_b, S.d_pay.p + kn * S.cap_words * 4);
     a.pay_clip_words = (uint32_t)S.cap_words;
     a.fault = (int *)S.d_fault.p + kn;
@@ -1904,6 +1918,7 @@ int mobi_batch_decode(mobi_batch *b, const uint8_t *const *data, const size_t *l
   // bookkeeping counts frames).  If the call itself fails below, no clip may report MOBI_OK for a frame that was never reconstructed.
   FailAll fail_all{rc, n, b->stream};
   if (up_err) return MOBI_E_DEVICE;
+  if (int e = b->guard_slot()) return e;
   if (base[n] + kPaySlack / 4 >= ((uint64_t)1 << 32)) return MOBI_E_ARG; // MbDesc.payload_off is a 32-bit word offset into the step's arena
   LevelPlan plan;
   plan.build(ok, b->g.mbw);
@@ -2026,6 +2041,49 @@ int mobi_batch_get_argb_at(mobi_batch *b, int clip, int ring_idx, uint32_t *out)
   HIP_TRY(hipStreamSynchronize(b->stream));
   HIP_TRY(hipMemcpy(out, b->d_argb, words * 4, hipMemcpyDeviceToHost));
   return MOBI_OK;
+}
+// ---- export of whole batches of pictures to host memory (the converter's decode -> AddFrame loop, MobiConverter/Program.cs:69-76) ----
+// The arguments are checked here against the batch; the pipeline, the tickets and the ring-slot guard are mobi_export.cpp's.
+int mobi_batch_export(mobi_batch *b, int format, int ring_idx, int n_frames, int clip0, int n_clips, void *dst, size_t dst_bytes, uint64_t *ticket_out) {
+  if (!b || !dst || (format != MOBI_EXPORT_I420 && format != MOBI_EXPORT_ARGB)) return MOBI_E_ARG;
+  if (clip0 < 0 || n_clips < 1 || clip0 > b->n - n_clips) return MOBI_E_ARG;
+  if (ring_idx < 0 || ring_idx > 5 || n_frames < 1 || ring_idx - n_frames + 1 < 0) return MOBI_E_ARG;
+  const size_t px = (size_t)b->g.width * b->g.height, pic = format == MOBI_EXPORT_I420 ? px * 3 / 2 : px * 4;
+  if (dst_bytes < pic * n_frames * n_clips) return MOBI_E_ARG;
+  if (b->poisoned) return MOBI_E_ARG;
+  if (ring_idx >= b->frames_started) return MOBI_E_NULLREF;
+  if (ring_idx - n_frames + 1 < b->async_count) return MOBI_E_ARG; // frames of steps not waited for: mobi_batch_wait may still repair them
+  HIP_TRY(hipSetDevice(b->device));
+  if (!b->exporter) b->exporter = mobi_exporter_new(b->device);
+  MobiExportJob job;
+  job.g = MobiExportGeom{b->arena + kGuard, b->clip_bytes, (uint32_t)b->slot_bytes, (int)b->g.width, (int)b->g.height, (int)b->g.stride, (int)b->g.mbw, b->g.lg};
+  job.format = format;
+  job.n_frames = n_frames;
+  job.clip0 = clip0;
+  job.n_clips = n_clips;
+  job.slot0 = (b->ring_base + 6 - ring_idx) % 6;
+  job.dst = dst;
+  job.src_stream = b->stream;
+  job.argb = [b](int c0, int n, int slot, uint32_t *out, hipStream_t s) {
+    MobiReconArgs a = b->args(nullptr, nullptr);
+    a.ring_base = slot;
+    return mobi_launch_argb(&a, b->version, c0, n, out, s);
+  };
+  job.run = [b](int n, const std::function<void(int)> &f) { b->pool->run(n, f); };
+  uint64_t t = 0;
+  if (int e = mobi_exporter_run(b->exporter, job, &t)) return e;
+  if (ticket_out) *ticket_out = t;
+  return MOBI_OK;
+}
+int mobi_batch_export_wait(mobi_batch *b, uint64_t ticket) {
+  if (!b || !b->exporter) return MOBI_E_ARG;
+  HIP_TRY(hipSetDevice(b->device));
+  return mobi_exporter_wait(b->exporter, ticket);
+}
+int mobi_batch_export_query(mobi_batch *b, uint64_t ticket) {
+  if (!b || !b->exporter) return MOBI_E_ARG;
+  HIP_TRY(hipSetDevice(b->device));
+  return mobi_exporter_query(b->exporter, ticket);
 }
 // ---- encoder-side analysis: Analyzer.InterPredict2x2 over the ring this batch keeps in HBM (Analyzer.cs:608-693) ----
 int mobi_batch_motion_search(mobi_batch *b, const uint8_t *const *src_y, uint32_t *out) {
@@ -2191,6 +2249,7 @@ int mobi_batch_replay(mobi_batch *b, int frame_idx) {
   b->step_tag = b->step_tag + 1 ? b->step_tag + 1 : 1;
   b->argb_all_valid = false;
   b->frames_started++;
+  if (int e = b->guard_slot()) return e;
   MobiReconArgs a = b->args(b->r_cmd.p + b->r_desc_off[frame_idx], b->r_cmd.p + b->r_payload_off[frame_idx]);
   return b->launch_plan(a, b->r_plan[frame_idx], (const uint32_t *)b->r_items.p + b->r_items_off[frame_idx]);
 }

@@ -15,6 +15,7 @@ reason in ``last_error``.  Reconstruction runs only on the GPU; there is no CPU 
 import ctypes as C
 import enum
 import os
+import weakref
 
 import numpy as np
 
@@ -85,6 +86,11 @@ _SIGS = {
     "mobi_batch_time_end": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "mobi_batch_set_kernel_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "mobi_batch_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "mobi_host_alloc": (C.c_void_p, [C.c_size_t]),
+    "mobi_host_free": (None, [C.c_void_p]),
+    "mobi_batch_export": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
+    "mobi_batch_export_wait": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "mobi_batch_export_query": (C.c_int, [C.c_void_p, C.c_uint64]),
     "mobi_error_string": (C.c_char_p, [C.c_int]),
     "mobi_build_info": (C.c_char_p, []),
 }
@@ -142,6 +148,65 @@ class _PlaneRing:
 
     def __len__(self):
         return 6
+
+
+# mobi_batch_export formats (include/mobiclip_hip.h, MOBI_EXPORT_*)
+EXPORT_FORMATS = {"i420": 0, "argb": 1}
+
+
+class _HostBlock:
+    """One mobi_host_alloc block (pinned, portable host memory) seen by numpy through the array interface; mobi_host_free runs when the
+    last array over it is gone."""
+
+    def __init__(self, nbytes):
+        lib = load_library()
+        self.ptr = lib.mobi_host_alloc(max(1, int(nbytes)))
+        if not self.ptr:
+            raise MobiclipError(f"mobi_host_alloc({nbytes}) failed (a HIP device is required)")
+        self.__array_interface__ = {"shape": (int(nbytes),), "typestr": "|u1", "data": (self.ptr, False), "version": 3}
+        weakref.finalize(self, lib.mobi_host_free, self.ptr)
+
+
+def host_empty(shape, dtype=np.uint8):
+    """np.empty() in memory from mobi_host_alloc: an export into it returns at once (MobiclipBatch.export(..., wait=False))"""
+    shape = (int(shape),) if np.isscalar(shape) else tuple(int(d) for d in shape)
+    dt = np.dtype(dtype)
+    n = int(np.prod(shape, dtype=np.int64)) * dt.itemsize
+    return np.asarray(_HostBlock(n))[:n].view(dt).reshape(shape)
+
+
+def split_i420(arr, W, H):
+    """(Y, U, V) views of packed I420 pictures (MobiclipBatch.export(fmt="i420")): arr[..., W*H*3/2] -> [..., H, W], [..., H/2, W/2] x 2"""
+    a = np.asarray(arr)
+    ys, cs = W * H, (W // 2) * (H // 2)
+    if a.shape[-1] != ys + 2 * cs:
+        raise ValueError(f"last dimension {a.shape[-1]} is not a {W}x{H} I420 picture ({ys + 2 * cs} bytes)")
+    lead = a.shape[:-1]
+    return (a[..., :ys].reshape(lead + (H, W)), a[..., ys:ys + cs].reshape(lead + (H // 2, W // 2)),
+            a[..., ys + cs:].reshape(lead + (H // 2, W // 2)))
+
+
+class ExportHandle:
+    """An export in flight (MobiclipBatch.export(..., wait=False)): done() asks, wait() waits and returns the array.  Keeps the destination
+    and the batch alive until then."""
+
+    def __init__(self, batch, ticket, out):
+        self._batch, self.ticket, self.out = batch, ticket, out
+
+    def done(self):
+        if not self._batch._h:
+            return True  # (mobi_batch_destroy waited for it)
+        r = self._batch._lib.mobi_batch_export_query(self._batch._h, self.ticket)
+        if r < 0:
+            raise MobiclipError(error_string(r))
+        return r == 1
+
+    def wait(self):
+        if self._batch._h:
+            r = self._batch._lib.mobi_batch_export_wait(self._batch._h, self.ticket)
+            if r != 0:
+                raise MobiclipError(error_string(r))
+        return self.out
 
 
 class MobiclipDecoder:
@@ -372,6 +437,38 @@ class MobiclipBatch:
         if rc != 0:
             raise MobiclipError(error_string(rc))
         return out
+
+    def export(self, fmt="i420", ring_idx=0, n_frames=1, clips=None, out=None, wait=True):
+        """Pictures of many clips and frames to host memory in one call (mobi_batch_export): frame j = ring index ring_idx - j (oldest first),
+        clips = a range / slice of clip numbers (step 1; None: all).  -> (n_frames, n_clips, W*H*3/2) uint8 (fmt="i420"; split_i420) or
+        (n_frames, n_clips, H, W) uint32 Bitmaps (fmt="argb").  out: an array of that shape and type to fill (default: host_empty()); with
+        wait=False an ExportHandle is returned at once -- the export runs behind the steps enqueued so far -- when out is host_empty() memory."""
+        if fmt not in EXPORT_FORMATS:
+            raise ValueError(f"fmt must be one of {sorted(EXPORT_FORMATS)}, not {fmt!r}")
+        if isinstance(ring_idx, bool) or not isinstance(ring_idx, (int, np.integer)) or not 0 <= ring_idx <= 5:
+            raise ValueError(f"ring_idx must be an int in 0..5, not {ring_idx!r}")
+        if isinstance(n_frames, bool) or not isinstance(n_frames, (int, np.integer)) or not 1 <= n_frames <= ring_idx + 1:
+            raise ValueError(f"n_frames must be an int in 1..ring_idx + 1 = {ring_idx + 1}, not {n_frames!r}")
+        if clips is None:
+            clips = range(self.n)
+        elif isinstance(clips, slice):
+            clips = range(self.n)[clips]
+        if not isinstance(clips, range) or clips.step != 1 or len(clips) < 1 or clips.start < 0 or clips.stop > self.n:
+            raise ValueError(f"clips must be a non-empty range / slice of step 1 inside 0..{self.n}, not {clips!r}")
+        W, H = self.Width, self.Height
+        shape, dtype = ((n_frames, len(clips), W * H * 3 // 2), np.uint8) if fmt == "i420" else ((n_frames, len(clips), H, W), np.uint32)
+        if out is None:
+            out = host_empty(shape, dtype)
+        elif (not isinstance(out, np.ndarray) or out.shape != shape or out.dtype != dtype or not out.flags.c_contiguous
+              or not out.flags.writeable):
+            raise ValueError(f"out must be a writeable C-contiguous {np.dtype(dtype).name} array of shape {shape}")
+        ticket = C.c_uint64(0)
+        rc = self._lib.mobi_batch_export(self._h, EXPORT_FORMATS[fmt], int(ring_idx), int(n_frames), clips.start, len(clips), out.ctypes.data,
+                                         out.nbytes, C.byref(ticket))
+        if rc != 0:
+            raise MobiclipError(error_string(rc))
+        h = ExportHandle(self, ticket.value, out)
+        return h.wait() if wait else h
 
     def quantizer(self, clip):
         return self._lib.mobi_batch_quantizer(self._h, clip)
