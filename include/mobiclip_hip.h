@@ -240,8 +240,43 @@ int mobi_batch_motion_search(mobi_batch *b, const uint8_t *const *src_y, uint32_
 /* The encoder's forward transforms: MobiEncoder.DCT64 (Encoder/MobiEncoder.cs:962-1010, n = 8) and DCT16
  * (:1146-1178, n = 4) of n_blocks residual blocks (Block - CompVals, Encoder/MacroBlock.cs:584-588), n*n int32 each, back to back;
  * out as the reference returns it (the second pass stores transposed).  Integer arithmetic, truncating divisions: bit-exact.
- * The quantiser behind it (float division + Math.Round, MacroBlock.cs:591-595) is not part of this library. */
+ * The quantiser, bit cost and reconstruction behind it are mobi_transform_code below. */
 int mobi_forward_dct(int device, int n, const int32_t *in, int32_t *out, size_t n_blocks);
+/* The encoder's transform coding of residual blocks: MacroBlock.EncodeDecode8x8Block / EncodeDecode4x4Block
+ * (Encoder/MacroBlock.cs:577-597, 605-626) and the SAD the analyzer scores a candidate with (Analyzer.GetScore8x8 / 4x4, Analyzer.cs:1201,
+ * 1269), for every source block against its prediction at one or more quantisers.  For one block of n x n pixels (n = 8 or 4), src and
+ * pred u8 row-major (the reference's Block and CompVals), quantiser q in [0, 53]:
+ *   Q       SetupQuantizationTables (MobiEncoder.cs:930-960): T[k] = (dq4[qmod6[q] * 16 + k] << (qdiv6[q] + 8)) >> 8 for n = 4,
+ *           (dq8[qmod6[q] * 64 + k] << (qdiv6[q] + 6)) >> 8 for n = 8; Q[zz[k]] = T[k] (zz = the decoder's scan order).  Integers.
+ *   levels  d = DCT64 / DCT16 (src - pred) as mobi_forward_dct computes it, lev[i] = round_half_even(d[i] / Q[i]) -- what
+ *           (int)Math.Round(d / QTable) gives (MacroBlock.cs:591-595): |d| <= 23 500 and Q is an integer, so the float quotient rounds
+ *           as the exact one does ("Transform coding").  Out in scan order, levels[k] = lev[zz[k]] (EncodeDct); |lev| < 2^15.
+ *   bits    CalculateNrBitsDCT(EncodeDct, 0) (MobiEncoder.cs:767-858): 0 when every level is 0; else the sum over the nonzero levels up to
+ *           the last one of the code length of (|level|, zeros since the previous nonzero level, is it the last), VLC table 0 with its
+ *           two escapes (+9 shorter run, +8 smaller value) and the 28-bit fallback.
+ *   recon   dequantised lev[i] * Q[i] through IDCT64 / IDCT16 (MobiEncoder.cs:1012, 1180) in int32, each pixel Vx2MinMaxTable[0x40 +
+ *           pred + (t >> 6)].  All-zero levels give recon == pred.
+ *   sad     sum |src - recon| (GetScore8x8 / 4x4).
+ *   flags   MOBI_TC_CODED: some level is nonzero (YUseComplex8x8 / YUseDCT4x4 stays set).  MOBI_TC_CLAMP: an index of the clamp table
+ *           fell outside [0, 384), where the reference throws IndexOutOfRangeException; that entry's recon and sad are unspecified,
+ *           its levels and bits are exact.  A clamp fault is not an error of the call.
+ * n_blocks blocks x n_q quantisers (1 <= n_q <= 54, each in [0, 53]); entry e = qi * n_blocks + b.  src / pred: n_blocks * n * n bytes.
+ * Per entry: levels_out n * n int16 (scan order), recon_out n * n bytes (row-major), bits_out / sad_out one int32, flags_out one byte.
+ * levels_out, recon_out and sad_out may be NULL (not computed out); bits_out and flags_out may not.  MOBI_E_ARG for a bad n, n_q or
+ * quantiser, a required NULL pointer while n_blocks > 0, or n_blocks * n_q >= 2^32; MOBI_E_DEVICE for a HIP failure; n_blocks == 0 is
+ * MOBI_OK.  The C# caller of one block is in INTEGRATION.md. */
+#define MOBI_TC_CODED 1
+#define MOBI_TC_CLAMP 2
+/* SetupQuantizationTables: QTable4x4 (16) / QTable8x8 (64) in natural DCT order, as the reference's float[] (either may be NULL).
+ * MOBI_E_ARG for a quantizer outside [0, 53].  Host only: needs no device. */
+int mobi_encoder_qtables(int quantizer, float *qtable4x4, float *qtable8x8);
+/* Host pointers; synchronous. */
+int mobi_transform_code(int device, int n, const int *quantizers, int n_q, const uint8_t *src, const uint8_t *pred, size_t n_blocks,
+                        int16_t *levels_out, uint8_t *recon_out, int32_t *bits_out, int32_t *sad_out, uint8_t *flags_out);
+/* The same on device pointers, enqueued on `stream` (a hipStream_t; NULL = the null stream); returns after the enqueue.  Allocates
+ * nothing per call (the per-device constant tables are uploaded once, at the first call on that device). */
+int mobi_transform_code_async(int device, void *stream, int n, const int *quantizers, int n_q, const uint8_t *src, const uint8_t *pred,
+                              size_t n_blocks, int16_t *levels_out, uint8_t *recon_out, int32_t *bits_out, int32_t *sad_out, uint8_t *flags_out);
 /* For batches made of copies (clip c was given the same stream as clip c mod modulus: a benchmark, a soak run): compares the newest frame
  * (ring slot 0) of EVERY clip with that of its source clip on the device, byte for byte, and returns how many clips differ (0 = none; < 0 =
  * MOBI_E_*).  n_diff_out, if not NULL, receives the number of differing 16-byte words per clip (n_clips entries).  Checking the `modulus`

@@ -13,5 +13,7 @@ from .decoder import (  # noqa: F401
     split_i420,
     load_library,
     unpack_motion_search,
+    quant_tables,
+    transform_code,
 )
 from .streamgen import GenParams, generate_clip, default_params  # noqa: F401

@@ -61,7 +61,7 @@ def build_hip(force=False, profiling=False):
     """profiling=True (python -m mobiclipdecoder_amd.build --profiling, tools/ only): a SECOND library, libmobiclip_hip_prof.so, with
     -DMOBI_PROFILING: the ablation / occupancy / stage-stop switches (MOBI_INTRA_DBG, MOBI_LDS_PAD, MOBI_INTRA_LDS_PAD, MOBI_STOP_STAGE,
     MOBI_DEBUG=9) and the mobi_debug_* test hooks.  The product library has none of them; tools select the other one with MOBI_LIB."""
-    srcs = [os.path.join(CSRC, f) for f in ("mobi_abi.cpp", "mobi_parse.cpp", "mobi_demux.cpp", "mobi_moflex.cpp", "mobi_export.cpp", "mobi_kernels.hip", "mobi_rgb.hip", "mobi_dparse.hip", "mobi_lsparse.hip", "mobi_gop.hip", "mobi_analysis.hip", "mobi_export.hip")]
+    srcs = [os.path.join(CSRC, f) for f in ("mobi_abi.cpp", "mobi_parse.cpp", "mobi_demux.cpp", "mobi_moflex.cpp", "mobi_export.cpp", "mobi_txcode.cpp", "mobi_kernels.hip", "mobi_rgb.hip", "mobi_dparse.hip", "mobi_lsparse.hip", "mobi_gop.hip", "mobi_analysis.hip", "mobi_export.hip", "mobi_txcode.hip")]
     deps = srcs + _hdrs(CSRC) + [os.path.join(ROOT, "include", "mobiclip_hip.h"), os.path.join(ROOT, "include", "mobiclip_demux.h"), os.path.abspath(__file__)]
     lib = LIB_HIP_PROF if profiling else LIB_HIP
     if not force and not _newer(lib, deps):
@@ -73,7 +73,7 @@ def build_hip(force=False, profiling=False):
     # (-O3: the host parser -- hand-overs, small batches, mobi_decode -- parses a 640x480 P-frame in 0.41 ms instead of 0.47)
     host_flags = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-fwrapv", "-fvisibility=hidden", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(ROCM, "include")] + prof
     objs = []
-    for s in srcs[:5]:
+    for s in srcs[:6]:
         o = os.path.join(obj, os.path.basename(s) + ".o")
         _run(["g++"] + host_flags + ["-c", s, "-o", o])
         objs.append(o)
@@ -84,7 +84,7 @@ def build_hip(force=False, profiling=False):
     extra = {"mobi_kernels.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp", "-fno-unroll-loops"],
              # the lock-step parser is one long dependent chain per wave: 24.8 against 25.6 ms per P-frame step (tools/exp_lsflags.sh)
              "mobi_lsparse.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]}
-    for s in srcs[5:]:
+    for s in srcs[6:]:
         ko = os.path.join(obj, os.path.basename(s) + ".o")
         _run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden"] + prof + extra.get(os.path.basename(s), []) + ["-c", s, "-o", ko])
         objs.append(ko)

@@ -63,6 +63,11 @@ _SIGS = {
     "mobi_batch_host_clips": (C.c_int, [C.c_void_p]),
     "mobi_batch_compare_clips": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "mobi_forward_dct": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "mobi_encoder_qtables": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p]),
+    "mobi_transform_code": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mobi_transform_code_async": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mobi_batch_get_planes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "mobi_batch_convert_argb": (C.c_int, [C.c_void_p]),
     "mobi_batch_get_argb": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
@@ -571,6 +576,97 @@ def forward_dct(blocks, device=None):
         raise ValueError("blocks must be (n, 64) or (n, 16)")
     out = np.empty_like(a)
     rc = load_library().mobi_forward_dct(default_device() if device is None else device, 8 if a.shape[1] == 64 else 4, a.ctypes.data, out.ctypes.data, a.shape[0])
+    if rc != 0:
+        raise MobiclipError(error_string(rc))
+    return out
+
+
+def quant_tables(q):
+    """MobiEncoder.SetupQuantizationTables (Encoder/MobiEncoder.cs:930-960) for quantiser q in [0, 53]: (QTable4x4 float32[16],
+    QTable8x8 float32[64]) in natural DCT order, as the reference's float[] holds them.  Needs no device."""
+    q4, q8 = np.empty(16, np.float32), np.empty(64, np.float32)
+    rc = load_library().mobi_encoder_qtables(int(q), q4.ctypes.data, q8.ctypes.data)
+    if rc != 0:
+        raise MobiclipError(error_string(rc))
+    return q4, q8
+
+
+_ONE_RUNTIME = False
+
+
+def _check_one_hip_runtime():
+    """torch's pointers and streams mean something to this library only if both use the same HIP runtime.  A torch wheel that bundles its own
+    libamdhip64 shares it with this library when torch is imported first; loaded the other way round the process holds two runtimes."""
+    global _ONE_RUNTIME
+    if _ONE_RUNTIME:
+        return
+    try:
+        maps = open("/proc/self/maps").read().split("\n")
+    except OSError:
+        return
+    paths = {ln.split()[-1] for ln in maps if "libamdhip64.so" in ln}
+    if len({os.path.realpath(x) for x in paths}) > 1:
+        raise MobiclipError("two HIP runtimes in this process (torch's and the one libmobiclip_hip.so was loaded with): import torch before "
+                            "the first use of mobiclipdecoder_amd to pass torch tensors")
+    _ONE_RUNTIME = True
+
+
+def transform_code(src, pred, quantizers, levels=True, recon=True, sad=True, device=None):
+    """MacroBlock.EncodeDecode8x8Block / EncodeDecode4x4Block (Encoder/MacroBlock.cs:577-626) and the analyzer's SAD on the GPU
+    (include/mobiclip_hip.h, mobi_transform_code): every block of src against the same block of pred at every quantiser.
+
+    src, pred: uint8 (n_blocks, 64) or (n_blocks, 16), row-major pixels.  quantizers: an int or a sequence of 1..54 ints in [0, 53].
+    Returns a dict of arrays shaped (n_q, n_blocks, ...): "bits" int32, "flags" uint8 (MOBI_TC_CODED 1, MOBI_TC_CLAMP 2), and unless
+    switched off "levels" int16 (.., n*n, scan order), "recon" uint8 (.., n*n), "sad" int32.  numpy inputs go through the host entry
+    point; torch tensors on the GPU through the asynchronous one, on torch.cuda.current_stream(), and come back as torch tensors (torch
+    must have been imported before this library was loaded, so that both use one HIP runtime)."""
+    qs = [int(quantizers)] if np.isscalar(quantizers) else [int(q) for q in quantizers]
+    if not 1 <= len(qs) <= 54:
+        raise ValueError("1 to 54 quantizers")
+    is_torch = type(src).__module__.startswith("torch")
+    if is_torch:
+        import torch
+        _check_one_hip_runtime()
+        if not (isinstance(pred, torch.Tensor) and src.is_cuda and pred.is_cuda and src.device == pred.device):
+            raise ValueError("src and pred must both be torch tensors on the same GPU")
+        if src.dtype != torch.uint8 or pred.dtype != torch.uint8:
+            raise ValueError("src and pred must be uint8")
+    else:
+        src, pred = np.asarray(src), np.asarray(pred)
+        if src.dtype != np.uint8 or pred.dtype != np.uint8:
+            raise ValueError("src and pred must be uint8")
+    if src.ndim != 2 or src.shape[1] not in (64, 16) or tuple(pred.shape) != tuple(src.shape):
+        raise ValueError("src and pred must be (n_blocks, 64) or (n_blocks, 16), of one shape")
+    nb, nn = int(src.shape[0]), int(src.shape[1])
+    n, nq = (8 if nn == 64 else 4), len(qs)
+    qarr = (C.c_int * nq)(*qs)
+    lib = load_library()
+    if is_torch:
+        src, pred = src.contiguous(), pred.contiguous()
+        dev = src.device
+        out = {"bits": torch.empty((nq, nb), dtype=torch.int32, device=dev), "flags": torch.empty((nq, nb), dtype=torch.uint8, device=dev)}
+        if levels:
+            out["levels"] = torch.empty((nq, nb, nn), dtype=torch.int16, device=dev)
+        if recon:
+            out["recon"] = torch.empty((nq, nb, nn), dtype=torch.uint8, device=dev)
+        if sad:
+            out["sad"] = torch.empty((nq, nb), dtype=torch.int32, device=dev)
+        ptr = {k: v.data_ptr() for k, v in out.items()}
+        rc = lib.mobi_transform_code_async(dev.index if dev.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(dev).cuda_stream,
+                                           n, qarr, nq, src.data_ptr(), pred.data_ptr(), nb, ptr.get("levels"), ptr.get("recon"), ptr["bits"],
+                                           ptr.get("sad"), ptr["flags"])
+    else:
+        src, pred = np.ascontiguousarray(src), np.ascontiguousarray(pred)
+        out = {"bits": np.empty((nq, nb), np.int32), "flags": np.empty((nq, nb), np.uint8)}
+        if levels:
+            out["levels"] = np.empty((nq, nb, nn), np.int16)
+        if recon:
+            out["recon"] = np.empty((nq, nb, nn), np.uint8)
+        if sad:
+            out["sad"] = np.empty((nq, nb), np.int32)
+        ptr = {k: v.ctypes.data for k, v in out.items()}
+        rc = lib.mobi_transform_code(default_device() if device is None else device, n, qarr, nq, src.ctypes.data, pred.ctypes.data, nb,
+                                     ptr.get("levels"), ptr.get("recon"), ptr["bits"], ptr.get("sad"), ptr["flags"])
     if rc != 0:
         raise MobiclipError(error_string(rc))
     return out
