@@ -230,6 +230,32 @@ int mobi_batch_export(mobi_batch *b, int format, int ring_idx, int n_frames, int
 int mobi_batch_export_wait(mobi_batch *b, uint64_t ticket);  /* this export and all earlier ones are in dst; MOBI_OK or MOBI_E_DEVICE
                                                                 (MOBI_E_ARG: a ticket this batch never issued) */
 int mobi_batch_export_query(mobi_batch *b, uint64_t ticket); /* 1 done, 0 not yet, < 0 error */
+/* ---- export of decoded pictures into device memory, on the caller's stream -------------------------------------------------------
+ * For consumers on the GPU (torch tensors, the caller's own HIP allocations): no staging, no copy engine, no ticket. */
+#define MOBI_EXPORT_RGB_PLANAR 2 /* per picture: R, G, B planes, each height x width elements (CHW) */
+#define MOBI_EXPORT_RGB_PACKED 3 /* per picture: height x width x 3 elements, R G B (HWC) */
+#define MOBI_DTYPE_U8 0  /* uint8 */
+#define MOBI_DTYPE_F16 1 /* IEEE half */
+#define MOBI_DTYPE_F32 2 /* IEEE single */
+/* The same pictures as mobi_batch_export, in the same order: picture j of clip c (ring index ring_idx - j) goes to
+ * dst + (j * n_clips + (c - clip0)) * picture_bytes.  MOBI_EXPORT_I420 and MOBI_EXPORT_ARGB (dtype MOBI_DTYPE_U8, scale_bias NULL) are byte
+ * for byte what mobi_batch_export writes.  RGB: R, G, B are bytes 2, 1, 0 of the Bitmap's 0xAARRGGBB word (mobi_batch_get_argb_at), in
+ * both versions; uint8 stores them as they are (scale_bias must be NULL); float32 stores (float)v * scale[ch] + bias[ch], a product and a
+ * sum each rounded in IEEE single (no fused multiply-add); float16 that float32 value rounded to nearest-even.  scale_bias = {scale R, G, B,
+ * bias R, G, B}, or NULL for scale 1 and bias 0.
+ *   STREAM:   stream is a hipStream_t (NULL: the null stream).  The export is enqueued on it and the call returns; on the GPU it waits for
+ *             everything enqueued on the batch so far (through an event, as mobi_batch_export does), and work the caller enqueues on stream
+ *             afterwards sees the data.  No host wait.
+ *   SNAPSHOT: as for mobi_batch_export: a later step that writes an exported ring slot waits, on the GPU, for the kernels that read it, behind
+ *             whatever the caller had enqueued on stream before them.  A caller that never lets stream run stalls the batch.
+ *   REFUSED:  the refusals of mobi_batch_export (ring / clip range, ring indices of steps in flight, a poisoned batch, MOBI_E_NULLREF), and
+ *             MOBI_E_ARG when dst is not device memory of the batch's device (host memory, mobi_host_alloc blocks, another device), when
+ *             dst is not 16-byte aligned or [dst, dst + the bytes needed) is larger than dst_bytes or its allocation, for a format / dtype /
+ *             scale_bias combination outside the list above, and when stream is capturing a graph.  A refused call enqueues nothing.
+ *   LIFETIME: dst and stream stay valid until the export has run on stream; mobi_batch_destroy waits for device exports that still read the
+ *             ring. */
+int mobi_batch_export_device(mobi_batch *b, int format, int dtype, const float *scale_bias, int ring_idx, int n_frames, int clip0,
+                             int n_clips, void *dst, size_t dst_bytes, void *stream);
 /* Encoder-side analysis: Analyzer.InterPredict2x2 (Analyzer.cs:608-681) for every 2x2 luma block of
  * every macroblock of every clip, as SolveInterPredictionPuzzle calls it (:683-693): three-step search (6, 3, 1 pels) in up
  * to five past frames = ring slots 0..4 of this batch (the encoder's PastFramesY, MobiEncoder.cs:138-144).

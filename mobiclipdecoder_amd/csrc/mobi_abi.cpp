@@ -546,7 +546,7 @@ long long mobi_debug_read_parse(mobi_batch *b, uint32_t *desc_out, uint32_t *ite
 #pragma GCC visibility pop
 #endif // MOBI_PROFILING
 
-const char *mobi_build_info(void) { return "libmobiclip_hip 0.6 (gfx950, macroblock-tiled planes; HIP kernels: mobi_recon_inter8, mobi_recon_intra, mobi_recon_step, mobi_recon_intra_cl, mobi_recon_intra_walk, mobi_parse_frames, mobi_parse_frames_ls, mobi_ls_deps, mobi_parse_tail, mobi_gop_prepare, mobi_gop_chain, mobi_gop_fronts, mobi_gop_front_starts, mobi_gop_scatter, mobi_untile, mobi_yuv_to_argb, mobi_export_i420, mobi_motion_search_2x2, mobi_fwd_dct8, mobi_fwd_dct4, mobi_txcode8, mobi_txcode4; no CPU reconstruction path)"; }
+const char *mobi_build_info(void) { return "libmobiclip_hip 0.6 (gfx950, macroblock-tiled planes; HIP kernels: mobi_recon_inter8, mobi_recon_intra, mobi_recon_step, mobi_recon_intra_cl, mobi_recon_intra_walk, mobi_parse_frames, mobi_parse_frames_ls, mobi_ls_deps, mobi_parse_tail, mobi_gop_prepare, mobi_gop_chain, mobi_gop_fronts, mobi_gop_front_starts, mobi_gop_scatter, mobi_untile, mobi_yuv_to_argb, mobi_export_i420, mobi_export_rgb, mobi_motion_search_2x2, mobi_fwd_dct8, mobi_fwd_dct4, mobi_txcode8, mobi_txcode4; no CPU reconstruction path)"; }
 
 const char *mobi_error_string(int rc) {
   switch (rc) {
@@ -2074,6 +2074,84 @@ int mobi_batch_export(mobi_batch *b, int format, int ring_idx, int n_frames, int
   if (int e = mobi_exporter_run(b->exporter, job, &t)) return e;
   if (ticket_out) *ticket_out = t;
   return MOBI_OK;
+}
+// ---- export into device memory, on the caller's stream (torch tensors, the caller's own HIP allocations) ----
+// The arguments are checked here; the stream order and the ring-slot guard are mobi_export.cpp's, the RGB kernel mobi_export_rgb.hip's.
+int mobi_batch_export_device(mobi_batch *b, int format, int dtype, const float *scale_bias, int ring_idx, int n_frames, int clip0, int n_clips,
+                             void *dst, size_t dst_bytes, void *stream) {
+  if (!b || !dst) return MOBI_E_ARG;
+  size_t esize = 0;
+  switch (format) {
+  case MOBI_EXPORT_I420:
+  case MOBI_EXPORT_ARGB:
+    if (dtype != MOBI_DTYPE_U8 || scale_bias) return MOBI_E_ARG;
+    break;
+  case MOBI_EXPORT_RGB_PLANAR:
+  case MOBI_EXPORT_RGB_PACKED:
+    if (dtype == MOBI_DTYPE_U8) { if (scale_bias) return MOBI_E_ARG; esize = 1; }
+    else if (dtype == MOBI_DTYPE_F16) esize = 2;
+    else if (dtype == MOBI_DTYPE_F32) esize = 4;
+    else return MOBI_E_ARG;
+    break;
+  default:
+    return MOBI_E_ARG;
+  }
+  if (clip0 < 0 || n_clips < 1 || clip0 > b->n - n_clips) return MOBI_E_ARG;
+  if (ring_idx < 0 || ring_idx > 5 || n_frames < 1 || ring_idx - n_frames + 1 < 0) return MOBI_E_ARG;
+  const size_t px = (size_t)b->g.width * b->g.height;
+  const size_t pic = format == MOBI_EXPORT_I420 ? px * 3 / 2 : format == MOBI_EXPORT_ARGB ? px * 4 : px * 3 * esize;
+  const size_t need = pic * n_frames * n_clips;
+  if (dst_bytes < need || ((uintptr_t)dst & 15)) return MOBI_E_ARG;
+  if (b->poisoned) return MOBI_E_ARG;
+  if (ring_idx >= b->frames_started) return MOBI_E_NULLREF;
+  if (ring_idx - n_frames + 1 < b->async_count) return MOBI_E_ARG; // frames of steps not waited for: mobi_batch_wait may still repair them
+  HIP_TRY(hipSetDevice(b->device));
+  // dst: device memory of this batch's device, the whole of [dst, dst + need) inside one allocation
+  hipPointerAttribute_t at;
+  memset(&at, 0, sizeof(at));
+  if (hipPointerGetAttributes(&at, dst) != hipSuccess) { (void)hipGetLastError(); return MOBI_E_ARG; }
+  if (at.type != hipMemoryTypeDevice || at.device != b->device) return MOBI_E_ARG;
+  hipDeviceptr_t base = nullptr;
+  size_t range = 0;
+  if (hipMemGetAddressRange(&base, &range, (hipDeviceptr_t)dst) != hipSuccess) { (void)hipGetLastError(); return MOBI_E_ARG; }
+  if ((uintptr_t)dst + need > (uintptr_t)base + range) return MOBI_E_ARG;
+  const hipStream_t s = (hipStream_t)stream;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(s, &cap) != hipSuccess) { (void)hipGetLastError(); return MOBI_E_ARG; }
+  if (cap != hipStreamCaptureStatusNone) return MOBI_E_ARG;
+  if (!b->exporter) b->exporter = mobi_exporter_new(b->device);
+  MobiExportJob job;
+  job.g = MobiExportGeom{b->arena + kGuard, b->clip_bytes, (uint32_t)b->slot_bytes, (int)b->g.width, (int)b->g.height, (int)b->g.stride, (int)b->g.mbw, b->g.lg};
+  job.format = format;
+  job.n_frames = n_frames;
+  job.clip0 = clip0;
+  job.n_clips = n_clips;
+  job.slot0 = (b->ring_base + 6 - ring_idx) % 6;
+  job.dst = dst;
+  job.src_stream = b->stream;
+  MobiRgbAffine sb{{1.f, 1.f, 1.f, 0.f, 0.f, 0.f}};
+  if (scale_bias) memcpy(sb.v, scale_bias, sizeof(sb.v));
+  // A GPU reader comes next.  Output that fits the 256 MiB MALL is read faster from the caches (plain stores: export + a reduction over it
+  // 4 - 13 % faster); larger output goes past them (0.3 - 4 % faster): tools/exp_export_device.py --nt, DESIGN.md "Export to device memory"
+  int nontemporal = need > ((size_t)256 << 20);
+#if defined(MOBI_PROFILING)
+  if (const char *e = getenv("MOBI_EXPORT_RGB_NT")) nontemporal = atoi(e); // (A/B: tools/exp_export_device.py)
+#endif
+  uint8_t *out = (uint8_t *)dst;
+  auto launch = [&](hipStream_t st) -> int {
+    if (format == MOBI_EXPORT_I420) return mobi_launch_export_i420(&job.g, 0, n_frames * n_clips, n_clips, clip0, job.slot0, out, st);
+    if (format == MOBI_EXPORT_ARGB) {
+      for (int j = 0; j < n_frames; j++) { // the Bitmap kernel converts clips of one slot: one launch per frame
+        MobiReconArgs a = b->args(nullptr, nullptr);
+        a.ring_base = (job.slot0 + j) % 6;
+        if (int e = mobi_launch_argb(&a, b->version, clip0, n_clips, (uint32_t *)(out + (size_t)j * n_clips * pic), st)) return e;
+      }
+      return 0;
+    }
+    return mobi_launch_export_rgb(&job.g, b->version, format == MOBI_EXPORT_RGB_PLANAR, (int)esize, nontemporal, n_frames, n_clips, clip0,
+                                  job.slot0, &sb, out, st);
+  };
+  return mobi_exporter_run_device(b->exporter, job, s, launch);
 }
 int mobi_batch_export_wait(mobi_batch *b, uint64_t ticket) {
   if (!b || !b->exporter) return MOBI_E_ARG;

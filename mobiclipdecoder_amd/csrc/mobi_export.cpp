@@ -7,6 +7,13 @@
 //   copy stream:  wait ev_packed[k]  hipMemcpyAsync D2H into dst (pinned) or into bounce chunk k (any other dst)  ev_copied[k]
 // so the pack of chunk i + 1 runs under the copy of chunk i, and a staging chunk is packed again only once the copy engine has read it.
 // The copy stream is in order: the event behind an export's last copy says "this export and every earlier one is in dst" (the ticket).
+//
+// Export to device memory (mobi_batch_export_device) has no pipeline: the caller's stream waits for the batch's stream and the kernels
+// write straight into dst.  A batch that only does that creates no streams and allocates no staging (init_events, not init_staging).
+//
+// The ring-slot guard keeps, per ring slot, the events of the exports that read it and may still run: packs on the pack stream and
+// device exports on callers' streams, which sit behind whatever the caller has enqueued there.  A step that writes the slot waits for
+// all of them (mobi_exporter_guard); finished ones are dropped whenever the set is looked at.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -57,8 +64,7 @@ struct MobiExporter {
   std::vector<hipEvent_t> ev_packed, ev_copied;
   std::vector<bool> used;                 // staging chunk k has been copied from at least once (ev_copied[k] recorded)
   uint64_t next_chunk = 0;                // chunks issued so far: chunk i uses staging chunk i mod n_chunks
-  hipEvent_t slot_ev[6] = {};             // the ring-slot guard: the last pack that read slot s ...
-  bool slot_armed[6] = {};                // ... and whether it may still be running
+  std::vector<hipEvent_t> readers[6];     // the ring-slot guard: the exports that read slot s and may still be running
   uint64_t next_ticket = 1, retired = 0;  // tickets 1 .. next_ticket - 1 issued; 1 .. retired known to be complete
   std::deque<std::pair<uint64_t, hipEvent_t>> pending;
   std::vector<hipEvent_t> ev_pool;
@@ -67,10 +73,39 @@ struct MobiExporter {
     if (!ev_pool.empty()) { *e = ev_pool.back(); ev_pool.pop_back(); return MOBI_OK; }
     return hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess ? MOBI_OK : MOBI_E_DEVICE;
   }
-  bool ready = false;                     // init() went through (a failed one is not tried again: the batch's exports are refused)
-  int init() {
+  // drop the events of slot s's readers that have finished (the set stays small: only exports still in flight are in it)
+  int prune(int s) {
+    auto &v = readers[s];
+    for (size_t i = 0; i < v.size();) {
+      const hipError_t q = hipEventQuery(v[i]);
+      if (q == hipSuccess) { ev_pool.push_back(v[i]); v[i] = v.back(); v.pop_back(); continue; }
+      if (q != hipErrorNotReady) { (void)hipGetLastError(); return MOBI_E_DEVICE; }
+      (void)hipGetLastError(); // (hipErrorNotReady stays with the thread otherwise)
+      i++;
+    }
+    return MOBI_OK;
+  }
+  // an export that reads slot s is enqueued on `stream`: a step that writes s waits for what is enqueued there now
+  int arm(int s, hipStream_t stream) {
+    if (int e = prune(s)) return e;
+    hipEvent_t ev = nullptr;
+    if (int e = get_event(&ev)) return e;
+    if (hipEventRecord(ev, stream) != hipSuccess) { ev_pool.push_back(ev); return MOBI_E_DEVICE; }
+    readers[s].push_back(ev);
+    return MOBI_OK;
+  }
+  bool events_ready = false;              // init_events() went through
+  int init_events() {
+    if (events_ready) return MOBI_OK;
+    if (!ev_src && hipEventCreateWithFlags(&ev_src, hipEventDisableTiming) != hipSuccess) { ev_src = nullptr; return MOBI_E_DEVICE; }
+    events_ready = true;
+    return MOBI_OK;
+  }
+  bool ready = false;                     // init_staging() went through (a failed one is not tried again: the batch's host exports are refused)
+  int init_staging() {
     if (ready) return MOBI_OK;
     if (pack_s) return MOBI_E_DEVICE;
+    if (int e = init_events()) return e;
 #if defined(MOBI_PROFILING)
     if (const char *e = getenv("MOBI_EXPORT_CHUNKS")) n_chunks = std::max(2, atoi(e));          // (A/B of the staging size: tools/exp_export.py)
     if (const char *e = getenv("MOBI_EXPORT_CHUNK_MB")) chunk_bytes = (size_t)std::max(9, atoi(e)) << 20;
@@ -88,7 +123,6 @@ struct MobiExporter {
 #endif
     if (hipStreamCreateWithPriority(&pack_s, hipStreamNonBlocking, prio_hi) != hipSuccess) { pack_s = nullptr; return MOBI_E_DEVICE; }
     if (hipStreamCreateWithPriority(&copy_s, hipStreamNonBlocking, prio_hi) != hipSuccess) return MOBI_E_DEVICE;
-    if (hipEventCreateWithFlags(&ev_src, hipEventDisableTiming) != hipSuccess) return MOBI_E_DEVICE;
     stage.assign(n_chunks, nullptr);
     ev_packed.assign(n_chunks, nullptr);
     ev_copied.assign(n_chunks, nullptr);
@@ -98,8 +132,6 @@ struct MobiExporter {
       if (hipEventCreateWithFlags(&ev_packed[k], hipEventDisableTiming) != hipSuccess) return MOBI_E_DEVICE;
       if (hipEventCreateWithFlags(&ev_copied[k], hipEventDisableTiming) != hipSuccess) return MOBI_E_DEVICE;
     }
-    for (auto &e : slot_ev)
-      if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return MOBI_E_DEVICE;
     ready = true;
     return MOBI_OK;
   }
@@ -125,9 +157,10 @@ struct MobiExporter {
   ~MobiExporter() {
     (void)hipSetDevice(device);
     drain(); // the copies of outstanding exports still read the staging chunks and write the callers' memory
+    for (auto &v : readers) // ... and device exports still read the ring, on the callers' streams
+      for (auto e : v) { (void)hipEventSynchronize(e); (void)hipEventDestroy(e); }
     for (auto &p : pending) (void)hipEventDestroy(p.second);
     for (auto e : ev_pool) (void)hipEventDestroy(e);
-    for (auto e : slot_ev) if (e) (void)hipEventDestroy(e);
     for (auto e : ev_packed) if (e) (void)hipEventDestroy(e);
     for (auto e : ev_copied) if (e) (void)hipEventDestroy(e);
     for (auto p : stage) if (p) (void)hipFree(p);
@@ -146,15 +179,15 @@ MobiExporter *mobi_exporter_new(int device) {
 void mobi_exporter_delete(MobiExporter *x) { delete x; }
 
 int mobi_exporter_guard(MobiExporter *x, int slot, hipStream_t stream) {
-  if (!x || !x->slot_armed[slot]) return MOBI_OK;
-  const hipError_t q = hipEventQuery(x->slot_ev[slot]);
-  if (q == hipSuccess) { x->slot_armed[slot] = false; return MOBI_OK; }
-  if (q != hipErrorNotReady) { (void)hipGetLastError(); return MOBI_E_DEVICE; }
-  return hipStreamWaitEvent(stream, x->slot_ev[slot], 0) == hipSuccess ? MOBI_OK : MOBI_E_DEVICE;
+  if (!x || x->readers[slot].empty()) return MOBI_OK;
+  if (int e = x->prune(slot)) return e;
+  for (hipEvent_t ev : x->readers[slot]) // (kept until they are seen finished: a later step may have to wait for them too)
+    if (hipStreamWaitEvent(stream, ev, 0) != hipSuccess) return MOBI_E_DEVICE;
+  return MOBI_OK;
 }
 
 int mobi_exporter_run(MobiExporter *x, const MobiExportJob &job, uint64_t *ticket_out) {
-  if (int e = x->init()) return e;
+  if (int e = x->init_staging()) return e;
   // tickets nobody waits for or asks about: the ones already done give their events back (a caller that never waits holds at most the
   // exports still in flight)
   while (!x->pending.empty() && hipEventQuery(x->pending.front().second) == hipSuccess) x->retire_upto(x->pending.front().first);
@@ -218,12 +251,9 @@ int mobi_exporter_run(MobiExporter *x, const MobiExportJob &job, uint64_t *ticke
     if (int e = hip(hipEventRecord(x->ev_copied[k], x->copy_s))) return e;
     x->used[k] = true;
   }
-  // the guard: a step that will write one of these slots waits for the last pack that read it
-  for (int j = 0; j < job.n_frames && j < 6; j++) {
-    const int s = (job.slot0 + j) % 6;
-    if (int e = hip(hipEventRecord(x->slot_ev[s], x->pack_s))) return e;
-    x->slot_armed[s] = true;
-  }
+  // the guard: a step that will write one of these slots waits for the packs that read it
+  for (int j = 0; j < job.n_frames && j < 6; j++)
+    if (int e = x->arm((job.slot0 + j) % 6, x->pack_s)) return e;
   if (!pinned) {
     for (uint64_t i = n_chunks > (uint64_t)x->n_chunks ? n_chunks - x->n_chunks : 0; i < n_chunks; i++)
       if (int e = consume(i)) return e;
@@ -240,6 +270,22 @@ int mobi_exporter_run(MobiExporter *x, const MobiExportJob &job, uint64_t *ticke
   const uint64_t t = x->next_ticket++;
   x->pending.emplace_back(t, done);
   *ticket_out = t;
+  return MOBI_OK;
+}
+
+int mobi_exporter_run_device(MobiExporter *x, const MobiExportJob &job, hipStream_t stream, const std::function<int(hipStream_t)> &launch) {
+  if (int e = x->init_events()) return e;
+  // whatever fails once something is enqueued: the kernels of this export have finished when the caller gets the error
+  struct Drain {
+    hipStream_t s; bool armed = true;
+    ~Drain() { if (armed) { (void)hipStreamSynchronize(s); (void)hipGetLastError(); } }
+  } drain{stream};
+  if (hipEventRecord(x->ev_src, job.src_stream) != hipSuccess) { drain.armed = false; (void)hipGetLastError(); return MOBI_E_DEVICE; }
+  if (hipStreamWaitEvent(stream, x->ev_src, 0) != hipSuccess) return MOBI_E_DEVICE; // the reconstruction of every frame exported is in front
+  if (launch(stream) != 0) return MOBI_E_DEVICE;
+  for (int j = 0; j < job.n_frames && j < 6; j++) // the guard: a step that will write one of these slots waits for these kernels
+    if (int e = x->arm((job.slot0 + j) % 6, stream)) return e;
+  drain.armed = false;
   return MOBI_OK;
 }
 

@@ -22,6 +22,13 @@ struct MobiExportGeom {
 extern "C" int mobi_launch_export_i420(const MobiExportGeom *g, uint32_t q0, int n_pics, int n_clips, int clip0, int slot0, uint8_t *out_dev,
                                        hipStream_t s);
 
+// mobi_export_rgb.hip: the pictures of an export (n_frames x n_clips, picture q = frame q / n_clips, clip clip0 + q % n_clips) -> out_dev as
+// RGB tensors: planar (CHW) or packed (HWC), esize 1 (uint8), 2 (float16) or 4 (float32); sb = scale[3], bias[3] (float only); nontemporal:
+// the stores go past the caches
+struct MobiRgbAffine { float v[6]; };
+extern "C" int mobi_launch_export_rgb(const MobiExportGeom *g, int version, int planar, int esize, int nontemporal, int n_frames, int n_clips,
+                                      int clip0, int slot0, const MobiRgbAffine *sb, uint8_t *out_dev, hipStream_t s);
+
 #if !defined(__HIPCC__) || !defined(__HIP_DEVICE_COMPILE__)
 struct MobiExporter;
 // one export of a checked request (mobi_batch_export).  slot0 = the ring slot of the OLDEST frame (ring index ring_idx); frame j is slot
@@ -38,10 +45,15 @@ struct MobiExportJob {
 MobiExporter *mobi_exporter_new(int device);
 void mobi_exporter_delete(MobiExporter *x); // waits for every export outstanding
 int mobi_exporter_run(MobiExporter *x, const MobiExportJob &job, uint64_t *ticket_out);
+// one export into device memory on the caller's stream (mobi_batch_export_device): `stream` waits for job.src_stream through an event,
+// launch(stream) enqueues the kernels, and every ring slot read is armed in the guard with an event recorded on `stream` behind them.  No
+// staging, no ticket.  On an error after something was enqueued the call waits for `stream` before it returns.
+int mobi_exporter_run_device(MobiExporter *x, const MobiExportJob &job, hipStream_t stream, const std::function<int(hipStream_t)> &launch);
 int mobi_exporter_wait(MobiExporter *x, uint64_t ticket);
 int mobi_exporter_query(MobiExporter *x, uint64_t ticket);
-// the ring-slot guard: before a step that writes ring slot `slot` is enqueued on `stream`, it waits for the last pack that read that slot --
-// if one may still be running.  No export outstanding: nothing at all (no event, no wait).
+// the ring-slot guard: before a step that writes ring slot `slot` is enqueued on `stream`, it waits for every export that read that slot
+// and may still be running -- host exports' packs and device exports on callers' streams alike.  No export outstanding: nothing at all
+// (no event, no wait).
 int mobi_exporter_guard(MobiExporter *x, int slot, hipStream_t stream);
 // is [p, p + bytes) inside one block of mobi_host_alloc?
 bool mobi_host_registered(const void *p, size_t bytes);

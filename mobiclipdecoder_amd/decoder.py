@@ -96,6 +96,8 @@ _SIGS = {
     "mobi_batch_export": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
     "mobi_batch_export_wait": (C.c_int, [C.c_void_p, C.c_uint64]),
     "mobi_batch_export_query": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "mobi_batch_export_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                           C.c_size_t, C.c_void_p]),
     "mobi_error_string": (C.c_char_p, [C.c_int]),
     "mobi_build_info": (C.c_char_p, []),
 }
@@ -157,6 +159,9 @@ class _PlaneRing:
 
 # mobi_batch_export formats (include/mobiclip_hip.h, MOBI_EXPORT_*)
 EXPORT_FORMATS = {"i420": 0, "argb": 1}
+# mobi_batch_export_device: (fmt, layout) -> MOBI_EXPORT_*; torch dtype name -> MOBI_DTYPE_*
+DEVICE_EXPORT_FORMATS = {("i420", None): 0, ("argb", None): 1, ("rgb", "nchw"): 2, ("rgb", "nhwc"): 3}
+DEVICE_EXPORT_DTYPES = {"uint8": 0, "float16": 1, "float32": 2}
 
 
 class _HostBlock:
@@ -313,7 +318,8 @@ class MobiclipBatch:
         self._lib = load_library()
         self.n, self.Width, self.Height, self.Version = int(n_clips), int(Width), int(Height), MobiclipVersion(Version)
         device = default_device() if device is None else device
-        self._h = self._lib.mobi_batch_create(self.n, self.Width, self.Height, int(self.Version), device)
+        self.device = int(device)
+        self._h = self._lib.mobi_batch_create(self.n, self.Width, self.Height, int(self.Version), self.device)
         if not self._h:
             raise MobiclipError(f"mobi_batch_create failed: {error_string(-8)}")
         self.Stride = self._lib.mobi_batch_stride(self._h)
@@ -474,6 +480,83 @@ class MobiclipBatch:
             raise MobiclipError(error_string(rc))
         h = ExportHandle(self, ticket.value, out)
         return h.wait() if wait else h
+
+    def export_tensor(self, fmt="rgb", ring_idx=0, n_frames=1, clips=None, layout="nchw", dtype=None, scale=None, bias=None, out=None,
+                      stream=None):
+        """Pictures of many clips and frames into a torch tensor on the batch's GPU (mobi_batch_export_device), enqueued on `stream`
+        (default: torch.cuda.current_stream of the batch's device) without a host wait: work enqueued on that stream afterwards sees them.
+        Frame j = ring index ring_idx - j (oldest first), clips = a range / slice of step 1 (None: all), as in export().
+
+        fmt="i420": (F, N, W*H*3/2) uint8, byte for byte what export() gives (split_i420 works on it).
+        fmt="argb": (F, N, H, W) int32 with the bits of the uint32 Bitmap.
+        fmt="rgb":  layout "nchw" -> (F, N, 3, H, W), "nhwc" -> (F, N, H, W, 3); dtype torch.uint8 (the Bitmap's R, G, B bytes, the default),
+                    torch.float16 or torch.float32: v * scale[ch] + bias[ch] in float32 (a product and a sum, each rounded), float16 rounded
+                    from that.  scale, bias: three floats each (default 1 and 0), for float dtypes only.  Normalising with a mean and a
+                    standard deviation is scale = 1 / std, bias = -mean / std, rounded to float32 first.
+        out: a contiguous, 16-byte aligned tensor of that shape and dtype on the batch's device to fill (default: a new one, allocated on
+        `stream`).  Every argument is checked before the library is called (ValueError); a refused export enqueues nothing."""
+        import torch
+        if fmt not in ("i420", "argb", "rgb"):
+            raise ValueError(f"fmt must be 'i420', 'argb' or 'rgb', not {fmt!r}")
+        if layout not in ("nchw", "nhwc"):
+            raise ValueError(f"layout must be 'nchw' or 'nhwc', not {layout!r}")
+        if dtype is None:
+            dtype = torch.uint8
+        if not isinstance(dtype, torch.dtype) or str(dtype).split(".")[-1] not in DEVICE_EXPORT_DTYPES:
+            raise ValueError(f"dtype must be torch.uint8, torch.float16 or torch.float32, not {dtype!r}")
+        dname = str(dtype).split(".")[-1]
+        if fmt != "rgb" and dtype != torch.uint8:
+            raise ValueError(f"fmt={fmt!r} has bytes only: dtype must be torch.uint8")
+        sb = None
+        if scale is not None or bias is not None:
+            if fmt != "rgb" or dtype == torch.uint8:
+                raise ValueError("scale and bias apply to fmt='rgb' with a float dtype only")
+            vals = []
+            for name, v, dflt in (("scale", scale, 1.0), ("bias", bias, 0.0)):
+                v = [dflt] * 3 if v is None else v
+                try:
+                    v = [float(x) for x in v]
+                except (TypeError, ValueError):
+                    raise ValueError(f"{name} must be three floats, not {v!r}") from None
+                if len(v) != 3 or not all(np.isfinite(v)):
+                    raise ValueError(f"{name} must be three finite floats, not {v!r}")
+                vals += v
+            sb = (C.c_float * 6)(*np.asarray(vals, np.float32).tolist())
+        if isinstance(ring_idx, bool) or not isinstance(ring_idx, (int, np.integer)) or not 0 <= ring_idx <= 5:
+            raise ValueError(f"ring_idx must be an int in 0..5, not {ring_idx!r}")
+        if isinstance(n_frames, bool) or not isinstance(n_frames, (int, np.integer)) or not 1 <= n_frames <= ring_idx + 1:
+            raise ValueError(f"n_frames must be an int in 1..ring_idx + 1 = {ring_idx + 1}, not {n_frames!r}")
+        if clips is None:
+            clips = range(self.n)
+        elif isinstance(clips, slice):
+            clips = range(self.n)[clips]
+        if not isinstance(clips, range) or clips.step != 1 or len(clips) < 1 or clips.start < 0 or clips.stop > self.n:
+            raise ValueError(f"clips must be a non-empty range / slice of step 1 inside 0..{self.n}, not {clips!r}")
+        F, N, W, H = int(n_frames), len(clips), self.Width, self.Height
+        if fmt == "i420":
+            shape, tdtype = (F, N, W * H * 3 // 2), torch.uint8
+        elif fmt == "argb":
+            shape, tdtype = (F, N, H, W), torch.int32
+        else:
+            shape, tdtype = ((F, N, 3, H, W) if layout == "nchw" else (F, N, H, W, 3)), dtype
+        dev = torch.device("cuda", self.device)
+        if stream is not None and (not isinstance(stream, torch.cuda.Stream) or stream.device != dev):
+            raise ValueError(f"stream must be a torch.cuda.Stream of {dev}, not {stream!r}")
+        if out is not None and (not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != tdtype or tuple(out.shape) != shape
+                                or not out.is_contiguous() or out.data_ptr() % 16):
+            raise ValueError(f"out must be a contiguous, 16-byte aligned {tdtype} tensor of shape {shape} on {dev}")
+        _check_one_hip_runtime()
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        if out is None:
+            with torch.cuda.stream(stream):
+                out = torch.empty(shape, dtype=tdtype, device=dev)
+        code = DEVICE_EXPORT_FORMATS[(fmt, layout if fmt == "rgb" else None)]
+        rc = self._lib.mobi_batch_export_device(self._h, code, DEVICE_EXPORT_DTYPES[dname], sb, int(ring_idx), F, clips.start, N,
+                                                out.data_ptr(), out.numel() * out.element_size(), stream.cuda_stream)
+        if rc != 0:
+            raise MobiclipError(error_string(rc))
+        return out
 
     def quantizer(self, clip):
         return self._lib.mobi_batch_quantizer(self._h, clip)
