@@ -123,6 +123,30 @@ int mobi_batch_host_clips(const mobi_batch *b);
 /* Parse mode 3: how many clips of the last finished frame step the lock-step parser finished itself (the rest went to the other one);
  * -1 in the other modes or before the first step. */
 int mobi_batch_lockstep_finished(const mobi_batch *b);
+/* Give each listed clip a new MobiclipDecoder(Width, Height, Version) (MD.cs:41-54) for its next frame: the caller ends one stream in a
+ * slot of the batch and starts the next file (or seeks: a suffix that starts at an I-frame) there, while the other clips go on.
+ *   WHEN:      from the next frame step the caller hands over: mobi_batch_decode, mobi_batch_submit, or the first frame of
+ *              mobi_batch_decode_gop / mobi_batch_gop_begin.  Steps and groups already in flight decode exactly as they would have without
+ *              the call; frames they report afterwards (mobi_batch_wait, mobi_batch_gop_finish, repairs included) are the old stream's.
+ *   NO WAIT:   never waits for the GPU and enqueues nothing; allowed while steps or groups are in flight (gop_begin(g + 1) before
+ *              gop_finish(g)).  The device side runs in front of that step's parse, one launch per step (mobi_reset_state).
+ *   WHAT:      everything a new decoder starts with: Quantizer, YuvFormat, Internal[] and the count of ring slots that hold a frame
+ *              (MOBI_E_NULLREF for a reference the new stream has not decoded yet), on the host parser and on the device; and the routing:
+ *              a clip the device parsers had handed to the host parser goes back to them (with a fresh count of clean frames, as at
+ *              creation); a clip of the hybrid mode's host share (parse mode 2) stays there, with a fresh host parser.
+ *   NOT:       no pixel.  The ring keeps the pictures it holds, and pictures being written by steps in flight, until it turns over them: the
+ *              old stream's last frames can still be exported after the reset and after the new stream's first frame was handed over.  The
+ *              getters and exports keep their batch-wide checks.  Ring index r of clip c holds a picture of the current stream exactly
+ *              when r < min(6, clip_frames[c]).  Version and geometry stay batch-wide: the new stream must match them (not checked: frames
+ *              carry neither, as with mobi_create).  The replay path parses with fresh parsers anyway: only the counts change there.
+ *   REFUSED:   MOBI_E_ARG for count < 0, clips NULL with count > 0 or any index outside [0, n_clips) -- all checked before anything
+ *              changes; MOBI_E_DEVICE for a poisoned batch (as mobi_batch_submit).  Duplicates are allowed; count == 0 does nothing. */
+int mobi_batch_reset_clips(mobi_batch *b, const int32_t *clips, int count);
+/* out[c] (n_clips entries) = frames handed over for clip c since the batch was created or the clip was last reset.  Host bookkeeping, never
+ * reads the GPU.  Counts ring turns: one per step (steps in flight included), one per frame of a group, one per mobi_batch_replay; frames
+ * that threw too (the reference turns its ring before anything can throw, MD.cs:102-108).  For a clip never reset: the frames the batch has
+ * been handed.  A reset sets it to 0 and the frames of groups begun before it do not count. */
+int mobi_batch_clip_frames(const mobi_batch *b, int32_t *out);
 /* Asynchronous frame steps, for callers that already hold the next frame of every clip (demuxed Moflex / Mods packets: the Offset
  * to start from does not depend on the previous frame's parse).  The batch must parse on the GPU (the default for large batches, see above;
  * mobi_batch_set_parse_mode(b, 1), 2 or 3 otherwise: the hybrid mode's host share is parsed inside mobi_batch_submit) and at most two steps

@@ -312,6 +312,7 @@ struct mobi_batch {
     std::vector<int> host_rc;
     std::vector<int32_t> host_off;
     std::vector<uint32_t> host_quant, host_yuv; // Quantizer / YuvFormat behind that frame (the parser itself may be a step further by the time of wait)
+    uint64_t serial = 0;             // the step's place among the steps handed over (stream generations: mobi_batch::stale)
   };
   AsyncSlot aslot[2];
   // frame-parallel groups (mobi_batch_gop_begin / mobi_batch_gop_finish, mobi_gop.h): K frames of every clip parsed side by side as n * K
@@ -326,6 +327,9 @@ struct mobi_batch {
     int n_iframes = 0;
     bool parse_enqueued = false, lockstep = false;
     int ring_in = 0;                 // the state ring entry the group's parse read
+    uint64_t serial = 0;             // the group's place among the steps handed over (stream generations: mobi_batch::stale)
+    size_t reset_off = 0;            // clips reset from this group on (mobi_batch_reset_clips): n_reset int32 at d_bits + reset_off, uploaded with
+    int n_reset = 0;                 // the group's bits; mobi_reset_state writes their fresh state in front of the group's parse
     std::vector<uint64_t> boff;      // [v] where the frame's bytes start in the staged image (behind its header)
     std::vector<uint32_t> lens;      // [v] their number (the header's copy carries MOBI_DP_SKIP for the host parser's clips)
     std::vector<int32_t> offs;       // [v] Offset at submission
@@ -370,6 +374,19 @@ struct mobi_batch {
   int acc_launches[2] = {0, 0};
   // export to host memory (mobi_batch_export, mobi_export.cpp): created at the first export; its staging chunks with it
   MobiExporter *exporter = nullptr;
+  // clip resets (mobi_batch_reset_clips).  A reset is recorded here and applied with the next step handed over (decode, submit, group): the
+  // host side (parser, routing) at once, the device side (mobi_reset_state) in front of that step's parse.  Stream generations: every step
+  // handed over gets the next serial, and stream_gen[c] is the serial of the step clip c's current stream started with; a step in flight
+  // with serial < stream_gen[c] belongs to the stream before, and its late bookkeeping (repairs and their cascade, on_host, dp_return,
+  // clean_run) leaves the clip's current state alone.  Its host parser is then retired[c] -- at most one older stream is ever in flight.
+  std::vector<int32_t> reset_list;     // clips reset and not handed over yet, each once
+  std::vector<uint8_t> reset_pending;  // [clip] in reset_list
+  std::vector<int> frames_base;        // [clip] the value of frames_started at which the current stream's first frame has turned the ring
+  std::vector<uint64_t> stream_gen;    // [clip] serial of the current stream's first step (0: the batch's first stream)
+  std::vector<std::unique_ptr<MobiStreamParser>> retired; // [clip] the parser of the stream before, while a step of it may be in flight
+  uint64_t handover = 0;               // serial of the last step handed over
+  bool stale(uint64_t serial, int c) const { return serial < stream_gen[c]; }
+  MobiStreamParser *parser_at(uint64_t serial, int c) const { return stale(serial, c) ? retired[c].get() : parsers[c].get(); }
 
   // The ring-slot guard, called by every step that writes a ring slot, right after the ring has turned and before anything of the step is
   // enqueued: the slot the step writes (ring_base) may still be read by the pack of an export; the batch's stream then waits for it.  With no
@@ -546,7 +563,7 @@ long long mobi_debug_read_parse(mobi_batch *b, uint32_t *desc_out, uint32_t *ite
 #pragma GCC visibility pop
 #endif // MOBI_PROFILING
 
-const char *mobi_build_info(void) { return "libmobiclip_hip 0.6 (gfx950, macroblock-tiled planes; HIP kernels: mobi_recon_inter8, mobi_recon_intra, mobi_recon_step, mobi_recon_intra_cl, mobi_recon_intra_walk, mobi_parse_frames, mobi_parse_frames_ls, mobi_ls_deps, mobi_parse_tail, mobi_gop_prepare, mobi_gop_chain, mobi_gop_fronts, mobi_gop_front_starts, mobi_gop_scatter, mobi_untile, mobi_yuv_to_argb, mobi_export_i420, mobi_export_rgb, mobi_motion_search_2x2, mobi_fwd_dct8, mobi_fwd_dct4, mobi_txcode8, mobi_txcode4; no CPU reconstruction path)"; }
+const char *mobi_build_info(void) { return "libmobiclip_hip 0.6 (gfx950, macroblock-tiled planes; HIP kernels: mobi_recon_inter8, mobi_recon_intra, mobi_recon_step, mobi_recon_intra_cl, mobi_recon_intra_walk, mobi_parse_frames, mobi_parse_frames_ls, mobi_ls_deps, mobi_parse_tail, mobi_gop_prepare, mobi_gop_chain, mobi_gop_fronts, mobi_gop_front_starts, mobi_gop_scatter, mobi_untile, mobi_yuv_to_argb, mobi_export_i420, mobi_export_rgb, mobi_reset_state, mobi_motion_search_2x2, mobi_fwd_dct8, mobi_fwd_dct4, mobi_txcode8, mobi_txcode4; no CPU reconstruction path)"; }
 
 const char *mobi_error_string(int rc) {
   switch (rc) {
@@ -585,6 +602,10 @@ mobi_batch *mobi_batch_create(int n_clips, uint32_t width, uint32_t height, int 
   b->slot_bytes = (size_t)b->g.stride * b->g.height * 3 / 2;
   b->clip_bytes = 6 * b->slot_bytes;
   b->cur.resize(n_clips);
+  b->reset_pending.assign(n_clips, 0);
+  b->frames_base.assign(n_clips, 0);
+  b->stream_gen.assign(n_clips, 0);
+  b->retired.resize(n_clips);
   b->h_fault.assign(n_clips, 0);
   b->on_host.assign(n_clips, 0);
   size_t arena_clips = (size_t)n_clips;
@@ -702,7 +723,10 @@ static int dp_init(mobi_batch *b) {
 }
 // stage [bit_off u64 x n][bit_len u32 x n][bits: each clip 8-byte aligned, zero padded] into pinned memory; the host parser's clips
 // (b->on_host) carry MOBI_DP_SKIP for a length and no bits
-struct DpStaged { size_t hdr_bytes = 0, bytes = 0, max_len = 0; int n_dev = 0, n_iframes = 0; }; // n_dev: clips the GPU parses; n_iframes: of them, I-frames (first bit)
+struct DpStaged { // n_dev: clips the GPU parses; n_iframes: of them, I-frames (first bit); reset_off / n_reset: where the clip list of the resets
+  size_t hdr_bytes = 0, bytes = 0, max_len = 0, reset_off = 0; // handed over with this step sits in the image (mobi_batch_reset_clips)
+  int n_dev = 0, n_iframes = 0, n_reset = 0;
+};
 // Which device parser is in front of this step (parse mode by default, r05; tools/exp_lsab.sh, tools/exp_dparse.py, 640x480, ms per step,
 // mobi_parse_frames against the lock-step parser at its best number of clips per wave):
 //   P-frames: 2048 clips 8.8 / 9.2, 4096: 11.2 / 13.7, 8192: 21.2 / 18.5, 16384: 42 / 23.5, 24576: 63 / 26.2
@@ -717,8 +741,9 @@ static bool ls_decide(const mobi_batch *b, const DpStaged &st) {
 // dev != nullptr: the image is also sent to *dev on `up`, chunk by chunk while the next chunk is gathered (one thread of the pool sits in
 // the copy calls, which return when the bus is done: 8 ms for the 370 MB of a step of 24576 clips; the others gather) -- r04: gathering and
 // sending were 12 of the 45 ms of such a step, one after the other.
+// resets != nullptr: these clip indices (int32) ride behind the bits, for mobi_reset_state
 static int dp_stage(mobi_batch *b, const uint8_t *const *data, const size_t *len, const int32_t *offsets, PinnedBuf &stage, DpStaged &st,
-                    DevBuf *dev = nullptr, bool dev_headroom = false, hipStream_t up = nullptr) {
+                    DevBuf *dev = nullptr, bool dev_headroom = false, hipStream_t up = nullptr, const std::vector<int32_t> *resets = nullptr) {
   const int n = b->n, nd = n, n_mbs = b->g.mbw * b->g.mbh;
   const auto t_stage0 = std::chrono::steady_clock::now();
   constexpr size_t kBitPad = 32; // the reader runs two 8-byte registers ahead
@@ -742,13 +767,18 @@ static int dp_stage(mobi_batch *b, const uint8_t *const *data, const size_t *len
     st.n_iframes += l >= 2 && (data[i][o + 1] & 0x80) != 0; // the frame's first bit: the top bit of its first 16-bit little-endian word (MD.cs:110-113)
   }
   pos += 64; // (a skipped clip's offset points at readable bytes too)
+  const size_t list_pos = pos, n_reset = resets ? resets->size() : 0;
+  pos += align_up(n_reset * 4, 16);
   const size_t hdr_bytes = align_up((size_t)nd * 12, 16);
   if (hdr_bytes + pos > stage.cap) // pinned memory is slow to allocate: leave room for the longer frames to come
     if (int e = stage.reserve(hdr_bytes + pos + (hdr_bytes + pos) / 4)) return e;
   uint8_t *hs = stage.p;
   memcpy(hs, boff.data(), (size_t)nd * 8);
   memcpy(hs + (size_t)nd * 8, blen.data(), (size_t)nd * 4);
-  memset(hs + hdr_bytes + pos - 64, 0, 64);
+  memset(hs + hdr_bytes + list_pos - 64, 0, 64);
+  if (n_reset) memcpy(hs + hdr_bytes + list_pos, resets->data(), n_reset * 4);
+  st.reset_off = hdr_bytes + list_pos;
+  st.n_reset = (int)n_reset;
   auto gather = [&](int i) {
     if (blen[i] == MOBI_DP_SKIP) return;
     uint8_t *dst = hs + hdr_bytes + boff[i];
@@ -897,7 +927,8 @@ static int dp_override(mobi_batch *b, const std::vector<int> &clips, const int *
 // the decoder state the clips of `cl` had when the step that read ring entry `in` started, into their host parsers: two asynchronous copies per
 // clip into pinned memory, ONE wait, the imports on the pool (r05 issued two blocking copies per clip: a step in which every clip of a large
 // batch is handed over at once -- a ModsDS batch that cuts to a quantiser below 12 -- sat in tens of thousands of them)
-static int dp_seed_parsers(mobi_batch *b, const std::vector<int> &cl, int in, PinnedBuf &stage, hipStream_t s) {
+// (into b->parsers, or into ps[j] for clip cl[j] when ps is given: a repair of a stream a reset has ended, mobi_batch::parser_at)
+static int dp_seed_parsers(mobi_batch *b, const std::vector<int> &cl, int in, PinnedBuf &stage, hipStream_t s, const std::vector<MobiStreamParser *> *ps = nullptr) {
   if (cl.empty()) return MOBI_OK;
   const size_t rec = sizeof(MobiDevState) + sizeof(MobiDevTail);
   if (int e = stage.reserve(cl.size() * rec)) return e;
@@ -907,7 +938,8 @@ static int dp_seed_parsers(mobi_batch *b, const std::vector<int> &cl, int in, Pi
   }
   HIP_TRY(hipStreamSynchronize(s));
   b->pool->run((int)cl.size(), [&](int j) {
-    b->parsers[cl[j]]->import_state(*(const MobiDevState *)(stage.p + (size_t)j * rec), *(const MobiDevTail *)(stage.p + (size_t)j * rec + sizeof(MobiDevState)));
+    MobiStreamParser *p = ps ? (*ps)[j] : b->parsers[cl[j]].get();
+    p->import_state(*(const MobiDevState *)(stage.p + (size_t)j * rec), *(const MobiDevTail *)(stage.p + (size_t)j * rec + sizeof(MobiDevState)));
   });
   return MOBI_OK;
 }
@@ -954,6 +986,32 @@ static int dp_return_list(mobi_batch *b, const std::vector<int> &back, int entry
   return MOBI_OK;
 }
 
+// ---- clip resets (mobi_batch_reset_clips) ----
+// The host side of the pending resets, for the step with serial `serial` being handed over: a new parser (the old one stays as retired[c]
+// while a step of its stream is in flight) and the routing a new decoder has -- back to the device parsers with clean_run = 0 and
+// clean_need = 4, or the hybrid share's fresh host parser.  A call that fails before it hands the step over leaves the list pending and the
+// next one comes here again with the same serial: clips that have it already are left alone.
+static void reset_apply_host(mobi_batch *b, uint64_t serial) {
+  const bool in_flight = b->async_count || b->gop_count;
+  for (int c : b->reset_list) {
+    if (b->stream_gen[c] == serial) continue;
+    if (in_flight) b->retired[c] = std::move(b->parsers[c]);
+    b->parsers[c].reset(new MobiStreamParser((uint32_t)b->g.width, (uint32_t)b->g.height, b->version));
+    b->stream_gen[c] = serial;
+    if (!b->host_share.empty()) { // (device-parse modes, after dp_init)
+      b->on_host[c] = b->host_share[c];
+      b->clean_run[c] = 0;
+      b->clean_need[c] = 4;
+    }
+  }
+}
+// the step with serial `serial` has been handed over, with the resets pending until now
+static void reset_commit(mobi_batch *b, uint64_t serial) {
+  b->handover = serial;
+  for (int c : b->reset_list) b->reset_pending[c] = 0;
+  b->reset_list.clear();
+}
+
 // Once the parsers have consumed a frame and the ring has turned, a call that fails before its reconstruction is complete must not leave
 // any clip reporting MOBI_OK for a frame that was never reconstructed (host-parsed and device-parsed steps alike: ADVICE r03)
 struct FailAll {
@@ -973,9 +1031,13 @@ static int decode_device_parse(mobi_batch *b, const uint8_t *const *data, const 
     return MOBI_OK; // DecodeFrame() returns before touching the ring (MD.cs:56-61)
   }
   if (b->g.mbw > 64 || b->async_count || b->gop_count) return MOBI_E_ARG; // (asynchronous steps / groups in flight: wait for them first)
+  const bool dev_state = b->d_pstate[0] != nullptr; // (before dp_init there is nothing on the device to reset)
   if (int e = dp_init(b)) return e;
   if (b->hybrid_host && b->frames_started == 0) // hybrid: the last clips are the host parsers' from the start (their state is a new decoder's: nothing to seed)
     for (int i = n - b->hybrid_host; i < n; i++) b->on_host[i] = b->host_share[i] = 1;
+  const uint64_t serial = b->handover + 1;
+  reset_apply_host(b, serial);
+  const std::vector<int32_t> *resets = dev_state && !b->reset_list.empty() ? &b->reset_list : nullptr;
   std::vector<int> host_clips;
   for (int i = 0; i < n; i++)
     if (b->on_host[i]) host_clips.push_back(i);
@@ -983,11 +1045,14 @@ static int decode_device_parse(mobi_batch *b, const uint8_t *const *data, const 
   using clk = std::chrono::steady_clock;
   auto ms_since = [](clk::time_point x) { return std::chrono::duration<float, std::milli>(clk::now() - x).count(); };
   const auto q0 = clk::now();
-  if (int e = dp_stage(b, data, len, offsets, b->h_stage, st, &b->d_bits, false, b->stream)) return e; // gathered and on their way
+  if (int e = dp_stage(b, data, len, offsets, b->h_stage, st, &b->d_bits, false, b->stream, resets)) return e; // gathered and on their way
   b->phase_ms[0] = ms_since(q0);
   b->lockstep = ls_decide(b, st);
+  if (st.n_reset && mobi_launch_reset_state((const int32_t *)(b->d_bits.p + st.reset_off), st.n_reset, n, b->d_pstate[b->ps_cur], b->d_ptail[b->ps_cur], b->stream) != 0)
+    return MOBI_E_DEVICE;
   int state_in = 0;
   if (int e = dp_parse(b, b->d_bits.p, st, false, DpOut{&b->d_pdesc, &b->d_ppay, &b->d_pitems, b->d_pres, b->stream}, &state_in)) return e;
+  reset_commit(b, serial);
   b->phase_ms[1] = ms_since(q0);
   const size_t cap_words = b->last_pay_cap;
   const DpRows rows{b->d_pdesc.p, b->d_ppay.p, b->d_pitems.p, b->d_pres, cap_words};
@@ -1145,9 +1210,13 @@ int mobi_batch_submit(mobi_batch *b, const uint8_t *const *data, const size_t *l
   if (b->parse_mode == 0) return MOBI_E_ARG; // the decoder state of this batch lives in the host parsers
   if (b->version != MOBI_VERSION_MODSDS && b->version != MOBI_VERSION_MOFLEX3DS) return MOBI_E_VERSION;
   if (b->g.mbw > 64 || b->async_count >= 2 || b->gop_count) return MOBI_E_ARG;
+  const bool dev_state = b->d_pstate[0] != nullptr;
   if (int e = dp_init(b)) return e;
   if (b->hybrid_host && b->frames_started == 0)
     for (int i = n - b->hybrid_host; i < n; i++) b->on_host[i] = b->host_share[i] = 1;
+  const uint64_t serial = b->handover + 1;
+  reset_apply_host(b, serial); // (before the staging: the routing decides which clips the device parses)
+  const std::vector<int32_t> *resets = dev_state && !b->reset_list.empty() ? &b->reset_list : nullptr;
   mobi_batch::AsyncSlot &S = b->aslot[(b->async_head + b->async_count) & 1];
   if (!S.ev_up) {
     HIP_TRY(hipEventCreateWithFlags(&S.ev_up, hipEventDisableTiming));
@@ -1157,7 +1226,7 @@ int mobi_batch_submit(mobi_batch *b, const uint8_t *const *data, const size_t *l
   if (!b->stream2) HIP_TRY(hipStreamCreateWithFlags(&b->stream2, hipStreamNonBlocking));
   if (!b->stream_p) HIP_TRY(hipStreamCreateWithFlags(&b->stream_p, hipStreamNonBlocking));
   DpStaged st;
-  if (int e = dp_stage(b, data, len, offsets, S.h_stage, st)) return e; // (this slot's previous step was waited for: its upload is done)
+  if (int e = dp_stage(b, data, len, offsets, S.h_stage, st, nullptr, false, nullptr, resets)) return e; // (this slot's previous step was waited for: its upload is done)
   if (int e = S.d_pres.reserve(sizeof(MobiDevResult) * n)) return e;
   if (st.bytes > S.d_bits.cap) // growing frees and allocates (a device-wide stall): leave room for the longer frames to come
     if (int e = S.d_bits.reserve(st.bytes + st.bytes / 4)) return e;
@@ -1165,6 +1234,7 @@ int mobi_batch_submit(mobi_batch *b, const uint8_t *const *data, const size_t *l
   if (int e = S.h_fault.reserve(sizeof(int) * n)) return e;
   S.offs.assign(offsets, offsets + n);
   S.n_dev = n;
+  S.serial = serial;
   b->lockstep = S.lockstep = ls_decide(b, st);
   S.hdr_bytes = st.hdr_bytes;
   S.is_host.assign(n, 0);
@@ -1214,6 +1284,9 @@ int mobi_batch_submit(mobi_batch *b, const uint8_t *const *data, const size_t *l
     if (b->async_seq > 0 && prev.ev_parsed && prev.parsed_recorded) HIP_TRY(hipStreamWaitEvent(ps, prev.ev_parsed, 0));
   }
   MobiDevResult *d_res = (MobiDevResult *)S.d_pres.p;
+  // clips reset from this step on: a new decoder's state into the entry the parse reads, behind whatever the step before wrote there
+  if (st.n_reset && mobi_launch_reset_state((const int32_t *)(S.d_bits.p + st.reset_off), st.n_reset, n, b->d_pstate[b->ps_cur], b->d_ptail[b->ps_cur], ps) != 0)
+    return MOBI_E_DEVICE;
   if (int e = dp_parse(b, S.d_bits.p, st, false, DpOut{&S.d_pdesc, &S.d_ppay, &S.d_pitems, d_res, ps, true}, &S.state_in)) return e;
   if (!host_clips.empty()) {
     if (int e = dp_override(b, host_clips, S.host_rc.data(), S.h_over, DpRows{S.d_pdesc.p, S.d_ppay.p, S.d_pitems.p, d_res, b->last_pay_cap}, ps)) return e;
@@ -1241,6 +1314,7 @@ int mobi_batch_submit(mobi_batch *b, const uint8_t *const *data, const size_t *l
   HIP_TRY(hipMemsetAsync(b->d_fault, 0, sizeof(int) * n, b->stream));
   HIP_TRY(hipEventRecord(S.ev_done, b->stream));
   poison.armed = false;
+  reset_commit(b, serial);
   b->async_count++;
   b->async_seq++;
   return MOBI_OK;
@@ -1256,38 +1330,54 @@ static int async_repair(mobi_batch *b, mobi_batch::AsyncSlot &S, const std::vect
   mobi_batch::AsyncSlot *S1 = b->async_count == 2 ? &b->aslot[(b->async_head + 1) & 1] : nullptr;
   const int n = b->n, k = (int)failed.size(), nT = S1 ? 2 : 1;
   mobi_batch::AsyncSlot *const T[2] = {&S, S1};
+  // A clip reset between the two steps (mobi_batch_reset_clips) has its new stream's first frame in S1, parsed from a new decoder's state: the
+  // repair stays in S, with the parser of the stream S belongs to (mobi_batch::parser_at), and leaves the clip's current state alone.
+  std::vector<MobiStreamParser *> parser(k);
+  std::vector<uint8_t> cascade(k, 0);
+  for (int j = 0; j < k; j++) {
+    parser[j] = b->parser_at(S.serial, failed[j]);
+    cascade[j] = S1 && b->stale(S.serial, failed[j]) == b->stale(S1->serial, failed[j]);
+  }
   // r06: a batch operation.  The start states in one go, the parses on the pool (a clip's two frames in order), then per affected step ONE
   // reconstruction of the failed clips (recon_clips) -- r05 did all of it clip by clip on the calling thread: a GOP damaged in every clip of a
   // batch, or a ModsDS batch that cuts to a quantiser below 12 in one frame, stalled mobi_batch_wait for ~1.5 ms x 2 x clips.
-  if (int e = dp_seed_parsers(b, failed, S.state_in, S.h_ret, b->stream)) return e;
+  if (int e = dp_seed_parsers(b, failed, S.state_in, S.h_ret, b->stream, &parser)) return e;
   if (b->gop_frames.size() < (size_t)k * 2) b->gop_frames.resize((size_t)k * 2);
   std::vector<int> prc((size_t)k * 2, MOBI_OK);
   b->pool->run(k, [&](int j) {
     const int c = failed[j];
-    for (int t = 0; t < nT; t++) {
+    for (int t = 0; t < (cascade[j] ? 2 : 1); t++) {
       const uint64_t boff = ((const uint64_t *)T[t]->h_stage.p)[c];
       const uint32_t blen = ((const uint32_t *)(T[t]->h_stage.p + (size_t)n * 8))[c];
       int32_t off = 0;
-      prc[(size_t)j * 2 + t] = b->parsers[c]->parse_frame(T[t]->h_stage.p + T[t]->hdr_bytes + boff, blen, &off, b->gop_frames[(size_t)j * 2 + t]);
+      prc[(size_t)j * 2 + t] = parser[j]->parse_frame(T[t]->h_stage.p + T[t]->hdr_bytes + boff, blen, &off, b->gop_frames[(size_t)j * 2 + t]);
       T[t]->is_host[c] = 1;
       T[t]->host_off[c] = T[t]->offs[c] + off;
-      T[t]->host_quant[c] = b->parsers[c]->quantizer();
-      T[t]->host_yuv[c] = b->parsers[c]->yuv_format();
+      T[t]->host_quant[c] = parser[j]->quantizer();
+      T[t]->host_yuv[c] = parser[j]->yuv_format();
     }
   });
-  std::vector<const ParsedFrame *> fr(k);
-  std::vector<int> fault(k);
   for (int t = 0; t < nT; t++) {
-    for (int j = 0; j < k; j++) fr[j] = prc[(size_t)j * 2 + t] == MOBI_OK ? &b->gop_frames[(size_t)j * 2 + t] : nullptr;
-    if (int e = recon_clips(b, failed, fr.data(), T[t]->ring_base, fault.data())) return e;
-    for (int j = 0; j < k; j++) {
-      int rc = prc[(size_t)j * 2 + t];
-      if (rc == MOBI_OK && fault[j]) rc = (fault[j] & 2) ? MOBI_E_DEVICE : MOBI_E_CLAMP;
-      T[t]->host_rc[failed[j]] = rc;
-      ((int *)T[t]->h_fault.p)[failed[j]] = 0;
+    std::vector<int> cl;
+    std::vector<const ParsedFrame *> fr;
+    std::vector<int> js;
+    for (int j = 0; j < k; j++)
+      if (t == 0 || cascade[j]) {
+        cl.push_back(failed[j]);
+        js.push_back(j);
+        fr.push_back(prc[(size_t)j * 2 + t] == MOBI_OK ? &b->gop_frames[(size_t)j * 2 + t] : nullptr);
+      }
+    std::vector<int> fault(cl.size());
+    if (int e = recon_clips(b, cl, fr.data(), T[t]->ring_base, fault.data())) return e;
+    for (size_t i = 0; i < cl.size(); i++) {
+      int rc = prc[(size_t)js[i] * 2 + t];
+      if (rc == MOBI_OK && fault[i]) rc = (fault[i] & 2) ? MOBI_E_DEVICE : MOBI_E_CLAMP;
+      T[t]->host_rc[cl[i]] = rc;
+      ((int *)T[t]->h_fault.p)[cl[i]] = 0;
     }
   }
   for (int c : failed) {
+    if (b->stale(S.serial, c)) continue; // (the clip's current stream started with S1 or starts with the next step: its routing is a new decoder's)
     b->on_host[c] = 1;
     b->clean_run[c] = 0;
     b->clean_need[c] = (uint16_t)std::min(256, 2 * (int)b->clean_need[c]);
@@ -1407,6 +1497,9 @@ static int gop_enqueue_parse(mobi_batch *b, mobi_batch::GopSlot &S, hipEvent_t a
   pa.n_clips = (int)nv; pa.version = b->version;
   pa.width = b->g.width; pa.height = b->g.height; pa.stride = b->g.stride; pa.lg = b->g.lg; pa.mbw = b->g.mbw; pa.mbh = b->g.mbh;
   const int in = b->ps_cur, out = (b->ps_cur + 1) % 3;
+  // clips reset from this group on: a new decoder's state into the entry the group starts from (behind dp_return_list, same stream)
+  if (S.n_reset && mobi_launch_reset_state((const int32_t *)(S.d_bits.p + S.reset_off), S.n_reset, n, b->d_pstate[in], b->d_ptail[in], ps) != 0)
+    return MOBI_E_DEVICE;
   G.ring_in = b->d_pstate[in]; G.ring_out = b->d_pstate[out];
   G.rtail_in = b->d_ptail[in]; G.rtail_out = b->d_ptail[out];
   G.n = n; G.K = K;
@@ -1438,6 +1531,7 @@ int mobi_batch_gop_begin(mobi_batch *b, int n_frames, const uint8_t *const *data
   if (b->parse_mode == 0) return MOBI_E_ARG; // the decoder state of this batch lives in the host parsers (mobi_batch_decode_gop serves those too)
   if (b->version != MOBI_VERSION_MODSDS && b->version != MOBI_VERSION_MOFLEX3DS) return MOBI_E_VERSION;
   if (b->g.mbw > 64 || b->async_count || b->gop_count >= 2 || nv >= ((size_t)1 << 22)) return MOBI_E_ARG;
+  const bool dev_state = b->d_pstate[0] != nullptr;
   if (int e = dp_init(b)) return e;
   if (b->hybrid_host && b->frames_started == 0 && b->gop_count == 0)
     for (int i = n - b->hybrid_host; i < n; i++) b->on_host[i] = b->host_share[i] = 1;
@@ -1464,6 +1558,8 @@ int mobi_batch_gop_begin(mobi_batch *b, int n_frames, const uint8_t *const *data
     pos += align_up(l + kBitPad, 8);
   }
   pos += 64;
+  const size_t list_pos = pos, n_reset = dev_state ? b->reset_list.size() : 0; // the clips reset from this group on, behind the bits
+  pos += align_up(n_reset * 4, 16);
   const size_t hdr_bytes = align_up(nv * 12, 16), need = hdr_bytes + pos;
   if (need > S.h_stage.cap)
     if (int e = S.h_stage.reserve(need + need / 4)) return e;
@@ -1471,7 +1567,10 @@ int mobi_batch_gop_begin(mobi_batch *b, int n_frames, const uint8_t *const *data
     if (int e = S.d_bits.reserve(need + need / 4)) return e;
   uint8_t *hs = S.h_stage.p;
   memcpy(hs, S.boff.data(), nv * 8);
-  memset(hs + hdr_bytes + pos - 64, 0, 64);
+  memset(hs + hdr_bytes + list_pos - 64, 0, 64);
+  if (n_reset) memcpy(hs + hdr_bytes + list_pos, b->reset_list.data(), n_reset * 4);
+  S.reset_off = hdr_bytes + list_pos;
+  S.n_reset = (int)n_reset;
   S.hdr_bytes = hdr_bytes; S.bytes = need; S.max_len = max_len;
   auto gather = [&](size_t v) {
     uint8_t *dst = hs + hdr_bytes + S.boff[v];
@@ -1507,6 +1606,10 @@ int mobi_batch_gop_begin(mobi_batch *b, int n_frames, const uint8_t *const *data
   S.resolved = S.returned = false;
   S.done = 0;
   if (int e = gop_reserve(b, S)) { (void)hipStreamSynchronize(b->stream2); return e; } // (does not fit: refused, nothing of it is in flight)
+  // the group is handed over: the pending resets' host side now (the routing its parse is enqueued with, here or in the finish in front)
+  S.serial = b->handover + 1;
+  reset_apply_host(b, S.serial);
+  reset_commit(b, S.serial);
   b->gop_count++;
   if (b->gop_count == 1) // nothing in front: the parse may start at once (else mobi_batch_gop_finish of the group in front enqueues it, once it knows whose clips are whose)
     if (int e = gop_enqueue_parse(b, S)) { (void)hipStreamSynchronize(b->stream2); (void)hipStreamSynchronize(b->stream_p); b->gop_count--; return e; }
@@ -1559,11 +1662,12 @@ int mobi_batch_gop_finish(mobi_batch *b, int32_t *offsets_out, int *rc) {
         for (int k = host_from[c]; k < K; k++) {
           const size_t v = (size_t)k * n + c;
           int32_t off = 0;
-          hrc[v] = b->parsers[c]->parse_frame(S.h_stage.p + S.hdr_bytes + S.boff[v], S.lens[v], &off, b->gop_frames[(size_t)hslot[c] * K + k]);
+          MobiStreamParser *p = b->parser_at(S.serial, c); // (the group's stream: a reset handed over with the group behind it left it retired)
+          hrc[v] = p->parse_frame(S.h_stage.p + S.hdr_bytes + S.boff[v], S.lens[v], &off, b->gop_frames[(size_t)hslot[c] * K + k]);
           hoff[v] = S.offs[v] + off;
-          hready[v] = hrc[v] == MOBI_OK && b->parsers[c]->device_ready();
-          hq[v] = b->parsers[c]->quantizer();
-          hy[v] = b->parsers[c]->yuv_format();
+          hready[v] = hrc[v] == MOBI_OK && p->device_ready();
+          hq[v] = p->quantizer();
+          hy[v] = p->yuv_format();
         }
       });
     };
@@ -1596,10 +1700,11 @@ int mobi_batch_gop_finish(mobi_batch *b, int32_t *offsets_out, int *rc) {
       for (size_t j = 0; j < fb.size(); j++) {
         const int c = fb[j];
         hslot[c] = (int)(base + j);
-        b->parsers[c]->import_state(*(const MobiDevState *)(S.h_seed.p + j * rec), *(const MobiDevTail *)(S.h_seed.p + j * rec + sizeof(MobiDevState)));
+        b->parser_at(S.serial, c)->import_state(*(const MobiDevState *)(S.h_seed.p + j * rec), *(const MobiDevTail *)(S.h_seed.p + j * rec + sizeof(MobiDevState)));
       }
       host_parse(fb);
       for (int c : fb) {
+        if (b->stale(S.serial, c)) continue; // (reset since: the clip's routing is a new decoder's)
         b->on_host[c] = 1;
         b->clean_run[c] = 0;
         b->clean_need[c] = (uint16_t)std::min(256, 2 * (int)b->clean_need[c]);
@@ -1710,7 +1815,7 @@ int mobi_batch_gop_finish(mobi_batch *b, int32_t *offsets_out, int *rc) {
     {
       std::vector<int> back;
       for (int c : all_host) {
-        if (b->host_share[c]) continue;
+        if (b->host_share[c] || b->stale(S.serial, c)) continue;
         int run = b->clean_run[c]; // consecutive frames the device parsers would have finished too
         for (int k = host_from[c]; k < K; k++) run = hready[(size_t)k * n + c] ? run + 1 : 0;
         b->clean_run[c] = (uint16_t)std::min(60000, run);
@@ -1808,6 +1913,35 @@ int mobi_batch_host_clips(const mobi_batch *b) {
 }
 int mobi_batch_lockstep_finished(const mobi_batch *b) { return b ? b->ls_finished : -1; }
 
+// new MobiclipDecoder(Width, Height, Version) for clips of the batch, from the next step handed over on (reset_apply_host, mobi_reset_state).
+// Records the list and the frame count's new origin; waits for nothing and enqueues nothing.
+int mobi_batch_reset_clips(mobi_batch *b, const int32_t *clips, int count) {
+  if (!b || count < 0 || (!clips && count > 0)) return MOBI_E_ARG;
+  for (int j = 0; j < count; j++)
+    if (clips[j] < 0 || clips[j] >= b->n) return MOBI_E_ARG; // (every index before anything changes)
+  if (b->poisoned) return MOBI_E_DEVICE;
+  // the frames of groups begun that have not turned the ring yet belong to the stream before
+  int later = 0;
+  for (int i = 0; i < b->gop_count; i++) {
+    const mobi_batch::GopSlot &S = b->gslot[(b->gop_head + i) & 1];
+    later += S.K - (S.resolved ? S.done : 0);
+  }
+  for (int j = 0; j < count; j++) {
+    const int c = clips[j];
+    b->frames_base[c] = b->frames_started + later;
+    if (!b->reset_pending[c]) {
+      b->reset_pending[c] = 1;
+      b->reset_list.push_back(c);
+    }
+  }
+  return MOBI_OK;
+}
+int mobi_batch_clip_frames(const mobi_batch *b, int32_t *out) {
+  if (!b || !out) return MOBI_E_ARG;
+  for (int c = 0; c < b->n; c++) out[c] = std::max(0, b->frames_started - b->frames_base[c]);
+  return MOBI_OK;
+}
+
 int mobi_batch_set_parse_mode(mobi_batch *b, int device_parse) {
   if (!b || b->frames_started != 0) return MOBI_E_ARG; // the decoder state lives either in the host parsers or in HBM, not both
   b->parse_mode = device_parse == 2 ? 2 : device_parse != 0;
@@ -1839,6 +1973,11 @@ int mobi_batch_decode(mobi_batch *b, const uint8_t *const *data, const size_t *l
     hybrid_share(b);
   }
   if (b->parse_mode) return decode_device_parse(b, data, len, offsets, rc);
+  { // clips reset since the last step: a new parser each (parse mode 0 keeps no decoder state on the device)
+    const uint64_t serial = b->handover + 1;
+    reset_apply_host(b, serial);
+    reset_commit(b, serial);
+  }
   const int n = b->n;
   // 1. host: serial VLC parse of one frame per clip -> command lists.  The clips are taken in chunks, three stages deep: in one round of
   // the pool chunk k is parsed, chunk k - 1 is written into the staging buffer, and chunk k - 2 is handed to the copy engine (a step of

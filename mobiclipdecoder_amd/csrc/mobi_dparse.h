@@ -59,4 +59,7 @@ struct MobiDevParseArgs {
 #define MOBI_DP_SKIP 0xFFFFFFFFu
 extern "C" int mobi_launch_parse(const MobiDevParseArgs *a, hipStream_t s); // the parse kernels, then mobi_parse_tail
 extern "C" int mobi_launch_parse_ls(const MobiDevParseArgs *a, hipStream_t s); // the two kernels in front (called by mobi_launch_parse)
+// mobi_batch_reset_clips (mobi_reset.hip): zero MobiDevState / MobiDevTail records -- a new decoder's -- for clips_dev[0 .. count) (unique,
+// each below n_clips) in one state ring entry
+extern "C" int mobi_launch_reset_state(const int32_t *clips_dev, int count, int n_clips, MobiDevState *state, MobiDevTail *tail, hipStream_t s);
 #endif

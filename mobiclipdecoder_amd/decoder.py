@@ -76,6 +76,8 @@ _SIGS = {
     "mobi_batch_yuv_format": (C.c_uint32, [C.c_void_p, C.c_int]),
     "mobi_batch_set_parse_mode": (C.c_int, [C.c_void_p, C.c_int]),
     "mobi_batch_lockstep_finished": (C.c_int, [C.c_void_p]),
+    "mobi_batch_reset_clips": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int]),
+    "mobi_batch_clip_frames": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "mobi_batch_last_decode_ms": (C.c_float, [C.c_void_p]),
     "mobi_batch_motion_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "mobi_batch_stride": (C.c_int, [C.c_void_p]),
@@ -414,6 +416,36 @@ class MobiclipBatch:
     def lockstep_finished(self):
         """device_parse="lockstep": clips of the last finished step the lock-step parser finished itself (-1 in other modes)."""
         return self._lib.mobi_batch_lockstep_finished(self._h)
+
+    def reset_clips(self, clips):
+        """A new MobiclipDecoder for each of `clips` (ints, or a bool mask of length n) from the next step handed over on: start the
+        next file -- or seek to an I-frame -- in a slot whose stream has ended.  Waits for nothing; steps and groups in flight, and the
+        pictures in the ring, are not touched (mobiclip_hip.h, mobi_batch_reset_clips)."""
+        arr = np.asarray(clips)
+        if arr.dtype == np.bool_:
+            if arr.shape != (self.n,):
+                raise ValueError(f"a clip mask must have {self.n} entries, not {arr.shape}")
+            idx = np.flatnonzero(arr)
+        else:
+            arr = arr.reshape(-1)
+            if arr.size and not np.issubdtype(arr.dtype, np.integer):
+                raise ValueError("clips must be integers or a bool mask")
+            idx = arr.astype(np.int64)
+            if idx.size and (idx.min() < 0 or idx.max() >= self.n):
+                raise ValueError(f"clip index outside [0, {self.n})")
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        e = self._lib.mobi_batch_reset_clips(self._h, idx.ctypes.data_as(C.POINTER(C.c_int32)), int(idx.size))
+        if e != 0:
+            raise MobiclipError(error_string(e))
+
+    def clip_frames(self):
+        """int32[n]: frames handed over per clip since the batch was created or the clip was last reset (steps in flight and every
+        frame of a finished group part count); ring index r of clip c holds the current stream's picture iff r < min(6, that)."""
+        out = np.zeros(self.n, np.int32)
+        e = self._lib.mobi_batch_clip_frames(self._h, out.ctypes.data_as(C.POINTER(C.c_int32)))
+        if e != 0:
+            raise MobiclipError(error_string(e))
+        return out
 
     def wait(self):
         """(rc list, new offsets list) of the oldest submitted step, when its reconstruction is done."""
