@@ -31,6 +31,16 @@ LIB_LSHOST = os.path.join(ROOT, "tests", "tools", "libmobi_lsparse_host.so")  # 
 ABI_CALLER = os.path.join(ROOT, "tests", "tools", "abi_caller")  # plain-C caller of the product library (test tool)
 
 
+# the sources of libmobiclip_hip.so: *.cpp are host objects (g++), *.hip kernel objects (hipcc --offload-arch=gfx950); linked in this order
+HIP_SOURCES = ("mobi_batch.cpp", "mobi_step_host.cpp", "mobi_step_device.cpp", "mobi_step_groups.cpp", "mobi_replay.cpp", "mobi_pictures.cpp", "mobi_parse.cpp", "mobi_demux.cpp", "mobi_moflex.cpp", "mobi_export.cpp", "mobi_txcode.cpp", "mobi_kernels.hip", "mobi_rgb.hip", "mobi_dparse.hip", "mobi_lsparse.hip", "mobi_gop.hip", "mobi_analysis.hip", "mobi_export.hip", "mobi_txcode.hip", "mobi_export_rgb.hip", "mobi_reset.hip")
+
+
+def hip_objects(profiling=False):
+    """the object files build_hip links, in link order (python -m mobiclipdecoder_amd.build --objects [--profiling]: tools/ that rebuild one of them)"""
+    obj = os.path.join(PKG, "_obj_prof" if profiling else "_obj")
+    return [os.path.join(obj, f + ".o") for f in HIP_SOURCES]
+
+
 def _newer(target, sources):
     if not os.path.exists(target):
         return True
@@ -61,7 +71,7 @@ def build_hip(force=False, profiling=False):
     """profiling=True (python -m mobiclipdecoder_amd.build --profiling, tools/ only): a SECOND library, libmobiclip_hip_prof.so, with
     -DMOBI_PROFILING: the ablation / occupancy / stage-stop switches (MOBI_INTRA_DBG, MOBI_LDS_PAD, MOBI_INTRA_LDS_PAD, MOBI_STOP_STAGE,
     MOBI_DEBUG=9) and the mobi_debug_* test hooks.  The product library has none of them; tools select the other one with MOBI_LIB."""
-    srcs = [os.path.join(CSRC, f) for f in ("mobi_abi.cpp", "mobi_parse.cpp", "mobi_demux.cpp", "mobi_moflex.cpp", "mobi_export.cpp", "mobi_txcode.cpp", "mobi_kernels.hip", "mobi_rgb.hip", "mobi_dparse.hip", "mobi_lsparse.hip", "mobi_gop.hip", "mobi_analysis.hip", "mobi_export.hip", "mobi_txcode.hip", "mobi_export_rgb.hip", "mobi_reset.hip")]
+    srcs = [os.path.join(CSRC, f) for f in HIP_SOURCES]
     deps = srcs + _hdrs(CSRC) + [os.path.join(ROOT, "include", "mobiclip_hip.h"), os.path.join(ROOT, "include", "mobiclip_demux.h"), os.path.abspath(__file__)]
     lib = LIB_HIP_PROF if profiling else LIB_HIP
     if not force and not _newer(lib, deps):
@@ -72,11 +82,10 @@ def build_hip(force=False, profiling=False):
     # only the entry points include/*.h declare leave the library (MOBI_API); everything else is hidden
     # (-O3: the host parser -- hand-overs, small batches, mobi_decode -- parses a 640x480 P-frame in 0.41 ms instead of 0.47)
     host_flags = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-fwrapv", "-fvisibility=hidden", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(ROCM, "include")] + prof
-    objs = []
-    for s in srcs[:6]:
-        o = os.path.join(obj, os.path.basename(s) + ".o")
-        _run(["g++"] + host_flags + ["-c", s, "-o", o])
-        objs.append(o)
+    objs = hip_objects(profiling)
+    for s, o in zip(srcs, objs):
+        if s.endswith(".cpp"):
+            _run(["g++"] + host_flags + ["-c", s, "-o", o])
     # the reconstruction kernels are bound by instruction issue: LLVM's ILP-first scheduling is worth 1.5 % on mobi_recon_inter8
     # (same registers, same occupancy; measured A/B on one box); the other kernels keep the default
     # r03: both kernels are bound by vector instruction issue; loops the source does not ask to unroll stay loops (-fno-unroll-loops:
@@ -84,10 +93,9 @@ def build_hip(force=False, profiling=False):
     extra = {"mobi_kernels.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp", "-fno-unroll-loops"],
              # the lock-step parser is one long dependent chain per wave: 24.8 against 25.6 ms per P-frame step (tools/exp_lsflags.sh)
              "mobi_lsparse.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]}
-    for s in srcs[6:]:
-        ko = os.path.join(obj, os.path.basename(s) + ".o")
-        _run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden"] + prof + extra.get(os.path.basename(s), []) + ["-c", s, "-o", ko])
-        objs.append(ko)
+    for s, ko in zip(srcs, objs):
+        if s.endswith(".hip"):
+            _run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden"] + prof + extra.get(os.path.basename(s), []) + ["-c", s, "-o", ko])
     # What leaves the library is exactly what include/*.h declares (the profiling twin adds its mobi_debug_* hooks): a linker version
     # script written from the headers -- no C++ symbols, no template instantiations, no kernel stubs.
     vs = os.path.join(obj, "exports.map")
@@ -141,6 +149,9 @@ def build_all(force=False):
 
 
 if __name__ == "__main__":
+    if "--objects" in sys.argv:
+        print(" ".join(hip_objects("--profiling" in sys.argv)))
+        sys.exit(0)
     if "--profiling" in sys.argv:
         build_hip(force="--force" in sys.argv, profiling=True)
     else:

@@ -29,7 +29,7 @@ struct MobiDevParseArgs {
   const uint32_t *bit_len;  // Data.Length - Offset of clip c (0: nothing readable; MOBI_DP_SKIP: the clip is the host parser's -- no kernel touches
                             // anything of it, its command list is uploaded into its rows beside the parse)
   const uint8_t *tables;    // MOBI_DT_BYTES blob
-  // [clip] decoder state: read from *_in, written to *_out -- two entries of a ring of three (mobi_abi.cpp), so that the state a frame
+  // [clip] decoder state: read from *_in, written to *_out -- two entries of a ring of three (mobi_batch.h), so that the state a frame
   // STARTED from is still there when its parse turns out not to be the device's to finish and the host parser takes the frame over
   const MobiDevState *state_in;
   MobiDevState *state_out;

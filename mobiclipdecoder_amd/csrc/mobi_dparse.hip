@@ -13,7 +13,7 @@
 //    dependency is raster-earlier); the launch interleaves clips so that a clip's chain never fills the machine;
 //  * exceptions become a sticky error code -- which, since r05, nobody outside sees: a frame this parser cannot finish (any error, any
 //    refusal) is parsed again by the HOST parser inside the same call, from the state the frame started with (the state ring: state_in /
-//    state_out, mobi_state.h, mobi_abi.cpp), and rc / Offset / planes are the host parser's.  All this parser owes is to be right on frames
+//    state_out, mobi_state.h, mobi_step_device.cpp), and rc / Offset / planes are the host parser's.  All this parser owes is to be right on frames
 //    that decode without incident and never to report one that does not as finished.  (What follows is how the error paths behave
 //    anyway: they were written to match the reference's exceptions and still do.)
 //  * The first error freezes the bit reader (Offset stays where the reference threw) and
@@ -785,7 +785,7 @@ extern "C" __global__ __launch_bounds__(64 * PWAVES) __attribute__((amdgpu_waves
     int32_t *mv = A.tail_out[clip].mvc;
     for (int i = lane; i < 2 * (A.mbw + 2); i += 64) mv[i] = L->mvc[i];
   }
-  // a failed clip: descriptors typed "intra" that no launch list references, so nothing of it is written (mobi_abi.cpp step_write)
+  // a failed clip: descriptors typed "intra" that no launch list references, so nothing of it is written (mobi_batch.h step_write)
   if (rcl != 0) {
     uint4 *d = (uint4 *)(A.desc + (size_t)clip * n_mbs);
     for (int mb = lane; mb < n_mbs; mb += 64) {

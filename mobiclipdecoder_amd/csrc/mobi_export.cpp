@@ -1,5 +1,5 @@
 // mobi_export.cpp -- decoded pictures out to host memory (include/mobiclip_hip.h, mobi_batch_export): the pinned-block registry of
-// mobi_host_alloc, the staging pipeline, the tickets and the ring-slot guard.  The C entry points are in mobi_abi.cpp; what they hand
+// mobi_host_alloc, the staging pipeline, the tickets and the ring-slot guard.  The C entry points are in mobi_pictures.cpp; what they hand
 // over is mobi_exporter.h's.
 //
 // Pipeline ("Export"): an export is cut into chunks of whole pictures.  Chunk i goes to staging chunk k = i mod kChunks:

@@ -1,4 +1,4 @@
-// mobi_kernels.h -- launch interface between the C-ABI layer (mobi_abi.cpp) and mobi_kernels.hip.
+// mobi_kernels.h -- launch interface between the C-ABI layer (mobi_batch.h and the units that include it) and mobi_kernels.hip.
 #ifndef MOBI_KERNELS_H
 #define MOBI_KERNELS_H
 #include <hip/hip_runtime_api.h>
@@ -36,7 +36,7 @@ static_assert(sizeof(MobiReconArgs) == 128, "kernarg block layout");
 
 // mobi_recon_inter8: every inter macroblock of the step, one wave per octet of macroblocks
 extern "C" int mobi_launch_inter(const MobiReconArgs *a, hipStream_t s);
-// items_dev: n_items launch items of 16 bytes (MOBI_INTRA_ITEM_WORDS words), sorted by dependency level -- see LevelPlan in mobi_abi.cpp
+// items_dev: n_items launch items of 16 bytes (MOBI_INTRA_ITEM_WORDS words), sorted by dependency level -- see LevelPlan in mobi_batch.h
 extern "C" int mobi_launch_intra(const MobiReconArgs *a, const uint32_t *items_dev, int n_items, hipStream_t s);
 // small batches: both of the above in one launch (mobi_recon_step: the intra fours wait for the inter macroblocks their halo reads)
 extern "C" int mobi_launch_step(const MobiReconArgs *a, const uint32_t *items_dev, int n_items, hipStream_t s);

@@ -1140,7 +1140,7 @@ __device__ __forceinline__ uint32_t quad_first(uint32_t v) { // lane 4k's value 
 #endif
 }
 
-// What a row of lanes needs to know to start on its macroblock.  The host-built launch list (mobi_abi.cpp, LevelPlan) carries it
+// What a row of lanes needs to know to start on its macroblock.  The host-built launch list (mobi_batch.h, LevelPlan) carries it
 // as one 16-byte item, so the first load already says where the records are and whether anybody has to be waited for.
 struct QItem {
   bool valid;        // false: padding (levels are padded to whole waves); the row works on zeros and stores nothing
@@ -1602,7 +1602,7 @@ __device__ __forceinline__ void recon_intra_quad(const MobiReconArgs &A, uint32_
   }
 }
 
-// Launch list built on the host (mobi_abi.cpp, LevelPlan): 16 bytes per intra macroblock, sorted by dependency level, every level
+// Launch list built on the host (mobi_batch.h, LevelPlan): 16 bytes per intra macroblock, sorted by dependency level, every level
 // padded to a whole number of waves with null items (x = ~0).
 //   x = clip << 13 | mb   y = MbDesc.w1   z = MbDesc.payload_off (inside this step's arena)
 //   w = [0] 16x16 plane present  [1] has intra dependencies  [2] has intra dependents  [3] unused (r02: the left neighbour's last
@@ -1622,7 +1622,7 @@ extern "C" __global__ __launch_bounds__(64) void mobi_recon_intra(MobiReconArgs 
 // ASSUMPTION: workgroups start in blockIdx order per XCD, so every octet workgroup holds a wave slot before an intra four that
 // waits for it can fill the chip.  HIP does not promise that order; the hardware dispatcher has always kept it.  Should a driver change it,
 // the waits do not hang: a four gives up after 2^21 polls and sets fault bit 2 -- and mobi_batch_decode then runs the SAME step again as
-// two launches (mobi_abi.cpp, launch_plan's retry), which need no order at all.  The padding tiles behind a picture's last macroblock are
+// two launches (mobi_step_host.cpp, the retry behind launch_plan), which need no order at all.  The padding tiles behind a picture's last macroblock are
 // not rewritten here (the two-launch octet kernel stores zeros there): they hold the zeros mobi_batch_create cleared the arena with.  Two launches cost a kernel boundary (the second waits until the first has drained, then starts cold) -- at 8 clips per
 // GPU (BASELINE config 4) that boundary is a fifth of the step; here an intra macroblock starts as soon as the inter macroblocks its halo
 // reads carry the step's tag.  Inter workgroups never wait and are dispatched first, so the waits cannot deadlock.
@@ -1697,7 +1697,7 @@ extern "C" __global__ __launch_bounds__(64) void mobi_recon_intra_walk(MobiRecon
 }
 
 // =====================================================================================================
-// launch wrappers (called from mobi_abi.cpp)
+// launch wrappers (called from the C-ABI layer: mobi_batch.h)
 // =====================================================================================================
 // Untile one frame: lin = the reference's Y[stride * height] followed by UV[stride * height / 2] (MD.cs:107-108, 414-415).  One lane = 8
 // bytes of a plane row (an 8-aligned run never leaves a quadrant row / one plane's half of a chroma tile row).

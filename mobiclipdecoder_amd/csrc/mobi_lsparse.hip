@@ -3,7 +3,7 @@
 //
 //   mobi_parse_frames_ls   one wave = `ls_clips` clips (the other lanes idle), four or eight waves per workgroup (mobi_launch_parse_ls).  Every lane walks its own frame with
 //                          ls_round(); the wave runs until the last one is done.  A lane that meets anything out of the ordinary bails out and
-//                          leaves its clip to mobi_parse_frames (which, r05, leaves what it cannot finish to the host parser: mobi_abi.cpp).
+//                          leaves its clip to mobi_parse_frames (which, r05, leaves what it cannot finish to the host parser: mobi_step_device.cpp).
 //   mobi_ls_deps           one lane per intra macroblock of the clips the first kernel finished: the dependency lists (MbDesc.w4..w7).
 //   mobi_parse_frames      (mobi_dparse.hip) runs afterwards, one wave per clip as always: a finished clip's wave only moves the new decoder
 //                          state from its shadow copy into place; every other clip is parsed as if the first kernel had not run.

@@ -22,7 +22,7 @@ struct ParsedFrame {
   std::vector<uint32_t> payload;
   std::vector<uint32_t> intra_mbs;   // MB indices, grouped by level (ascending), by class inside a level (class_start), raster order inside a class
   std::vector<uint32_t> level_start; // size n_levels+2: intra_mbs[level_start[L] .. level_start[L+1]) for L = 1..n_levels
-  // The same macroblocks as launch items (mobi_recon_intra; LevelPlan in mobi_abi.cpp), four words each, in the order of intra_mbs:
+  // The same macroblocks as launch items (mobi_recon_intra; LevelPlan in mobi_batch.h), four words each, in the order of intra_mbs:
   //   [0] mb   [1] MbDesc.w1   [2] MbDesc.payload_off (inside this clip's payload)   [3] flags: [0] 16x16 plane present, [1] has intra
   //   dependencies, [2] has intra dependents, [3] at the picture's left / right / top edge, [14:5] level words, [31:16] plane parameter.
   // Written by the parser while the descriptors are in its cache: the step's launch list is then a concatenation, not 60 random
@@ -80,12 +80,12 @@ class MobiStreamParser {
   int parse_frame(const uint8_t *data, size_t len, int32_t *offset, ParsedFrame &out);
 
   // The decoder state that survives a frame, as the device parsers keep it (mobi_state.h): a clip whose frame the device parser could not
-  // finish is parsed again here from the state it had when that frame started, and stays with this parser from then on (mobi_abi.cpp).
+  // finish is parsed again here from the state it had when that frame started, and stays with this parser from then on (mobi_step_device.cpp).
   void import_state(const MobiDevState &st, const MobiDevTail &tail);
   void export_state(MobiDevState &st, MobiDevTail &tail);
   uint32_t internal_word(uint32_t idx); // Internal[idx] as the reference holds it between frames, 10 <= idx < 392 (tests: against the oracle's)
   // The last frame was one the device parsers would have finished too (no walk, no token without a level, no value beyond their fields),
-  // and nothing a walk once wrote behind the MV row cache is left: the clip may go back to the device parsers (mobi_abi.cpp, dp_return).
+  // and nothing a walk once wrote behind the MV row cache is left: the clip may go back to the device parsers (mobi_step_device.cpp, dp_return).
   bool device_ready() const;
 
   uint32_t quantizer() const { return quant_; }

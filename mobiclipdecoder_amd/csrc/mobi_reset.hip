@@ -1,6 +1,6 @@
 // mobi_reset.hip -- new MobiclipDecoder(Width, Height, Version) (MD.cs:41-54) for a list of clips of a batch, on the device side: the decoder
 // state a fresh decoder starts from is all zero (dp_init memsets the state ring), so a reset writes zero MobiDevState and MobiDevTail records
-// (64 + 1056 bytes per clip) into the state ring entry the next parse reads (mobi_batch_reset_clips, mobi_abi.cpp).  One wave per clip, 70
+// (64 + 1056 bytes per clip) into the state ring entry the next parse reads (mobi_batch_reset_clips, mobi_batch.cpp).  One wave per clip, 70
 // 16-byte vector stores per clip over 64 lanes; the list is unique (the host removes duplicates) and every index is below n_clips.
 #include <hip/hip_runtime.h>
 

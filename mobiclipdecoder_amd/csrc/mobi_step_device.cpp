@@ -1,0 +1,659 @@
+// mobi_step_device.cpp -- device-parsed frame steps: behind mobi_batch_decode, mobi_batch_submit / mobi_batch_wait, and what the groups share with them
+#include "mobi_batch.h"
+
+// DecodeFrame() of every clip with the bitstream parse on the GPU: upload Data[Offset..) of every clip, one parse launch
+// (one wave per clip) that leaves descriptors, payload and intra lists in HBM, then the usual reconstruction launches.
+//
+// r05: WHICH side parses never shows in the result.  The device parsers finish the frames that decode without incident.  A frame they
+// cannot finish -- every condition under which the reference throws, every walk through Internal[] (MD.cs:3424-3429), every value the
+// command list has to escape (mobi_parse.cpp) -- is parsed again by the host parser INSIDE THE SAME CALL, from the decoder state the clip
+// had when the frame started (the device keeps a ring of three states per clip: mobi_dparse.h, mobi_state.h), and its command list is
+// written over the blank one the parse kernel left.  rc, Offset, Quantizer and the planes are then the host parser's, i.e. the same as
+// at any other batch size; the clip stays with the host parser from there on (`on_host`), parsed beside the GPU's clips like the
+// host-parsed share of the hybrid mode, which is the same mechanism with the last clips of the batch marked from the start.
+//
+// first use of the device-side parser: zeroed decoder state (a new MobiclipDecoder), result array, tables -- all of it or none of it
+int dp_init(mobi_batch *b) {
+  const int n = b->n;
+  if (b->d_pstate[0]) return MOBI_OK;
+  auto init = [&]() -> int {
+    if (int e = b->d_pres.alloc(n)) return e;
+    HIP_TRY(hipMemset(b->d_pres, 0, sizeof(MobiDevResult) * n));
+    std::vector<uint8_t> blob(MOBI_DT_BYTES);
+    mobi_dparse_build_tables(b->version, blob.data());
+    if (int e = b->d_ptables.alloc(MOBI_DT_BYTES)) return e;
+    HIP_TRY(hipMemcpy(b->d_ptables, blob.data(), MOBI_DT_BYTES, hipMemcpyHostToDevice));
+    if (int e = b->h_pres.reserve(sizeof(MobiDevResult) * n)) return e;
+    if (int e = b->d_pstate_ls.alloc(n)) return e;
+    for (int k = 0; k < 3; k++) {
+      if (int e = b->d_ptail[k].alloc(n)) return e;
+      HIP_TRY(hipMemset(b->d_ptail[k], 0, sizeof(MobiDevTail) * n));
+    }
+    for (int k = 2; k >= 0; k--) { // entry 0 last: its presence means "initialised"
+      if (int e = b->d_pstate[k].alloc(n)) return e;
+      HIP_TRY(hipMemset(b->d_pstate[k], 0, sizeof(MobiDevState) * n));
+    }
+    return MOBI_OK;
+  };
+  if (int e = init()) {
+    b->d_pres.free(); b->d_ptables.free(); b->d_pstate_ls.free();
+    for (int k = 0; k < 3; k++) { b->d_pstate[k].free(); b->d_ptail[k].free(); }
+    return e;
+  }
+  b->dev_quant.assign(n, 0);
+  b->dev_yuvfmt.assign(n, 0);
+  if ((int)b->on_host.size() != n) b->on_host.assign(n, 0);
+  b->host_share.assign(n, 0);
+  b->clean_run.assign(n, 0);
+  b->clean_need.assign(n, 4);
+  return MOBI_OK;
+}
+// Which device parser is in front of this step (parse mode by default, r05; tools/exp_lsab.sh, tools/exp_dparse.py, 640x480, ms per step,
+// mobi_parse_frames against the lock-step parser at its best number of clips per wave):
+//   P-frames: 2048 clips 8.8 / 9.2, 4096: 11.2 / 13.7, 8192: 21.2 / 18.5, 16384: 42 / 23.5, 24576: 63 / 26.2
+//   I-frames: 1024 clips 23.4 / 11.7, 2048: 30.0 / 11.3, 4096: 30.0 / 16.5, 8192: 54.9 / 23.6
+// -- one wave per clip wins while every clip has a wave slot of its own and the frames are P-frames; an I-frame's macroblocks are all of one
+// kind, which is what lanes in lock step like.
+bool ls_decide(const mobi_batch *b, const DpStaged &st) {
+  if (b->ls_policy != 2) return b->ls_policy == 1;
+  const bool iframe_step = 2 * st.n_iframes > st.n_dev;
+  return st.n_dev >= 5120 || (iframe_step && st.n_dev >= 768);
+}
+// stage [bit_off u64 x n][bit_len u32 x n][bits: each clip 8-byte aligned, zero padded] into pinned memory; the host parser's clips
+// (b->on_host) carry MOBI_DP_SKIP for a length and no bits
+// dev != nullptr: the image is also sent to *dev on `up`, chunk by chunk while the next chunk is gathered (one thread of the pool sits in
+// the copy calls, which return when the bus is done: 8 ms for the 370 MB of a step of 24576 clips; the others gather) -- r04: gathering and
+// sending were 12 of the 45 ms of such a step, one after the other.
+// resets != nullptr: these clip indices (int32) ride behind the bits, for mobi_reset_state
+static int dp_stage(mobi_batch *b, const uint8_t *const *data, const size_t *len, const int32_t *offsets, PinnedBuf &stage, DpStaged &st,
+                    DevBuf *dev = nullptr, bool dev_headroom = false, hipStream_t up = nullptr, const std::vector<int32_t> *resets = nullptr) {
+  const int n = b->n, nd = n, n_mbs = b->g.mbw * b->g.mbh;
+  const auto t_stage0 = std::chrono::steady_clock::now();
+  constexpr size_t kBitPad = 32; // the reader runs two 8-byte registers ahead
+  std::vector<uint64_t> boff(nd);
+  std::vector<uint32_t> blen(nd);
+  size_t pos = 0, max_len = 0;
+  const size_t frame_bound = (size_t)n_mbs * 4096 + 64;
+  for (int i = 0; i < n; i++) {
+    const int64_t o = offsets[i];
+    size_t l = (data[i] && o >= 0 && (uint64_t)o < len[i]) ? len[i] - (size_t)o : 0; // nothing readable: the first ReadU16LE throws
+    // MOC5 callers pass the whole file as Data (Form1.cs:292-302).  The reader advances two bytes per refill and refills at most
+    // once per syntax element: <= ~1450 refills per macroblock (127 partition nodes, 384 levels of up to three reads each), so
+    // bytes beyond 4 KB per macroblock cannot influence the parse of this frame
+    l = std::min(l, frame_bound);
+    max_len = std::max(max_len, l); // (the host parser's clips too: their share of the payload bound counts)
+    boff[i] = pos;
+    if (b->on_host[i]) { blen[i] = MOBI_DP_SKIP; continue; }
+    blen[i] = (uint32_t)l;
+    pos += align_up(l + kBitPad, 8);
+    st.n_dev++;
+    st.n_iframes += l >= 2 && (data[i][o + 1] & 0x80) != 0; // the frame's first bit: the top bit of its first 16-bit little-endian word (MD.cs:110-113)
+  }
+  pos += 64; // (a skipped clip's offset points at readable bytes too)
+  const size_t list_pos = pos, n_reset = resets ? resets->size() : 0;
+  pos += align_up(n_reset * 4, 16);
+  const size_t hdr_bytes = align_up((size_t)nd * 12, 16);
+  if (hdr_bytes + pos > stage.cap) // pinned memory is slow to allocate: leave room for the longer frames to come
+    if (int e = stage.reserve(hdr_bytes + pos + (hdr_bytes + pos) / 4)) return e;
+  uint8_t *hs = stage.p;
+  memcpy(hs, boff.data(), (size_t)nd * 8);
+  memcpy(hs + (size_t)nd * 8, blen.data(), (size_t)nd * 4);
+  memset(hs + hdr_bytes + list_pos - 64, 0, 64);
+  if (n_reset) memcpy(hs + hdr_bytes + list_pos, resets->data(), n_reset * 4);
+  st.reset_off = hdr_bytes + list_pos;
+  st.n_reset = (int)n_reset;
+  auto gather = [&](int i) {
+    if (blen[i] == MOBI_DP_SKIP) return;
+    uint8_t *dst = hs + hdr_bytes + boff[i];
+    if (blen[i]) memcpy(dst, data[i] + offsets[i], blen[i]);
+    memset(dst + blen[i], 0, align_up(blen[i] + kBitPad, 8) - blen[i]);
+  };
+  constexpr int kRun = 32; // frames per pool task (one per frame has the pool's threads queue at its counter: gop_begin measured it)
+  if (!dev) {
+    b->pool->run((nd + kRun - 1) / kRun, [&](int j) { for (int i = j * kRun, e = std::min(nd, i + kRun); i < e; i++) gather(i); });
+  } else {
+    const size_t need = hdr_bytes + pos;
+    if (need > dev->cap) // growing frees and allocates (a device-wide stall): asynchronous steps leave room for the longer frames to come
+      if (int e = dev->reserve(dev_headroom ? need + need / 4 : need)) return e;
+    const int chunks = nd >= 2048 ? 4 : 1;
+    std::atomic<int> up_err{0};
+    auto end_of = [&](int c1) { return c1 < nd ? hdr_bytes + (size_t)boff[c1] : need; }; // byte offset where clip c1's bits start
+    for (int k = 0; k <= chunks; k++) {
+      const int c0 = k < chunks ? (int)((long)nd * k / chunks) : nd, c1 = k < chunks ? (int)((long)nd * (k + 1) / chunks) : nd;
+      const int u0 = k >= 1 ? (int)((long)nd * (k - 1) / chunks) : 0, u1 = k >= 1 ? (int)((long)nd * k / chunks) : 0; // gathered in the round before
+      const int n_up = u1 > u0 ? 1 : 0;
+      if (n_up + (c1 - c0) == 0) continue;
+      b->pool->run(n_up + (c1 - c0 + kRun - 1) / kRun, [&](int j) {
+        if (j < n_up) {
+          const size_t a = u0 == 0 ? 0 : end_of(u0), e = end_of(u1); // (the first chunk takes the header along)
+          if (e > a && (hipSetDevice(b->device) != hipSuccess || hipMemcpyAsync(dev->p + a, hs + a, e - a, hipMemcpyHostToDevice, up) != hipSuccess)) up_err = 1;
+          return;
+        }
+        for (int i = c0 + (j - n_up) * kRun, e = std::min(c1, i + kRun); i < e; i++) gather(i);
+      });
+    }
+    if (up_err) return MOBI_E_DEVICE;
+  }
+  b->last_stage_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_stage0).count();
+  st.hdr_bytes = hdr_bytes;
+  st.bytes = hdr_bytes + pos;
+  st.max_len = max_len;
+  return MOBI_OK;
+}
+// output buffers + the parse launch.  A clip's payload can never exceed 448 words per macroblock, nor 64 per macroblock + one level
+// per THREE bits read (a level word stands for a token with a level, and the shortest of those -- either table, either version -- has two
+// bits and a sign: mobi_dparse_build_tables; tests/test_parse_fallback.py checks the tables for it).  `busy`: earlier steps may still be using the buffers (asynchronous steps): drain the stream before growing one.
+// *state_in: which entry of the state ring the step reads (the state its frames start from).
+struct DpOut { DevBuf *desc, *pay, *items; MobiDevResult *res; hipStream_t stream; bool async = false; };
+static int dp_parse(mobi_batch *b, const uint8_t *d_bits, const DpStaged &st, bool busy, const DpOut &o, int *state_in) {
+  const int n = b->n, n_mbs = b->g.mbw * b->g.mbh;
+  // (the longest frame of a step varies from step to step: the bound follows it upwards in steps of a quarter, so that the payload
+  // arena -- gigabytes for thousands of clips -- is not freed and allocated again every few frames)
+  if (st.max_len > b->dp_len_hint) b->dp_len_hint = st.max_len + st.max_len / 4;
+  const size_t cap_words = std::min<size_t>((size_t)n_mbs * 448 + MOBI_WIDE_PARAMS, (size_t)n_mbs * 64 + (8 * b->dp_len_hint + 2) / 3) + 448 + 64;
+  // MbDesc.payload_off is relative to the clip's own part of the arena, which may then be as large as HBM lets it (24576 clips of
+  // 640x480 need 13 G words for an I-frame); the host parser's clips write into their own parts like everybody else (dp_override)
+  b->pay_clip_words = (uint32_t)cap_words;
+  const size_t want_desc = align_up((size_t)n * n_mbs * sizeof(MbDesc) + 8 * sizeof(MbDesc), kAlign), want_pay = align_up((size_t)n * cap_words * 4 + kPaySlack, kAlign),
+               want_items = (size_t)n * n_mbs * 4;
+  if (busy && (want_desc > (*o.desc).cap || want_pay > (*o.pay).cap || want_items > (*o.items).cap)) HIP_TRY(hipStreamSynchronize(o.stream));
+  if (int e = (*o.desc).reserve(want_desc)) return e;
+  if (int e = (*o.pay).reserve(want_pay)) return e;
+  if (int e = (*o.items).reserve(want_items)) return e;
+  MobiDevParseArgs pa;
+  memset(&pa, 0, sizeof(pa));
+  pa.bits = d_bits + st.hdr_bytes;
+  pa.bit_off = (const uint64_t *)d_bits;
+  pa.bit_len = (const uint32_t *)(d_bits + (size_t)n * 8);
+  pa.tables = b->d_ptables;
+  const int in = b->ps_cur, out = (b->ps_cur + 1) % 3;
+  pa.state_in = b->d_pstate[in]; pa.state_out = b->d_pstate[out];
+  pa.tail_in = b->d_ptail[in]; pa.tail_out = b->d_ptail[out];
+  pa.scale = b->d_scale;
+  pa.state_ls = b->d_pstate_ls;
+  pa.lockstep = b->lockstep ? (o.async ? 2 : 1) : 0; // (2: an asynchronous step; the launch has had one shape for both since r05: mobi_launch_parse_ls)
+  pa.pay_local = 1;
+  pa.desc = (MbDesc *)(*o.desc).p;
+  pa.payload = (uint32_t *)(*o.pay).p;
+  pa.items = (uint32_t *)(*o.items).p;
+  pa.res = o.res;
+  pa.pay_cap = (uint32_t)cap_words;
+  b->last_pay_cap = cap_words;
+  pa.n_clips = n; pa.version = b->version;
+  pa.width = b->g.width; pa.height = b->g.height; pa.stride = b->g.stride; pa.lg = b->g.lg; pa.mbw = b->g.mbw; pa.mbh = b->g.mbh;
+  if (b->ktiming && !b->ev_p0) { (void)hipEventCreate(&b->ev_p0.h); (void)hipEventCreate(&b->ev_p1.h); }
+  const bool ptime = b->ktiming && b->ev_p0 && b->ev_p1;
+  if (ptime) (void)hipEventRecord(b->ev_p0, o.stream);
+  if (mobi_launch_parse(&pa, o.stream) != 0) return MOBI_E_DEVICE;
+  if (ptime) (void)hipEventRecord(b->ev_p1, o.stream);
+  b->ps_cur = out;
+  *state_in = in;
+  return MOBI_OK;
+}
+
+// The command lists of host-parsed clips of a device-parsed step (`clips`, ascending; b->cur[c] holds clip c's frame when rc[c] is MOBI_OK):
+// staged in pinned memory and copied into the clips' own rows of what the parse kernels leave -- descriptor rows, payload parts, item
+// rows, result records -- on stream s.  Runs of neighbouring clips (the hybrid mode's share) go as one copy per table.
+// frames != nullptr: frames[j] is clips[j]'s parsed frame (nullptr: it failed) and rcs[j] its rc -- both by POSITION in `clips` (the
+// frame-parallel path: a clip has K frames); else b->cur[c] and rc[c] by clip.
+int dp_override(mobi_batch *b, const std::vector<int> &clips, const int *rc, PinnedBuf &stage, const DpRows &d, hipStream_t s,
+                const ParsedFrame *const *frames, const int *rcs) {
+  const int k = (int)clips.size(), n_mbs = b->g.mbw * b->g.mbh;
+  if (k == 0) return MOBI_OK;
+  auto frame_of = [&](int j) -> const ParsedFrame * { return frames ? frames[j] : (rc[clips[j]] == MOBI_OK ? &b->cur[clips[j]] : nullptr); };
+  auto rc_of = [&](int j) { return frames ? rcs[j] : rc[clips[j]]; };
+  size_t pitch_w = 0; // payload words per clip in the staging area
+  for (int j = 0; j < k; j++)
+    if (const ParsedFrame *f = frame_of(j)) pitch_w = std::max(pitch_w, f->payload.size());
+  pitch_w = align_up(pitch_w + 4, 4);
+  if (pitch_w > d.cap_words) return MOBI_E_DEVICE; // cannot happen: cap_words bounds any clip's payload
+  const size_t desc_b = (size_t)n_mbs * sizeof(MbDesc), item_b = (size_t)n_mbs * 4, res_b = sizeof(MobiDevResult), pay_b = pitch_w * 4;
+  const size_t o_item = align_up((size_t)k * desc_b, 16), o_res = o_item + align_up((size_t)k * item_b, 16), o_pay = o_res + align_up((size_t)k * res_b, 16);
+  if (int e = stage.reserve(o_pay + (size_t)k * pay_b)) return e;
+  uint8_t *h = stage.p;
+  const int groups = std::min(k, 32);
+  b->pool->run(groups, [&](int g) {
+    for (int j = (int)((long)k * g / groups), e = (int)((long)k * (g + 1) / groups); j < e; j++) {
+      const ParsedFrame *f = frame_of(j);
+      MbDesc *dd = (MbDesc *)(h + (size_t)j * desc_b);
+      uint32_t *it = (uint32_t *)(h + o_item + (size_t)j * item_b);
+      MobiDevResult *rr = (MobiDevResult *)(h + o_res + (size_t)j * res_b);
+      memset(rr, 0, sizeof(*rr));
+      rr->rc = rc_of(j);
+      if (!f) { // a failed clip: descriptors typed "intra" that no launch list references
+        for (int m = 0; m < n_mbs; m++) dd[m] = MbDesc{0, MOBI_MB_INTRA, 0, 0, 0, 0, 0, 0};
+        continue;
+      }
+      memcpy(dd, f->desc.data(), desc_b); // (payload_off counts from the clip's own part of the arena, as the parser wrote it)
+      if (!f->payload.empty()) memcpy(h + o_pay + (size_t)j * pay_b, f->payload.data(), f->payload.size() * 4);
+      if (!f->intra_mbs.empty()) memcpy(it, f->intra_mbs.data(), f->intra_mbs.size() * 4); // level order: a valid order for the waits
+      rr->n_intra = f->hdr.n_intra;
+      rr->payload_words = f->hdr.payload_words;
+      rr->quant = f->hdr.quantizer;
+      rr->frame_type = f->hdr.frame_type;
+    }
+  });
+  for (int j0 = 0; j0 < k;) {
+    int j1 = j0 + 1;
+    while (j1 < k && clips[j1] == clips[j1 - 1] + 1) j1++;
+    const size_t c0 = (size_t)clips[j0], run = (size_t)(j1 - j0);
+    HIP_TRY(hipMemcpyAsync(d.desc + c0 * desc_b, h + (size_t)j0 * desc_b, run * desc_b, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d.items + c0 * item_b, h + o_item + (size_t)j0 * item_b, run * item_b, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync((uint8_t *)(d.res + c0), h + o_res + (size_t)j0 * res_b, run * res_b, hipMemcpyHostToDevice, s));
+    if (run == 1) HIP_TRY(hipMemcpyAsync(d.pay + c0 * d.cap_words * 4, h + o_pay + (size_t)j0 * pay_b, pay_b, hipMemcpyHostToDevice, s));
+    else HIP_TRY(hipMemcpy2DAsync(d.pay + c0 * d.cap_words * 4, d.cap_words * 4, h + o_pay + (size_t)j0 * pay_b, pay_b, pay_b, run, hipMemcpyHostToDevice, s));
+    j0 = j1;
+  }
+  return MOBI_OK;
+}
+// the decoder state the clips of `cl` had when the step that read ring entry `in` started, into their host parsers: two asynchronous copies per
+// clip into pinned memory, ONE wait, the imports on the pool (r05 issued two blocking copies per clip: a step in which every clip of a large
+// batch is handed over at once -- a ModsDS batch that cuts to a quantiser below 12 -- sat in tens of thousands of them)
+// (into b->parsers, or into ps[j] for clip cl[j] when ps is given: a repair of a stream a reset has ended, mobi_batch::parser_at)
+static int dp_seed_parsers(mobi_batch *b, const std::vector<int> &cl, int in, PinnedBuf &stage, hipStream_t s, const std::vector<MobiStreamParser *> *ps = nullptr) {
+  if (cl.empty()) return MOBI_OK;
+  const size_t rec = sizeof(MobiDevState) + sizeof(MobiDevTail);
+  if (int e = stage.reserve(cl.size() * rec)) return e;
+  for (size_t j = 0; j < cl.size(); j++) {
+    HIP_TRY(hipMemcpyAsync(stage.p + j * rec, b->d_pstate[in] + cl[j], sizeof(MobiDevState), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(stage.p + j * rec + sizeof(MobiDevState), b->d_ptail[in] + cl[j], sizeof(MobiDevTail), hipMemcpyDeviceToHost, s));
+  }
+  HIP_TRY(hipStreamSynchronize(s));
+  b->pool->run((int)cl.size(), [&](int j) {
+    MobiStreamParser *p = ps ? (*ps)[j] : b->parsers[cl[j]].get();
+    p->import_state(*(const MobiDevState *)(stage.p + (size_t)j * rec), *(const MobiDevTail *)(stage.p + (size_t)j * rec + sizeof(MobiDevState)));
+  });
+  return MOBI_OK;
+}
+
+// A clip the host parser took over goes BACK to the device parsers once its frames are again the kind they finish: `clean_need`
+// consecutive frames without a walk, a token without a level or a value beyond the device parsers' fields (MobiStreamParser::device_ready),
+// doubled with every hand-over (4, 8, ... 256: a clip whose every frame needs the host parser -- a ModsDS stream below quantiser 12 -- costs
+// a wasted device parse every few hundred frames, a glitch in an otherwise clean stream a handful of host-parsed frames).  The parser's state
+// goes into entry `entry` of the state ring -- the one the next step's parse reads -- on stream s, through `stage`.
+static int dp_return(mobi_batch *b, const std::vector<int> &host_clips, const int *rc, int entry, PinnedBuf &stage, hipStream_t s) {
+  std::vector<int> back;
+  for (int c : host_clips) {
+    if (b->host_share[c]) continue;
+    if (rc[c] == MOBI_OK && b->parsers[c]->device_ready()) b->clean_run[c]++;
+    else b->clean_run[c] = 0;
+    if (b->clean_run[c] >= b->clean_need[c]) back.push_back(c);
+  }
+  return dp_return_list(b, back, entry, stage, s);
+}
+int dp_return_list(mobi_batch *b, const std::vector<int> &back, int entry, PinnedBuf &stage, hipStream_t s) {
+  if (back.empty()) return MOBI_OK;
+  const size_t rec = sizeof(MobiDevState) + sizeof(MobiDevTail);
+  if (int e = stage.reserve(back.size() * rec)) return e;
+  for (size_t k = 0; k < back.size(); k++) {
+    const int c = back[k];
+    MobiDevState *st = (MobiDevState *)(stage.p + k * rec);
+    MobiDevTail *tail = (MobiDevTail *)(stage.p + k * rec + sizeof(MobiDevState));
+    b->parsers[c]->export_state(*st, *tail);
+    HIP_TRY(hipMemcpyAsync(b->d_pstate[entry] + c, st, sizeof(*st), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(b->d_ptail[entry] + c, tail, sizeof(*tail), hipMemcpyHostToDevice, s));
+    b->on_host[c] = 0;
+    b->clean_run[c] = 0;
+    b->returns++;
+  }
+  return MOBI_OK;
+}
+
+int decode_device_parse(mobi_batch *b, const uint8_t *const *data, const size_t *len, int32_t *offsets, int *rc) {
+  const int n = b->n;
+  if (!b->version_known()) {
+    for (int i = 0; i < n; i++) rc[i] = MOBI_E_VERSION;
+    return MOBI_OK; // DecodeFrame() returns before touching the ring (MD.cs:56-61)
+  }
+  if (b->g.mbw > 64 || b->async_count || b->gop_count) return MOBI_E_ARG; // (asynchronous steps / groups in flight: wait for them first)
+  const bool dev_state = b->d_pstate[0] != nullptr; // (before dp_init there is nothing on the device to reset)
+  if (int e = dp_init(b)) return e;
+  b->mark_hybrid_share();
+  const uint64_t serial = b->handover + 1;
+  reset_apply_host(b, serial);
+  const std::vector<int32_t> *resets = dev_state && !b->reset_list.empty() ? &b->reset_list : nullptr;
+  std::vector<int> host_clips;
+  for (int i = 0; i < n; i++)
+    if (b->on_host[i]) host_clips.push_back(i);
+  DpStaged st;
+  using clk = std::chrono::steady_clock;
+  const auto q0 = clk::now();
+  if (int e = dp_stage(b, data, len, offsets, b->h_stage, st, &b->d_bits, false, b->stream, resets)) return e; // gathered and on their way
+  b->phase_ms[0] = ms_since(q0);
+  b->lockstep = ls_decide(b, st);
+  if (st.n_reset && mobi_launch_reset_state((const int32_t *)(b->d_bits.p + st.reset_off), st.n_reset, n, b->d_pstate[b->ps_cur], b->d_ptail[b->ps_cur], b->stream) != 0)
+    return MOBI_E_DEVICE;
+  int state_in = 0;
+  if (int e = dp_parse(b, b->d_bits.p, st, false, DpOut{&b->d_pdesc, &b->d_ppay, &b->d_pitems, b->d_pres, b->stream}, &state_in)) return e;
+  reset_commit(b, serial);
+  b->phase_ms[1] = ms_since(q0);
+  const size_t cap_words = b->last_pay_cap;
+  const DpRows rows{b->d_pdesc.p, b->d_ppay.p, b->d_pitems.p, b->d_pres, cap_words};
+  const bool ptime = b->ktiming && b->ev_p0 && b->ev_p1;
+  MobiDevResult *res = (MobiDevResult *)b->h_pres.p;
+  HIP_TRY(hipMemcpyAsync(res, b->d_pres, sizeof(MobiDevResult) * n, hipMemcpyDeviceToHost, b->stream));
+  auto host_parse = [&](const std::vector<int> &cl) {
+    b->pool->run((int)cl.size(), [&](int j) { const int i = cl[j]; rc[i] = parse_host(b->parsers[i].get(), data[i], len[i], &offsets[i], b->cur[i]); });
+  };
+  if (!host_clips.empty()) { // while the GPU parses its clips, the host pool parses its own and sends their command lists up beside it
+    if (int e = ensure_stream(b->stream2)) return e;
+    if (int e = ensure_event(b->ev_up)) return e;
+    host_parse(host_clips);
+    if (int e = dp_override(b, host_clips, rc, b->h_stage2, rows, b->stream2)) return e; // (no kernel touches these clips' rows: MOBI_DP_SKIP)
+    HIP_TRY(hipEventRecord(b->ev_up, b->stream2));
+    HIP_TRY(hipStreamWaitEvent(b->stream, b->ev_up, 0));
+    HIP_TRY(hipStreamSynchronize(b->stream2));
+  }
+  HIP_TRY(hipStreamSynchronize(b->stream)); // the launch sizes below depend on what the parse found
+  b->phase_ms[2] = ms_since(q0);
+  if (ptime) { float ms = 0; if (hipEventElapsedTime(&ms, b->ev_p0, b->ev_p1) == hipSuccess) b->last_parse_ms = ms; }
+  // frames the device parsers could not finish: the host parser takes them over from the state they started with
+  std::vector<int> fb;
+  for (int i = 0; i < n; i++)
+    if (!b->on_host[i] && res[i].rc != MOBI_OK) fb.push_back(i);
+  if (!fb.empty()) {
+    if (int e = dp_seed_parsers(b, fb, state_in, b->h_ret, b->stream)) return e; // (the stream is idle: it was waited for above)
+    host_parse(fb);
+    for (int c : fb) {
+      b->route_to_host(c);
+      host_clips.push_back(c);
+    }
+    b->fallbacks += fb.size();
+    if (int e = dp_override(b, fb, rc, b->h_stage2, rows, b->stream)) return e; // (behind the parse kernels, which blanked these clips' rows)
+  }
+  uint32_t K = 0;
+  b->ls_finished = b->lockstep ? 0 : -1;
+  for (int i = 0; i < n; i++) {
+    if (b->on_host[i]) {
+      b->dev_quant[i] = b->parsers[i]->quantizer();
+      b->dev_yuvfmt[i] = b->parsers[i]->yuv_format();
+      if (rc[i] == MOBI_OK) K = std::max(K, b->cur[i].hdr.n_intra);
+      continue;
+    }
+    if (b->lockstep && res[i].pad == MOBI_LS_MAGIC) b->ls_finished++;
+    rc[i] = res[i].rc;
+    offsets[i] += res[i].consumed;
+    b->dev_quant[i] = res[i].quant;
+    b->dev_yuvfmt[i] = res[i].yuvfmt;
+    K = std::max(K, res[i].n_intra);
+  }
+  // 3. reconstruction straight from what the parse left in HBM
+  FailAll fail_all{rc, n, b->stream}; // rc[], Offset, the ring and the decoder state have advanced: the launches below must complete
+  if (int e = b->begin_step()) return e;
+  MobiReconArgs a = b->args(b->d_pdesc.p, b->d_ppay.p);
+  a.pay_clip_words = b->pay_clip_words;
+  a.done = b->d_done;
+  if (mobi_launch_inter(&a, b->stream) != 0) return MOBI_E_DEVICE;
+  if (K && mobi_launch_intra_cl(&a, (const uint32_t *)b->d_pitems.p, &b->d_pres[0].n_intra, (int)(sizeof(MobiDevResult) / 4), (int)K, 0, b->stream) != 0)
+    return MOBI_E_DEVICE;
+  if (int e = b->read_faults(b->h_fault.data())) return e;
+  if (!host_clips.empty())
+    if (int e = dp_return(b, host_clips, rc, b->ps_cur, b->h_ret, b->stream)) return e; // (ps_cur: what the next step's parse reads)
+  b->phase_ms[3] = ms_since(q0);
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  b->phase_ms[4] = ms_since(q0);
+  fail_all.armed = false;
+  for (int i = 0; i < n; i++) rc[i] = fault_rc(rc[i], b->h_fault[i]);
+  return MOBI_OK;
+}
+
+// Frames of SOME clips through the reconstruction kernels on their own, into the ring slot `ring_base` names: the repair of clips whose
+// asynchronous step had been enqueued before anybody knew that their frame was not the device parser's to finish (mobi_batch_wait).
+// `clips` ascending, frames[j] = clips[j]'s parsed frame (nullptr: the host parser rejected it: nothing is written).  Neighbouring clips
+// form a run, and a run is one compact frame step of its own -- its descriptor table, its payload arena, its launch items, planes and
+// tags offset to its first clip -- so "every clip of the batch at once" is ONE set of launches and a lone glitch a set of its own.  One
+// upload, one read-back of the fault words, one wait for the lot (r05: a parse, an upload, launches and a wait PER CLIP, on the calling thread).
+static int recon_clips(mobi_batch *b, const std::vector<int> &clips, const ParsedFrame *const *frames, int ring_base, int *fault_out) {
+  const int n_mbs = b->g.mbw * b->g.mbh, k = (int)clips.size();
+  if (k == 0) return MOBI_OK;
+  struct Run { int j0, j1; size_t desc_off, pay_off, item_off; LevelPlan plan; };
+  std::vector<Run> runs;
+  size_t total = 0;
+  for (int j0 = 0; j0 < k;) {
+    int j1 = j0 + 1;
+    while (j1 < k && clips[j1] == clips[j1 - 1] + 1) j1++;
+    Run r;
+    r.j0 = j0; r.j1 = j1;
+    std::vector<const ParsedFrame *> fr(frames + j0, frames + j1);
+    r.plan.build(fr, b->g.mbw);
+    const size_t desc_bytes = align_up((size_t)(j1 - j0) * n_mbs * sizeof(MbDesc) + 8 * sizeof(MbDesc), kAlign), pay_bytes = align_up(step_payload_words(fr) * 4 + kPaySlack, kAlign);
+    if (step_payload_words(fr) + kPaySlack / 4 >= ((uint64_t)1 << 32)) return MOBI_E_ARG;
+    r.desc_off = total; r.pay_off = total + desc_bytes; r.item_off = r.pay_off + pay_bytes;
+    total = r.item_off + align_up(r.plan.items.size() * 4 + 16, kAlign);
+    runs.push_back(std::move(r));
+    j0 = j1;
+  }
+  if (int e = b->h_fix.reserve(total)) return e;
+  if (int e = b->d_fix.reserve(total)) return e;
+  b->pool->run((int)runs.size(), [&](int i) {
+    const Run &r = runs[i];
+    std::vector<const ParsedFrame *> fr(frames + r.j0, frames + r.j1);
+    memset(b->h_fix.p + r.desc_off, 0, r.item_off - r.desc_off);
+    step_write(fr, n_mbs, (MbDesc *)(b->h_fix.p + r.desc_off), (uint32_t *)(b->h_fix.p + r.pay_off));
+    if (!r.plan.items.empty()) memcpy(b->h_fix.p + r.item_off, r.plan.items.data(), r.plan.items.size() * 4);
+  });
+  HIP_TRY(hipMemcpyAsync(b->d_fix.p, b->h_fix.p, total, hipMemcpyHostToDevice, b->stream));
+  b->next_tag(); // (one tag for all runs: they touch different clips' tags)
+  for (const Run &r : runs) {
+    const int c0 = clips[r.j0], m = r.j1 - r.j0;
+    MobiReconArgs a = b->args(b->d_fix.p + r.desc_off, b->d_fix.p + r.pay_off);
+    a.planes += (size_t)c0 * b->clip_bytes;
+    a.n_clips = m;
+    a.fault = b->d_fault + c0;
+    a.done = b->d_done + (size_t)c0 * n_mbs;
+    a.ring_base = ring_base;
+    // (two launches, never the one-launch step: its give-up path -- fault bit 2, a dispatch order never seen -- has no retry here)
+    if (int e = b->launch_plan(a, r.plan, (const uint32_t *)(b->d_fix.p + r.item_off), m, false)) return e;
+  }
+  HIP_TRY(hipMemcpyAsync(b->h_fault.data(), b->d_fault, sizeof(int) * b->n, hipMemcpyDeviceToHost, b->stream));
+  for (const Run &r : runs) HIP_TRY(hipMemsetAsync(b->d_fault + clips[r.j0], 0, sizeof(int) * (r.j1 - r.j0), b->stream));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  b->drain_events();
+  for (int j = 0; j < k; j++) fault_out[j] = b->h_fault[clips[j]];
+  return MOBI_OK;
+}
+
+// ---- asynchronous frame steps (device parse) -------------------------------------------------------------------------------
+// mobi_batch_decode is DecodeFrame(): it returns when the frame is there.  A caller that already holds the next frame of every clip
+// (demuxed Moflex / Mods packets: Offset does not depend on the previous frame's parse) can keep two steps in flight instead:
+// submit gathers the bytes into pinned memory, uploads them on a second stream and enqueues parse + reconstruction behind the
+// previous step without a host round trip in between (the intra launch covers every slot a clip could use; workgroups past a
+// clip's count leave at once); wait hands out rc[] / Offset of the oldest step when its reconstruction is done.  The host gathers
+// step n + 1 while the GPU parses step n, and the GPU never waits for the host between parse and reconstruction.
+// A frame the device parser cannot finish shows up in wait: the clip's frame (and the next one, if a second step is in flight) is then
+// parsed by the host parser and reconstructed on its own there (async_repair), and the clip is the host parser's in later submits.
+int mobi_batch_submit(mobi_batch *b, const uint8_t *const *data, const size_t *len, const int32_t *offsets) {
+  if (!b || !data || !len || !offsets) return MOBI_E_ARG;
+  HIP_TRY(hipSetDevice(b->device));
+  const int n = b->n, n_mbs = b->g.mbw * b->g.mbh;
+  settle_parse_mode(b, b->frames_started == 0 && b->async_seq == 0, 0, true); // an asynchronous batch parses on the GPU from its first frame
+  if (b->poisoned) return MOBI_E_DEVICE;
+  if (b->parse_mode == 0) return MOBI_E_ARG; // the decoder state of this batch lives in the host parsers
+  if (!b->version_known()) return MOBI_E_VERSION;
+  if (b->g.mbw > 64 || b->async_count >= 2 || b->gop_count) return MOBI_E_ARG;
+  const bool dev_state = b->d_pstate[0] != nullptr;
+  if (int e = dp_init(b)) return e;
+  b->mark_hybrid_share();
+  const uint64_t serial = b->handover + 1;
+  reset_apply_host(b, serial); // (before the staging: the routing decides which clips the device parses)
+  const std::vector<int32_t> *resets = dev_state && !b->reset_list.empty() ? &b->reset_list : nullptr;
+  mobi_batch::AsyncSlot &S = b->aslot[(b->async_head + b->async_count) & 1];
+  for (Event *ev : {&S.ev_up, &S.ev_done, &S.ev_parsed})
+    if (int e = ensure_event(*ev)) return e;
+  if (int e = ensure_stream(b->stream2)) return e;
+  if (int e = ensure_stream(b->stream_p)) return e;
+  DpStaged st;
+  if (int e = dp_stage(b, data, len, offsets, S.h_stage, st, nullptr, false, nullptr, resets)) return e; // (this slot's previous step was waited for: its upload is done)
+  if (int e = S.d_pres.reserve(sizeof(MobiDevResult) * n)) return e;
+  if (st.bytes > S.d_bits.cap) // growing frees and allocates (a device-wide stall): leave room for the longer frames to come
+    if (int e = S.d_bits.reserve(st.bytes + st.bytes / 4)) return e;
+  if (int e = S.h_pres.reserve(sizeof(MobiDevResult) * n)) return e;
+  if (int e = S.h_fault.reserve(sizeof(int) * n)) return e;
+  S.offs.assign(offsets, offsets + n);
+  S.n_dev = n;
+  S.serial = serial;
+  b->lockstep = S.lockstep = ls_decide(b, st);
+  S.hdr_bytes = st.hdr_bytes;
+  S.is_host.assign(n, 0);
+  S.host_rc.assign(n, MOBI_OK);
+  S.host_off.assign(n, 0);
+  S.host_quant.assign(n, 0);
+  S.host_yuv.assign(n, 0);
+  // the host parser's clips: parsed now (the caller's bytes are only good during this call), their command lists staged for the copy below
+  std::vector<int> host_clips;
+  for (int i = 0; i < n; i++)
+    if (b->on_host[i]) host_clips.push_back(i);
+  if (!host_clips.empty()) {
+    for (int i : host_clips) { S.is_host[i] = 1; S.host_off[i] = offsets[i]; }
+    b->pool->run((int)host_clips.size(), [&](int j) {
+      const int i = host_clips[j];
+      S.host_rc[i] = parse_host(b->parsers[i].get(), data[i], len[i], &S.host_off[i], b->cur[i]);
+      S.host_quant[i] = b->parsers[i]->quantizer();
+      S.host_yuv[i] = b->parsers[i]->yuv_format();
+    });
+  }
+  // Everything that can fail without touching the device is behind us.  From the first enqueue on, a failure leaves work in flight
+  // that reads this slot's pinned memory and (later) a ring that has turned without a step to wait for: the batch is drained and
+  // POISONED -- every later call reports MOBI_E_DEVICE -- rather than left in a state where the next submit reuses the slot.
+  Poison poison{b};
+  HIP_TRY(hipMemcpyAsync(S.d_bits.p, S.h_stage.p, st.bytes, hipMemcpyHostToDevice, b->stream2)); // beside whatever the step before is doing
+  HIP_TRY(hipEventRecord(S.ev_up, b->stream2));
+  // Three streams: the upload (stream2), the parse (stream_p: after the upload; the decoder state goes from parse to parse in its order)
+  // and the reconstruction (stream: after this step's parse; the ring goes from step to step in its order).  The parse of this step
+  // runs under the reconstruction of the one before -- the lock-step parser leaves most of the chip idle -- because what it writes
+  // (descriptors, payload, intra lists, results) belongs to the slot, whose previous step has been waited for.
+  // (Only the lock-step parser gets the stream of its own: the one-wave-per-clip parser fills every wave slot of the chip with 122-register
+  // waves, and a reconstruction launched beside it waits for them to leave anyway -- 20.5 instead of 13.2 ms per step of 4096 clips.)
+  hipStream_t ps = b->lockstep ? b->stream_p : b->stream;
+  HIP_TRY(hipStreamWaitEvent(ps, S.ev_up, 0));
+  { // the parser in front is chosen step by step (ls_decide), and with it the stream: the state this parse reads is the one the step before wrote
+    mobi_batch::AsyncSlot &prev = b->aslot[(b->async_head + b->async_count + 1) & 1];
+    if (b->async_seq > 0 && prev.ev_parsed && prev.parsed_recorded) HIP_TRY(hipStreamWaitEvent(ps, prev.ev_parsed, 0));
+  }
+  MobiDevResult *d_res = (MobiDevResult *)S.d_pres.p;
+  // clips reset from this step on: a new decoder's state into the entry the parse reads, behind whatever the step before wrote there
+  if (st.n_reset && mobi_launch_reset_state((const int32_t *)(S.d_bits.p + st.reset_off), st.n_reset, n, b->d_pstate[b->ps_cur], b->d_ptail[b->ps_cur], ps) != 0)
+    return MOBI_E_DEVICE;
+  if (int e = dp_parse(b, S.d_bits.p, st, false, DpOut{&S.d_pdesc, &S.d_ppay, &S.d_pitems, d_res, ps, true}, &S.state_in)) return e;
+  if (!host_clips.empty()) {
+    if (int e = dp_override(b, host_clips, S.host_rc.data(), S.h_over, DpRows{S.d_pdesc.p, S.d_ppay.p, S.d_pitems.p, d_res, b->last_pay_cap}, ps)) return e;
+    if (int e = dp_return(b, host_clips, S.host_rc.data(), b->ps_cur, S.h_ret, ps)) return e; // (the parse kernels skip these clips: their entries are free to write)
+  }
+  HIP_TRY(hipMemcpyAsync(S.h_pres.p, d_res, sizeof(MobiDevResult) * n, hipMemcpyDeviceToHost, ps));
+  HIP_TRY(hipEventRecord(S.ev_parsed, ps));
+  S.parsed_recorded = true;
+  if (ps != b->stream) HIP_TRY(hipStreamWaitEvent(b->stream, S.ev_parsed, 0));
+  // reconstruction straight from what the parse leaves in HBM (failed clips: blank descriptors, no items)
+  if (int e = b->begin_step()) return e;
+  S.ring_base = b->ring_base;
+  MobiReconArgs a = b->args(S.d_pdesc.p, S.d_ppay.p);
+  a.pay_clip_words = b->pay_clip_words;
+  a.done = b->d_done;
+  if (mobi_launch_inter(&a, b->stream) != 0) return MOBI_E_DEVICE;
+  // the parse has not run yet, so nobody knows how many intra macroblocks the longest list will have: MOBI_ASYNC_INTRA_SLOTS slots are launched
+  // (a P-frame's lists are shorter), and a second launch (mobi_recon_intra_walk, one workgroup per four clips) goes through the rest of theirs (an I-frame: every macroblock)
+  if (mobi_launch_intra_cl(&a, (const uint32_t *)S.d_pitems.p, &d_res[0].n_intra, (int)(sizeof(MobiDevResult) / 4), std::min(n_mbs, MOBI_ASYNC_INTRA_SLOTS), 1, b->stream) != 0) return MOBI_E_DEVICE;
+  if (int e = b->read_faults((int *)S.h_fault.p)) return e;
+  HIP_TRY(hipEventRecord(S.ev_done, b->stream));
+  poison.armed = false;
+  reset_commit(b, serial);
+  b->async_count++;
+  b->async_seq++;
+  return MOBI_OK;
+}
+// Clips of the oldest step in flight whose frame the device parser could not finish.  Everything enqueued is drained first (a second step
+// in flight parsed these clips from a state the failed frame left behind: its frame is repaired as well); then, per clip: the state the
+// frame started from goes into the host parser, the staged bitstream is parsed again, and the frame is reconstructed on its own into the
+// ring slot its step wrote.  The results replace the device's in the slots' host-side tables.
+static int async_repair(mobi_batch *b, mobi_batch::AsyncSlot &S, const std::vector<int> &failed) {
+  if (b->stream2) HIP_TRY(hipStreamSynchronize(b->stream2));
+  if (b->stream_p) HIP_TRY(hipStreamSynchronize(b->stream_p));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  mobi_batch::AsyncSlot *S1 = b->async_count == 2 ? &b->aslot[(b->async_head + 1) & 1] : nullptr;
+  const int n = b->n, k = (int)failed.size(), nT = S1 ? 2 : 1;
+  mobi_batch::AsyncSlot *const T[2] = {&S, S1};
+  // A clip reset between the two steps (mobi_batch_reset_clips) has its new stream's first frame in S1, parsed from a new decoder's state: the
+  // repair stays in S, with the parser of the stream S belongs to (mobi_batch::parser_at), and leaves the clip's current state alone.
+  std::vector<MobiStreamParser *> parser(k);
+  std::vector<uint8_t> cascade(k, 0);
+  for (int j = 0; j < k; j++) {
+    parser[j] = b->parser_at(S.serial, failed[j]);
+    cascade[j] = S1 && b->stale(S.serial, failed[j]) == b->stale(S1->serial, failed[j]);
+  }
+  // r06: a batch operation.  The start states in one go, the parses on the pool (a clip's two frames in order), then per affected step ONE
+  // reconstruction of the failed clips (recon_clips) -- r05 did all of it clip by clip on the calling thread: a GOP damaged in every clip of a
+  // batch, or a ModsDS batch that cuts to a quantiser below 12 in one frame, stalled mobi_batch_wait for ~1.5 ms x 2 x clips.
+  if (int e = dp_seed_parsers(b, failed, S.state_in, S.h_ret, b->stream, &parser)) return e;
+  if (b->gop_frames.size() < (size_t)k * 2) b->gop_frames.resize((size_t)k * 2);
+  std::vector<int> prc((size_t)k * 2, MOBI_OK);
+  b->pool->run(k, [&](int j) {
+    const int c = failed[j];
+    for (int t = 0; t < (cascade[j] ? 2 : 1); t++) {
+      const uint64_t boff = ((const uint64_t *)T[t]->h_stage.p)[c];
+      const uint32_t blen = ((const uint32_t *)(T[t]->h_stage.p + (size_t)n * 8))[c];
+      int32_t off = 0;
+      prc[(size_t)j * 2 + t] = parser[j]->parse_frame(T[t]->h_stage.p + T[t]->hdr_bytes + boff, blen, &off, b->gop_frames[(size_t)j * 2 + t]);
+      T[t]->is_host[c] = 1;
+      T[t]->host_off[c] = T[t]->offs[c] + off;
+      T[t]->host_quant[c] = parser[j]->quantizer();
+      T[t]->host_yuv[c] = parser[j]->yuv_format();
+    }
+  });
+  for (int t = 0; t < nT; t++) {
+    std::vector<int> cl;
+    std::vector<const ParsedFrame *> fr;
+    std::vector<int> js;
+    for (int j = 0; j < k; j++)
+      if (t == 0 || cascade[j]) {
+        cl.push_back(failed[j]);
+        js.push_back(j);
+        fr.push_back(prc[(size_t)j * 2 + t] == MOBI_OK ? &b->gop_frames[(size_t)j * 2 + t] : nullptr);
+      }
+    std::vector<int> fault(cl.size());
+    if (int e = recon_clips(b, cl, fr.data(), T[t]->ring_base, fault.data())) return e;
+    for (size_t i = 0; i < cl.size(); i++) {
+      T[t]->host_rc[cl[i]] = fault_rc(prc[(size_t)js[i] * 2 + t], fault[i]);
+      ((int *)T[t]->h_fault.p)[cl[i]] = 0;
+    }
+  }
+  for (int c : failed) {
+    if (b->stale(S.serial, c)) continue; // (the clip's current stream started with S1 or starts with the next step: its routing is a new decoder's)
+    b->route_to_host(c);
+  }
+  b->fallbacks += failed.size();
+  return MOBI_OK;
+}
+int mobi_batch_wait(mobi_batch *b, int32_t *offsets_out, int *rc) {
+  if (!b || !rc) return MOBI_E_ARG;
+  HIP_TRY(hipSetDevice(b->device));
+  if (b->poisoned) return MOBI_E_DEVICE;
+  if (b->async_count == 0) return MOBI_E_ARG;
+  mobi_batch::AsyncSlot &S = b->aslot[b->async_head & 1];
+  HIP_TRY(hipEventSynchronize(S.ev_done));
+  const MobiDevResult *res = (const MobiDevResult *)S.h_pres.p;
+  const int *fault = (const int *)S.h_fault.p;
+  std::vector<int> failed;
+  for (int i = 0; i < S.n_dev; i++)
+    if (!S.is_host[i] && res[i].rc != MOBI_OK) failed.push_back(i);
+  if (!failed.empty())
+    if (int e = async_repair(b, S, failed)) { b->poisoned = true; return e; }
+  b->ls_finished = S.lockstep ? 0 : -1; // (of the step being reported, not of the one submitted last: ADVICE r05)
+  for (int i = 0; i < S.n_dev; i++) {
+    if (S.is_host[i]) {
+      rc[i] = S.host_rc[i];
+      if (offsets_out) offsets_out[i] = S.host_off[i];
+      b->dev_quant[i] = S.host_quant[i];
+      b->dev_yuvfmt[i] = S.host_yuv[i];
+    } else {
+      if (S.lockstep && res[i].pad == MOBI_LS_MAGIC) b->ls_finished++;
+      rc[i] = res[i].rc;
+      if (offsets_out) offsets_out[i] = S.offs[i] + (int32_t)res[i].consumed;
+      b->dev_quant[i] = res[i].quant;
+      b->dev_yuvfmt[i] = res[i].yuvfmt;
+    }
+    rc[i] = fault_rc(rc[i], fault[i]);
+  }
+  b->async_head ^= 1;
+  b->async_count--;
+  return MOBI_OK;
+}

@@ -1,5 +1,5 @@
 """The launch items of intra macroblocks (ParsedFrame::intra_items, mobi_parse.cpp finish_levels) against the descriptors they summarise.
-The step's launch list (LevelPlan, mobi_abi.cpp) is a concatenation of these, so what a wave of mobi_recon_intra is told -- where the
+The step's launch list (LevelPlan, mobi_batch.h) is a concatenation of these, so what a wave of mobi_recon_intra is told -- where the
 records are, whether to poll tags, whether to publish its own -- is decided here, in the parser."""
 import numpy as np
 import pytest

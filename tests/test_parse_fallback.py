@@ -1,5 +1,5 @@
 """r05: the answer must not depend on which side parses.  The device parsers finish frames that decode without incident; every other frame
-is parsed again by the host parser from the decoder state the clip had when the frame started (mobi_state.h, mobi_abi.cpp).  What that rests
+is parsed again by the host parser from the decoder state the clip had when the frame started (mobi_state.h, mobi_step_device.cpp).  What that rests
 on, checked here without a GPU:
 
   * the host parser's picture of Internal[] -- dequant words, the coefficient block, the transforms' scratch, the MV predictor and row
@@ -282,7 +282,7 @@ def _fuzz_streams(n, seed):
 
 
 def test_the_payload_bound_the_device_arena_is_sized_by():
-    """mobi_abi.cpp dp_parse sizes a clip's part of the payload arena as 64 words per macroblock + one level word per THREE bits of the frame
+    """mobi_step_device.cpp dp_parse sizes a clip's part of the payload arena as 64 words per macroblock + one level word per THREE bits of the frame
     (+ slack): every command list -- the device parsers' and the host parser's, which is copied over a clip's rows when it takes the clip
     over -- has to fit, whatever the stream.  Clean and corrupted frames, both versions; and the reason it holds: no table code with a level
     is shorter than three bits."""

@@ -3,7 +3,7 @@
 # I-frame step at 4096 and CLIPS clips (tools/exp_iframe.py) and the headline P-frame line (bench.py, no side legs)
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}; P=$REPO/mobiclipdecoder_amd; O=$P/_obj
 cp $P/libmobiclip_hip.so /tmp/lib_keep.so; cp $O/mobi_kernels.hip.o /tmp/k_keep.o
-OBJS="$O/mobi_abi.cpp.o $O/mobi_parse.cpp.o $O/mobi_demux.cpp.o $O/mobi_moflex.cpp.o $O/mobi_kernels.hip.o $O/mobi_rgb.hip.o $O/mobi_dparse.hip.o $O/mobi_lsparse.hip.o $O/mobi_analysis.hip.o"
+OBJS=$(cd $REPO && python -m mobiclipdecoder_amd.build --objects)  # what build.py links
 for ROUND in $(seq 1 ${ROUNDS:-2}); do
   for V in $VARIANTS; do
     F=$(echo $V | tr ',' ' ')  # (a variant may be several -D flags joined by commas)

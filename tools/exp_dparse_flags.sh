@@ -2,7 +2,7 @@
 # usage (GPU box): tools/exp_dparse_flags.sh  -- the device parser built with several compiler settings, parse time per 4096 clips
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}; P=$REPO/mobiclipdecoder_amd; O=$P/_obj
 cp $P/libmobiclip_hip.so /tmp/lib_keep.so; cp $O/mobi_dparse.hip.o /tmp/dparse_keep.o
-OBJS="$O/mobi_abi.cpp.o $O/mobi_parse.cpp.o $O/mobi_demux.cpp.o $O/mobi_moflex.cpp.o $O/mobi_kernels.hip.o $O/mobi_rgb.hip.o $O/mobi_dparse.hip.o $O/mobi_lsparse.hip.o $O/mobi_analysis.hip.o"
+OBJS=$(cd $REPO && python -m mobiclipdecoder_amd.build --objects)  # what build.py links
 run() {
   echo "== $*"
   hipcc --offload-arch=gfx950 -std=c++17 -fPIC "$@" -c $P/csrc/mobi_dparse.hip -o $O/mobi_dparse.hip.o 2>&1 | grep -E "error|Spill" | head -3

@@ -4,7 +4,7 @@
 # kernels by events and the pipelined ms per frame step (tools/exp_gop.py on the twin: its reconstruction kernels carry stage-stop tests).
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}; P=$REPO/mobiclipdecoder_amd; O=$P/_obj_prof
 cp $P/libmobiclip_hip_prof.so /tmp/lib_keep.so
-OBJS="$O/mobi_abi.cpp.o $O/mobi_parse.cpp.o $O/mobi_demux.cpp.o $O/mobi_moflex.cpp.o $O/mobi_kernels.hip.o $O/mobi_rgb.hip.o $O/mobi_dparse.hip.o /tmp/lsv.o $O/mobi_gop.hip.o $O/mobi_analysis.hip.o"
+OBJS=$(cd $REPO && python -m mobiclipdecoder_amd.build --objects --profiling | sed "s#$O/mobi_lsparse.hip.o#/tmp/lsv.o#")  # what build.py links, with the object rebuilt here in its place
 export MOBI_LIB=$P/libmobiclip_hip_prof.so GOP_STEPWISE=0
 for ROUND in 1 2; do
   for F in "$@"; do
