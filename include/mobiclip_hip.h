@@ -35,6 +35,7 @@ extern "C" {
 /* Return codes.  0 = frame decoded.  Negative = the reference would have thrown inside
  * DecodeVXS2 and returned a null Bitmap (MD.cs:325-328); the code says which check fired. */
 #define MOBI_OK 0
+#define MOBI_IDLE 1              /* not an error: the frame slot was marked idle (mobi_batch_set_idle) -- nothing parsed, nothing written */
 #define MOBI_E_INDEX (-1)        /* managed array bounds: MC source window, intra neighbour at a negative
                                     offset, VLC/CBP/quantizer table index, bitstream read past Data */
 #define MOBI_E_NULLREF (-2)      /* reference frame slot Y[ref] never decoded (MD.cs:413) */
@@ -147,6 +148,41 @@ int mobi_batch_reset_clips(mobi_batch *b, const int32_t *clips, int count);
  * that threw too (the reference turns its ring before anything can throw, MD.cs:102-108).  For a clip never reset: the frames the batch has
  * been handed.  A reset sets it to 0 and the frames of groups begun before it do not count. */
 int mobi_batch_clip_frames(const mobi_batch *b, int32_t *out);
+/* Idle frame slots: "clip c has no frame here, its stream has ended".  A batch moves in lock step, so a clip whose stream ends inside a
+ * group (or a step before the caller has the next file) still owes the call a slot; an empty packet there is a damaged stream
+ * (MOBI_E_INDEX, and the clip goes to the host parser).  An idle slot is never parsed, on either side, never handed to the host parser,
+ * changes no decoder state and writes no pixel.
+ *   MASK:      idle[k * n_clips + c] != 0 marks frame k of clip c of the NEXT step or group handed over (mobi_batch_decode,
+ *              mobi_batch_submit: n_frames = 1; mobi_batch_decode_gop, mobi_batch_gop_begin: n_frames = that call's).  The mask is copied,
+ *              consumed by that hand-over and forgotten.  idle == NULL drops a mask set and not yet consumed (n_frames is ignored then).
+ *   NO WAIT:   never waits for the GPU and enqueues nothing; allowed while steps or groups are in flight.  The device side is one launch
+ *              (mobi_idle_rows) in front of that hand-over's parse, and only when it has idle slots; a hand-over without a mask enqueues
+ *              exactly what it always did.
+ *   SLOT:      for an idle slot data[..] may be NULL and len[..] / offsets[..] are ignored; rc[..] is MOBI_IDLE and the Offset reported is
+ *              the one handed in.
+ *   ENDS:      an idle slot ENDS the clip's stream.  Within a group the idle slots of a clip are a suffix (once idle, idle to the group's
+ *              end), and a clip that has had an idle slot takes a live frame again only after mobi_batch_reset_clips named it.  Resuming a
+ *              paused stream is NOT supported: the ring turns batch-wide, so a clip that sat out a step has its references shifted.  A reset
+ *              and an idle mark may name the same clip for the same hand-over if the idle slots still are a suffix (reset and idle from
+ *              frame 0 on: an empty slot of the batch).
+ *   RING:      the ring still turns once per frame for every clip.  An idle slot writes nothing: the clip's earlier pictures move to higher
+ *              ring indices and the slot that comes round holds an older picture of that clip -- unspecified but initialised memory; the
+ *              getters and exports keep their batch-wide checks and deliver it.  With idle[c] = mobi_batch_clip_idle and clip_frames[c] =
+ *              mobi_batch_clip_frames (LIVE frames only; for a caller that never sets a mask what it always counted), ring index r of clip
+ *              c holds a picture of the current stream exactly when idle[c] <= r < min(6, idle[c] + clip_frames[c]) -- this replaces the
+ *              rule under mobi_batch_reset_clips.
+ *   STATE:     mobi_batch_quantizer / mobi_batch_yuv_format of such a clip stay those of its last live frame.  The clip is not counted by
+ *              mobi_batch_host_clips, and by mobi_batch_lockstep_finished neither as finished nor as left over.  mobi_batch_reset_clips
+ *              works on it as on any other clip and clears the "ended" mark and the idle count with the step it applies to.
+ *   REFUSED:   here: MOBI_E_ARG for n_frames outside [1, 128] with idle != NULL, MOBI_E_DEVICE for a poisoned batch.  By the hand-over,
+ *              before anything changes: MOBI_E_ARG when its n_frames differs from the mask's (the mask stays), when a clip's idle slots are
+ *              not a suffix, and for a live frame of a clip whose stream has ended and that no reset has named. */
+int mobi_batch_set_idle(mobi_batch *b, const uint8_t *idle, int n_frames);
+/* out[c] (n_clips entries) = idle slots handed over for clip c since its last live frame or reset.  Host bookkeeping, steps and groups in
+ * flight included; never reads the GPU. */
+int mobi_batch_clip_idle(const mobi_batch *b, int32_t *out);
+/* how many launches of the idle-slot kernel (mobi_idle_rows) the batch has made so far: 0 for a caller that never sets a mask */
+int mobi_batch_idle_launches(const mobi_batch *b);
 /* Asynchronous frame steps, for callers that already hold the next frame of every clip (demuxed Moflex / Mods packets: the Offset
  * to start from does not depend on the previous frame's parse).  The batch must parse on the GPU (the default for large batches, see above;
  * mobi_batch_set_parse_mode(b, 1), 2 or 3 otherwise: the hybrid mode's host share is parsed inside mobi_batch_submit) and at most two steps

@@ -9,6 +9,7 @@ from .decoder import (  # noqa: F401
     MobiclipBatch,
     MobiclipVersion,
     MobiclipError,
+    MOBI_IDLE,
     host_empty,
     split_i420,
     load_library,

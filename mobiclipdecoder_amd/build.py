@@ -6,6 +6,7 @@
   oracle/_build/libmobi_oracle.so   CPU oracle = TEST INFRASTRUCTURE             (gcc)
   tests/tools/libmobi_cmdinterp.so  CPU command-list interpreter = TEST TOOL     (g++)
   tests/tools/libmobi_lsparse_host.so  lock-step parser's lane functions on the CPU = TEST TOOL (g++)
+  tests/tools/libmobi_idle_host.so  the frame-parallel chain's kernel bodies on the CPU, idle slots = TEST TOOL (g++)
   tests/tools/abi_caller            plain-C caller of the product's C ABI = TEST TOOL (gcc)
 
 hipcc cross-compiles gfx950 without a GPU.  The built .so files are git-ignored but travel to the
@@ -28,11 +29,12 @@ LIB_GEN = os.path.join(PKG, "libmobi_streamgen.so")
 LIB_ORACLE = os.path.join(ROOT, "oracle", "_build", "libmobi_oracle.so")
 LIB_INTERP = os.path.join(ROOT, "tests", "tools", "libmobi_cmdinterp.so")
 LIB_LSHOST = os.path.join(ROOT, "tests", "tools", "libmobi_lsparse_host.so")  # the lock-step parser's lane functions on the CPU (test tool)
+LIB_IDLEHOST = os.path.join(ROOT, "tests", "tools", "libmobi_idle_host.so")  # mobi_gop_prepare / mobi_gop_chain bodies on the CPU (test tool)
 ABI_CALLER = os.path.join(ROOT, "tests", "tools", "abi_caller")  # plain-C caller of the product library (test tool)
 
 
 # the sources of libmobiclip_hip.so: *.cpp are host objects (g++), *.hip kernel objects (hipcc --offload-arch=gfx950); linked in this order
-HIP_SOURCES = ("mobi_batch.cpp", "mobi_step_host.cpp", "mobi_step_device.cpp", "mobi_step_groups.cpp", "mobi_replay.cpp", "mobi_pictures.cpp", "mobi_parse.cpp", "mobi_demux.cpp", "mobi_moflex.cpp", "mobi_export.cpp", "mobi_txcode.cpp", "mobi_kernels.hip", "mobi_rgb.hip", "mobi_dparse.hip", "mobi_lsparse.hip", "mobi_gop.hip", "mobi_analysis.hip", "mobi_export.hip", "mobi_txcode.hip", "mobi_export_rgb.hip", "mobi_reset.hip")
+HIP_SOURCES = ("mobi_batch.cpp", "mobi_step_host.cpp", "mobi_step_device.cpp", "mobi_step_groups.cpp", "mobi_replay.cpp", "mobi_pictures.cpp", "mobi_parse.cpp", "mobi_demux.cpp", "mobi_moflex.cpp", "mobi_export.cpp", "mobi_txcode.cpp", "mobi_kernels.hip", "mobi_rgb.hip", "mobi_dparse.hip", "mobi_lsparse.hip", "mobi_gop.hip", "mobi_analysis.hip", "mobi_export.hip", "mobi_txcode.hip", "mobi_export_rgb.hip", "mobi_reset.hip", "mobi_idle.hip")
 
 
 def hip_objects(profiling=False):
@@ -137,6 +139,14 @@ def build_lshost(force=False):
     return LIB_LSHOST
 
 
+def build_idlehost(force=False):
+    src = os.path.join(ROOT, "tests", "tools", "mobi_idle_host.cpp")
+    parse = os.path.join(CSRC, "mobi_parse.cpp")
+    if force or _newer(LIB_IDLEHOST, [src, parse] + _hdrs(CSRC)):
+        _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-fwrapv", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(ROCM, "include"), "-I" + CSRC, src, parse, "-o", LIB_IDLEHOST])
+    return LIB_IDLEHOST
+
+
 def build_caller(force=False):
     src = os.path.join(ROOT, "tests", "tools", "abi_caller.c")
     if force or _newer(ABI_CALLER, [src, os.path.join(ROOT, "include", "mobiclip_hip.h"), LIB_HIP]):
@@ -145,7 +155,7 @@ def build_caller(force=False):
 
 
 def build_all(force=False):
-    return [build_hip(force), build_hip(force, profiling=True), build_gen(force), build_oracle(force), build_interp(force), build_lshost(force), build_caller(force)]
+    return [build_hip(force), build_hip(force, profiling=True), build_gen(force), build_oracle(force), build_interp(force), build_lshost(force), build_idlehost(force), build_caller(force)]
 
 
 if __name__ == "__main__":

@@ -59,7 +59,7 @@ long long mobi_debug_read_parse(mobi_batch *b, uint32_t *desc_out, uint32_t *ite
 #pragma GCC visibility pop
 #endif // MOBI_PROFILING
 
-const char *mobi_build_info(void) { return "libmobiclip_hip 0.6 (gfx950, macroblock-tiled planes; HIP kernels: mobi_recon_inter8, mobi_recon_intra, mobi_recon_step, mobi_recon_intra_cl, mobi_recon_intra_walk, mobi_parse_frames, mobi_parse_frames_ls, mobi_ls_deps, mobi_parse_tail, mobi_gop_prepare, mobi_gop_chain, mobi_gop_fronts, mobi_gop_front_starts, mobi_gop_scatter, mobi_untile, mobi_yuv_to_argb, mobi_export_i420, mobi_export_rgb, mobi_reset_state, mobi_motion_search_2x2, mobi_fwd_dct8, mobi_fwd_dct4, mobi_txcode8, mobi_txcode4; no CPU reconstruction path)"; }
+const char *mobi_build_info(void) { return "libmobiclip_hip 0.6 (gfx950, macroblock-tiled planes; HIP kernels: mobi_recon_inter8, mobi_recon_intra, mobi_recon_step, mobi_recon_intra_cl, mobi_recon_intra_walk, mobi_parse_frames, mobi_parse_frames_ls, mobi_ls_deps, mobi_parse_tail, mobi_gop_prepare, mobi_gop_chain, mobi_gop_fronts, mobi_gop_front_starts, mobi_gop_scatter, mobi_untile, mobi_yuv_to_argb, mobi_export_i420, mobi_export_rgb, mobi_reset_state, mobi_idle_rows, mobi_motion_search_2x2, mobi_fwd_dct8, mobi_fwd_dct4, mobi_txcode8, mobi_txcode4; no CPU reconstruction path)"; }
 
 const char *mobi_error_string(int rc) {
   switch (rc) {
@@ -102,6 +102,8 @@ mobi_batch *mobi_batch_create(int n_clips, uint32_t width, uint32_t height, int 
   b->frames_base.assign(n_clips, 0);
   b->stream_gen.assign(n_clips, 0);
   b->retired.resize(n_clips);
+  b->ended.assign(n_clips, 0);
+  b->idle_count.assign(n_clips, 0);
   b->h_fault.assign(n_clips, 0);
   b->on_host.assign(n_clips, 0);
   size_t arena_clips = (size_t)n_clips;
@@ -226,6 +228,8 @@ int mobi_batch_host_clips(const mobi_batch *b) {
   if (!b->parse_mode) return b->n;
   int k = 0;
   for (uint8_t h : b->on_host) k += h;
+  if (b->n_ended) // a clip whose stream has ended (mobi_batch_set_idle) is nobody's to parse
+    for (int c = 0; c < b->n && c < (int)b->on_host.size(); c++) k -= b->on_host[c] && b->ended[c];
   return k;
 }
 int mobi_batch_lockstep_finished(const mobi_batch *b) { return b ? b->ls_finished : -1; }
@@ -256,7 +260,72 @@ int mobi_batch_reset_clips(mobi_batch *b, const int32_t *clips, int count) {
 int mobi_batch_clip_frames(const mobi_batch *b, int32_t *out) {
   if (!b || !out) return MOBI_E_ARG;
   for (int c = 0; c < b->n; c++) out[c] = std::max(0, b->frames_started - b->frames_base[c]);
+  if (!b->n_ended) return MOBI_OK;
+  // live frames only: the idle slots of the clip's stream that have turned the ring do not count (idle_count is booked at the hand-over,
+  // the ring turns in mobi_batch_gop_finish: the idle slots of groups begun that have not turned it yet are still to come)
+  std::vector<int32_t> turned(b->idle_count);
+  for (int i = 0; i < b->gop_count; i++) {
+    const mobi_batch::GopSlot &S = b->gslot[(b->gop_head + i) & 1];
+    if (S.idle_from.empty()) continue;
+    const int done = S.resolved ? S.done : 0;
+    for (int c = 0; c < b->n; c++)
+      if (!b->stale(S.serial, c)) turned[c] -= S.K - std::max(done, (int)S.idle_from[c]);
+  }
+  for (int c = 0; c < b->n; c++)
+    if (b->ended[c]) out[c] = std::max(0, out[c] - std::max(0, turned[c]));
   return MOBI_OK;
+}
+
+// ---- idle frame slots (mobi_batch_set_idle) ----
+int mobi_batch_set_idle(mobi_batch *b, const uint8_t *idle, int n_frames) {
+  if (!b) return MOBI_E_ARG;
+  if (b->poisoned) return MOBI_E_DEVICE;
+  if (!idle) { b->idle_frames = 0; return MOBI_OK; }
+  if (n_frames < 1 || n_frames > MOBI_GOP_PARSE_MAX) return MOBI_E_ARG;
+  b->idle_mask.assign(idle, idle + (size_t)n_frames * b->n);
+  b->idle_frames = n_frames;
+  return MOBI_OK;
+}
+int mobi_batch_clip_idle(const mobi_batch *b, int32_t *out) {
+  if (!b || !out) return MOBI_E_ARG;
+  for (int c = 0; c < b->n; c++) out[c] = b->idle_count[c];
+  return MOBI_OK;
+}
+int mobi_batch_idle_launches(const mobi_batch *b) { return b ? b->idle_launches : 0; }
+int idle_check(const mobi_batch *b, int K, std::vector<uint8_t> &from) {
+  from.clear();
+  if (!b->idle_frames && !b->n_ended) return MOBI_OK; // (a caller that never sets a mask: no per-clip work)
+  if (b->idle_frames && b->idle_frames != K) return MOBI_E_ARG;
+  const int n = b->n;
+  bool any = false;
+  from.assign(n, (uint8_t)K);
+  for (int c = 0; c < n; c++) {
+    int first = K;
+    if (b->idle_frames) {
+      while (first > 0 && b->idle_mask[(size_t)(first - 1) * n + c]) first--; // the idle suffix ...
+      for (int k = 0; k < first; k++)
+        if (b->idle_mask[(size_t)k * n + c]) return MOBI_E_ARG; // ... and nothing idle in front of it
+    }
+    if (first > 0 && b->ended[c] && !b->reset_pending[c]) return MOBI_E_ARG; // a live frame, and the stream has ended
+    from[c] = (uint8_t)first;
+    any = any || first < K;
+  }
+  if (!any) from.clear();
+  return MOBI_OK;
+}
+void idle_commit(mobi_batch *b, int K, const std::vector<uint8_t> &from) {
+  b->idle_frames = 0;
+  if (!b->n_ended && from.empty()) return;
+  for (int c : b->reset_list) { // the resets that apply to this hand-over: a new stream
+    if (b->ended[c]) { b->ended[c] = 0; b->n_ended--; }
+    b->idle_count[c] = 0;
+  }
+  if (from.empty()) return;
+  for (int c = 0; c < b->n; c++) {
+    if (from[c] >= K) continue;
+    if (!b->ended[c]) { b->ended[c] = 1; b->n_ended++; }
+    b->idle_count[c] = from[c] > 0 ? K - from[c] : b->idle_count[c] + K;
+  }
 }
 
 int mobi_batch_set_parse_mode(mobi_batch *b, int device_parse) {

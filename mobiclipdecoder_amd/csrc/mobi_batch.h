@@ -325,6 +325,8 @@ struct mobi_batch {
     std::vector<int32_t> host_off;
     std::vector<uint32_t> host_quant, host_yuv; // Quantizer / YuvFormat behind that frame (the parser itself may be a step further by the time of wait)
     uint64_t serial = 0;             // the step's place among the steps handed over (stream generations: mobi_batch::stale)
+    std::vector<uint8_t> idle;       // [clip] 1: an idle slot of this step (mobi_batch_set_idle); empty: the step has none
+    bool is_idle(int c) const { return !idle.empty() && idle[c] != 0; }
   };
   AsyncSlot aslot[2];
   // frame-parallel groups (mobi_batch_gop_begin / mobi_batch_gop_finish, mobi_gop.h): K frames of every clip parsed side by side as n * K
@@ -357,6 +359,10 @@ struct mobi_batch {
     std::vector<int32_t> hoff;
     std::vector<uint32_t> hq, hy;
     std::vector<uint8_t> hready;
+    std::vector<uint8_t> idle_from;  // [c] the clip's first idle frame of the group (K: none; mobi_batch_set_idle); empty: the group has no idle slot
+    size_t idle_off = 0;             // ... in the staged image: n_idle clip indices (int32), then idle_from[n], uploaded with the group's bits
+    int n_idle = 0;
+    int live_end(int c) const { return idle_from.empty() ? K : idle_from[c]; } // frames [0, live_end) of clip c are live
   };
   GopSlot gslot[2];
   int gop_head = 0, gop_count = 0;
@@ -398,6 +404,15 @@ struct mobi_batch {
   uint64_t handover = 0;               // serial of the last step handed over
   bool stale(uint64_t serial, int c) const { return serial < stream_gen[c]; }
   MobiStreamParser *parser_at(uint64_t serial, int c) const { return stale(serial, c) ? retired[c].get() : parsers[c].get(); }
+  // idle frame slots (mobi_batch_set_idle).  The mask waits here for the next hand-over, which checks it (idle_check: before anything changes),
+  // keeps the slots out of gather, upload and both parsers, launches mobi_idle_rows in front of its parse (only with idle slots) and books
+  // the slots (idle_commit, beside reset_commit).  A caller that never sets a mask has idle_frames == 0 and n_ended == 0: nothing below runs.
+  std::vector<uint8_t> idle_mask;      // [k * n + c] of the next hand-over
+  int idle_frames = 0;                 // its n_frames (0: no mask set)
+  std::vector<uint8_t> ended;          // [clip] the stream has ended (an idle slot was handed over): live frames only after a reset
+  int n_ended = 0;                     // clips with the mark
+  std::vector<int32_t> idle_count;     // [clip] idle slots handed over since the clip's last live frame or reset
+  int idle_launches = 0;               // launches of mobi_idle_rows so far (mobi_batch_idle_launches)
 
   // The ring-slot guard, called by every step that writes a ring slot, right after the ring has turned and before anything of the step is
   // enqueued: the slot the step writes (ring_base) may still be read by the pack of an export; the batch's stream then waits for it.  With no
@@ -526,9 +541,15 @@ struct Poison {
 void settle_parse_mode(mobi_batch *b, bool first, size_t lanes, bool force_device, const uint8_t *const *data = nullptr, const size_t *len = nullptr, const int32_t *offsets = nullptr);
 void reset_apply_host(mobi_batch *b, uint64_t serial);
 void reset_commit(mobi_batch *b, uint64_t serial);
+// idle slots of a hand-over of K frames: from[c] = clip c's first idle frame (K: none), empty when there is no idle slot at all.  MOBI_E_ARG for
+// a mask of another n_frames, idle slots that are not a suffix, a live frame of an ended clip no pending reset names; changes nothing.
+int idle_check(const mobi_batch *b, int K, std::vector<uint8_t> &from);
+void idle_commit(mobi_batch *b, int K, const std::vector<uint8_t> &from); // the hand-over is made: marks and counts, the mask is consumed; BEFORE reset_commit
 struct DpStaged { // n_dev: clips the GPU parses; n_iframes: of them, I-frames (first bit); reset_off / n_reset: where the clip list of the resets
   size_t hdr_bytes = 0, bytes = 0, max_len = 0, reset_off = 0; // handed over with this step sits in the image (mobi_batch_reset_clips)
   int n_dev = 0, n_iframes = 0, n_reset = 0;
+  size_t idle_off = 0; // the step's idle clips (mobi_batch_set_idle), n_idle int32 behind the reset list
+  int n_idle = 0;
 };
 struct DpRows { uint8_t *desc, *pay, *items; MobiDevResult *res; size_t cap_words; };
 int dp_init(mobi_batch *b);

@@ -62,4 +62,20 @@ extern "C" int mobi_launch_parse_ls(const MobiDevParseArgs *a, hipStream_t s); /
 // mobi_batch_reset_clips (mobi_reset.hip): zero MobiDevState / MobiDevTail records -- a new decoder's -- for clips_dev[0 .. count) (unique,
 // each below n_clips) in one state ring entry
 extern "C" int mobi_launch_reset_state(const int32_t *clips_dev, int count, int n_clips, MobiDevState *state, MobiDevTail *tail, hipStream_t s);
+// idle frame slots (mobi_batch_set_idle, mobi_idle.hip): the empty rows of the idle slots of one hand-over -- frames [idle_from[c], K) of every
+// listed clip, virtual clip v = k * n + c as in the frame-parallel parse -- in front of its parse kernels
+struct MobiIdleArgs {
+  const int32_t *clips;      // the clips with an idle slot (unique, each below n)
+  int count;
+  const uint8_t *idle_from;  // [n] first idle frame of the clip; nullptr: 0 (a single step)
+  int n, K, n_mbs;
+  MbDesc *desc;              // [v][n_mbs]
+  MobiDevResult *res;        // [v]
+  // single steps: the clip's decoder state goes from the state ring entry the parse reads to the one it writes; nullptr: not carried (groups)
+  const MobiDevState *state_in;
+  MobiDevState *state_out;
+  const MobiDevTail *tail_in;
+  MobiDevTail *tail_out;
+};
+extern "C" int mobi_launch_idle_rows(const MobiIdleArgs *a, hipStream_t s);
 #endif

@@ -105,7 +105,82 @@ struct MobiGopArgs {
   const MobiDevTail *rtail_in;
   MobiDevTail *rtail_out;
   int n, K;
+  // idle frame slots (mobi_batch_set_idle): idle_from[c] = the clip's first idle frame, K when it has none -- frames [idle_from[c], K) have no
+  // bitstream (their lengths say MOBI_DP_SKIP, like every frame of a host parser's clip) and the clip's stream ENDS behind frame
+  // idle_from[c] - 1.  nullptr: the group has no idle slot.
+  const uint8_t *idle_from;
 };
+struct alignas(16) MobiDescQuad { uint32_t x, y, z, w; }; // the first four words of an MbDesc, as one 16-byte load
+
+// The bodies of the two kernels around the frame-parallel parse (mobi_gop.hip), one lane per CLIP; compiled for the host by the tests.
+// mobi_gop_prepare: start states of every virtual clip -- frame 0 starts from the batch's state ring, frame k + 1 from frame k's start state
+// and frame k's header.  The walk stops at the clip's first idle frame.
+MOBI_ST_FN void mobi_gop_prepare_clip(const MobiGopArgs &A, int c) {
+  const int Kc = A.idle_from ? (int)A.idle_from[c] : A.K; // the clip's live frames
+  if (Kc == 0 || A.P.bit_len[c] == MOBI_DP_SKIP) return; // nothing live / the host parser's clip (all its live entries say so)
+  MobiDevState g = A.ring_in[c];
+  MobiDevState *sin = (MobiDevState *)A.P.state_in;
+  sin[c] = g;
+  const int moflex = A.P.version == 2 /* MOBI_VERSION_MOFLEX3DS */;
+  for (int k = 1; k < Kc; k++) {
+    const size_t v = (size_t)(k - 1) * A.n + c;
+    mobi_gop_next_guess(moflex, A.P.bits + A.P.bit_off[v], A.P.bit_len[v], g); // (the staging area carries 32 zero bytes behind every frame)
+    sin[v + A.n] = g;
+  }
+}
+// mobi_gop_chain, behind the parse kernels: frame by frame, was the start state the true one?  Then what the frame left, merged with what it
+// did not touch, is the true state behind it, and its tail follows from its command list and the tail before (mobi_state.h).  The first frame
+// of a clip that a device parser did not finish, or that started from a wrong prediction, ends the clip's chain: the host parser takes that
+// frame and the live ones behind it over, from state_in[v] -- which this function overwrites with the TRUE start state -- and the tail before
+// it.  The clip's first IDLE frame ends the chain cleanly: its start slot gets the state behind the last live frame, which is also what goes
+// into the batch's state ring; nothing is flagged, nothing goes to the host parser.
+// izz: 80 bytes, the inverse zigzag orders (8x8, then 4x4) of the parse tables.
+MOBI_ST_FN void mobi_gop_chain_clip(const MobiGopArgs &A, int c, const uint8_t *izz) {
+  const int Kc = A.idle_from ? (int)A.idle_from[c] : A.K;
+  if (Kc > 0 && A.P.bit_len[c] == MOBI_DP_SKIP) return; // the host parser's clip
+  MobiDevState *sin = (MobiDevState *)A.P.state_in;
+  const int n_mbs = A.P.mbw * A.P.mbh;
+  MobiDevState cur = A.ring_in[c];
+  const MobiDevTail *tprev = A.rtail_in + c;
+  for (int k = 0; k < Kc; k++) {
+    const size_t v = (size_t)k * A.n + c;
+    MobiDevResult *r = A.P.res + v;
+    if (k > 0 && !mobi_gop_guess_ok(sin[v], cur)) {
+      r->rc = MOBI_GOP_RC_CHAIN;
+      sin[v] = cur;
+      return;
+    }
+    sin[v] = cur; // (equal in everything a parse reads; the carried bytes are now the true ones: a hand-over starts here)
+    if (r->rc != 0) return;
+    const bool iframe = r->frame_type == 1;
+    MobiDevState out = A.P.state_out[v];
+    mobi_gop_merge(cur, iframe, out);
+    A.P.state_out[v] = out;
+    cur = out;
+    // the tail (Internal[90..217], the MV row cache): as mobi_parse_tail, with the tail of the frame before as its input
+    const MbDesc *desc = A.P.desc + v * n_mbs;
+    const uint32_t *pay = A.P.payload + v * A.P.pay_cap; // (pay_local: MbDesc.payload_off counts from the virtual clip's own part)
+    MobiTailScan sc;
+    mobi_tail_scan_init(sc);
+    for (int mb = n_mbs - 1; mb >= 0 && !sc.done; mb--) {
+      const MobiDescQuad d = *(const MobiDescQuad *)(desc + mb);
+      const int nw = (int)(d.z & 0x3FF);
+      if (!nw) continue;
+      const bool intra = (d.y & 1) == MOBI_MB_INTRA;
+      const uint32_t nl = (d.y >> 1) & 0x7F, dual = (d.y >> 26) & 3;
+      const uint32_t woff = d.x + (intra ? MOBI_INTRA_RECORDS : (nl > 1 && !dual) ? MOBI_MV_CELLS : 0);
+      mobi_tail_scan_mb(sc, pay + woff, nw, woff, (d.y >> 14) & 0x3F, izz, izz + 64);
+    }
+    MobiDevTail *tout = A.P.tail_out + v;
+    mobi_tail_finish(sc, pay, A.P.scale + (size_t)(cur.quant & 63) * MOBI_SCALE_STRIDE, *tprev, *tout);
+    if (iframe) // an I-frame does not touch the MV row cache (MD.cs:224-249); a P-frame's was written by the parse kernels
+      for (int i = 0; i < 2 * (A.P.mbw + 2); i++) tout->mvc[i] = tprev->mvc[i];
+    tprev = tout;
+  }
+  if (Kc < A.K) sin[(size_t)Kc * A.n + c] = cur; // the stream ends here
+  A.ring_out[c] = cur;
+  A.rtail_out[c] = *tprev;
+}
 // The intra macroblocks of the group's frames as launch items in WAVEFRONT order (mobi_recon_intra's own format: mobi_kernels.h), built on
 // the device from what the parsers left -- per virtual clip raster-order lists and the descriptors -- behind the host parser's overrides.
 // The raster-order launch (mobi_recon_intra_cl: a wave = the same list slot of four clips, every row polling the rows it depends on) takes

@@ -65,8 +65,11 @@ bool ls_decide(const mobi_batch *b, const DpStaged &st) {
 // the copy calls, which return when the bus is done: 8 ms for the 370 MB of a step of 24576 clips; the others gather) -- r04: gathering and
 // sending were 12 of the 45 ms of such a step, one after the other.
 // resets != nullptr: these clip indices (int32) ride behind the bits, for mobi_reset_state
+// idle != nullptr: (*idle)[i] == 0 marks clip i's slot idle (idle_check): nothing of it is read, gathered or uploaded, its length says
+// MOBI_DP_SKIP to the parse kernels, and the list of these clips rides behind the resets, for mobi_idle_rows
 static int dp_stage(mobi_batch *b, const uint8_t *const *data, const size_t *len, const int32_t *offsets, PinnedBuf &stage, DpStaged &st,
-                    DevBuf *dev = nullptr, bool dev_headroom = false, hipStream_t up = nullptr, const std::vector<int32_t> *resets = nullptr) {
+                    DevBuf *dev = nullptr, bool dev_headroom = false, hipStream_t up = nullptr, const std::vector<int32_t> *resets = nullptr,
+                    const std::vector<uint8_t> *idle = nullptr) {
   const int n = b->n, nd = n, n_mbs = b->g.mbw * b->g.mbh;
   const auto t_stage0 = std::chrono::steady_clock::now();
   constexpr size_t kBitPad = 32; // the reader runs two 8-byte registers ahead
@@ -74,7 +77,9 @@ static int dp_stage(mobi_batch *b, const uint8_t *const *data, const size_t *len
   std::vector<uint32_t> blen(nd);
   size_t pos = 0, max_len = 0;
   const size_t frame_bound = (size_t)n_mbs * 4096 + 64;
+  std::vector<int32_t> idle_list;
   for (int i = 0; i < n; i++) {
+    if (idle && (*idle)[i] == 0) { boff[i] = pos; blen[i] = MOBI_DP_SKIP; idle_list.push_back(i); continue; }
     const int64_t o = offsets[i];
     size_t l = (data[i] && o >= 0 && (uint64_t)o < len[i]) ? len[i] - (size_t)o : 0; // nothing readable: the first ReadU16LE throws
     // MOC5 callers pass the whole file as Data (Form1.cs:292-302).  The reader advances two bytes per refill and refills at most
@@ -92,6 +97,8 @@ static int dp_stage(mobi_batch *b, const uint8_t *const *data, const size_t *len
   pos += 64; // (a skipped clip's offset points at readable bytes too)
   const size_t list_pos = pos, n_reset = resets ? resets->size() : 0;
   pos += align_up(n_reset * 4, 16);
+  const size_t idle_pos = pos;
+  pos += align_up(idle_list.size() * 4, 16);
   const size_t hdr_bytes = align_up((size_t)nd * 12, 16);
   if (hdr_bytes + pos > stage.cap) // pinned memory is slow to allocate: leave room for the longer frames to come
     if (int e = stage.reserve(hdr_bytes + pos + (hdr_bytes + pos) / 4)) return e;
@@ -102,6 +109,9 @@ static int dp_stage(mobi_batch *b, const uint8_t *const *data, const size_t *len
   if (n_reset) memcpy(hs + hdr_bytes + list_pos, resets->data(), n_reset * 4);
   st.reset_off = hdr_bytes + list_pos;
   st.n_reset = (int)n_reset;
+  if (!idle_list.empty()) memcpy(hs + hdr_bytes + idle_pos, idle_list.data(), idle_list.size() * 4);
+  st.idle_off = hdr_bytes + idle_pos;
+  st.n_idle = (int)idle_list.size();
   auto gather = [&](int i) {
     if (blen[i] == MOBI_DP_SKIP) return;
     uint8_t *dst = hs + hdr_bytes + boff[i];
@@ -183,6 +193,16 @@ static int dp_parse(mobi_batch *b, const uint8_t *d_bits, const DpStaged &st, bo
   pa.width = b->g.width; pa.height = b->g.height; pa.stride = b->g.stride; pa.lg = b->g.lg; pa.mbw = b->g.mbw; pa.mbh = b->g.mbh;
   if (b->ktiming && !b->ev_p0) { (void)hipEventCreate(&b->ev_p0.h); (void)hipEventCreate(&b->ev_p1.h); }
   const bool ptime = b->ktiming && b->ev_p0 && b->ev_p1;
+  if (st.n_idle) { // the idle slots' empty rows, and their clips' state carried into the entry the next parse reads (in front of the parse kernels: mobi_idle.hip)
+    MobiIdleArgs ia;
+    memset(&ia, 0, sizeof(ia));
+    ia.clips = (const int32_t *)(d_bits + st.idle_off); ia.count = st.n_idle;
+    ia.n = n; ia.K = 1; ia.n_mbs = n_mbs;
+    ia.desc = pa.desc; ia.res = pa.res;
+    ia.state_in = pa.state_in; ia.state_out = pa.state_out; ia.tail_in = pa.tail_in; ia.tail_out = pa.tail_out;
+    if (mobi_launch_idle_rows(&ia, o.stream) != 0) return MOBI_E_DEVICE;
+    b->idle_launches++;
+  }
   if (ptime) (void)hipEventRecord(b->ev_p0, o.stream);
   if (mobi_launch_parse(&pa, o.stream) != 0) return MOBI_E_DEVICE;
   if (ptime) (void)hipEventRecord(b->ev_p1, o.stream);
@@ -306,6 +326,9 @@ int decode_device_parse(mobi_batch *b, const uint8_t *const *data, const size_t 
     return MOBI_OK; // DecodeFrame() returns before touching the ring (MD.cs:56-61)
   }
   if (b->g.mbw > 64 || b->async_count || b->gop_count) return MOBI_E_ARG; // (asynchronous steps / groups in flight: wait for them first)
+  std::vector<uint8_t> idle; // [clip] 0: an idle slot (mobi_batch_set_idle); empty: none
+  if (int e = idle_check(b, 1, idle)) return e;
+  auto is_idle = [&](int i) { return !idle.empty() && idle[i] == 0; };
   const bool dev_state = b->d_pstate[0] != nullptr; // (before dp_init there is nothing on the device to reset)
   if (int e = dp_init(b)) return e;
   b->mark_hybrid_share();
@@ -314,17 +337,18 @@ int decode_device_parse(mobi_batch *b, const uint8_t *const *data, const size_t 
   const std::vector<int32_t> *resets = dev_state && !b->reset_list.empty() ? &b->reset_list : nullptr;
   std::vector<int> host_clips;
   for (int i = 0; i < n; i++)
-    if (b->on_host[i]) host_clips.push_back(i);
+    if (b->on_host[i] && !is_idle(i)) host_clips.push_back(i);
   DpStaged st;
   using clk = std::chrono::steady_clock;
   const auto q0 = clk::now();
-  if (int e = dp_stage(b, data, len, offsets, b->h_stage, st, &b->d_bits, false, b->stream, resets)) return e; // gathered and on their way
+  if (int e = dp_stage(b, data, len, offsets, b->h_stage, st, &b->d_bits, false, b->stream, resets, idle.empty() ? nullptr : &idle)) return e; // gathered and on their way
   b->phase_ms[0] = ms_since(q0);
   b->lockstep = ls_decide(b, st);
   if (st.n_reset && mobi_launch_reset_state((const int32_t *)(b->d_bits.p + st.reset_off), st.n_reset, n, b->d_pstate[b->ps_cur], b->d_ptail[b->ps_cur], b->stream) != 0)
     return MOBI_E_DEVICE;
   int state_in = 0;
   if (int e = dp_parse(b, b->d_bits.p, st, false, DpOut{&b->d_pdesc, &b->d_ppay, &b->d_pitems, b->d_pres, b->stream}, &state_in)) return e;
+  idle_commit(b, 1, idle);
   reset_commit(b, serial);
   b->phase_ms[1] = ms_since(q0);
   const size_t cap_words = b->last_pay_cap;
@@ -350,7 +374,7 @@ int decode_device_parse(mobi_batch *b, const uint8_t *const *data, const size_t 
   // frames the device parsers could not finish: the host parser takes them over from the state they started with
   std::vector<int> fb;
   for (int i = 0; i < n; i++)
-    if (!b->on_host[i] && res[i].rc != MOBI_OK) fb.push_back(i);
+    if (!b->on_host[i] && !is_idle(i) && res[i].rc != MOBI_OK) fb.push_back(i);
   if (!fb.empty()) {
     if (int e = dp_seed_parsers(b, fb, state_in, b->h_ret, b->stream)) return e; // (the stream is idle: it was waited for above)
     host_parse(fb);
@@ -364,6 +388,7 @@ int decode_device_parse(mobi_batch *b, const uint8_t *const *data, const size_t 
   uint32_t K = 0;
   b->ls_finished = b->lockstep ? 0 : -1;
   for (int i = 0; i < n; i++) {
+    if (is_idle(i)) { rc[i] = MOBI_IDLE; continue; } // (Offset as handed in; Quantizer / YuvFormat stay the last live frame's)
     if (b->on_host[i]) {
       b->dev_quant[i] = b->parsers[i]->quantizer();
       b->dev_yuvfmt[i] = b->parsers[i]->yuv_format();
@@ -471,6 +496,8 @@ int mobi_batch_submit(mobi_batch *b, const uint8_t *const *data, const size_t *l
   if (b->parse_mode == 0) return MOBI_E_ARG; // the decoder state of this batch lives in the host parsers
   if (!b->version_known()) return MOBI_E_VERSION;
   if (b->g.mbw > 64 || b->async_count >= 2 || b->gop_count) return MOBI_E_ARG;
+  std::vector<uint8_t> idle; // [clip] 0: an idle slot (mobi_batch_set_idle); empty: none
+  if (int e = idle_check(b, 1, idle)) return e;
   const bool dev_state = b->d_pstate[0] != nullptr;
   if (int e = dp_init(b)) return e;
   b->mark_hybrid_share();
@@ -483,7 +510,7 @@ int mobi_batch_submit(mobi_batch *b, const uint8_t *const *data, const size_t *l
   if (int e = ensure_stream(b->stream2)) return e;
   if (int e = ensure_stream(b->stream_p)) return e;
   DpStaged st;
-  if (int e = dp_stage(b, data, len, offsets, S.h_stage, st, nullptr, false, nullptr, resets)) return e; // (this slot's previous step was waited for: its upload is done)
+  if (int e = dp_stage(b, data, len, offsets, S.h_stage, st, nullptr, false, nullptr, resets, idle.empty() ? nullptr : &idle)) return e; // (this slot's previous step was waited for: its upload is done)
   if (int e = S.d_pres.reserve(sizeof(MobiDevResult) * n)) return e;
   if (st.bytes > S.d_bits.cap) // growing frees and allocates (a device-wide stall): leave room for the longer frames to come
     if (int e = S.d_bits.reserve(st.bytes + st.bytes / 4)) return e;
@@ -499,10 +526,12 @@ int mobi_batch_submit(mobi_batch *b, const uint8_t *const *data, const size_t *l
   S.host_off.assign(n, 0);
   S.host_quant.assign(n, 0);
   S.host_yuv.assign(n, 0);
+  S.idle.clear();
+  if (!idle.empty()) { S.idle.resize(n); for (int i = 0; i < n; i++) S.idle[i] = idle[i] == 0; }
   // the host parser's clips: parsed now (the caller's bytes are only good during this call), their command lists staged for the copy below
   std::vector<int> host_clips;
   for (int i = 0; i < n; i++)
-    if (b->on_host[i]) host_clips.push_back(i);
+    if (b->on_host[i] && !S.is_idle(i)) host_clips.push_back(i);
   if (!host_clips.empty()) {
     for (int i : host_clips) { S.is_host[i] = 1; S.host_off[i] = offsets[i]; }
     b->pool->run((int)host_clips.size(), [&](int j) {
@@ -556,6 +585,7 @@ int mobi_batch_submit(mobi_batch *b, const uint8_t *const *data, const size_t *l
   if (int e = b->read_faults((int *)S.h_fault.p)) return e;
   HIP_TRY(hipEventRecord(S.ev_done, b->stream));
   poison.armed = false;
+  idle_commit(b, 1, idle);
   reset_commit(b, serial);
   b->async_count++;
   b->async_seq++;
@@ -578,7 +608,7 @@ static int async_repair(mobi_batch *b, mobi_batch::AsyncSlot &S, const std::vect
   std::vector<uint8_t> cascade(k, 0);
   for (int j = 0; j < k; j++) {
     parser[j] = b->parser_at(S.serial, failed[j]);
-    cascade[j] = S1 && b->stale(S.serial, failed[j]) == b->stale(S1->serial, failed[j]);
+    cascade[j] = S1 && b->stale(S.serial, failed[j]) == b->stale(S1->serial, failed[j]) && !S1->is_idle(failed[j]); // (an idle slot behind: nothing to repair there)
   }
   // r06: a batch operation.  The start states in one go, the parses on the pool (a clip's two frames in order), then per affected step ONE
   // reconstruction of the failed clips (recon_clips) -- r05 did all of it clip by clip on the calling thread: a GOP damaged in every clip of a
@@ -634,11 +664,16 @@ int mobi_batch_wait(mobi_batch *b, int32_t *offsets_out, int *rc) {
   const int *fault = (const int *)S.h_fault.p;
   std::vector<int> failed;
   for (int i = 0; i < S.n_dev; i++)
-    if (!S.is_host[i] && res[i].rc != MOBI_OK) failed.push_back(i);
+    if (!S.is_host[i] && !S.is_idle(i) && res[i].rc != MOBI_OK) failed.push_back(i);
   if (!failed.empty())
     if (int e = async_repair(b, S, failed)) { b->poisoned = true; return e; }
   b->ls_finished = S.lockstep ? 0 : -1; // (of the step being reported, not of the one submitted last: ADVICE r05)
   for (int i = 0; i < S.n_dev; i++) {
+    if (S.is_idle(i)) { // (Offset as handed in; Quantizer / YuvFormat stay the last live frame's)
+      rc[i] = MOBI_IDLE;
+      if (offsets_out) offsets_out[i] = S.offs[i];
+      continue;
+    }
     if (S.is_host[i]) {
       rc[i] = S.host_rc[i];
       if (offsets_out) offsets_out[i] = S.host_off[i];

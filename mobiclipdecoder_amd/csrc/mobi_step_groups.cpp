@@ -40,7 +40,7 @@ static int gop_enqueue_parse(mobi_batch *b, mobi_batch::GopSlot &S, hipEvent_t a
   uint32_t *blen = (uint32_t *)(S.h_stage.p + nv * 8);
   DpStaged st;
   for (size_t v = 0; v < nv; v++) {
-    if (S.is_host[v % n]) { blen[v] = MOBI_DP_SKIP; continue; }
+    if (S.is_host[v % n] || (int)(v / n) >= S.live_end((int)(v % n))) { blen[v] = MOBI_DP_SKIP; continue; } // the host parser's clip / an idle slot
     blen[v] = S.lens[v];
     st.n_dev++;
     st.n_iframes += S.lens[v] >= 2 && (S.h_stage.p[S.hdr_bytes + S.boff[v] + 1] & 0x80) != 0;
@@ -84,6 +84,17 @@ static int gop_enqueue_parse(mobi_batch *b, mobi_batch::GopSlot &S, hipEvent_t a
   G.ring_in = b->d_pstate[in]; G.ring_out = b->d_pstate[out];
   G.rtail_in = b->d_ptail[in]; G.rtail_out = b->d_ptail[out];
   G.n = n; G.K = K;
+  if (S.n_idle) { // the idle slots' empty rows, in front of the parse kernels (mobi_idle.hip); their clips' chains end at idle_from (mobi_gop.h)
+    G.idle_from = S.d_bits.p + S.idle_off + align_up((size_t)S.n_idle * 4, 16);
+    MobiIdleArgs ia;
+    memset(&ia, 0, sizeof(ia));
+    ia.clips = (const int32_t *)(S.d_bits.p + S.idle_off); ia.count = S.n_idle;
+    ia.idle_from = G.idle_from;
+    ia.n = n; ia.K = K; ia.n_mbs = b->g.mbw * b->g.mbh;
+    ia.desc = pa.desc; ia.res = pa.res;
+    if (mobi_launch_idle_rows(&ia, ps) != 0) return MOBI_E_DEVICE;
+    b->idle_launches++;
+  }
   if (b->ktiming && !b->ev_p0) { (void)hipEventCreate(&b->ev_p0.h); (void)hipEventCreate(&b->ev_p1.h); }
   const bool ptime = b->ktiming && b->ev_p0 && b->ev_p1;
   if (ptime) (void)hipEventRecord(b->ev_p0, ps);
@@ -110,6 +121,8 @@ int mobi_batch_gop_begin(mobi_batch *b, int n_frames, const uint8_t *const *data
   if (b->parse_mode == 0) return MOBI_E_ARG; // the decoder state of this batch lives in the host parsers (mobi_batch_decode_gop serves those too)
   if (!b->version_known()) return MOBI_E_VERSION;
   if (b->g.mbw > 64 || b->async_count || b->gop_count >= 2 || nv >= ((size_t)1 << 22)) return MOBI_E_ARG;
+  std::vector<uint8_t> idle_from; // [c] first idle frame (mobi_batch_set_idle); empty: the group has no idle slot
+  if (int e = idle_check(b, K, idle_from)) return e;
   const bool dev_state = b->d_pstate[0] != nullptr;
   if (int e = dp_init(b)) return e;
   if (b->gop_count == 0) b->mark_hybrid_share();
@@ -126,9 +139,11 @@ int mobi_batch_gop_begin(mobi_batch *b, int n_frames, const uint8_t *const *data
   S.offs.assign(offsets, offsets + nv);
   size_t pos = 0, max_len = 0;
   const size_t frame_bound = (size_t)n_mbs * 4096 + 64; // (dp_stage: bytes beyond cannot influence the parse of one frame)
+  S.idle_from = idle_from;
   for (size_t v = 0; v < nv; v++) {
     const int64_t o = offsets[v];
-    size_t l = (data[v] && o >= 0 && (uint64_t)o < len[v]) ? len[v] - (size_t)o : 0;
+    const bool idle = !idle_from.empty() && v / n >= idle_from[v % n]; // nothing of an idle slot is read, gathered or uploaded
+    size_t l = (!idle && data[v] && o >= 0 && (uint64_t)o < len[v]) ? len[v] - (size_t)o : 0;
     l = std::min(l, frame_bound);
     max_len = std::max(max_len, l);
     S.boff[v] = pos;
@@ -138,6 +153,11 @@ int mobi_batch_gop_begin(mobi_batch *b, int n_frames, const uint8_t *const *data
   pos += 64;
   const size_t list_pos = pos, n_reset = dev_state ? b->reset_list.size() : 0; // the clips reset from this group on, behind the bits
   pos += align_up(n_reset * 4, 16);
+  std::vector<int32_t> idle_list; // the clips with an idle slot, then idle_from[n]: for mobi_idle_rows, mobi_gop_prepare and mobi_gop_chain
+  for (int c = 0; c < n && !idle_from.empty(); c++)
+    if (idle_from[c] < K) idle_list.push_back(c);
+  const size_t idle_pos = pos;
+  if (!idle_list.empty()) pos += align_up(idle_list.size() * 4, 16) + align_up((size_t)n, 16);
   const size_t hdr_bytes = align_up(nv * 12, 16), need = hdr_bytes + pos;
   if (need > S.h_stage.cap)
     if (int e = S.h_stage.reserve(need + need / 4)) return e;
@@ -149,6 +169,12 @@ int mobi_batch_gop_begin(mobi_batch *b, int n_frames, const uint8_t *const *data
   if (n_reset) memcpy(hs + hdr_bytes + list_pos, b->reset_list.data(), n_reset * 4);
   S.reset_off = hdr_bytes + list_pos;
   S.n_reset = (int)n_reset;
+  S.idle_off = hdr_bytes + idle_pos;
+  S.n_idle = (int)idle_list.size();
+  if (S.n_idle) {
+    memcpy(hs + S.idle_off, idle_list.data(), idle_list.size() * 4);
+    memcpy(hs + S.idle_off + align_up(idle_list.size() * 4, 16), idle_from.data(), (size_t)n);
+  }
   S.hdr_bytes = hdr_bytes; S.bytes = need; S.max_len = max_len;
   auto gather = [&](size_t v) {
     uint8_t *dst = hs + hdr_bytes + S.boff[v];
@@ -187,6 +213,7 @@ int mobi_batch_gop_begin(mobi_batch *b, int n_frames, const uint8_t *const *data
   // the group is handed over: the pending resets' host side now (the routing its parse is enqueued with, here or in the finish in front)
   S.serial = b->handover + 1;
   reset_apply_host(b, S.serial);
+  idle_commit(b, K, idle_from);
   reset_commit(b, S.serial);
   b->gop_count++;
   if (b->gop_count == 1) // nothing in front: the parse may start at once (else mobi_batch_gop_finish of the group in front enqueues it, once it knows whose clips are whose)
@@ -201,7 +228,7 @@ static void gop_host_parse(mobi_batch *b, mobi_batch::GopSlot &S, const std::vec
   auto &host_from = S.host_from, &hslot = S.hslot, &hrc = S.hrc; auto &hoff = S.hoff; auto &hq = S.hq, &hy = S.hy; auto &hready = S.hready;
   b->pool->run((int)cl.size(), [&](int j) {
     const int c = cl[j];
-    for (int k = host_from[c]; k < K; k++) {
+    for (int k = host_from[c], ke = S.live_end(c); k < ke; k++) { // (the pool skips the clip's idle frames)
       const size_t v = (size_t)k * n + c;
       int32_t off = 0;
       MobiStreamParser *p = b->parser_at(S.serial, c); // (the group's stream: a reset handed over with the group behind it left it retired)
@@ -239,7 +266,7 @@ static int gop_device_results(mobi_batch *b, mobi_batch::GopSlot &S, const std::
   const MobiDevResult *res = (const MobiDevResult *)S.h_res.p;
   for (int c = 0; c < n; c++) {
     if (S.is_host[c]) continue;
-    for (int k = 0; k < K; k++)
+    for (int k = 0, ke = S.live_end(c); k < ke; k++)
       if (res[(size_t)k * n + c].rc != MOBI_OK) { host_from[c] = k; fb.push_back(c); break; }
   }
   if (!fb.empty()) { // hand-overs: the state the first unfinished frame started from (mobi_gop_chain left the true one in its start slot) and the tail before it
@@ -282,7 +309,7 @@ static int gop_overrides(mobi_batch *b, mobi_batch::GopSlot &S, const std::vecto
     std::vector<const ParsedFrame *> fr;
     std::vector<int> rcs;
     for (int c : all_host)
-      if (host_from[c] <= k) {
+      if (host_from[c] <= k && k < S.live_end(c)) { // (an idle frame's rows are mobi_idle_rows')
         const size_t v = (size_t)k * n + c;
         cl.push_back(c);
         rcs.push_back(hrc[v]);
@@ -314,6 +341,7 @@ static int gop_sort(mobi_batch *b, mobi_batch::GopSlot &S) {
       uint64_t sum = 0;
       for (int c = 0; c < n; c++) {
         const size_t v = (size_t)k * n + c;
+        if (k >= S.live_end(c)) continue; // (the sort counts nothing for an idle slot)
         sum += k >= host_from[c] ? (hrc[v] == MOBI_OK ? b->gop_frames[(size_t)hslot[c] * K + k].hdr.n_intra : 0u) : res[v].n_intra;
       }
       S.sorted_items[k] = sum ? (uint32_t)(align_up(sum, 4) + 3 * MOBI_SORT_LEVELS + 4) & ~3u : 0u; // (every wavefront starts on a wave of four: at most three rows of padding each)
@@ -351,6 +379,7 @@ static int gop_recon_part(mobi_batch *b, mobi_batch::GopSlot &S, int k0, int k1)
     uint32_t Kint = 0;
     for (int c = 0; c < n; c++) {
       const size_t v = kn + c;
+      if (k >= S.live_end(c)) continue;
       if (k >= host_from[c]) { if (hrc[v] == MOBI_OK) Kint = std::max(Kint, b->gop_frames[(size_t)hslot[c] * K + k].hdr.n_intra); }
       else Kint = std::max(Kint, res[v].n_intra);
     }
@@ -380,7 +409,7 @@ static int gop_return_clips(mobi_batch *b, mobi_batch::GopSlot &S) {
   for (int c : all_host) {
     if (b->host_share[c] || b->stale(S.serial, c)) continue;
     int run = b->clean_run[c]; // consecutive frames the device parsers would have finished too
-    for (int k = host_from[c]; k < K; k++) run = hready[(size_t)k * n + c] ? run + 1 : 0;
+    for (int k = host_from[c], ke = S.live_end(c); k < ke; k++) run = hready[(size_t)k * n + c] ? run + 1 : 0;
     b->clean_run[c] = (uint16_t)std::min(60000, run);
     if (run >= b->clean_need[c]) back.push_back(c);
   }
@@ -419,6 +448,11 @@ static void gop_report(mobi_batch *b, mobi_batch::GopSlot &S, int k0, int k1, in
   for (int k = k0; k < k1; k++)
     for (int c = 0; c < n; c++) {
       const size_t v = (size_t)k * n + c, o = (size_t)(k - k0) * n + c; // (the part's results count from its first frame)
+      if (k >= S.live_end(c)) { // an idle slot: Offset as handed in
+        rc[o] = MOBI_IDLE;
+        if (offsets_out) offsets_out[o] = S.offs[v];
+        continue;
+      }
       if (k >= host_from[c]) {
         rc[o] = hrc[v];
         if (offsets_out) offsets_out[o] = hoff[v];
@@ -428,7 +462,7 @@ static void gop_report(mobi_batch *b, mobi_batch::GopSlot &S, int k0, int k1, in
         if (offsets_out) offsets_out[o] = S.offs[v] + (int32_t)res[v].consumed;
       }
       rc[o] = fault_rc(rc[o], fault[v]);
-      if (k == k1 - 1) {
+      if (k == std::min(k1, S.live_end(c)) - 1) { // (behind the part's last LIVE frame of the clip)
         b->dev_quant[c] = k >= host_from[c] ? hq[v] : res[v].quant;
         b->dev_yuvfmt[c] = k >= host_from[c] ? hy[v] : res[v].yuvfmt;
       }
@@ -496,8 +530,14 @@ int mobi_batch_decode_gop(mobi_batch *b, int n_frames, const uint8_t *const *dat
   const int n = b->n;
   if (b->parse_auto) settle_parse_mode(b, b->frames_started == 0, (size_t)n * n_frames, false); // as mobi_batch_decode chooses, with the lanes a group offers counted: n_clips * n_frames
   if (b->parse_mode == 0 || (size_t)n * n_frames >= ((size_t)1 << 22) || !b->version_known()) {
-    for (int k = 0; k < n_frames; k++) // the host parser's batch (or a version no parser knows): K calls, the same results
+    std::vector<uint8_t> idle_from, mask;
+    if (int e = idle_check(b, n_frames, idle_from)) return e; // the group's idle mask: checked as a whole before anything changes, then row by row
+    if (b->idle_frames) mask.swap(b->idle_mask);
+    b->idle_frames = 0;
+    for (int k = 0; k < n_frames; k++) { // the host parser's batch (or a version no parser knows): K calls, the same results
+      if (!idle_from.empty() && mobi_batch_set_idle(b, mask.data() + (size_t)k * n, 1) != MOBI_OK) return MOBI_E_DEVICE;
       if (int e = mobi_batch_decode(b, data + (size_t)k * n, len + (size_t)k * n, offsets + (size_t)k * n, rc + (size_t)k * n)) return e;
+    }
     return MOBI_OK;
   }
   if (int e = mobi_batch_gop_begin(b, n_frames, data, len, offsets)) return e;

@@ -13,9 +13,12 @@ int mobi_batch_decode(mobi_batch *b, const uint8_t *const *data, const size_t *l
   if (b->gop_count) return MOBI_E_ARG; // (groups in flight: mobi_batch_gop_finish first)
   settle_parse_mode(b, b->frames_started == 0, (size_t)b->n, false, data, len, offsets);
   if (b->parse_mode) return decode_device_parse(b, data, len, offsets, rc);
+  std::vector<uint8_t> idle; // [clip] 0: an idle slot (mobi_batch_set_idle): the pool skips the clip, its command list is empty; empty: none
+  if (int e = idle_check(b, 1, idle)) return e;
   { // clips reset since the last step: a new parser each (parse mode 0 keeps no decoder state on the device)
     const uint64_t serial = b->handover + 1;
     reset_apply_host(b, serial);
+    idle_commit(b, 1, idle);
     reset_commit(b, serial);
   }
   const int n = b->n;
@@ -69,6 +72,7 @@ int mobi_batch_decode(mobi_batch *b, const uint8_t *const *data, const size_t *l
       j -= n_up;
       if (j < n_stage) { stage_range(s0 + (int)((long)(s1 - s0) * j / n_stage), s0 + (int)((long)(s1 - s0) * (j + 1) / n_stage)); return; }
       const int i = c0 + (j - n_stage);
+      if (!idle.empty() && idle[i] == 0) { rc[i] = MOBI_IDLE; return; }
       rc[i] = parse_host(b->parsers[i].get(), data[i], len[i], &offsets[i], b->cur[i]);
     });
     parse_ms += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();

@@ -34,6 +34,7 @@ class MobiclipError(RuntimeError):
 
 
 MOBI_E_ARG = -7  # include/mobiclip_hip.h
+MOBI_IDLE = 1  # rc of a frame slot marked idle (MobiclipBatch.set_idle): not an error
 
 
 # names must match include/mobiclip_hip.h (tests/test_abi_symbols.py checks the header against the .so)
@@ -78,6 +79,9 @@ _SIGS = {
     "mobi_batch_lockstep_finished": (C.c_int, [C.c_void_p]),
     "mobi_batch_reset_clips": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int]),
     "mobi_batch_clip_frames": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "mobi_batch_set_idle": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "mobi_batch_clip_idle": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "mobi_batch_idle_launches": (C.c_int, [C.c_void_p]),
     "mobi_batch_last_decode_ms": (C.c_float, [C.c_void_p]),
     "mobi_batch_motion_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "mobi_batch_stride": (C.c_int, [C.c_void_p]),
@@ -139,7 +143,12 @@ def error_string(rc):
     return load_library().mobi_error_string(rc).decode()
 
 
+_NO_DATA = np.zeros(0, np.uint8)
+
+
 def _as_u8(data):
+    if data is None:  # an idle slot (MobiclipBatch.set_idle): a NULL pointer for the library
+        return _NO_DATA
     a = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data
     if a.dtype != np.uint8:
         a = a.view(np.uint8)
@@ -338,7 +347,7 @@ class MobiclipBatch:
         """One DecodeFrame() per clip.  datas: list of byte buffers; offsets: list of ints.
         Returns (rc list, new offsets list)."""
         bufs = [_as_u8(d) for d in datas]
-        ptrs = (C.c_void_p * self.n)(*[b.ctypes.data for b in bufs])
+        ptrs = (C.c_void_p * self.n)(*[None if b is _NO_DATA else b.ctypes.data for b in bufs])
         lens = (C.c_size_t * self.n)(*[b.size for b in bufs])
         offs = (C.c_int32 * self.n)(*[int(o) for o in offsets])
         rcs = (C.c_int * self.n)()
@@ -351,7 +360,7 @@ class MobiclipBatch:
         """Asynchronous decode(): enqueue one frame step (device parse only, at most two in flight); the buffers may be reused at
         once.  Results come from wait(), oldest step first."""
         bufs = [_as_u8(d) for d in datas]
-        ptrs = (C.c_void_p * self.n)(*[b.ctypes.data for b in bufs])
+        ptrs = (C.c_void_p * self.n)(*[None if b is _NO_DATA else b.ctypes.data for b in bufs])
         lens = (C.c_size_t * self.n)(*[b.size for b in bufs])
         offs = (C.c_int32 * self.n)(*[int(o) for o in offsets])
         e = self._lib.mobi_batch_submit(self._h, ptrs, lens, offs)
@@ -362,9 +371,13 @@ class MobiclipBatch:
     def _gop_arrays(self, frames, offsets):
         """frames[k][c] = byte buffer of frame k of clip c; offsets[k][c] (or None: all 0) -> the C arrays, [k * n + c]"""
         K = len(frames)
+        for k, fr in enumerate(frames):
+            if len(fr) != self.n:
+                raise ValueError(f"frames[{k}] has {len(fr)} entries, the batch has {self.n} clips")
+        if offsets is not None and (len(offsets) != K or any(len(row) != self.n for row in offsets)):
+            raise ValueError(f"offsets must have the shape of frames: {K} rows of {self.n}")
         bufs = [_as_u8(d) for fr in frames for d in fr]
-        assert len(bufs) == K * self.n
-        ptrs = (C.c_void_p * (K * self.n))(*[b.ctypes.data for b in bufs])
+        ptrs = (C.c_void_p * (K * self.n))(*[None if b is _NO_DATA else b.ctypes.data for b in bufs])
         lens = (C.c_size_t * (K * self.n))(*[b.size for b in bufs])
         flat = [0] * (K * self.n) if offsets is None else [int(o) for row in offsets for o in row]
         offs = (C.c_int32 * (K * self.n))(*flat)
@@ -438,9 +451,42 @@ class MobiclipBatch:
         if e != 0:
             raise MobiclipError(error_string(e))
 
+    def set_idle(self, mask):
+        """Mark frame slots of the NEXT step or group handed over as idle: "this clip has no frame here, its stream has ended".  mask:
+        array-like [K][n] (groups) or [n] (decode / submit), nonzero = idle; None drops a mask not consumed yet.  An idle slot is not
+        parsed, changes no decoder state and writes no pixel; its rc is MOBI_IDLE and its entry in datas / frames may be None.  The idle
+        slots of a clip are a suffix of a group, and the clip takes live frames again only after reset_clips (mobiclip_hip.h,
+        mobi_batch_set_idle)."""
+        if mask is None:
+            e = self._lib.mobi_batch_set_idle(self._h, None, 0)
+        else:
+            m = np.asarray(mask)
+            if m.ndim == 1:
+                m = m.reshape(1, -1)
+            if m.ndim != 2 or m.shape[1] != self.n or not 1 <= m.shape[0] <= 128:
+                raise ValueError(f"an idle mask is [K][{self.n}] or [{self.n}], 1 <= K <= 128, not {np.asarray(mask).shape}")
+            m = np.ascontiguousarray(m != 0, dtype=np.uint8)
+            e = self._lib.mobi_batch_set_idle(self._h, m.ctypes.data, int(m.shape[0]))
+        if e != 0:
+            raise MobiclipError(error_string(e))
+
+    def clip_idle(self):
+        """int32[n]: idle slots handed over per clip since its last live frame or reset (steps and groups in flight included).  Ring
+        index r of clip c holds a picture of its current stream iff clip_idle()[c] <= r < min(6, clip_idle()[c] + clip_frames()[c])."""
+        out = np.zeros(self.n, np.int32)
+        e = self._lib.mobi_batch_clip_idle(self._h, out.ctypes.data_as(C.POINTER(C.c_int32)))
+        if e != 0:
+            raise MobiclipError(error_string(e))
+        return out
+
+    def idle_launches(self):
+        """launches of the idle-slot kernel so far (0 for a batch that never had an idle slot)"""
+        return self._lib.mobi_batch_idle_launches(self._h)
+
     def clip_frames(self):
-        """int32[n]: frames handed over per clip since the batch was created or the clip was last reset (steps in flight and every
-        frame of a finished group part count); ring index r of clip c holds the current stream's picture iff r < min(6, that)."""
+        """int32[n]: LIVE frames handed over per clip since the batch was created or the clip was last reset (steps in flight and every
+        frame of a finished group part count; idle slots do not); without idle slots ring index r of clip c holds the current stream's
+        picture iff r < min(6, that) -- clip_idle() has the general rule."""
         out = np.zeros(self.n, np.int32)
         e = self._lib.mobi_batch_clip_frames(self._h, out.ctypes.data_as(C.POINTER(C.c_int32)))
         if e != 0:

@@ -3,12 +3,13 @@
 
 4096 Moflex3DS 640x480 clips, each a stream of 12..96 frames (a prefix of one of --pool generated streams: every one starts with an
 I-frame).  Pipelined groups of K = 6 frames (gop_begin(g + 1) before gop_finish(g)).  A clip whose stream ends inside a group decodes empty
-packets for the rest of it (idle frame slots); before the next group is begun it is reset and handed its next stream.  Reported: Gpixels/s
+packets for the rest of it -- or, with --idle, has those slots marked idle (mobi_batch_set_idle: not parsed, not handed to the host parser;
+same seed, same streams, same resets) --; before the next group is begun it is reset and handed its next stream.  Reported: Gpixels/s
 of live frames, the share of idle frame slots, the host time of the reset calls; --equal feeds every clip streams of one length, a
 multiple of K (no idle slot; every clip is reset at the same boundaries).  The kernel's time comes from a rocprofv3 --kernel-trace --stats
 run of this script (mobi_reset_state in its stats).
 
-  python tools/exp_refill.py [--clips 4096] [--groups 40] [--equal] [--out profiles/refill_runs.jsonl]
+  python tools/exp_refill.py [--clips 4096] [--groups 40] [--equal] [--idle] [--label NAME] [--out profiles/refill_runs.jsonl]
 """
 import argparse
 import json
@@ -34,6 +35,8 @@ def main():
     ap.add_argument("--max-len", type=int, default=96)
     ap.add_argument("--equal", action="store_true", help="every stream --equal-len frames long")
     ap.add_argument("--equal-len", type=int, default=54)
+    ap.add_argument("--idle", action="store_true", help="mark the ended clips' slots idle instead of feeding them empty packets")
+    ap.add_argument("--label", default=None, help="copied into the result line (which build, which leg)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     W, H, n, K = 640, 480, a.clips, a.k
@@ -70,6 +73,10 @@ def main():
             length[ended] = [new_len() for _ in range(ended.size)]
             pos[ended] = 0
         frames = []
+        if a.idle:
+            mask = pos[None, :] + np.arange(K)[:, None] >= length[None, :]
+            if mask.any():
+                b.set_idle(mask)
         for k in range(K):
             row = []
             for c in range(n):
@@ -78,7 +85,7 @@ def main():
                     row.append(pool[src[c]][f])
                     live_frames += 1
                 else:
-                    row.append(empty)
+                    row.append(None if a.idle else empty)
                     idle_slots += 1
             frames.append(row)
         pos[:] = np.minimum(pos + K, length)
@@ -106,8 +113,10 @@ def main():
     while pending:
         finish()
     dt = time.perf_counter() - t0
+    host_clips_end = b.host_clips()
+    b_idle_launches = b.idle_launches() if hasattr(b, "idle_launches") else None
     b.close()
-    out = {"clips": n, "K": K, "groups": a.groups, "equal": a.equal, "lengths": [a.equal_len] * 2 if a.equal else [a.min_len, a.max_len],
+    out = {"label": a.label, "idle_mask": a.idle, "idle_launches": b_idle_launches, "host_clips_end": host_clips_end, "clips": n, "K": K, "groups": a.groups, "equal": a.equal, "lengths": [a.equal_len] * 2 if a.equal else [a.min_len, a.max_len],
            "live_gpixels_s": round(live_frames * W * H / dt / 1e9, 3), "frame_slots_s": round((live_frames + idle_slots) / dt, 1),
            "idle_share": round(idle_slots / max(1, live_frames + idle_slots), 4), "wall_s": round(dt, 3),
            "reset_calls": reset_calls, "reset_clips": reset_clips, "max_clips_per_reset": max_reset,
