@@ -259,6 +259,10 @@ __device__ __forceinline__ void idct_pass2_q(const int *t, bool is8, int r, uint
 // long as no intermediate leaves int16, and every intermediate of a pass is a sum of inputs with coefficients of magnitude <= 3/2 (plus
 // the truncation of at most a handful of shifts), so after both passes |x| <= 9/4 * (sum of |coefficient| of the area + 32) + 104.  The
 // scatter adds up |coefficient| per area (P_SUM); an octet with an area above MOBI_PK_LIMIT takes the 32-bit rounds instead (wave-uniform).
+// The bound is checked, not only argued: tests/test_residual_edges.py runs both passes in int64 and with every intermediate wrapped to int16,
+// in the operation order of bfly8_pk / bfly4_pk.  The first sum at which the two differ is 14549 (one coefficient at row 1, column 1); at
+// 14000 nothing differs.  No block the reference decodes was found to differ at any sum: the limit guards frames the reference REJECTS,
+// whose wrapped residuals could land back inside the clamp table's domain and come back as pixels.
 #define MOBI_PK_LIMIT 14000 /* 9/4 * (14000 + 32) + 104 = 31676 < 32768 */
 // (r05, measured and not kept: the same bound says when the clamp table CANNOT be left -- sums below 1700 give |x >> 6| <= 64 -- and an octet
 // of such areas could run its pixel update without the sixteen packed min / max per lane that track the range; with the second copy of the

@@ -9,8 +9,11 @@
 #include "mobi_streamgen.h"
 #include "mobi_tables.h"
 
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <map>
+#include <utility>
 #include <vector>
 
 namespace {
@@ -501,6 +504,52 @@ struct Gen {
       }
     }
   }
+
+  // ------------------------------------------------------------ scripted P-frames (mobi_gen_clip_scripted)
+  typedef std::map<std::pair<int, int>, std::vector<mobi_gen_script_tok>> TokMap; // (macroblock, block) -> tokens by position
+  // one coded block: the script's levels instead of gen_block's draw (and no retry loop: the residuals are whatever they are)
+  void put_block_scripted(const std::vector<mobi_gen_script_tok> &t) {
+    int prev = -1;
+    for (size_t i = 0; i < t.size(); i++) {
+      Sym s{i + 1 == t.size(), t[i].pos - prev - 1, t[i].level};
+      put_sym(s, std::abs(t[i].level) >= 32 ? 3 : t[i].form);
+      prev = t[i].pos;
+    }
+  }
+  void put_area_scripted(const mobi_gen_script_mb &m, int k, const TokMap &tm) {
+    if ((m.t8 >> k) & 1) { bw.put(1, 1); put_block_scripted(tm.at({m.mb, 4 * k})); return; } // loc_11652C / sub_116508
+    const int m4 = m.cbp4[k];
+    if (m.intra) bw.ue(m4 == 0 ? 2 : inv_cbp4_intra[m4]); else bw.ue(inv_cbp4_inter[m4]);
+    for (int q = 0; q < 4; q++) if ((m4 >> q) & 1) put_block_scripted(tm.at({m.mb, 4 * k + q}));
+  }
+  void gen_pframe_scripted(int dq, const std::map<int, mobi_gen_script_mb> &mbs, const TokMap &tm) {
+    bw.put(0, 1);
+    bw.se(dq);
+    if (ver == 0) { if (quant == 0) setup_quant(0); else if (dq) setup_quant(quant + dq); }
+    else if (dq) setup_quant(quant + dq);
+    vlc_table = 0;
+    for (int mb = 0; mb < mbw * mbh; mb++) { // every vector is (0, 0): so is every predictor
+      mobi_gen_script_mb none;
+      memset(&none, 0, sizeof(none));
+      none.mb = mb;
+      auto it = mbs.find(mb);
+      const mobi_gen_script_mb &m = it == mbs.end() ? none : it->second;
+      if (m.intra) { // DecIntraFullBlockPMode, MD.cs:1759-1786, mode 3 = DC
+        bw.put(pinv[0].code[6], pinv[0].nbits[6]);
+        bw.ue(inv_cbp_intra[m.cbp]);
+        bw.put(3, 3);
+        for (int k = 0; k < 4; k++) if ((m.cbp >> k) & 1) put_area_scripted(m, k, tm);
+        bw.put(3, 3);
+        for (int k = 4; k < 6; k++) if ((m.cbp >> k) & 1) put_area_scripted(m, k, tm);
+      } else {
+        bw.put(pinv[0].code[1], pinv[0].nbits[1]);
+        bw.se(0);
+        bw.se(0);
+        bw.ue(inv_cbp_inter[m.cbp]);
+        for (int k = 0; k < 6; k++) if ((m.cbp >> k) & 1) put_area_scripted(m, k, tm);
+      }
+    }
+  }
 };
 
 } // namespace
@@ -533,6 +582,76 @@ extern "C" int64_t mobi_gen_clip(const mobi_gen_params *p, uint8_t *out, size_t 
     g.bw = BitWriter();
     bool iframe = (f == 0) || (p->iframe_interval > 0 && f % p->iframe_interval == 0);
     if (iframe) g.gen_iframe(); else g.gen_pframe();
+    g.bw.align();
+    g.frames_done++;
+    size_t n = g.bw.out.size();
+    if (out && total + n <= cap) memcpy(out + total, g.bw.out.data(), n);
+    total += n;
+  }
+  if (frame_off) frame_off[p->n_frames] = (uint32_t)total;
+  if (total > cap) return -(int64_t)total;
+  return (int64_t)total;
+}
+
+extern "C" int64_t mobi_gen_clip_scripted(const mobi_gen_params *p, const int32_t *frame_qdelta, const mobi_gen_script_mb *mbs, int32_t n_mbs,
+                                          const mobi_gen_script_tok *toks, int32_t n_toks, uint8_t *out, size_t cap, uint32_t *frame_off) {
+  if (!p || p->width == 0 || p->height == 0 || (p->width & 15) || (p->height & 15) || p->width > 1024) return -1;
+  if (p->version != 1 && p->version != 2) return -1;
+  if (p->quantizer < 12 || p->quantizer > 52 || p->n_frames < 1) return -1;
+  if (n_mbs < 0 || n_toks < 0 || (n_mbs && !mbs) || (n_toks && !toks)) return -1;
+  const int n_mb = (int)(p->width / 16) * (int)(p->height / 16);
+  auto is_iframe = [&](int f) { return f == 0 || (p->iframe_interval > 0 && f % p->iframe_interval == 0); };
+  // the script, frame by frame, checked: a coded block has tokens, a token has a coded block, positions are distinct and in range
+  std::vector<std::map<int, mobi_gen_script_mb>> fm(p->n_frames);
+  std::vector<Gen::TokMap> ft(p->n_frames);
+  for (int i = 0; i < n_mbs; i++) {
+    const mobi_gen_script_mb &m = mbs[i];
+    if (m.frame < 0 || m.frame >= p->n_frames || is_iframe(m.frame) || m.mb < 0 || m.mb >= n_mb || (m.intra & ~1) || (m.cbp & ~63) || (m.t8 & ~63)) return -1;
+    for (int k = 0; k < 6; k++)
+      if (((m.cbp >> k) & 1) && !((m.t8 >> k) & 1) && (m.cbp4[k] < (m.intra ? 0 : 1) || m.cbp4[k] > 15)) return -1;
+    if (!fm[m.frame].emplace(m.mb, m).second) return -1;
+  }
+  for (int i = 0; i < n_toks; i++) {
+    const mobi_gen_script_tok &t = toks[i];
+    if (t.frame < 0 || t.frame >= p->n_frames || t.block < 0 || t.block >= 24 || t.level == 0 || t.level < -2048 || t.level > 2047 || t.form < 0 || t.form > 3) return -1;
+    auto it = fm[t.frame].find(t.mb);
+    if (it == fm[t.frame].end()) return -1;
+    const mobi_gen_script_mb &m = it->second;
+    const int k = t.block >> 2, q = t.block & 3;
+    if (!((m.cbp >> k) & 1)) return -1;
+    const bool is8 = (m.t8 >> k) & 1;
+    if (is8 ? q != 0 : !((m.cbp4[k] >> q) & 1)) return -1;
+    if (t.pos < 0 || t.pos >= (is8 ? 64 : 16)) return -1;
+    ft[t.frame][{t.mb, t.block}].push_back(t);
+  }
+  for (int f = 0; f < p->n_frames; f++) {
+    for (auto &kv : ft[f]) {
+      auto &v = kv.second;
+      std::sort(v.begin(), v.end(), [](const mobi_gen_script_tok &a, const mobi_gen_script_tok &b) { return a.pos < b.pos; });
+      for (size_t i = 1; i < v.size(); i++) if (v[i].pos == v[i - 1].pos) return -1;
+    }
+    for (auto &kv : fm[f]) {
+      const mobi_gen_script_mb &m = kv.second;
+      for (int k = 0; k < 6; k++) {
+        if (!((m.cbp >> k) & 1)) continue;
+        const int m4 = ((m.t8 >> k) & 1) ? 1 : m.cbp4[k];
+        for (int q = 0; q < 4; q++) if (((m4 >> q) & 1) && !ft[f].count({m.mb, 4 * k + q})) return -1;
+      }
+    }
+  }
+  Gen g(*p);
+  size_t total = 0;
+  long q = p->quantizer;
+  for (int f = 0; f < p->n_frames; f++) {
+    if (frame_off) frame_off[f] = (uint32_t)total;
+    g.bw = BitWriter();
+    if (is_iframe(f)) g.gen_iframe();
+    else {
+      const int dq = frame_qdelta ? frame_qdelta[f] : 0;
+      q += dq;
+      if (q < 12 || q > 52) return -1;
+      g.gen_pframe_scripted(dq, fm[f], ft[f]);
+    }
     g.bw.align();
     g.frames_done++;
     size_t n = g.bw.out.size();

@@ -57,6 +57,33 @@ void mobi_gen_default_params(mobi_gen_params *p, int config, uint64_t seed);
  * or -(needed bytes) when cap is too small, or -1 on bad parameters. */
 int64_t mobi_gen_clip(const mobi_gen_params *p, uint8_t *out, size_t cap, uint32_t *frame_off);
 
+/* ---- scripted P-frames: exact levels at exact scan positions (tests/test_residual_edges.py) ----
+ * mobi_gen_clip draws its residual blocks and redraws them until every residual is within +-64; streams at the edges of the residual
+ * stage (coefficient sums at the kernels' 16-bit limit, prediction + residual at the ends of the clamp table's domain, raw 12-bit
+ * levels) have to be written down instead.  Frame 0 (and every iframe_interval-th frame) is the I-frame mobi_gen_clip would begin with;
+ * every other frame is a P-frame made of the script's macroblocks.  A macroblock no entry names is inter 16x16, vector (0, 0),
+ * reference 1, nothing coded: it copies the frame before. */
+typedef struct mobi_gen_script_mb {
+  int32_t frame;   /* index of a P-frame of the clip */
+  int32_t mb;      /* macroblock, raster order */
+  int32_t intra;   /* 0: inter 16x16, vector (0, 0), reference 1;  1: intra, DC prediction for luma and chroma (DecIntraFullBlockPMode) */
+  int32_t cbp;     /* coded areas, bit k = area k: 0..3 the luma quadrants, 4 = U, 5 = V */
+  int32_t t8;      /* bit k: area k is one 8x8 transform; else 4x4 blocks */
+  int32_t cbp4[6]; /* an area of 4x4 blocks: which of the four are coded (inter: 1..15, intra: 0..15) */
+} mobi_gen_script_mb;
+typedef struct mobi_gen_script_tok {
+  int32_t frame, mb;
+  int32_t block;   /* area * 4 + the 4x4 block inside it (0 for an 8x8 transform) */
+  int32_t pos;     /* scan position: 0..63 or 0..15 */
+  int32_t level;   /* -2048..2047, not 0 */
+  int32_t form;    /* how the token is written: 0 = shortest, 1..3 = what escape_prob forces (3 = raw 12-bit); |level| >= 32 is always raw */
+} mobi_gen_script_tok;
+
+/* As mobi_gen_clip.  frame_qdelta: NULL or n_frames quantizer deltas (read for P-frames; the sum must stay in 12..52).  Every coded block
+ * needs at least one token and every token a coded block; tokens may come in any order.  -1 also for a script that breaks these rules. */
+int64_t mobi_gen_clip_scripted(const mobi_gen_params *p, const int32_t *frame_qdelta, const mobi_gen_script_mb *mbs, int32_t n_mbs,
+                               const mobi_gen_script_tok *toks, int32_t n_toks, uint8_t *out, size_t cap, uint32_t *frame_off);
+
 #ifdef __cplusplus
 }
 #endif
