@@ -1,6 +1,7 @@
 // mobi_dparse.hip -- device-side bitstream parser for gfx950: one wave per clip.
 //
-// Same syntax walk as mobi_parse.cpp (which cites MobiclipDecoder.cs, "MD.cs", line by line): bit reader (:2970-3015),
+// Same syntax walk as mobi_parse.cpp (which cites MobiclipDecoder.cs, "MD.cs", line by line; what both know about the format's leaves and
+// the command list's words is mobi_syntax.h): bit reader (:2970-3015),
 // frame headers (:113-143, :224-236), MV prediction (:163-208), partition tree (:469-1746), residual CBP/VLC
 // (:1818-1833, :2909-2968, :3330-3432), intra macroblock syntax (:1759-1880, :2776-2902).  The parse of one clip is a
 // chain of data-dependent reads, so a wave runs it on ONE lane; the machine is filled by clips instead (8 waves per SIMD
@@ -26,6 +27,7 @@
 #include "../../include/mobiclip_hip.h"
 #include "mobi_dparse.h"
 #include "mobi_kernels.h"
+#include "mobi_syntax.h"
 
 namespace {
 enum { PWAVES = 4 }; // clips per workgroup: they share one LDS copy of the tables
@@ -38,16 +40,13 @@ struct WaveLds { // private to one wave = one clip
   uint8_t mcache[40];              // Internal[0..9]
 };
 
-__device__ __forceinline__ uint32_t shl(uint32_t x, int n) { return x << (n & 31); } // C# masks shift counts to 5 bits
-__device__ __forceinline__ uint32_t shr(uint32_t x, int n) { return x >> (n & 31); }
-__device__ __forceinline__ int clz32(uint32_t v) { return v ? __builtin_clz(v) : 32; }
 __device__ __forceinline__ int imin(int a, int b) { return a < b ? a : b; }
 __device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }
 
 typedef const __attribute__((address_space(3))) uint8_t *lds_u8;
 typedef const __attribute__((address_space(3))) uint16_t *lds_u16;
 
-// Bit reader (MD.cs:2970-3015).  Small enough to travel through a function call in registers.
+// Bit reader (MD.cs:2970-3015; its codes: mobi_rd_* of mobi_syntax.h).  Small enough to travel through a function call in registers.
 struct BitR {
   // stream: Data[Offset ..), 8-byte aligned on the device; two 8-byte registers run ahead of the reader
   const uint8_t *pf;
@@ -77,38 +76,7 @@ struct BitR {
     }
     off += 2;
     nbr += 16;
-    win |= shl(w, 16 - nbr);
-  }
-  __device__ __forceinline__ void take(int n) {
-    win = shl(win, n);
-    nbr -= n;
-    if (nbr < 0) fill_bits();
-  }
-  __device__ __forceinline__ uint32_t ue() { // Elias-gamma, value = 2^z - 1 + suffix
-    const int z = clz32(win);
-    win = shl(win, z);
-    win += win;
-    uint32_t v = (z == 0) ? 0 : shr(win, 32 - z);
-    v += shl(1u, z);
-    v--;
-    win = shl(win, z);
-    nbr -= 2 * z;
-    if (--nbr < 0) fill_bits();
-    return v;
-  }
-  __device__ __forceinline__ int se() { // odd codes map to non-positive values (MD.cs:3009-3010)
-    const int z = clz32(win);
-    win = shl(win, z);
-    win += win;
-    uint32_t u = (z == 0) ? 0 : shr(win, 32 - z);
-    u += shl(1u, z);
-    int v = (int)u;
-    if (v & 1) v = (int)(1u - u);
-    v >>= 1;
-    win = shl(win, z);
-    nbr -= 2 * z;
-    if (--nbr < 0) fill_bits();
-    return v;
+    win |= mobi_shl(w, 16 - nbr);
   }
 };
 
@@ -125,69 +93,14 @@ __device__ __noinline__ ResidOut resid_block_fn(BitR r, uint32_t n_coefs, lds_u8
   int p = 0;
   for (;;) {
     int skip, value;
-    uint32_t e;
-    if ((r.win >> 25) == 3) { // escape prefix 0000011
-      r.win <<= 7;
-      bool c = (r.win >> 31) == 1;
-      r.win <<= 1;
-      if (!c) { // "0": table code, level += B[last<<6|run]
-        r.nbr -= 8;
-        if (r.nbr < 0) r.fill_bits();
-        e = A[r.win >> 20];
-        value = (int)((e >> 4) & 0x1F) + B[e >> 9];
-        r.win = shl(r.win, (int)(e & 0xF) - 1);
-        if (r.win >> 31) value = -value;
-        r.win <<= 1;
-        r.nbr -= (int)(e & 0xF);
-        if (r.nbr < 0) r.fill_bits();
-        skip = (int)((e >> 9) & 0x3F);
-        e >>= 15;
-      } else {
-        c = (r.win >> 31) == 1;
-        r.win <<= 1;
-        r.nbr -= 9;
-        if (r.nbr < 0) r.fill_bits();
-        if (!c) { // "10": table code, run += B[0x80 + level + (last<<6)]
-          e = A[r.win >> 20];
-          value = (int)((e >> 4) & 0x1F);
-          skip = (int)((e >> 9) & 0x3F) + B[0x80 + value + ((e >> 15) << 6)];
-          r.win = shl(r.win, (int)(e & 0xF) - 1);
-          if (r.win >> 31) value = -value;
-          r.win <<= 1;
-          r.nbr -= (int)(e & 0xF);
-          if (r.nbr < 0) r.fill_bits();
-          e >>= 15;
-        } else { // "11": raw last(1) run(6) level(s12)
-          e = r.win >> 31;
-          r.win <<= 1;
-          skip = (int)(r.win >> 26);
-          r.win <<= 6;
-          r.nbr -= 7;
-          if (r.nbr < 0) r.fill_bits();
-          value = (int32_t)r.win >> 20;
-          r.win <<= 12;
-          r.nbr -= 12;
-          if (r.nbr < 0) r.fill_bits();
-        }
-      }
-    } else {
-      e = A[r.win >> 20];
-      value = (int)((e >> 4) & 0x1F);
-      r.win = shl(r.win, (int)(e & 0xF) - 1);
-      if (r.win >> 31) value = -value;
-      r.win <<= 1;
-      r.nbr -= (int)(e & 0xF);
-      if (r.nbr < 0) r.fill_bits();
-      skip = (int)((e >> 9) & 0x3F);
-      e >>= 15;
-    }
+    const uint32_t last = mobi_rd_token(r, A, B, skip, value);
     p += skip; // (no test for a pending error here: the reader is frozen, p still advances, the loop ends within N tokens)
     if (p >= N) { r.fail(MOBI_E_UNSUPPORTED); break; } // the reference would walk past the dequant words (Internal[] aliasing)
     const int idx = (flags & 4) ? zz[p] : 0; // low byte of the dequant word = zigzag target (MD.cs:3426); all zero before the first SetupQuantTables
     p++;
     if (value != 0) out[n_coefs++] = (uint32_t)(tile + idx) | ((uint32_t)(int)(int16_t)value << 16);
     else r.fail(MOBI_E_UNSUPPORTED); // a token without a level: the frame's command list would not name every token (mobi_state.h): the host parser's
-    if (e & 1) break;
+    if (last) break;
   }
   return ResidOut{r, n_coefs};
 }
@@ -212,39 +125,20 @@ struct DP {
 
   __device__ __forceinline__ void fail(int c) { r.fail(c); }
   __device__ __forceinline__ void fill_bits() { r.fill_bits(); }
-  __device__ __forceinline__ void take(int n) { r.take(n); }
-  __device__ __forceinline__ uint32_t ue() { return r.ue(); }
-  __device__ __forceinline__ int se() { return r.se(); }
+  __device__ __forceinline__ void take(int n) { mobi_rd_take(r, n); }
+  __device__ __forceinline__ uint32_t ue() { return mobi_rd_ue(r); }
+  __device__ __forceinline__ int se() { return mobi_rd_se(r); }
 
   // ---------------------------------------------------------------- quantiser (MD.cs:3884-3925)
   __device__ __forceinline__ void setup_quant(uint32_t q) {
-    if (version == MOBI_VERSION_MOFLEX3DS) q = q < 12 ? 12 : q > 52 ? 52 : q;
+    q = mobi_clamp_quant(version == MOBI_VERSION_MOFLEX3DS, q);
     quant = q; // assigned before the table index can throw
-    if (q >= 54) { fail(MOBI_E_INDEX); return; }
+    if (q >= MOBI_QUANT_LIMIT) { fail(MOBI_E_INDEX); return; }
     tables_set = 1;
-    L->mcache[1] = 9; L->mcache[2] = 9; L->mcache[3] = 9; L->mcache[4] = 9; // "no neighbour" marks, re-armed only here
-    L->mcache[8] = 9; L->mcache[0x10] = 9; L->mcache[0x18] = 9; L->mcache[0x20] = 9;
+    mobi_rearm_borders([&](int i) -> uint8_t & { return L->mcache[i]; });
   }
 
-  // ---------------------------------------------------------------- geometry (MobiGeom of mobi_parse.h)
-  __device__ __forceinline__ int owner_luma(int a) const {
-    if (a < 0) return -1;
-    const int row = a >> lg, col = a & (stride - 1);
-    if (col >= width || row >= height) return -1;
-    return (row >> 4) * mbw + (col >> 4);
-  }
-  __device__ __forceinline__ int owner_chroma(int a) const {
-    if (a < 0) return -1;
-    const int row = a >> lg, col = a & (stride - 1);
-    const int x = col >= stride / 2 ? col - stride / 2 : col;
-    if (x >= width / 2 || row >= height / 2) return -1;
-    return (row >> 3) * mbw + (x >> 3);
-  }
-  __device__ __forceinline__ int area_offset(int area, int sub) const {
-    const int S = stride;
-    const int o = (area < 4) ? cur_off + (area >> 1) * 8 * S + (area & 1) * 8 : cur_off / 2 + (area == 5 ? S / 2 : 0);
-    return o + (sub >> 1) * 4 * S + (sub & 1) * 4;
-  }
+  __device__ __forceinline__ int area_offset(int area, int sub) const { return mobi_area_offset(cur_off, stride, area, sub); }
 
   // ---------------------------------------------------------------- per-macroblock assembly
   __device__ __forceinline__ void begin_mb(int mb, int mx, int my, int type) {
@@ -268,24 +162,7 @@ struct DP {
   // inter macroblock: all leaves are known once the partition tree is done; decide how they travel, then the levels follow
   __device__ __forceinline__ int classify_leaves(uint32_t &nl) const {
     nl = (uint32_t)n_leaf_words / 2;
-    int dual = MOBI_DUAL_NONE;
-    if (nl == 2) {
-      const uint32_t a = L->leaves[0] & 0xFFF, b = L->leaves[2] & 0xFFF;
-      if (a == (0u | (1u << 10)) && b == ((4u << 4) | (1u << 10))) dual = MOBI_DUAL_TB;
-      if (a == (0u | (1u << 8)) && b == (4u | (1u << 8))) dual = MOBI_DUAL_LR;
-    }
-    return dual;
-  }
-  bool dep_intra = false;
-  __device__ __forceinline__ void add_dep(int o, uint32_t *deps, int &n_deps) {
-    if (o < 0 || o >= cur_mb) return; // raster-later owners read as the fresh plane's zeros (the kernel masks them)
-    #pragma nounroll
-    for (int k = 0; k < n_deps; k++)
-      if ((int)(deps[k] & 0x1FFF) == o) return;
-    if (n_deps == MOBI_INTRA_DEPS) { fail(MOBI_E_UNSUPPORTED); return; }
-    const uint32_t inter = (desc[o].w1 & 1) == MOBI_MB_INTRA ? 0u : MOBI_DEP_INTER; // this lane wrote desc[o] itself
-    deps[n_deps++] = (uint32_t)o | inter;
-    if (!inter) { desc[o].w3 |= 4u; dep_intra = true; } // w3 [1] has intra dependencies, [2] has intra dependents (mobi_recon_intra_cl)
+    return nl == 2 ? mobi_dual_kind(L->leaves[0], L->leaves[2]) : MOBI_DUAL_NONE;
   }
   __device__ __forceinline__ void end_mb() {
     if (r.err) return;
@@ -298,20 +175,10 @@ struct DP {
     int dual = MOBI_DUAL_NONE;
     if (mb_type == MOBI_MB_INTER) {
       dual = classify_leaves(nl);
-      if (nl == 1 || dual) { // leaf records: positions and phases instead of motion vectors (MD.cs:400-416)
-        const int S = stride;
+      if (nl == 1 || dual) { // leaf records instead of motion vectors
         uint32_t pos[4] = {0, 0, 0, 0};
         #pragma nounroll
-        for (uint32_t i = 0; i < nl; i++) {
-          const uint32_t w0 = L->leaves[2 * i], w1 = L->leaves[2 * i + 1];
-          const int ref = (w0 >> 12) & 7;
-          const int dx = (int16_t)(w1 & 0xFFFF), dy = (int16_t)(w1 >> 16), cdx = dx >> 1, cdy = dy >> 1;
-          pos[2 * i] = (uint32_t)(cur_off + (dy >> 1) * S + (dx >> 1));
-          pos[2 * i + 1] = (uint32_t)(cur_off / 2 + (cdy >> 1) * S + (cdx >> 1));
-          d.w2 |= (uint32_t)ref << (10 + 3 * i);
-          d.w2 |= (uint32_t)((dx & 1) | ((dy & 1) << 1)) << (16 + 4 * i);
-          d.w2 |= (uint32_t)((cdx & 1) | ((cdy & 1) << 1)) << (18 + 4 * i);
-        }
+        for (uint32_t i = 0; i < nl; i++) d.w2 |= mobi_leaf_record((int)i, L->leaves[2 * i], L->leaves[2 * i + 1], cur_off, stride, pos[2 * i], pos[2 * i + 1]);
         d.w3 = pos[0]; d.w4 = pos[1]; d.w5 = pos[2]; d.w6 = pos[3];
       } else { // the 64-entry MV cell map, in the 64 words p_residual() left free in front of the levels
         uint32_t *cells = pay + pay_base + mb_pay;
@@ -330,41 +197,20 @@ struct DP {
       uint32_t *rec_out = pay + pay_base + mb_pay;
       #pragma nounroll
       for (int i = 0; i < MOBI_INTRA_RECORDS; i++) rec_out[i] = L->recs[i];
-      // the raster-earlier macroblocks this one's prediction halo touches (finish_levels of mobi_parse.cpp scans the whole
-      // halo; these probes hit every distinct owner in the same order: the halo above is three 16-aligned runs, the columns
-      // left and right change owner at most once, between the first row and the rest)
+      // the raster-earlier macroblocks this one's prediction halo touches (mobi_syntax.h)
       uint32_t deps[MOBI_INTRA_DEPS];
       int n_deps = 0;
-      dep_intra = false;
-      const int S = stride, o = cur_off;
-      add_dep(owner_luma(o - S - 1), deps, n_deps);
-      add_dep(owner_luma(o - S), deps, n_deps);
-      add_dep(owner_luma(o - S + 16), deps, n_deps);
-      add_dep(owner_luma(o - 1), deps, n_deps);
-      add_dep(owner_luma(o + 16), deps, n_deps);
-      add_dep(owner_luma(o + S - 1), deps, n_deps);
-      add_dep(owner_luma(o + S + 16), deps, n_deps);
-      #pragma nounroll
-      for (int v = 0; v < 2; v++) {
-        const int b = o / 2 + v * (S / 2);
-        add_dep(owner_chroma(b - S - 1), deps, n_deps);
-        add_dep(owner_chroma(b - S), deps, n_deps);
-        add_dep(owner_chroma(b - S + 8), deps, n_deps);
-        add_dep(owner_chroma(b - 1), deps, n_deps);
-        add_dep(owner_chroma(b + 8), deps, n_deps);
-        add_dep(owner_chroma(b + S - 1), deps, n_deps);
-        add_dep(owner_chroma(b + S + 8), deps, n_deps);
-      }
-      #pragma nounroll
-      for (int k = n_deps; k < MOBI_INTRA_DEPS; k++) deps[k] = MOBI_DEP_NONE;
-      d.w4 = deps[0] | (deps[1] << 16);
-      d.w5 = deps[2] | (deps[3] << 16);
-      d.w6 = deps[4] | (deps[5] << 16);
-      d.w7 = deps[6] | (deps[7] << 16);
-      if (dep_intra) d.w3 |= 2u;
+      bool dep_intra = false;
+      mobi_halo_owners(width, height, stride, lg, mbw, cur_off, [&](int o) {
+        const int added = mobi_dep_add(deps, n_deps, cur_mb, o, [&](int k) { return mobi_w1_intra(desc[k].w1); }); // this lane wrote desc[k] itself
+        if (added == MOBI_DEP_FULL) fail(MOBI_E_UNSUPPORTED);
+        if (added == MOBI_DEP_ADDED_INTRA) { desc[o].w3 |= MOBI_W3_HAS_DEPENDENTS; dep_intra = true; }
+      });
+      mobi_deps_pack(deps, n_deps, d.w4, d.w5, d.w6, d.w7);
+      if (dep_intra) d.w3 |= MOBI_W3_HAS_INTRA_DEPS;
       items[n_items++] = MOBI_ITEM(clip, cur_mb);
     }
-    d.w1 = (uint32_t)mb_type | (nl << 1) | (cbp6 << 8) | (t8mask << 14) | ((quant & 63) << 20) | ((uint32_t)dual << 26);
+    d.w1 = mobi_desc_w1(mb_type, nl, cbp6, t8mask, quant, dual);
     uint4 *dp = (uint4 *)(desc + cur_mb);
     dp[0] = uint4{d.payload_off, d.w1, d.w2, d.w3};
     dp[1] = uint4{d.w4, d.w5, d.w6, d.w7};
@@ -372,37 +218,23 @@ struct DP {
   }
 
   // ---------------------------------------------------------------- motion (MD.cs:400-456)
-  __device__ __forceinline__ void check_window(long long pos, int w, int h, int phase, long long plane_len) {
-    if (pos < 0) { fail(MOBI_E_INDEX); return; }
-    const long long last = pos + (long long)(h - 1) * stride;
-    long long hi = last + w - 1;           // phase 0: Array.Copy end is exclusive
-    if (phase & 1) hi += 1;
-    if (phase & 2) hi += stride;
-    if (hi >= plane_len) fail(MOBI_E_INDEX);
-  }
   __device__ __forceinline__ void mc_leaf(int wi, int hi, int x, int y, int ref, int dx, int dy, int mv_slot) {
     const int w = 16 >> wi, h = 16 >> hi;
     L->mvc[mv_slot] = dx; // every leaf overwrites the macroblock's exported MV (MD.cs:411-412)
     L->mvc[mv_slot + 1] = dy;
     if (ref > imin(5, frames_started - 1)) { fail(MOBI_E_NULLREF); return; } // Y[ref] == null
     const bool in_range = dx >= -MOBI_MV_LIMIT && dx <= MOBI_MV_LIMIT && dy >= -MOBI_MV_LIMIT && dy <= MOBI_MV_LIMIT;
-    if (in_range) { // every position fits 32 bits: would CopyBlock throw?  (rows are visited top to bottom: first row / last row bound the rest)
-      const int S = stride, o = cur_off + y * S + x, ylen = S * height;
-      const int pos = o + (dy >> 1) * S + (dx >> 1);
-      const int hi_y = pos + (h - 1) * S + w - 1 + (dx & 1) + ((dy & 1) ? S : 0); // phase 0: Array.Copy end is exclusive
-      const int cdx = dx >> 1, cdy = dy >> 1;
-      const int cpos = o / 2 + (cdy >> 1) * S + (cdx >> 1);
-      const int hi_c = cpos + S / 2 + ((h >> 1) - 1) * S + (w >> 1) - 1 + (cdx & 1) + ((cdy & 1) ? S : 0); // the V window ends last
-      if (pos < 0 || hi_y >= ylen || cpos < 0 || hi_c >= ylen / 2) { fail(MOBI_E_INDEX); return; }
+    if (in_range) { // every position fits 32 bits: would CopyBlock throw?
+      if (!mobi_mc_windows_ok(stride, height, cur_off + y * stride + x, w, h, dx, dy)) { fail(MOBI_E_INDEX); return; }
     } else {
-      const long long S = stride;
+      const long long S = stride, ylen = S * height;
       const long long o = (long long)cur_off + (long long)y * S + x;
-      check_window(o + (long long)(dy >> 1) * S + (dx >> 1), w, h, (dx & 1) | ((dy & 1) << 1), S * height);
       const int cdx = dx >> 1, cdy = dy >> 1;
       const long long cpos = o / 2 + (long long)(cdy >> 1) * S + (cdx >> 1);
       const int cph = (cdx & 1) | ((cdy & 1) << 1);
-      check_window(cpos, w >> 1, h >> 1, cph, S * height / 2);
-      check_window(cpos + S / 2, w >> 1, h >> 1, cph, S * height / 2);
+      if (!mobi_window_ok(o + (long long)(dy >> 1) * S + (dx >> 1), w, h, (dx & 1) | ((dy & 1) << 1), S, ylen) || !mobi_window_ok(cpos, w >> 1, h >> 1, cph, S, ylen / 2) ||
+          !mobi_window_ok(cpos + S / 2, w >> 1, h >> 1, cph, S, ylen / 2))
+        fail(MOBI_E_INDEX);
       fail(MOBI_E_UNSUPPORTED); // (an index error above wins: the first error sticks)
       return;
     }
@@ -413,7 +245,7 @@ struct DP {
 
   // ---------------------------------------------------------------- residual (MD.cs:3330-3432)
   __device__ __forceinline__ void resid_block(int area, int sub, bool is8) {
-    if (quant < 12) { fail(MOBI_E_UNSUPPORTED); return; } // see mobi_parse.cpp: below q=12 the reference depends on Internal[] aliasing
+    if (quant < 12) { fail(MOBI_E_UNSUPPORTED); return; } // below q = 12 the reference depends on Internal[] aliasing (mobi_parse.cpp, resid_block: the host parser walks with it)
     const ResidOut o = resid_block_fn(r, n_coefs, T, pay + pay_base + mb_pay + hdr_words, is8 ? area * 64 : area * 64 + sub * 16,
                                       (is8 ? 1u : 0u) | (vlc == 1 ? 2u : 0u) | (tables_set ? 4u : 0u));
     r = o.r;
@@ -439,7 +271,7 @@ struct DP {
   __device__ __forceinline__ void p_residual() { // loc_1161A0, MD.cs:1818-1833
     uint32_t nl;
     const int dual = classify_leaves(nl);
-    hdr_words = (nl == 1 || dual) ? 0 : MOBI_MV_CELLS; // end_mb() fills the cell map
+    hdr_words = mobi_inter_hdr_words(nl, dual); // end_mb() fills the cell map
     const uint32_t u = ue();
     if (u >= 64) { fail(MOBI_E_INDEX); return; }
     cbp6 = T[MOBI_DT_CBP_P + u];
@@ -451,18 +283,13 @@ struct DP {
   }
 
   // ---------------------------------------------------------------- intra syntax
-  __device__ __forceinline__ void check_intra_reads(int mode, int o) { // see mobi_parse.cpp
-    const uint32_t top = 0x1E5, left = 0x0F6; // modes 0,2,5,6,7,8 read the row above; 1,2,4,5,6,7 the column to the left
-    if (((top >> mode) & 1) && o < stride) { fail(MOBI_E_INDEX); return; }
-    if (((left >> mode) & 1) && o < 1) fail(MOBI_E_INDEX);
+  __device__ __forceinline__ void check_intra_reads(int mode, int o) { // the reference indexes below the plane: it throws
+    if (!mobi_intra_reads_ok(mode, o, stride)) fail(MOBI_E_INDEX);
   }
-  // predicted-mode code shared by loc_116220 / loc_116368 / sub_1163DC (MD.cs:1840-1859, 2785-2804, 2841-2858)
+  // the predicted-mode code (mobi_syntax.h) and its place in the mode cache
   __device__ __forceinline__ int pmode(int ci, bool four) {
-    int pred = imin(L->mcache[ci - 8], L->mcache[ci - 1]);
-    if (pred == 9) pred = 3;
-    int v = (int)(r.win >> 28), nb = 1, mode = pred;
-    if (v >= pred) v++;
-    if (v < 9) { mode = v; nb = 4; }
+    int nb;
+    const int mode = mobi_pmode_decode(L->mcache[ci - 8], L->mcache[ci - 1], r.win, nb);
     if (!r.err) { // the cache survives the frame: nothing may touch it after the (sticky) error = the reference's throw
       if (four) L->mcache[ci] = (uint8_t)mode;
       else L->mcache[ci] = L->mcache[ci + 1] = L->mcache[ci + 8] = L->mcache[ci + 9] = (uint8_t)mode;
@@ -815,12 +642,10 @@ extern "C" __global__ __launch_bounds__(64) void mobi_parse_tail(MobiDevParseArg
   mobi_tail_scan_init(sc);
   for (int mb = n_mbs - 1; mb >= 0 && !sc.done; mb--) {
     const uint4 d = *(const uint4 *)(desc + mb);
-    const int n = (int)(d.z & 0x3FF);
+    const int n = (int)mobi_w2_coefs(d.z);
     if (!n) continue;
-    const bool intra = (d.y & 1) == MOBI_MB_INTRA;
-    const uint32_t nl = (d.y >> 1) & 0x7F, dual = (d.y >> 26) & 3;
-    const uint32_t woff = d.x - rel + (intra ? MOBI_INTRA_RECORDS : (nl > 1 && !dual) ? MOBI_MV_CELLS : 0);
-    mobi_tail_scan_mb(sc, pay + woff, n, woff, (d.y >> 14) & 0x3F, izz, izz + 64);
+    const uint32_t woff = d.x - rel + mobi_levels_offset(d.y);
+    mobi_tail_scan_mb(sc, pay + woff, n, woff, mobi_w1_t8mask(d.y), izz, izz + 64);
   }
   const MobiDevTail *in = A.tail_in + clip;
   MobiDevTail *out = A.tail_out + clip;

@@ -26,6 +26,7 @@
 #include <stdint.h>
 
 #include "mobi_state.h"
+#include "mobi_syntax.h"
 
 #define MOBI_GOP_MAX 6 /* the ring holds six pictures (MD.cs:19-20): every frame of a group is still there when the call returns */
 #define MOBI_GOP_PARSE_MAX 128 /* mobi_batch_gop_begin: frames parsed side by side (one turn of full waves of the lock-step parser = 131 072: 4096 clips x 32, 1024 x 128); mobi_batch_gop_finish hands them out six at a time */
@@ -52,23 +53,19 @@ MOBI_ST_FN bool mobi_gop_header(int version_moflex, const uint8_t *p, uint32_t l
     const uint32_t nq = (win << 2) >> 26;
     if (q != nq) { q = nq; setup = true; }
   } else {
-    int z = 0;
+    int z = 0; // (leading zeros, counted to 8 and no further: as mobi_clz32() this walk holds two more registers in mobi_gop_prepare)
     while (z < 8 && !((win << z) >> 31)) z++;
     if (z >= 8) return false; // (a code of more than 15 bits: the device parsers hand the frame over)
-    const uint32_t u = (z ? ((win << (z + 1)) >> (32 - z)) : 0u) + (1u << z);
-    int dq = (int)u;
-    if (dq & 1) dq = (int)(1u - u);
-    dq >>= 1;
+    const int dq = mobi_gamma_signed(mobi_gamma_value(win, z));
     if (version_moflex && q == 0) setup = true;
     else if (dq != 0) { q += (uint32_t)dq; setup = true; }
   }
   if (setup) {
-    if (version_moflex) q = q < 12 ? 12 : q > 52 ? 52 : q;
-    if (q >= 54) return false; // SetupQuantizationTables throws after assigning Quantizer (MD.cs:3886-3890): the host parser's frame
+    q = mobi_clamp_quant(version_moflex != 0, q);
+    if (q >= MOBI_QUANT_LIMIT) return false; // SetupQuantizationTables throws after assigning Quantizer (MD.cs:3886-3890): the host parser's frame
     st.quant = q;
     st.tables_set = 1;
-    st.mcache[1] = st.mcache[2] = st.mcache[3] = st.mcache[4] = 9;
-    st.mcache[8] = st.mcache[16] = st.mcache[24] = st.mcache[32] = 9;
+    mobi_rearm_borders([&](int i) -> uint8_t & { return st.mcache[i]; });
   }
   return true;
 }
@@ -164,12 +161,10 @@ MOBI_ST_FN void mobi_gop_chain_clip(const MobiGopArgs &A, int c, const uint8_t *
     mobi_tail_scan_init(sc);
     for (int mb = n_mbs - 1; mb >= 0 && !sc.done; mb--) {
       const MobiDescQuad d = *(const MobiDescQuad *)(desc + mb);
-      const int nw = (int)(d.z & 0x3FF);
+      const int nw = (int)mobi_w2_coefs(d.z);
       if (!nw) continue;
-      const bool intra = (d.y & 1) == MOBI_MB_INTRA;
-      const uint32_t nl = (d.y >> 1) & 0x7F, dual = (d.y >> 26) & 3;
-      const uint32_t woff = d.x + (intra ? MOBI_INTRA_RECORDS : (nl > 1 && !dual) ? MOBI_MV_CELLS : 0);
-      mobi_tail_scan_mb(sc, pay + woff, nw, woff, (d.y >> 14) & 0x3F, izz, izz + 64);
+      const uint32_t woff = d.x + mobi_levels_offset(d.y);
+      mobi_tail_scan_mb(sc, pay + woff, nw, woff, mobi_w1_t8mask(d.y), izz, izz + 64);
     }
     MobiDevTail *tout = A.P.tail_out + v;
     mobi_tail_finish(sc, pay, A.P.scale + (size_t)(cur.quant & 63) * MOBI_SCALE_STRIDE, *tprev, *tout);

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "mobi_cmd.h"
+#include "mobi_syntax.h"
 
 // Everything one reconstruction launch needs.  HBM layout:
 //   planes : [clip][slot 0..5][ Y: stride*height | UV: stride*height/2 ], each plane as macroblock TILES (mobi_tile.h): a
@@ -56,8 +57,7 @@ extern "C" int mobi_launch_fwd_dct(int n, const int32_t *in_dev, int32_t *out_de
 extern "C" int mobi_launch_compare_clips(const MobiReconArgs *a, int modulus, uint32_t *out_dev, hipStream_t s);
 // slot (tiled Y + UV planes of one frame) -> lin_dev: the same frame as the reference's row-major Y[stride*height] then UV[stride*height/2]
 extern "C" int mobi_launch_untile(const uint8_t *slot, uint8_t *lin_dev, int stride, int height, hipStream_t s);
-// intra launch item, word 0: (clip << 13) | mb; words 1..3: MbDesc.w1, MbDesc.payload_off, flags (mobi_recon_intra in mobi_kernels.hip)
-#define MOBI_ITEM(clip, mb) (((uint32_t)(clip) << 13) | (uint32_t)(mb))
+// intra launch item: word 0 = MOBI_ITEM(clip, mb) (mobi_syntax.h); words 1..3: MbDesc.w1, MbDesc.payload_off, flags (mobi_recon_intra in mobi_kernels.hip)
 #define MOBI_INTRA_ITEM_WORDS 4
 #define MOBI_ITEM_NONE 0xFFFFFFFFu /* padding: every dependency level starts on a wave of four items */
 #endif

@@ -22,6 +22,7 @@
 // of bits consumed: it refills lazily, one 16-bit word whenever fewer than 16 bits remain, so after c bits it has fetched 1 + ceil(c / 16)
 // words (every syntax element that consumes more than 16 bits between two of its checks is a bail-out here).
 //
+// What this walk shares with the other two -- geometry, the descriptor's words, the window and mode rules, the codes -- is mobi_syntax.h.
 // Host-compilable: tests/tools/mobi_lsparse_host.cpp runs the same functions lane by lane on the CPU against mobi_parse.cpp.
 #ifndef MOBI_LSPARSE_H
 #define MOBI_LSPARSE_H
@@ -30,6 +31,7 @@
 #include "../../include/mobiclip_hip.h"
 #include "mobi_cmd.h"
 #include "mobi_dparse_tables.h"
+#include "mobi_syntax.h"
 
 #if defined(__HIPCC__)
 #define LS_FN __host__ __device__ __forceinline__
@@ -123,7 +125,7 @@ typedef uint32_t ls_u32x4 __attribute__((ext_vector_type(4), aligned(4)));
 #else
 #define LS_ANY(cond) (cond)
 #endif
-LS_FN int ls_clz(uint32_t v) { return v ? __builtin_clz(v) : 32; }
+LS_FN int ls_clz(uint32_t v) { return mobi_clz32(v); }
 LS_FN int ls_ctz(uint32_t v) { return __builtin_ctz(v); }
 LS_FN int ls_min(int a, int b) { return a < b ? a : b; }
 LS_FN int ls_max(int a, int b) { return a > b ? a : b; }
@@ -153,20 +155,15 @@ LS_FN uint32_t ls_ue(LsLane &s) {
   const uint32_t w = ls_win(s);
   const int z = ls_clz(w);
   if (z >= 8) { ls_bail(s, 1); return 0; }
-  const uint32_t v = (z ? ((w << (z + 1)) >> (32 - z)) : 0u) + (1u << z) - 1u;
-  ls_take(s, 2 * z + 1);
-  return v;
+  ls_take(s, mobi_gamma_bits(z));
+  return mobi_gamma_value(w, z);
 }
 LS_FN int ls_se(LsLane &s) {
   const uint32_t w = ls_win(s);
   const int z = ls_clz(w);
   if (z >= 8) { ls_bail(s, 1); return 0; }
-  const uint32_t u = (z ? ((w << (z + 1)) >> (32 - z)) : 0u) + (1u << z);
-  int v = (int)u;
-  if (v & 1) v = (int)(1u - u);
-  v >>= 1;
-  ls_take(s, 2 * z + 1);
-  return v;
+  ls_take(s, mobi_gamma_bits(z));
+  return mobi_gamma_signed(mobi_gamma_value(w, z));
 }
 
 // The partition-code table of this parser's copy of the blob: entry = code | code length << 4, or 0xFF where the reference throws (a code the
@@ -180,12 +177,11 @@ LS_FN void ls_prepare_tables(uint8_t *T, int i) {
 // ---------------------------------------------------------------- frame header (MD.cs:113-143, :224-236)
 template <class S>
 LS_FN void ls_setup_quant(LsLane &s, S &m, const LsCtx &c, uint32_t q) { // MD.cs:3884-3925
-  if (c.version == MOBI_VERSION_MOFLEX3DS) q = q < 12 ? 12 : q > 52 ? 52 : q;
+  q = mobi_clamp_quant(c.version == MOBI_VERSION_MOFLEX3DS, q);
   s.quant = q;
-  if (q >= 54) { ls_bail(s, 2); return; }
+  if (q >= MOBI_QUANT_LIMIT) { ls_bail(s, 2); return; }
   s.tables_set = 1;
-  m.mc(1) = 9; m.mc(2) = 9; m.mc(3) = 9; m.mc(4) = 9;
-  m.mc(8) = 9; m.mc(0x10) = 9; m.mc(0x18) = 9; m.mc(0x20) = 9;
+  mobi_rearm_borders([&](int i) -> uint8_t & { return m.mc(i); });
 }
 // s.quant, yuvfmt, tables_set, frames_started (already advanced) and the mode cache are loaded; the ring holds the first 64 bytes
 template <class S>
@@ -229,14 +225,9 @@ LS_FN void ls_begin_frame(LsLane &s, S &m, const LsCtx &c, uint32_t len) {
 }
 
 // ---------------------------------------------------------------- pieces of the walk
-LS_FN int ls_area_offset(const LsLane &s, const LsCtx &c, int area, int sub) {
-  const int S = c.stride;
-  const int o = (area < 4) ? s.cur_off + (area >> 1) * 8 * S + (area & 1) * 8 : s.cur_off / 2 + (area == 5 ? S / 2 : 0);
-  return o + (sub >> 1) * 4 * S + (sub & 1) * 4;
-}
+LS_FN int ls_area_offset(const LsLane &s, const LsCtx &c, int area, int sub) { return mobi_area_offset(s.cur_off, c.stride, area, sub); }
 LS_FN void ls_check_intra_reads(LsLane &s, const LsCtx &c, int mode, int o) { // the reference indexes below the plane: it throws
-  const uint32_t top = 0x1E5, left = 0x0F6;
-  if ((((top >> mode) & 1) && o < c.stride) || (((left >> mode) & 1) && o < 1)) ls_bail(s, 4);
+  if (!mobi_intra_reads_ok(mode, o, c.stride)) ls_bail(s, 4);
 }
 LS_FN void ls_block(LsLane &s, int area, int sub, bool is8) { // one transform block's tokens follow (MD.cs:3330)
   if (s.quant < 12) { ls_bail(s, 5); return; }
@@ -245,14 +236,11 @@ LS_FN void ls_block(LsLane &s, int area, int sub, bool is8) { // one transform b
   s.blk_tile = is8 ? area * 64 : area * 64 + sub * 16;
   s.blk_flags = (is8 ? 1u : 0u) | (s.vlc == 1 ? 2u : 0u) | (s.tables_set ? 4u : 0u);
 }
-// predicted-mode code (MD.cs:1840-1859, 2785-2804, 2841-2858)
+// the predicted-mode code and its place in the mode cache
 template <class S>
 LS_FN int ls_pmode(LsLane &s, S &m, int ci, bool four) {
-  int pred = ls_min(m.mc(ci - 8), m.mc(ci - 1));
-  if (pred == 9) pred = 3;
-  int v = (int)(ls_win(s) >> 28), nb = 1, mode = pred;
-  if (v >= pred) v++;
-  if (v < 9) { mode = v; nb = 4; }
+  int nb;
+  const int mode = mobi_pmode_decode(m.mc(ci - 8), m.mc(ci - 1), ls_win(s), nb);
   if (four) m.mc(ci) = (uint8_t)mode;
   else m.mc(ci) = m.mc(ci + 1) = m.mc(ci + 8) = m.mc(ci + 9) = (uint8_t)mode;
   ls_take(s, nb);
@@ -278,13 +266,7 @@ LS_FN void ls_leaf(LsLane &s, S &m, const LsCtx &c, int wi, int hi, int x, int y
   s.mv_cur = mobi_leaf_w1(dx, dy); // (the row cache holds a vector as two int16 in one word -- a vector beyond +-8191 ends the lane right below)
   if (ref > ls_min(5, s.frames_started - 1)) { ls_bail(s, 6); return; }
   if (dx < -MOBI_MV_LIMIT || dx > MOBI_MV_LIMIT || dy < -MOBI_MV_LIMIT || dy > MOBI_MV_LIMIT) { ls_bail(s, 7); return; }
-  const int o = s.cur_off + y * S_ + x, ylen = S_ * c.height;
-  const int pos = o + (dy >> 1) * S_ + (dx >> 1);
-  const int hi_y = pos + (h - 1) * S_ + w - 1 + (dx & 1) + ((dy & 1) ? S_ : 0);
-  const int cdx = dx >> 1, cdy = dy >> 1;
-  const int cpos = o / 2 + (cdy >> 1) * S_ + (cdx >> 1);
-  const int hi_c = cpos + S_ / 2 + ((h >> 1) - 1) * S_ + (w >> 1) - 1 + (cdx & 1) + ((cdy & 1) ? S_ : 0);
-  if (pos < 0 || hi_y >= ylen || cpos < 0 || hi_c >= ylen / 2) { ls_bail(s, 8); return; }
+  if (!mobi_mc_windows_ok(S_, c.height, s.cur_off + y * S_ + x, w, h, dx, dy)) { ls_bail(s, 8); return; }
   const uint32_t w0 = mobi_leaf_w0(x, y, wi, hi, ref), w1 = mobi_leaf_w1(dx, dy);
   const bool first = s.nleaf == 0, second = s.nleaf == 1; // (selects, not stores behind a compare: those became an indexed store into scratch)
   s.l0a = first ? w0 : s.l0a; s.l0b = first ? w1 : s.l0b;
@@ -311,13 +293,7 @@ LS_FN void ls_leaf(LsLane &s, S &m, const LsCtx &c, int wi, int hi, int x, int y
   }
 #endif
 }
-LS_FN int ls_classify(const LsLane &s) {
-  if (s.nleaf != 2) return MOBI_DUAL_NONE;
-  const uint32_t a = s.l0a & 0xFFF, b = s.l1a & 0xFFF;
-  if (a == (0u | (1u << 10)) && b == ((4u << 4) | (1u << 10))) return MOBI_DUAL_TB;
-  if (a == (0u | (1u << 8)) && b == (4u | (1u << 8))) return MOBI_DUAL_LR;
-  return MOBI_DUAL_NONE;
-}
+LS_FN int ls_classify(const LsLane &s) { return s.nleaf == 2 ? mobi_dual_kind(s.l0a, s.l1a) : MOBI_DUAL_NONE; }
 
 // ---- one residual token (MD.cs:3330-3432).  Also called on its own (ls_token_rounds): tokens are half of all syntax elements, and a round of
 // the whole walk costs the wave twenty times what this region does ----
@@ -437,11 +413,11 @@ LS_FN void ls_next_fast(LsLane &s, S &m, const LsCtx &c) {
         got = is8 = true;
       } else { // which of its 4x4 blocks are coded (MD.cs:2917-2927)
         const int z = ls_clz(w);
-        const uint32_t u = (z ? ((w << (z + 1)) >> (32 - z)) : 0u) + (1u << z) - 1u;
+        const uint32_t u = mobi_gamma_value(w, z);
         if (z >= 8 || u >= 16) slow = true;
         else {
           s.area_mask &= s.area_mask - 1;
-          ls_take(s, 2 * z + 1);
+          ls_take(s, mobi_gamma_bits(z));
           s.sub_mask = c.T[MOBI_DT_CBP4_P + u];
           s.cur_area = a;
         }
@@ -527,12 +503,12 @@ LS_FN void ls_token_fast(LsLane &s, S &m, const LsCtx &c) {
               ls_refill(s, m);
               const uint32_t w = ls_win(s); // (its first bit is 0)
               const int z = ls_clz(w);
-              const uint32_t u = (z ? ((w << (z + 1)) >> (32 - z)) : 0u) + (1u << z) - 1u;
+              const uint32_t u = mobi_gamma_value(w, z);
               const uint32_t pat = (z < 8 && u < 16) ? c.T[MOBI_DT_CBP4_P + u] : 0u;
               if (pat) { // (anything else -- a code the table does not have, a pattern without blocks -- is left to ls_next_fast / ls_next)
                 const int ar = ls_ctz(s.area_mask), sub = ls_ctz(pat);
                 s.area_mask &= s.area_mask - 1;
-                ls_take(s, 2 * z + 1);
+                ls_take(s, mobi_gamma_bits(z));
                 s.cur_area = ar;
                 s.sub_mask = pat & (pat - 1);
                 s.blk_tile = ar * 64 + sub * 16;
@@ -565,31 +541,21 @@ LS_FN void ls_step_main(LsLane &s, S &m, const LsCtx &c) {
       nl = (uint32_t)s.nleaf;
       dual = ls_classify(s);
       if (nl == 1 || dual) {
-        // leaf records: positions and phases instead of motion vectors (MD.cs:400-416).  (No arrays here: an array indexed by a loop
-        // counter lives in scratch memory on the GPU, and a wave alone on its SIMD waits out every one of those round trips.)
-        const int S_ = c.stride;
-        auto leaf = [&](uint32_t a0, uint32_t a1, int i, uint32_t &py, uint32_t &pc) {
-          const int ref = (a0 >> 12) & 7;
-          const int dx = (int16_t)(a1 & 0xFFFF), dy = (int16_t)(a1 >> 16), cdx = dx >> 1, cdy = dy >> 1;
-          py = (uint32_t)(s.cur_off + (dy >> 1) * S_ + (dx >> 1));
-          pc = (uint32_t)(s.cur_off / 2 + (cdy >> 1) * S_ + (cdx >> 1));
-          w2 |= (uint32_t)ref << (10 + 3 * i);
-          w2 |= (uint32_t)((dx & 1) | ((dy & 1) << 1)) << (16 + 4 * i);
-          w2 |= (uint32_t)((cdx & 1) | ((cdy & 1) << 1)) << (18 + 4 * i);
-        };
-        leaf(s.l0a, s.l0b, 0, w3, w4);
+        // leaf records instead of motion vectors.  (No arrays here: an array indexed by a loop counter lives in scratch memory on the
+        // GPU, and a wave alone on its SIMD waits out every one of those round trips.)
+        w2 |= mobi_leaf_record(0, s.l0a, s.l0b, s.cur_off, c.stride, w3, w4);
         w5 = w6 = 0;
-        if (nl == 2) leaf(s.l1a, s.l1b, 1, w5, w6);
+        if (nl == 2) w2 |= mobi_leaf_record(1, s.l1a, s.l1b, s.cur_off, c.stride, w5, w6);
       }
     } else {
       uint32_t *rec_out = s.pay + s.pay_base + s.mb_pay;
       for (int i = 0; i < MOBI_INTRA_RECORDS; i++) rec_out[i] = m.rec(i);
       w4 = w5 = w6 = w7 = MOBI_DEP_NONE | (MOBI_DEP_NONE << 16); // ls_intra_deps fills them in
-      s.items[s.n_items++] = (s.clip << 13) | (uint32_t)s.mb;
+      s.items[s.n_items++] = MOBI_ITEM(s.clip, s.mb);
     }
     MbDesc d;
     d.payload_off = s.pay_base + s.mb_pay;
-    d.w1 = (uint32_t)s.mb_type | (nl << 1) | (s.cbp6 << 8) | (s.t8mask << 14) | ((s.quant & 63) << 20) | ((uint32_t)dual << 26);
+    d.w1 = mobi_desc_w1(s.mb_type, nl, s.cbp6, s.t8mask, s.quant, dual);
     d.w2 = w2; d.w3 = w3; d.w4 = w4; d.w5 = w5; d.w6 = w6; d.w7 = w7;
     s.desc[s.mb] = d;
     s.pay_pos = s.mb_pay + s.hdr_words + s.n_coefs;
@@ -678,7 +644,7 @@ LS_FN void ls_step_main(LsLane &s, S &m, const LsCtx &c) {
   // ---- inter macroblock: which areas are coded (loc_1161A0, MD.cs:1818-1833) ----
   if (s.st == LS_P_CBP) {
     ls_refill(s, m);
-    s.hdr_words = (s.nleaf == 1 || ls_classify(s)) ? 0 : MOBI_MV_CELLS;
+    s.hdr_words = mobi_inter_hdr_words((uint32_t)s.nleaf, ls_classify(s));
     const uint32_t u = ls_ue(s);
     if (!s.bail) {
       if (u >= 64) ls_bail(s, 12);
@@ -705,12 +671,12 @@ LS_FN void ls_step_main(LsLane &s, S &m, const LsCtx &c) {
         else if (s.cbp6 && s.quant >= 12) { // ... or as 4x4 blocks: the pattern (a code of at most 15 bits whose first is that 0; 17 are left)
           const uint32_t w = ls_win(s);
           const int z = ls_clz(w | 1u);
-          const uint32_t u = (z ? ((w << (z + 1)) >> (32 - z)) : 0u) + (1u << z) - 1u;
+          const uint32_t u = mobi_gamma_value(w, z);
           const uint32_t pat = (z < 8 && u < 16) ? T[MOBI_DT_CBP4_P + u] : 0u;
           if (pat) {
             const int ar = ls_ctz(s.area_mask), sub = ls_ctz(pat);
             s.area_mask &= s.area_mask - 1;
-            ls_take(s, 2 * z + 1);
+            ls_take(s, mobi_gamma_bits(z));
             s.cur_area = ar;
             s.sub_mask = pat & (pat - 1);
             s.blk_p = 0;
@@ -945,59 +911,27 @@ LS_FN int ls_consumed(uint32_t cbits, uint32_t len) {
 
 // ---------------------------------------------------------------- dependency lists of the intra macroblocks (one lane per macroblock)
 struct LsGeom { int width, height, stride, lg, mbw; };
-LS_FN int ls_owner_luma(const LsGeom &g, int a) {
-  if (a < 0) return -1;
-  const int row = a >> g.lg, col = a & (g.stride - 1);
-  if (col >= g.width || row >= g.height) return -1;
-  return (row >> 4) * g.mbw + (col >> 4);
-}
-LS_FN int ls_owner_chroma(const LsGeom &g, int a) {
-  if (a < 0) return -1;
-  const int row = a >> g.lg, col = a & (g.stride - 1);
-  const int x = col >= g.stride / 2 ? col - g.stride / 2 : col;
-  if (x >= g.width / 2 || row >= g.height / 2) return -1;
-  return (row >> 3) * g.mbw + (x >> 3);
-}
 #if defined(__HIP_DEVICE_COMPILE__)
 LS_FN void ls_or_u32(uint32_t *p, uint32_t v) { atomicOr(p, v); }
 #else
 LS_FN void ls_or_u32(uint32_t *p, uint32_t v) { *p |= v; }
 #endif
-// the raster-earlier macroblocks the prediction halo of macroblock mb touches, as mobi_dparse.hip's end_mb lists them.  desc = the clip's row.
-// Returns false when there are more than MOBI_INTRA_DEPS (mobi_parse_frames refuses such a stream).
+// the raster-earlier macroblocks the prediction halo of macroblock mb touches (mobi_syntax.h), as mobi_dparse.hip's end_mb lists them.
+// desc = the clip's row.  Returns false when there are more than MOBI_INTRA_DEPS (mobi_parse_frames refuses such a stream).
 LS_FN bool ls_intra_deps(const LsGeom &g, MbDesc *desc, int mb) {
   uint32_t deps[MOBI_INTRA_DEPS];
   int n = 0;
   bool ok = true;
-  const int S = g.stride, o = ((mb / g.mbw) * 16) * S + (mb % g.mbw) * 16;
-  int probes[21];
-  probes[0] = ls_owner_luma(g, o - S - 1); probes[1] = ls_owner_luma(g, o - S); probes[2] = ls_owner_luma(g, o - S + 16);
-  probes[3] = ls_owner_luma(g, o - 1); probes[4] = ls_owner_luma(g, o + 16); probes[5] = ls_owner_luma(g, o + S - 1); probes[6] = ls_owner_luma(g, o + S + 16);
-  for (int v = 0; v < 2; v++) {
-    const int b = o / 2 + v * (S / 2);
-    int *p = probes + 7 + 7 * v;
-    p[0] = ls_owner_chroma(g, b - S - 1); p[1] = ls_owner_chroma(g, b - S); p[2] = ls_owner_chroma(g, b - S + 8);
-    p[3] = ls_owner_chroma(g, b - 1); p[4] = ls_owner_chroma(g, b + 8); p[5] = ls_owner_chroma(g, b + S - 1); p[6] = ls_owner_chroma(g, b + S + 8);
-  }
-  for (int i = 0; i < 21; i++) {
-    const int ow = probes[i];
-    if (ow < 0 || ow >= mb) continue;
-    bool seen = false;
-    for (int k = 0; k < n; k++) seen = seen || (int)(deps[k] & 0x1FFF) == ow;
-    if (seen) continue;
-    if (n == MOBI_INTRA_DEPS) { ok = false; break; }
-    const bool intra = (desc[ow].w1 & 1) == MOBI_MB_INTRA;
-    deps[n++] = (uint32_t)ow | (intra ? 0u : MOBI_DEP_INTER);
-    if (intra) { // w3 [1] has intra dependencies, [2] has intra dependents (mobi_recon_intra_cl); other lanes mark other words' bits at the same time
-      ls_or_u32(&desc[ow].w3, 4u);
-      ls_or_u32(&desc[mb].w3, 2u);
+  mobi_halo_owners(g.width, g.height, g.stride, g.lg, g.mbw, ((mb / g.mbw) * 16) * g.stride + (mb % g.mbw) * 16, [&](int ow) {
+    if (!ok) return;
+    const int added = mobi_dep_add(deps, n, mb, ow, [&](int k) { return mobi_w1_intra(desc[k].w1); });
+    if (added == MOBI_DEP_FULL) ok = false;
+    if (added == MOBI_DEP_ADDED_INTRA) { // other lanes mark other words' bits at the same time
+      ls_or_u32(&desc[ow].w3, MOBI_W3_HAS_DEPENDENTS);
+      ls_or_u32(&desc[mb].w3, MOBI_W3_HAS_INTRA_DEPS);
     }
-  }
-  for (int k = n; k < MOBI_INTRA_DEPS; k++) deps[k] = MOBI_DEP_NONE;
-  desc[mb].w4 = deps[0] | (deps[1] << 16);
-  desc[mb].w5 = deps[2] | (deps[3] << 16);
-  desc[mb].w6 = deps[4] | (deps[5] << 16);
-  desc[mb].w7 = deps[6] | (deps[7] << 16);
+  });
+  mobi_deps_pack(deps, n, desc[mb].w4, desc[mb].w5, desc[mb].w6, desc[mb].w7);
   return ok;
 }
 #endif

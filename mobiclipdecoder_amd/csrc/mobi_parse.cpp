@@ -15,9 +15,7 @@ std::atomic<unsigned long> mobi_literal_frame_count;
 std::atomic<unsigned long> mobi_scratch_read_count; // walks that read the transforms' scratch, Internal[154..217] (r01-r04 refused them): a measuring aid
 
 namespace {
-inline uint32_t shl(uint32_t x, int n) { return x << (n & 31); } // C# masks shift counts to 5 bits
-inline uint32_t shr(uint32_t x, int n) { return x >> (n & 31); }
-inline int clz32(uint32_t v) { return v ? __builtin_clz(v) : 32; } // MD.cs:3927
+inline uint32_t shl(uint32_t x, int n) { return mobi_shl(x, n); } // C# masks shift counts to 5 bits
 } // namespace
 
 void ParsedFrame::clear() {
@@ -45,59 +43,28 @@ MobiStreamParser::MobiStreamParser(uint32_t width, uint32_t height, int version)
   mvc_.assign(2 * (g_.mbw + 2), 0);
 }
 
-// ------------------------------------------------------------------ bit reader (MD.cs:2970-3015)
-uint32_t MobiStreamParser::data_u16(long off) const { // IOUtil.ReadU16LE
-  if (off < 0 || off + 1 >= len_) fail(MOBI_E_INDEX);
-  return ((uint32_t)data_[off + 1] << 8) | data_[off];
+// ------------------------------------------------------------------ bit reader (MD.cs:2970-3015; take / ue / se: mobi_syntax.h)
+uint32_t MobiStreamParser::Bits::data_u16(long o) const { // IOUtil.ReadU16LE
+  if (o < 0 || o + 1 >= len) throw Err{MOBI_E_INDEX};
+  return ((uint32_t)data[o + 1] << 8) | data[o];
 }
-void MobiStreamParser::fill_bits() { // FillBits: one 16-bit LE word, no refill at/after Data.Length
-  if (off_ >= len_) return;
-  uint32_t w = data_u16(off_);
-  off_ += 2;
-  nbr_ += 16;
-  win_ |= shl(w, 16 - nbr_);
-}
-void MobiStreamParser::take(int n) {
-  win_ = shl(win_, n);
-  nbr_ -= n;
-  if (nbr_ < 0) fill_bits();
-}
-uint32_t MobiStreamParser::ue() { // Elias-gamma, value = 2^z - 1 + suffix
-  int z = clz32(win_);
-  win_ = shl(win_, z);
-  win_ += win_;
-  uint32_t v = (z == 0) ? 0 : shr(win_, 32 - z);
-  v += shl(1u, z);
-  v--;
-  win_ = shl(win_, z);
-  nbr_ -= 2 * z;
-  if (--nbr_ < 0) fill_bits();
-  return v;
-}
-int MobiStreamParser::se() { // odd codes map to non-positive values (MD.cs:3009-3010)
-  int z = clz32(win_);
-  win_ = shl(win_, z);
-  win_ += win_;
-  uint32_t u = (z == 0) ? 0 : shr(win_, 32 - z);
-  u += shl(1u, z);
-  int v = (int)u;
-  if (v & 1) v = (int)(1u - u);
-  v >>= 1;
-  win_ = shl(win_, z);
-  nbr_ -= 2 * z;
-  if (--nbr_ < 0) fill_bits();
-  return v;
+void MobiStreamParser::Bits::fill_bits() { // FillBits: one 16-bit LE word, no refill at/after Data.Length
+  if (off >= len) return;
+  uint32_t w = data_u16(off);
+  off += 2;
+  nbr += 16;
+  win |= shl(w, 16 - nbr);
 }
 
 // ------------------------------------------------------------------ quantiser (MD.cs:3884-3925)
 void MobiStreamParser::setup_quant(uint32_t q) {
-  if (version_ == MOBI_VERSION_MOFLEX3DS) q = std::min<uint32_t>(std::max<uint32_t>(q, 12), 52);
+  static_assert(sizeof(mobi_qdiv6) == MOBI_QUANT_LIMIT, "the table whose index throws");
+  q = mobi_clamp_quant(version_ == MOBI_VERSION_MOFLEX3DS, q);
   quant_ = q; // assigned before the table index can throw: the old tables then serve the new Quantizer (tq_)
-  if (q >= sizeof(mobi_qdiv6)) fail(MOBI_E_INDEX);
+  if (q >= MOBI_QUANT_LIMIT) fail(MOBI_E_INDEX);
   tq_ = q;
   build_dq();
-  static const int border[8] = {1, 2, 3, 4, 8, 0x10, 0x18, 0x20}; // "no neighbour" marks, re-armed only here
-  for (int b : border) mcache_[b] = 9;
+  mobi_rearm_borders([&](int i) -> uint8_t & { return mcache_[i]; });
 }
 void MobiStreamParser::build_dq() { // Internal[10..89] for quantiser tq_ (MD.cs:3892-3911)
   if (tq_ >= sizeof(mobi_qdiv6)) { memset(dq8_, 0, sizeof(dq8_)); memset(dq4_, 0, sizeof(dq4_)); return; }
@@ -172,24 +139,10 @@ void MobiStreamParser::end_mb() {
   d.w3 = w3_;
   if (mb_type_ == MOBI_MB_INTER) {
     nl = (uint32_t)(n_leaf_words_ / 2);
-    if (nl == 2) { // two halves (leaf word 0: x/2 | y/2<<4 | wi<<8 | hi<<10 | ref<<12)
-      const uint32_t a = leaves_[0] & 0xFFF, b = leaves_[2] & 0xFFF;
-      if (a == (0u | (1u << 10)) && b == ((4u << 4) | (1u << 10))) dual = MOBI_DUAL_TB;
-      if (a == (0u | (1u << 8)) && b == (4u | (1u << 8))) dual = MOBI_DUAL_LR;
-    }
-    if (nl == 1 || dual) { // leaf records: positions and phases instead of motion vectors (MD.cs:400-416)
-      const long S = g_.stride;
-      uint32_t pos[4] = {0, 0, 0, 0};
-      for (uint32_t i = 0; i < nl; i++) {
-        const int ref = (leaves_[2 * i] >> 12) & 7;
-        const int dx = (int16_t)(leaves_[2 * i + 1] & 0xFFFF), dy = (int16_t)(leaves_[2 * i + 1] >> 16), cdx = dx >> 1, cdy = dy >> 1;
-        pos[2 * i] = (uint32_t)(int32_t)(cur_off_ + (long)(dy >> 1) * S + (dx >> 1));
-        pos[2 * i + 1] = (uint32_t)(int32_t)(cur_off_ / 2 + (long)(cdy >> 1) * S + (cdx >> 1));
-        d.w2 |= (uint32_t)ref << (10 + 3 * i);
-        d.w2 |= (uint32_t)((dx & 1) | ((dy & 1) << 1)) << (16 + 4 * i);
-        d.w2 |= (uint32_t)((cdx & 1) | ((cdy & 1) << 1)) << (18 + 4 * i);
-      }
-      d.w3 = pos[0]; d.w4 = pos[1]; d.w5 = pos[2]; d.w6 = pos[3];
+    if (nl == 2) dual = mobi_dual_kind(leaves_[0], leaves_[2]);
+    if (nl == 1 || dual) { // leaf records instead of motion vectors
+      d.w2 |= mobi_leaf_record(0, leaves_[0], leaves_[1], cur_off_, (long)g_.stride, d.w3, d.w4);
+      if (nl == 2) d.w2 |= mobi_leaf_record(1, leaves_[2], leaves_[3], cur_off_, (long)g_.stride, d.w5, d.w6);
     } else {
       build_cells();
       out_->payload.insert(out_->payload.end(), cells_, cells_ + MOBI_MV_CELLS);
@@ -199,29 +152,12 @@ void MobiStreamParser::end_mb() {
   }
   out_->payload.insert(out_->payload.end(), coefs_, coefs_ + n_coefs_);
   if (mb_type_ == MOBI_MB_INTRA && any_wide_) out_->payload.insert(out_->payload.end(), (const uint32_t *)wide_, (const uint32_t *)wide_ + MOBI_WIDE_PARAMS);
-  d.w1 = (uint32_t)mb_type_ | (nl << 1) | (cbp6_ << 8) | (t8mask_ << 14) | ((tq_ & 63) << 20) | ((uint32_t)dual << 26);
+  d.w1 = mobi_desc_w1(mb_type_, nl, cbp6_, t8mask_, tq_, dual);
   out_->desc.push_back(d);
-}
-long MobiStreamParser::area_offset(int area, int sub) const {
-  const long S = g_.stride;
-  long o = (area < 4) ? cur_off_ + (area >> 1) * 8 * S + (area & 1) * 8 : cur_off_ / 2 + (area == 5 ? S / 2 : 0);
-  return o + (sub >> 1) * 4 * S + (sub & 1) * 4;
 }
 
 // ------------------------------------------------------------------ motion (MD.cs:400-456)
-// Would CopyBlock throw?  Rows are visited top to bottom, so first row / last row bound the rest.
-void MobiStreamParser::check_window(long pos, int w, int h, int phase, long plane_len) const {
-  if (pos < 0) fail(MOBI_E_INDEX);
-  long last = pos + (long)(h - 1) * g_.stride;
-  long hi; // highest index touched (phase 0: Array.Copy end is exclusive)
-  switch (phase) {
-    case 0: hi = last + w - 1; break;
-    case 1: hi = last + w; break;
-    case 2: hi = last + w - 1 + g_.stride; break;
-    default: hi = last + w + g_.stride; break;
-  }
-  if (hi >= plane_len) fail(MOBI_E_INDEX);
-}
+// Would CopyBlock throw?  mobi_syntax.h: mobi_mc_windows_ok (all three windows of an in-range vector), mobi_window_ok (one window)
 void MobiStreamParser::mc_leaf(int wi, int hi, int x, int y, int ref, int dx, int dy, int mv_slot) {
   const long S = g_.stride;
   const int w = 16 >> wi, h = 16 >> hi;
@@ -233,15 +169,12 @@ void MobiStreamParser::mc_leaf(int wi, int hi, int x, int y, int ref, int dx, in
   const long cpos = off / 2 + (cdy >> 1) * S + (cdx >> 1);
   const int cph = (int)((cdx & 1) | ((cdy & 1) << 1));
   if (dx >= -MOBI_MV_LIMIT && dx <= MOBI_MV_LIMIT && dy >= -MOBI_MV_LIMIT && dy <= MOBI_MV_LIMIT) {
-    // the three windows at once: the luma one, and of the two chroma ones U starts first and V (S/2 further) ends last
-    const long pos = off + (long)(dy >> 1) * S + (dx >> 1), ylen = S * g_.height;
-    const long hi_y = pos + (long)(h - 1) * S + w - 1 + (dx & 1) + ((dy & 1) ? S : 0); // phase 0: Array.Copy end is exclusive
-    const long hi_c = cpos + S / 2 + (long)((h >> 1) - 1) * S + (w >> 1) - 1 + (cdx & 1) + ((cdy & 1) ? S : 0);
-    if (pos < 0 || hi_y >= ylen || cpos < 0 || hi_c >= ylen / 2) fail(MOBI_E_INDEX);
+    if (!mobi_mc_windows_ok(S, g_.height, off, w, h, dx, dy)) fail(MOBI_E_INDEX);
   } else {
-    check_window(off + (long)(dy >> 1) * S + (dx >> 1), w, h, (dx & 1) | ((dy & 1) << 1), S * g_.height);
-    check_window(cpos, w >> 1, h >> 1, cph, S * g_.height / 2);
-    check_window(cpos + S / 2, w >> 1, h >> 1, cph, S * g_.height / 2);
+    const long ylen = S * g_.height;
+    if (!mobi_window_ok(off + (long)(dy >> 1) * S + (dx >> 1), w, h, (dx & 1) | ((dy & 1) << 1), S, ylen)) fail(MOBI_E_INDEX);
+    if (!mobi_window_ok(cpos, w >> 1, h >> 1, cph, S, ylen / 2)) fail(MOBI_E_INDEX);
+    if (!mobi_window_ok(cpos + S / 2, w >> 1, h >> 1, cph, S, ylen / 2)) fail(MOBI_E_INDEX);
     // A vector beyond the command list's fields whose windows lie inside the planes (r01-r04: refused).  The reference addresses LINEARLY
     // (MD.cs:400-416): luma source = off + (dy >> 1) * S + (dx >> 1), chroma = off / 2 + (dy >> 2) * S + (dx >> 2), phases = the low bits --
     // so (dx - 4 t S, dy + 4 t) is the same copy for every t (t rows down and t * S samples back, in luma: 2 t rows and 2 t S samples;
@@ -270,7 +203,7 @@ void MobiStreamParser::build_cells() {
 // ReadPBlock*/SwitchPBlock* (MD.cs:469-1746) as one table-driven routine; x,y are MB-relative.
 void MobiStreamParser::pblock(int wi, int hi, int x, int y, int mv_slot) {
   const int s = wi * 4 + hi, w = 16 >> wi, h = 16 >> hi;
-  uint32_t code = mobi_part_lut[ver_][s][win_ >> mobi_part_shift[ver_][s]];
+  uint32_t code = mobi_part_lut[ver_][s][r_.win >> mobi_part_shift[ver_][s]];
   if (code >= mobi_part_nbits_len[ver_][s]) fail(MOBI_E_INDEX);
   take(mobi_part_bits[ver_][s][code]);
   if (code == 0) {
@@ -350,62 +283,7 @@ void MobiStreamParser::resid_block(int area, int sub, bool is8) {
   const int tile = is8 ? area * 64 : area * 64 + sub * 16;
   for (;;) {
     int skip, value;
-    uint32_t e;
-    if ((win_ >> 25) == 3) { // escape prefix 0000011
-      win_ <<= 7;
-      bool c = (win_ >> 31) == 1;
-      win_ <<= 1;
-      if (!c) { // "0": table code, level += B[last<<6|run]
-        nbr_ -= 8;
-        if (nbr_ < 0) fill_bits();
-        e = A[win_ >> 20];
-        value = (int)((e >> 4) & 0x1F) + B[e >> 9];
-        win_ = shl(win_, (int)(e & 0xF) - 1);
-        if (win_ >> 31) value = -value;
-        win_ <<= 1;
-        nbr_ -= (int)(e & 0xF);
-        if (nbr_ < 0) fill_bits();
-        skip = (int)((e >> 9) & 0x3F);
-        e >>= 15;
-      } else {
-        c = (win_ >> 31) == 1;
-        win_ <<= 1;
-        nbr_ -= 9;
-        if (nbr_ < 0) fill_bits();
-        if (!c) { // "10": table code, run += B[0x80 + level + (last<<6)]
-          e = A[win_ >> 20];
-          value = (int)((e >> 4) & 0x1F);
-          skip = (int)((e >> 9) & 0x3F) + B[0x80 + value + ((e >> 15) << 6)];
-          win_ = shl(win_, (int)(e & 0xF) - 1);
-          if (win_ >> 31) value = -value;
-          win_ <<= 1;
-          nbr_ -= (int)(e & 0xF);
-          if (nbr_ < 0) fill_bits();
-          e >>= 15;
-        } else { // "11": raw last(1) run(6) level(s12)
-          e = win_ >> 31;
-          win_ <<= 1;
-          skip = (int)(win_ >> 26);
-          win_ <<= 6;
-          nbr_ -= 7;
-          if (nbr_ < 0) fill_bits();
-          value = (int32_t)win_ >> 20;
-          win_ <<= 12;
-          nbr_ -= 12;
-          if (nbr_ < 0) fill_bits();
-        }
-      }
-    } else {
-      e = A[win_ >> 20];
-      value = (int)((e >> 4) & 0x1F);
-      win_ = shl(win_, (int)(e & 0xF) - 1);
-      if (win_ >> 31) value = -value;
-      win_ <<= 1;
-      nbr_ -= (int)(e & 0xF);
-      if (nbr_ < 0) fill_bits();
-      skip = (int)((e >> 9) & 0x3F);
-      e >>= 15;
-    }
+    const uint32_t last = mobi_rd_token(r_, A, B, skip, value);
     r12 += (uint32_t)skip;
     if (!odd && r12 < start + (uint32_t)N) { // the word is the block's own and its low byte a position inside the block
       const uint32_t word = dq[r12 - start], cv = (word >> 8) * (uint32_t)value; // (int * int in the reference: the low 32 bits either way)
@@ -422,7 +300,7 @@ void MobiStreamParser::resid_block(int area, int sub, bool is8) {
       internal_write(90 + (r8 & 0xFF), (r8 >> 8) * (uint32_t)value);
     }
     r12++;
-    if (e & 1) break;
+    if (last) break;
   }
   // the transform variant the reference runs (by the final index, MD.cs:2939-2942, 2954-2955, 2966-2967) and what it reads
   enum { V1, V3, V16, VALL };
@@ -508,10 +386,9 @@ void MobiStreamParser::literal_frame(ParsedFrame &out) {
   int32_t sc[MOBI_SCALE_STRIDE];
   mobi_build_scale_table((int)tq_, sc);
   for (MbDesc &d : out.desc) {
-    const bool intra = (d.w1 & 1) == MOBI_MB_INTRA;
-    const uint32_t nl = (d.w1 >> 1) & 0x7F, dual = (d.w1 >> 26) & 3, t8 = (d.w1 >> 14) & 0x3F;
-    uint32_t *w = out.payload.data() + d.payload_off + (intra ? MOBI_INTRA_RECORDS : (nl > 1 && !dual) ? MOBI_MV_CELLS : 0);
-    for (uint32_t i = 0, n = d.w2 & 0x3FF; i < n; i++) {
+    const uint32_t t8 = mobi_w1_t8mask(d.w1);
+    uint32_t *w = out.payload.data() + d.payload_off + mobi_levels_offset(d.w1);
+    for (uint32_t i = 0, n = mobi_w2_coefs(d.w2); i < n; i++) {
       if (w[i] & 0x8000u) { w[i] &= ~0x8000u; continue; }
       const int t = (int)(w[i] & 0x1FF), p = t & 63;
       const int32_t v = sc[((t8 >> (t >> 6)) & 1) ? p : 64 + (p & 15)] * (int32_t)(int16_t)(w[i] >> 16);
@@ -527,9 +404,9 @@ void MobiStreamParser::literal_frame(ParsedFrame &out) {
   }
 }
 void MobiStreamParser::resid_area(int area) { // loc_11652C, MD.cs:2909-2929
-  if (win_ >> 31) {
-    win_ += win_;
-    nbr_--;
+  if (r_.win >> 31) {
+    r_.win += r_.win;
+    r_.nbr--;
     t8mask_ |= 1u << area;
     resid_block(area, 0, true);
   } else {
@@ -549,20 +426,13 @@ void MobiStreamParser::p_residual() { // loc_1161A0, MD.cs:1818-1833
 }
 
 // ------------------------------------------------------------------ intra syntax
-// Reads PredictIntra (MD.cs:1883-2774) / the plane predictors (:3017-3327) make outside the block:
-// the top row needs Offset-Stride >= 0, the left column Offset-1 >= 0; anything else is in range.
-void MobiStreamParser::check_intra_reads(int mode, long off, bool) const {
-  static const bool top[10] = {1, 0, 1, 0, 0, 1, 1, 1, 1, 0}, left[10] = {0, 1, 1, 0, 1, 1, 1, 1, 0, 0};
-  if (top[mode] && off < g_.stride) fail(MOBI_E_INDEX);
-  if (left[mode] && off < 1) fail(MOBI_E_INDEX);
+void MobiStreamParser::check_intra_reads(int mode, long off) const { // the reference indexes below the plane: it throws
+  if (!mobi_intra_reads_ok(mode, off, g_.stride)) fail(MOBI_E_INDEX);
 }
-// predicted-mode code shared by loc_116220 / loc_116368 / sub_1163DC (MD.cs:1840-1859, 2785-2804, 2841-2858)
+// the predicted-mode code (mobi_syntax.h) and its place in the mode cache: one 8x8 block's four entries, or one 4x4 block's own
 int MobiStreamParser::pmode(int ci, bool four) {
-  int pred = std::min(mcache_[ci - 8], mcache_[ci - 1]);
-  if (pred == 9) pred = 3;
-  int v = (int)(win_ >> 28), nb = 1, mode = pred;
-  if (v >= pred) v++;
-  if (v < 9) { mode = v; nb = 4; }
+  int nb;
+  const int mode = mobi_pmode_decode(mcache_[ci - 8], mcache_[ci - 1], r_.win, nb);
   if (four) mcache_[ci] = (uint8_t)mode;
   else mcache_[ci] = mcache_[ci + 1] = mcache_[ci + 8] = mcache_[ci + 9] = (uint8_t)mode;
   take(nb);
@@ -581,14 +451,14 @@ uint32_t MobiStreamParser::plane_param(int p, int r) {
 // sub_116508 (MD.cs:2869-2896) or a bare PredictIntra: one 8x8 area whose mode is already known
 void MobiStreamParser::intra_area_fixed(int area, int mode, bool coded) {
   if (!coded) {
-    check_intra_reads(mode, area_offset(area, 0), false);
+    check_intra_reads(mode, area_offset(area, 0));
     recs_[area * 4] |= mobi_intra_rec(mode, 0, 0, 0, 0);
     return;
   }
-  if (win_ >> 31) {
-    win_ += win_;
-    nbr_--;
-    check_intra_reads(mode, area_offset(area, 0), false);
+  if (r_.win >> 31) {
+    r_.win += r_.win;
+    r_.nbr--;
+    check_intra_reads(mode, area_offset(area, 0));
     recs_[area * 4] |= mobi_intra_rec(mode, 1, 0, 0, 0);
     cbp6_ |= 1u << area;
     t8mask_ |= 1u << area;
@@ -598,7 +468,7 @@ void MobiStreamParser::intra_area_fixed(int area, int mode, bool coded) {
     if (u >= sizeof(mobi_cbp4_intra)) fail(MOBI_E_INDEX);
     uint32_t m4 = mobi_cbp4_intra[u];
     for (int sub = 0; sub < 4; sub++) {
-      check_intra_reads(mode, area_offset(area, sub), true);
+      check_intra_reads(mode, area_offset(area, sub));
       int c = (m4 >> sub) & 1;
       recs_[area * 4 + sub] |= mobi_intra_rec(mode, c, 1, 0, 0);
       if (c) {
@@ -609,13 +479,13 @@ void MobiStreamParser::intra_area_fixed(int area, int mode, bool coded) {
   }
 }
 void MobiStreamParser::intra_chroma(uint32_t cbp) { // loc_116290, MD.cs:1864-1880
-  int m = (int)(win_ >> 29);
+  int m = (int)(r_.win >> 29);
   take(3);
   if (m == 2) {
     m = 9;
     for (int area = 4; area < 6; area++) {
       const int p = se();
-      check_intra_reads(2, area_offset(area, 0), false);
+      check_intra_reads(2, area_offset(area, 0));
       recs_[area * 4] |= mobi_intra_rec(0, 0, 0, 1, 0) | plane_param(p, area * 4);
     }
   }
@@ -626,12 +496,12 @@ void MobiStreamParser::intra_full() { // DecIntraFullBlockPMode, MD.cs:1759-1786
   uint32_t u = ue();
   if (u >= sizeof(mobi_cbp_intra)) fail(MOBI_E_INDEX);
   uint32_t cbp = mobi_cbp_intra[u];
-  int m = (int)(win_ >> 29);
+  int m = (int)(r_.win >> 29);
   take(3);
   if (m == 2) {
     m = 9;
     const int p = se();
-    check_intra_reads(2, cur_off_, false);
+    check_intra_reads(2, cur_off_);
     const uint32_t pp = plane_param(p, 24);
     w3_ = 1u | (pp == MOBI_REC_WIDE ? MOBI_W3_WIDE : pp);
   }
@@ -647,14 +517,14 @@ void MobiStreamParser::intra_sub() { // DecIntraSubBlockPMode, MD.cs:1789-1807
     bool coded = (cbp >> k) & 1;
     bool whole = true;
     if (coded) { // loc_116368, MD.cs:2776
-      if (win_ >> 31) { win_ <<= 1; nbr_--; }
+      if (r_.win >> 31) { r_.win <<= 1; r_.nbr--; }
       else whole = false;
     }
     if (whole) {
       int m = pmode(ci[k], false);
       uint32_t pp = 0;
       if (m == 2) pp = plane_param(se(), k * 4); // the predictor itself reads its parameter (MD.cs:1915-1919)
-      check_intra_reads(m, area_offset(k, 0), false);
+      check_intra_reads(m, area_offset(k, 0));
       recs_[k * 4] |= mobi_intra_rec(m, coded, 0, 0, 0) | pp;
       if (coded) {
         cbp6_ |= 1u << k;
@@ -669,7 +539,7 @@ void MobiStreamParser::intra_sub() { // DecIntraSubBlockPMode, MD.cs:1789-1807
         int m = pmode(ci[k] + d5[sub], true);
         uint32_t pp = 0;
         if (m == 2) pp = plane_param(se(), k * 4 + sub);
-        check_intra_reads(m, area_offset(k, sub), true);
+        check_intra_reads(m, area_offset(k, sub));
         int c = (m4 >> sub) & 1;
         recs_[k * 4 + sub] |= mobi_intra_rec(m, c, 1, 0, 0) | pp;
         if (c) {
@@ -684,7 +554,7 @@ void MobiStreamParser::intra_sub() { // DecIntraSubBlockPMode, MD.cs:1789-1807
 
 // ------------------------------------------------------------------ frames (MD.cs:97-259)
 void MobiStreamParser::parse_p(ParsedFrame &out) {
-  if (--nbr_ < 0) fill_bits();
+  if (--r_.nbr < 0) r_.fill_bits();
   if (version_ == MOBI_VERSION_MOFLEX3DS) {
     uint32_t q = quant_;
     int dq = se();
@@ -712,22 +582,22 @@ void MobiStreamParser::parse_p(ParsedFrame &out) {
   }
 }
 void MobiStreamParser::parse_i(ParsedFrame &out) {
-  yuvfmt_ = win_ >> 31;
-  win_ += win_;
-  vlc_table_ = (int)(win_ >> 31);
+  yuvfmt_ = r_.win >> 31;
+  r_.win += r_.win;
+  vlc_table_ = (int)(r_.win >> 31);
   i218_ = (uint32_t)vlc_table_;
-  win_ += win_;
-  nbr_ -= 3;
-  if (nbr_ < 0) fill_bits();
-  uint32_t q = win_ >> 26;
+  r_.win += r_.win;
+  r_.nbr -= 3;
+  if (r_.nbr < 0) r_.fill_bits();
+  uint32_t q = r_.win >> 26;
   take(6);
   if (quant_ != q) setup_quant(q);
   out.hdr.frame_type = 1;
   for (int mb = 0; mb < g_.mbw * g_.mbh; mb++) {
-    bool sub = (win_ >> 31) == 1;
-    win_ += win_;
-    nbr_--;
-    if (nbr_ < 0) fill_bits();
+    bool sub = (r_.win >> 31) == 1;
+    r_.win += r_.win;
+    r_.nbr--;
+    if (r_.nbr < 0) r_.fill_bits();
     begin_mb(mb, MOBI_MB_INTRA);
     if (sub) intra_sub(); else intra_full();
     end_mb();
@@ -748,46 +618,20 @@ void MobiStreamParser::finish_levels(ParsedFrame &out) {
     n_intra++;
     long off = (long)(mb / g_.mbw) * 16 * S + (mb % g_.mbw) * 16;
     int lv = 0;
-    uint16_t deps[MOBI_INTRA_DEPS];
+    uint32_t deps[MOBI_INTRA_DEPS];
     int n_deps = 0;
     auto dep = [&](int o) {
-      if (o < 0 || o >= mb) return; // raster-later owners read as the fresh plane's zeros (the kernel masks them)
-      if (level[o] > lv) lv = level[o]; // levels order intra macroblocks only (inter ones are level 0) ...
+      if (o >= 0 && o < mb && level[o] > lv) lv = level[o]; // levels order intra macroblocks only (inter ones are level 0) ...
       // ... but the dependency list names every raster-earlier owner: in a one-launch step the inter quads run alongside
-      for (int k = 0; k < n_deps; k++)
-        if ((deps[k] & 0x1FFF) == o) return;
-      if (n_deps == MOBI_INTRA_DEPS) fail(MOBI_E_UNSUPPORTED); // cannot happen: the halo touches at most 7 macroblocks
-      deps[n_deps++] = (uint16_t)(o | (level[o] == 0 ? MOBI_DEP_INTER : 0));
-      if (level[o] != 0) { flag[mb] |= 2; flag[o] |= 4; }
+      const int added = mobi_dep_add(deps, n_deps, mb, o, [&](int k) { return level[k] != 0; });
+      if (added == MOBI_DEP_FULL) fail(MOBI_E_UNSUPPORTED);
+      if (added == MOBI_DEP_ADDED_INTRA) { flag[mb] |= 2; flag[o] |= 4; }
     };
-    // The halo is the row above (columns -1 .. +23 luma, -1 .. +15 chroma) and the columns left and right of the macroblock.
-    // Its owners change only at 16-pixel (8 for chroma) boundaries and, in the side columns, between the first row and the
-    // rest (row wrap when width == stride), so these probes meet every distinct owner, in the order a full scan would.
-    dep(g_.owner_luma(off - S - 1));
-    dep(g_.owner_luma(off - S));
-    dep(g_.owner_luma(off - S + 16));
-    dep(g_.owner_luma(off - 1));
-    dep(g_.owner_luma(off + 16));
-    dep(g_.owner_luma(off + S - 1));
-    dep(g_.owner_luma(off + S + 16));
-    for (int v = 0; v < 2; v++) {
-      const long base = off / 2 + v * (S / 2);
-      dep(g_.owner_chroma(base - S - 1));
-      dep(g_.owner_chroma(base - S));
-      dep(g_.owner_chroma(base - S + 8));
-      dep(g_.owner_chroma(base - 1));
-      dep(g_.owner_chroma(base + 8));
-      dep(g_.owner_chroma(base + S - 1));
-      dep(g_.owner_chroma(base + S + 8));
-    }
+    mobi_halo_owners(g_.width, g_.height, g_.stride, g_.lg, g_.mbw, off, dep); // (the probes and their order: mobi_syntax.h)
     level[mb] = (uint16_t)(lv + 1);
     if (lv + 1 > maxl) maxl = lv + 1;
-    for (int k = n_deps; k < MOBI_INTRA_DEPS; k++) deps[k] = MOBI_DEP_NONE;
     MbDesc &d = out.desc[mb];
-    d.w4 = deps[0] | ((uint32_t)deps[1] << 16);
-    d.w5 = deps[2] | ((uint32_t)deps[3] << 16);
-    d.w6 = deps[4] | ((uint32_t)deps[5] << 16);
-    d.w7 = deps[6] | ((uint32_t)deps[7] << 16);
+    mobi_deps_pack(deps, n_deps, d.w4, d.w5, d.w6, d.w7);
   }
   // Launch order inside a level: by CLASS = (at a picture edge ? 8 : 0) + (has intra dependents ? 4 : 0) + min(split areas, 3).  A wave of
   // mobi_recon_intra carries four macroblocks and runs as many steps as the longest of them has (6 + 3 per split area); three in four have
@@ -837,19 +681,19 @@ void MobiStreamParser::finish_levels(ParsedFrame &out) {
 int MobiStreamParser::parse_frame(const uint8_t *data, size_t len, int32_t *offset, ParsedFrame &out) {
   out.clear();
   if (version_ != MOBI_VERSION_MODSDS && version_ != MOBI_VERSION_MOFLEX3DS) return MOBI_E_VERSION;
-  data_ = data;
-  len_ = (long)len;
-  off_ = *offset;
+  r_.data = data;
+  r_.len = (long)len;
+  r_.off = *offset;
   out_ = &out;
   int rc = MOBI_OK;
   frames_started_++; // ring rotation + fresh planes happen before anything can throw (MD.cs:102-108)
   try {
-    nbr_ = 0;
-    win_ = data_u16(off_);
-    off_ += 2;
-    win_ <<= 16;
-    bool iframe = (win_ >> 31) == 1;
-    win_ += win_;
+    r_.nbr = 0;
+    r_.win = r_.data_u16(r_.off);
+    r_.off += 2;
+    r_.win <<= 16;
+    bool iframe = (r_.win >> 31) == 1;
+    r_.win += r_.win;
     frame_literal_ = frame_fault_ = big_unsure_ = frame_host_only_ = false;
     if (iframe) parse_i(out); else parse_p(out);
     if (frame_literal_) literal_frame(out);
@@ -858,7 +702,7 @@ int MobiStreamParser::parse_frame(const uint8_t *data, size_t len, int32_t *offs
   } catch (const Err &e) {
     rc = e.code;
   }
-  *offset = off_;
+  *offset = r_.off;
   last_frame_ok_ = rc == MOBI_OK;
   return rc;
 }

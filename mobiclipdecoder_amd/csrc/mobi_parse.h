@@ -14,6 +14,7 @@
 
 #include "mobi_cmd.h"
 #include "mobi_state.h"
+#include "mobi_syntax.h"
 
 enum { MOBI_INTRA_CLASSES = 16 }; // launch classes of intra macroblocks inside a dependency level (finish_levels)
 struct ParsedFrame {
@@ -33,24 +34,12 @@ struct ParsedFrame {
   size_t cmd_bytes() const { return desc.size() * sizeof(MbDesc) + payload.size() * 4; }
 };
 
-// Geometry helpers shared by the parser (dependency levels) and the kernels (availability):
-// which macroblock owns the pixel at linear address `a` of the Y / UV plane; -1 = padding / outside.
+// Picture geometry; which macroblock owns the pixel at linear address `a` of the Y / UV plane (-1 = padding / outside): mobi_syntax.h
 struct MobiGeom {
   int width, height, stride, mbw, mbh;
-  int lg; // log2(stride): the stride is 256 / 512 / 1024 (MD.cs:50-52), so rows and columns come by shift and mask
-  int owner_luma(long a) const {
-    if (a < 0) return -1;
-    const long row = a >> lg, col = a & (stride - 1);
-    if (col >= width || row >= height) return -1;
-    return (int)((row >> 4) * mbw + (col >> 4));
-  }
-  int owner_chroma(long a) const {
-    if (a < 0) return -1;
-    const long row = a >> lg, col = a & (stride - 1);
-    const long x = col >= stride / 2 ? col - stride / 2 : col;
-    if (x >= width / 2 || row >= height / 2) return -1;
-    return (int)((row >> 3) * mbw + (x >> 3));
-  }
+  int lg; // log2(stride)
+  int owner_luma(long a) const { return mobi_owner_luma(width, height, stride, lg, mbw, a); }
+  int owner_chroma(long a) const { return mobi_owner_chroma(width, height, stride, lg, mbw, a); }
 };
 // halo the intra kernel loads around a macroblock (must match mobi_kernels.hip)
 enum { MOBI_HALO_Y_RIGHT = 23, MOBI_HALO_C_RIGHT = 15 };
@@ -101,12 +90,19 @@ class MobiStreamParser {
   [[noreturn]] void fail(int code) const { throw Err{code}; }
   // MOBI_E_UNSUPPORTED by cause (INTEGRATION.md error table): counted for tools/exp_refusals.py
   [[noreturn]] void refuse(int cause) const { mobi_refusal_count[cause].fetch_add(1, std::memory_order_relaxed); throw Err{-6 /* MOBI_E_UNSUPPORTED */}; }
-  // bit reader
-  uint32_t data_u16(long off) const;
-  void fill_bits();
-  void take(int n);
-  uint32_t ue();
-  int se();
+  // bit reader (MD.cs:2970-3015): the reference's 32-bit window, refilled a 16-bit word at a time; its codes are mobi_syntax.h's
+  struct Bits {
+    const uint8_t *data = nullptr;
+    long len = 0;
+    int off = 0;
+    uint32_t win = 0; // r3
+    int nbr = 0;      // nrBitsRemaining
+    uint32_t data_u16(long o) const;
+    void fill_bits();
+  };
+  void take(int n) { mobi_rd_take(r_, n); }
+  uint32_t ue() { return mobi_rd_ue(r_); }
+  int se() { return mobi_rd_se(r_); }
   // syntax
   void setup_quant(uint32_t q);
   void parse_p(ParsedFrame &out);
@@ -114,7 +110,6 @@ class MobiStreamParser {
   void pblock(int wi, int hi, int x, int y, int mv_slot);
   void mc_leaf(int wi, int hi, int x, int y, int ref, int dx, int dy, int mv_slot);
   void build_cells();
-  void check_window(long pos, int w, int h, int phase, long plane_len) const;
   void p_residual();
   void resid_area(int area);
   void resid_block(int area, int sub, bool is8);
@@ -130,20 +125,15 @@ class MobiStreamParser {
   void intra_area_fixed(int area, int mode, bool coded);
   int pmode(int ci, bool four);
   uint32_t plane_param(int p, int r);
-  void check_intra_reads(int mode, long off, bool four) const;
-  long area_offset(int area, int sub) const;
+  void check_intra_reads(int mode, long off) const;
+  long area_offset(int area, int sub) const { return mobi_area_offset(cur_off_, (long)g_.stride, area, sub); }
   void begin_mb(int mb, int type);
   void end_mb();
   void finish_levels(ParsedFrame &out);
 
   MobiGeom g_;
   int version_, ver_; // ver_: table index 0 = Moflex3DS, 1 = ModsDS
-  // stream
-  const uint8_t *data_ = nullptr;
-  long len_ = 0;
-  int off_ = 0;
-  uint32_t win_ = 0; // r3
-  int nbr_ = 0;      // nrBitsRemaining
+  Bits r_; // the stream
   // persistent decoder state
   uint32_t quant_ = 0, yuvfmt_ = 0;
   uint32_t tq_ = MOBI_TQ_NONE; // the quantiser dq8_ / dq4_ were built for: SetupQuantizationTables assigns Quantizer before its table index can

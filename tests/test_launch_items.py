@@ -99,3 +99,55 @@ def test_a_picture_as_wide_as_its_stride_wraps_to_a_later_wavefront():
     mbw = p.width // 16
     later = [(mb, dep) for mb, dep in _intra_deps_by_frame(p) if dep % mbw + 2 * (dep // mbw) >= mb % mbw + 2 * (mb // mbw)]
     assert later and all(mb % mbw == 0 and dep == mb - 1 for mb, dep in later)
+
+
+def _halo_scan(mb, w, h, mbw, stride):
+    """the owners of every sample of macroblock mb's prediction halo, in scan order: per plane (Y, U, V) the row above from the corner to the
+    last column the predictors read (+23 luma, +15 chroma), then row by row the sample to the left and the samples to the right.  Stated from
+    the plane layout alone: linear offsets into a plane of `stride` columns, U in the left half of the chroma plane and V in the right."""
+    def owner(a, chroma):
+        if a < 0:
+            return -1
+        row, col = divmod(a, stride)
+        if chroma and col >= stride // 2:
+            col -= stride // 2
+        n = 8 if chroma else 16
+        if col >= w // (2 if chroma else 1) or row >= h // (2 if chroma else 1):
+            return -1
+        return (row // n) * mbw + col // n
+    off = (mb // mbw) * 16 * stride + (mb % mbw) * 16
+    for base, chroma in ((off, False), (off // 2, True), (off // 2 + stride // 2, True)):
+        n = 8 if chroma else 16
+        for c in range(-1, n + 8):
+            yield owner(base - stride + c, chroma)
+        for r in range(n):
+            yield owner(base + r * stride - 1, chroma)
+            for c in range(n, n + 8):
+                yield owner(base + r * stride + c, chroma)
+
+
+@pytest.mark.parametrize("kw", [dict(width=64, height=48, pm_intra=500), dict(width=176, height=144, version=2, pm_intra=700, iframe_interval=2),
+                                dict(width=256, height=64, pm_intra=900, iframe_interval=1), dict(width=1024, height=32, version=2, pm_intra=400)])
+def test_dependency_lists_are_the_halo_scanned_in_order(kw):
+    """MbDesc.w4..w7 of every intra macroblock against a scan of its whole halo: the raster-earlier owners, each once, in the order the scan
+    meets them, inter ones flagged, the rest of the eight entries empty.  (The parsers probe 21 addresses instead, mobi_syntax.h: this is what
+    the probes and their order have to reproduce -- all three parsers share them, so their agreement with each other does not show it.)"""
+    p = default_params("A", BASE_SEED + 6400, **{"n_frames": 3, **kw})
+    data, fo = generate_clip(p)
+    d = InterpDecoder(p.width, p.height, p.version)
+    mbw, stride = p.width // 16, 256 if p.width <= 256 else 512 if p.width <= 512 else 1024
+    longest = n_lists = 0
+    for f in range(p.n_frames):
+        d.Data, d.Offset = data[: fo[f + 1]], int(fo[f])
+        assert d.DecodeFrame() is not None
+        desc, mbs, _, _ = d.command_list()
+        for mb in (int(x) for x in mbs):
+            want = []
+            for o in _halo_scan(mb, p.width, p.height, mbw, stride):
+                if 0 <= o < mb and o not in [x & 0x1FFF for x in want]:
+                    want.append(o | (0 if desc[o, 1] & 1 else DEP_INTER))
+            w = desc[mb, 4:8]
+            got = [int(x) for pair in zip(w & 0xFFFF, w >> 16) for x in pair]
+            assert got == want + [DEP_NONE] * (8 - len(want)), (f, mb, got, want)
+            longest = max(longest, len(want)); n_lists += 1
+    assert n_lists > 10 and longest >= 4

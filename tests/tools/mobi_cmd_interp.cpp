@@ -90,12 +90,12 @@ void exec_inter(Interp &I, int mb, const MbDesc &d) {
   const MobiGeom &g = I.g;
   const long S = g.stride;
   const uint32_t *pl = I.pf.payload.data() + d.payload_off;
-  const int nl = (d.w1 >> 1) & 0x7F, cbp6 = (d.w1 >> 8) & 0x3F, t8 = (d.w1 >> 14) & 0x3F, ncoef = d.w2 & 0x3FF;
+  const int nl = (int)mobi_w1_leaves(d.w1), cbp6 = (d.w1 >> 8) & 0x3F, t8 = (int)mobi_w1_t8mask(d.w1), ncoef = (int)mobi_w2_coefs(d.w2);
   const long off = (long)(mb / g.mbw) * 16 * S + (mb % g.mbw) * 16;
   uint8_t ty[16 * TP], tc[2][8 * TP]; // prediction tiles (interior only; pitch TP, origin at byte 0)
   // per pixel group: the leaf record of the descriptor (single / two halves) or the MV cell under it (deeper trees).
   // A source = (reference slot, position of the macroblock origin's image, CopyBlock phase), for luma and chroma.
-  const int dual = (d.w1 >> 26) & 3; // two inline halves: no cell map in the payload
+  const int dual = (int)mobi_w1_dual(d.w1); // two inline halves: no cell map in the payload
   struct Src { int ref; long ypos, cpos; int yph, cph; };
   auto src_at = [&](int cellx, int celly) {
     Src s;
@@ -144,10 +144,10 @@ void exec_inter(Interp &I, int mb, const MbDesc &d) {
       tc[v01][row * TP + c4 + k] = (uint8_t)(v >> (8 * k));
     }
   }
-  const uint32_t *cw = pl + (nl > 1 && !dual ? MOBI_MV_CELLS : 0);
+  const uint32_t *cw = pl + mobi_levels_offset(d.w1);
   if (cbp6) {
     int coef[6 * 64];
-    dequant_into((d.w1 >> 20) & 63, cw, ncoef, t8, coef);
+    dequant_into(mobi_w1_quant(d.w1), cw, ncoef, t8, coef);
     for (int a = 0; a < 6; a++) {
       if (!((cbp6 >> a) & 1)) continue;
       uint8_t *t = a < 4 ? ty + (a >> 1) * 8 * TP + (a & 1) * 8 : tc[a - 4];
@@ -196,7 +196,7 @@ void exec_intra(Interp &I, int mb, const MbDesc &d) {
   const MobiGeom &g = I.g;
   const long S = g.stride;
   const uint32_t *rec = I.pf.payload.data() + d.payload_off;
-  const int t8 = (d.w1 >> 14) & 0x3F, ncoef = d.w2 & 0x3FF;
+  const int t8 = (int)mobi_w1_t8mask(d.w1), ncoef = (int)mobi_w2_coefs(d.w2);
   const long off = (long)(mb / g.mbw) * 16 * S + (mb % g.mbw) * 16;
   uint8_t *y0 = I.Y(0), *uv0 = I.UV(0);
   uint8_t ty[17 * TP], tc[2][9 * TP];
@@ -219,7 +219,7 @@ void exec_intra(Interp &I, int mb, const MbDesc &d) {
       for (int c = 8; c <= MOBI_HALO_C_RIGHT; c++) tc[v][(r + 1) * TP + 4 + c] = chroma(base + r * S + c);
   }
   int coef[6 * 64];
-  dequant_into((d.w1 >> 20) & 63, rec + MOBI_INTRA_RECORDS, ncoef, t8, coef);
+  dequant_into(mobi_w1_quant(d.w1), rec + mobi_levels_offset(d.w1), ncoef, t8, coef);
   const int32_t *wide = (const int32_t *)rec + MOBI_INTRA_RECORDS + ncoef; // parameters that do not fit a record's 16 bits (mobi_cmd.h)
   auto param_of = [&](uint32_t r, int idx) { return (r & MOBI_REC_WIDE) ? wide[idx] : (int)(int16_t)(r >> 16); };
   if (d.w3 & 1) run_block(I, ty, 0, 0, 16, 2, (d.w3 & MOBI_W3_WIDE) ? wide[24] : (int16_t)(d.w3 >> 16), false, nullptr, false, 0, off, false);
@@ -324,15 +324,13 @@ void mobi_cmdinterp_tail(void *p, const MobiDevTail *in, MobiDevTail *out) {
   const ParsedFrame &f = I.pf;
   for (int mb = (int)f.desc.size() - 1; mb >= 0 && !sc.done; mb--) {
     const MbDesc &d = f.desc[mb];
-    const int n = (int)(d.w2 & 0x3FF);
+    const int n = (int)mobi_w2_coefs(d.w2);
     if (!n) continue;
-    const bool intra = (d.w1 & 1) == MOBI_MB_INTRA;
-    const uint32_t nl = (d.w1 >> 1) & 0x7F, dual = (d.w1 >> 26) & 3;
-    const uint32_t woff = d.payload_off + (intra ? MOBI_INTRA_RECORDS : (nl > 1 && !dual) ? MOBI_MV_CELLS : 0);
-    mobi_tail_scan_mb(sc, f.payload.data() + woff, n, woff, (d.w1 >> 14) & 0x3F, izz8, izz4);
+    const uint32_t woff = d.payload_off + mobi_levels_offset(d.w1);
+    mobi_tail_scan_mb(sc, f.payload.data() + woff, n, woff, mobi_w1_t8mask(d.w1), izz8, izz4);
   }
   int32_t scale[MOBI_SCALE_STRIDE];
-  mobi_build_scale_table((int)(f.desc.empty() ? 0 : (f.desc[0].w1 >> 20) & 63), scale);
+  mobi_build_scale_table((int)(f.desc.empty() ? 0 : mobi_w1_quant(f.desc[0].w1)), scale);
   *out = *in;
   mobi_tail_finish(sc, f.payload.data(), scale, *in, *out);
 }

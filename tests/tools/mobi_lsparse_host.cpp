@@ -93,7 +93,7 @@ int mobi_lshost_parse(void *p, const uint8_t *data, size_t len, int32_t *consume
   if (s.bail) return s.bail;
   const LsGeom g{C.w, C.h, C.g.stride, C.g.lg, C.g.mbw};
   for (uint32_t i = 0; i < s.n_items; i++)
-    if (!ls_intra_deps(g, C.desc.data(), (int)(C.items[i] & 0x1FFF))) return 17;
+    if (!ls_intra_deps(g, C.desc.data(), (int)MOBI_ITEM_MB(C.items[i]))) return 17;
   C.m = m;
   C.quant = s.quant; C.yuvfmt = s.yuvfmt; C.tables_set = s.tables_set; C.frames_started = s.frames_started;
   C.predx = s.predx; C.predy = s.predy;
@@ -328,7 +328,7 @@ int mobi_lshost_compare(uint32_t w, uint32_t h, int version, const uint8_t *data
     for (size_t mb = 0; same && mb < pf.desc.size(); mb++) {
       const MbDesc &a = C->desc[mb], &b = pf.desc[mb];
       bool eq = a.payload_off == b.payload_off && a.w1 == b.w1 && a.w2 == b.w2 && a.w3 == b.w3;
-      if ((a.w1 & 1) == MOBI_MB_INTER) eq = eq && a.w4 == b.w4 && a.w5 == b.w5 && a.w6 == b.w6 && a.w7 == b.w7;
+      if (!mobi_w1_intra(a.w1)) eq = eq && a.w4 == b.w4 && a.w5 == b.w5 && a.w6 == b.w6 && a.w7 == b.w7;
       else { // the same SET of dependencies
         uint32_t da[8], db[8];
         for (int k = 0; k < 4; k++) {
