@@ -316,6 +316,24 @@ int mobi_batch_export_query(mobi_batch *b, uint64_t ticket); /* 1 done, 0 not ye
  *             ring. */
 int mobi_batch_export_device(mobi_batch *b, int format, int dtype, const float *scale_bias, int ring_idx, int n_frames, int clip0,
                              int n_clips, void *dst, size_t dst_bytes, void *stream);
+/* The same export for consumers that want a fixed, smaller size: the crop (crop_x, crop_y, crop_w, crop_h) of every picture, area-averaged
+ * down to out_w x out_h, as RGB tensors (MOBI_EXPORT_RGB_PLANAR / _PACKED only; dtype and scale_bias as above).  One kernel: no full-size
+ * RGB is written anywhere.  Picture order, dst indexing, STREAM, SNAPSHOT and LIFETIME are mobi_batch_export_device's, with picture_bytes =
+ * 3 * out_w * out_h * element size.  One crop per call, the same for every clip.
+ *   VALUES:   exact, in integers.  P[y][x] is the Bitmap's word (mobi_batch_get_argb_at) and v one of its bytes 2, 1, 0 (R, G, B); the chroma
+ *             neighbours and the last-row / last-column rule are the PICTURE's, not the crop's.  Separable area weights:
+ *               wx(ox, s) = max(0, min((s + 1) * out_w, (ox + 1) * crop_w) - max(s * out_w, ox * crop_w)),  s = 0 .. crop_w - 1,
+ *               wy(oy, t) the same with out_h and crop_h;   S = sum_t sum_s wy * wx * v[crop_y + t][crop_x + s];   D = crop_w * crop_h;
+ *               q = (S + D / 2) / D   (floor division, D / 2 floored).
+ *             uint8 stores q; float32 (float)q * scale[ch] + bias[ch], a product and a sum each rounded; float16 that value rounded to
+ *             nearest-even.  out_w == crop_w and out_h == crop_h is a pure crop (q = v); the whole picture at its own size is byte for byte
+ *             mobi_batch_export_device's RGB.  The result does not depend on the order of execution.
+ *   REFUSED:  every refusal of mobi_batch_export_device, and MOBI_E_ARG for a format other than the two RGB ones, a crop that is empty or
+ *             not inside the picture, out_w or out_h below 1, out_w > crop_w or out_h > crop_h (no upscaling), out_w not a multiple of 4,
+ *             and crop_w * crop_h > 2^23 (the sums are 32-bit).  A refused call enqueues nothing. */
+int mobi_batch_export_device_scaled(mobi_batch *b, int format, int dtype, const float *scale_bias, int crop_x, int crop_y, int crop_w, int crop_h,
+                                    int out_w, int out_h, int ring_idx, int n_frames, int clip0, int n_clips, void *dst, size_t dst_bytes,
+                                    void *stream);
 /* Encoder-side analysis: Analyzer.InterPredict2x2 (Analyzer.cs:608-681) for every 2x2 luma block of
  * every macroblock of every clip, as SolveInterPredictionPuzzle calls it (:683-693): three-step search (6, 3, 1 pels) in up
  * to five past frames = ring slots 0..4 of this batch (the encoder's PastFramesY, MobiEncoder.cs:138-144).

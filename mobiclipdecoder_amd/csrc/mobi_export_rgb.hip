@@ -19,24 +19,11 @@ namespace {
 using namespace mobi_rgb;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-// the 16-bit pattern of x rounded to nearest-even (v_cvt_f16_f32 in the default rounding mode)
-__device__ __forceinline__ uint32_t half_bits(float x) { return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)x); }
-
 // Element k (0 .. 11) of the lane's four pixels in output order -- planar: channel ch's pixels t = 0 .. 3 (k = t, per plane); packed:
-// pixel k / 3, channel k % 3 -- as the bits of one element of ESIZE bytes.
+// pixel k / 3, channel k % 3 -- as the bits of one element of ESIZE bytes (mobi_rgb.h, tensor_element).
 template <int ESIZE>
 __device__ __forceinline__ uint32_t element(const uint32_t (&argb)[4], int t, int ch, const MobiRgbAffine &sb) {
-  const uint32_t v = (argb[t] >> (16 - 8 * ch)) & 0xFFu; // R = byte 2, G = byte 1, B = byte 0
-  if (ESIZE == 1) return v;
-  // a product and a sum, each rounded: written here, under contract(off) -- __fmul_rn / __fadd_rn are plain operators in the HIP headers,
-  // compiled where contraction is on, and the backend fused them into one v_fma_f32
-  float f;
-  {
-#pragma clang fp contract(off)
-    const float p = (float)v * sb.v[ch];
-    f = p + sb.v[3 + ch];
-  }
-  return ESIZE == 2 ? half_bits(f) : __float_as_uint(f);
+  return tensor_element<ESIZE>((argb[t] >> (16 - 8 * ch)) & 0xFFu, ch, sb.v); // R = byte 2, G = byte 1, B = byte 0
 }
 } // namespace
 

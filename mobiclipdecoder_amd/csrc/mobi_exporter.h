@@ -9,6 +9,8 @@
 
 #include <functional>
 
+#include "mobi_export_scale.h"
+
 // the ring of one batch as the export reads it (MobiReconArgs' layout: [clip][slot 0..5][tiled Y | tiled UV])
 struct MobiExportGeom {
   const uint8_t *planes;
@@ -28,6 +30,11 @@ extern "C" int mobi_launch_export_i420(const MobiExportGeom *g, uint32_t q0, int
 struct MobiRgbAffine { float v[6]; };
 extern "C" int mobi_launch_export_rgb(const MobiExportGeom *g, int version, int planar, int esize, int nontemporal, int n_frames, int n_clips,
                                       int clip0, int slot0, const MobiRgbAffine *sb, uint8_t *out_dev, hipStream_t s);
+
+// mobi_export_scale.hip: the same pictures, the crop and output size of `plan` (mobi_export_scale.h), area-averaged: RGB tensors of
+// plan->ow x plan->oh
+extern "C" int mobi_launch_export_scale(const MobiExportGeom *g, int version, int planar, int esize, const MobiScalePlan *plan, int n_frames,
+                                        int n_clips, int clip0, int slot0, const MobiRgbAffine *sb, uint8_t *out_dev, hipStream_t s);
 
 #if !defined(__HIPCC__) || !defined(__HIP_DEVICE_COMPILE__)
 struct MobiExporter;

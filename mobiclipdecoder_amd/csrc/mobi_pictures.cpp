@@ -104,30 +104,20 @@ int mobi_batch_export(mobi_batch *b, int format, int ring_idx, int n_frames, int
   return MOBI_OK;
 }
 // ---- export into device memory, on the caller's stream (torch tensors, the caller's own HIP allocations) ----
-// The arguments are checked here; the stream order and the ring-slot guard are mobi_export.cpp's, the RGB kernel mobi_export_rgb.hip's.
-int mobi_batch_export_device(mobi_batch *b, int format, int dtype, const float *scale_bias, int ring_idx, int n_frames, int clip0, int n_clips,
-                             void *dst, size_t dst_bytes, void *stream) {
-  if (!b || !dst) return MOBI_E_ARG;
-  size_t esize = 0;
-  switch (format) {
-  case MOBI_EXPORT_I420:
-  case MOBI_EXPORT_ARGB:
-    if (dtype != MOBI_DTYPE_U8 || scale_bias) return MOBI_E_ARG;
-    break;
-  case MOBI_EXPORT_RGB_PLANAR:
-  case MOBI_EXPORT_RGB_PACKED:
-    if (dtype == MOBI_DTYPE_U8) { if (scale_bias) return MOBI_E_ARG; esize = 1; }
-    else if (dtype == MOBI_DTYPE_F16) esize = 2;
-    else if (dtype == MOBI_DTYPE_F32) esize = 4;
-    else return MOBI_E_ARG;
-    break;
-  default:
-    return MOBI_E_ARG;
-  }
+// The arguments are checked here; the stream order and the ring-slot guard are mobi_export.cpp's, the RGB kernels mobi_export_rgb.hip's and
+// mobi_export_scale.hip's.
+namespace {
+// element size of an RGB export's dtype; 0: a combination the RGB formats do not have
+size_t rgb_esize(int dtype, const float *scale_bias) {
+  if (dtype == MOBI_DTYPE_U8) return scale_bias ? 0 : 1;
+  return dtype == MOBI_DTYPE_F16 ? 2 : dtype == MOBI_DTYPE_F32 ? 4 : 0;
+}
+// What every device export checks once its format is known, and the hand-over: pictures of `pic` bytes each, n_frames x n_clips of them
+// into dst on `stream`; launch(job, need, stream) enqueues the kernels (need = the bytes the export writes).
+int export_device(mobi_batch *b, int format, size_t pic, int ring_idx, int n_frames, int clip0, int n_clips, void *dst, size_t dst_bytes, void *stream,
+                  const std::function<int(const MobiExportJob &, size_t, hipStream_t)> &launch) {
   if (clip0 < 0 || n_clips < 1 || clip0 > b->n - n_clips) return MOBI_E_ARG;
   if (ring_idx < 0 || ring_idx > 5 || n_frames < 1 || ring_idx - n_frames + 1 < 0) return MOBI_E_ARG;
-  const size_t px = (size_t)b->g.width * b->g.height;
-  const size_t pic = format == MOBI_EXPORT_I420 ? px * 3 / 2 : format == MOBI_EXPORT_ARGB ? px * 4 : px * 3 * esize;
   const size_t need = pic * n_frames * n_clips;
   if (dst_bytes < need || ((uintptr_t)dst & 15)) return MOBI_E_ARG;
   if (b->poisoned) return MOBI_E_ARG;
@@ -157,16 +147,31 @@ int mobi_batch_export_device(mobi_batch *b, int format, int dtype, const float *
   job.slot0 = (b->ring_base + 6 - ring_idx) % 6;
   job.dst = dst;
   job.src_stream = b->stream;
+  return mobi_exporter_run_device(b->exporter, job, s, [&](hipStream_t st) { return launch(job, need, st); });
+}
+} // namespace
+int mobi_batch_export_device(mobi_batch *b, int format, int dtype, const float *scale_bias, int ring_idx, int n_frames, int clip0, int n_clips,
+                             void *dst, size_t dst_bytes, void *stream) {
+  if (!b || !dst) return MOBI_E_ARG;
+  size_t esize = 0;
+  switch (format) {
+  case MOBI_EXPORT_I420:
+  case MOBI_EXPORT_ARGB:
+    if (dtype != MOBI_DTYPE_U8 || scale_bias) return MOBI_E_ARG;
+    break;
+  case MOBI_EXPORT_RGB_PLANAR:
+  case MOBI_EXPORT_RGB_PACKED:
+    if (!(esize = rgb_esize(dtype, scale_bias))) return MOBI_E_ARG;
+    break;
+  default:
+    return MOBI_E_ARG;
+  }
+  const size_t px = (size_t)b->g.width * b->g.height;
+  const size_t pic = format == MOBI_EXPORT_I420 ? px * 3 / 2 : format == MOBI_EXPORT_ARGB ? px * 4 : px * 3 * esize;
   MobiRgbAffine sb{{1.f, 1.f, 1.f, 0.f, 0.f, 0.f}};
   if (scale_bias) memcpy(sb.v, scale_bias, sizeof(sb.v));
-  // A GPU reader comes next.  Output that fits the 256 MiB MALL is read faster from the caches (plain stores: export + a reduction over it
-  // 4 - 13 % faster); larger output goes past them (0.3 - 4 % faster): tools/exp_export_device.py --nt, DESIGN.md "Export to device memory"
-  int nontemporal = need > ((size_t)256 << 20);
-#if defined(MOBI_PROFILING)
-  if (const char *e = getenv("MOBI_EXPORT_RGB_NT")) nontemporal = atoi(e); // (A/B: tools/exp_export_device.py)
-#endif
   uint8_t *out = (uint8_t *)dst;
-  auto launch = [&](hipStream_t st) -> int {
+  auto launch = [&](const MobiExportJob &job, size_t need, hipStream_t st) -> int {
     if (format == MOBI_EXPORT_I420) return mobi_launch_export_i420(&job.g, 0, n_frames * n_clips, n_clips, clip0, job.slot0, out, st);
     if (format == MOBI_EXPORT_ARGB) {
       for (int j = 0; j < n_frames; j++) { // the Bitmap kernel converts clips of one slot: one launch per frame
@@ -176,10 +181,36 @@ int mobi_batch_export_device(mobi_batch *b, int format, int dtype, const float *
       }
       return 0;
     }
+    // A GPU reader comes next.  Output that fits the 256 MiB MALL is read faster from the caches (plain stores: export + a reduction over it
+    // 4 - 13 % faster); larger output goes past them (0.3 - 4 % faster): tools/exp_export_device.py --nt, DESIGN.md "Export to device memory"
+    int nontemporal = need > ((size_t)256 << 20);
+#if defined(MOBI_PROFILING)
+    if (const char *e = getenv("MOBI_EXPORT_RGB_NT")) nontemporal = atoi(e); // (A/B: tools/exp_export_device.py)
+#endif
     return mobi_launch_export_rgb(&job.g, b->version, format == MOBI_EXPORT_RGB_PLANAR, (int)esize, nontemporal, n_frames, n_clips, clip0,
                                   job.slot0, &sb, out, st);
   };
-  return mobi_exporter_run_device(b->exporter, job, s, launch);
+  return export_device(b, format, pic, ring_idx, n_frames, clip0, n_clips, dst, dst_bytes, stream, launch);
+}
+// The crop, area-averaged down to out_w x out_h (mobi_export_scale.h): RGB tensors only, one crop per call.
+int mobi_batch_export_device_scaled(mobi_batch *b, int format, int dtype, const float *scale_bias, int crop_x, int crop_y, int crop_w, int crop_h,
+                                    int out_w, int out_h, int ring_idx, int n_frames, int clip0, int n_clips, void *dst, size_t dst_bytes, void *stream) {
+  if (!b || !dst || (format != MOBI_EXPORT_RGB_PLANAR && format != MOBI_EXPORT_RGB_PACKED)) return MOBI_E_ARG;
+  const size_t esize = rgb_esize(dtype, scale_bias);
+  if (!esize) return MOBI_E_ARG;
+  const int W = (int)b->g.width, H = (int)b->g.height;
+  if (crop_w < 1 || crop_h < 1 || crop_x < 0 || crop_y < 0 || crop_x > W - crop_w || crop_y > H - crop_h) return MOBI_E_ARG;
+  if (out_w < 1 || out_h < 1 || out_w > crop_w || out_h > crop_h || (out_w & 3)) return MOBI_E_ARG;
+  if ((uint64_t)crop_w * (uint64_t)crop_h > ((uint64_t)1 << 23)) return MOBI_E_ARG; // the sums stay below 2^31
+  const MobiScalePlan plan = mobi_scale_plan((uint32_t)crop_x, (uint32_t)crop_y, (uint32_t)crop_w, (uint32_t)crop_h, (uint32_t)out_w, (uint32_t)out_h);
+  MobiRgbAffine sb{{1.f, 1.f, 1.f, 0.f, 0.f, 0.f}};
+  if (scale_bias) memcpy(sb.v, scale_bias, sizeof(sb.v));
+  auto launch = [&](const MobiExportJob &job, size_t, hipStream_t st) -> int {
+    return mobi_launch_export_scale(&job.g, b->version, format == MOBI_EXPORT_RGB_PLANAR, (int)esize, &plan, n_frames, n_clips, clip0, job.slot0, &sb,
+                                    (uint8_t *)dst, st);
+  };
+  return export_device(b, format, mobi_scale_picture_bytes((uint32_t)out_w, (uint32_t)out_h, (uint32_t)esize), ring_idx, n_frames, clip0, n_clips, dst,
+                       dst_bytes, stream, launch);
 }
 int mobi_batch_export_wait(mobi_batch *b, uint64_t ticket) {
   if (!b || !b->exporter) return MOBI_E_ARG;

@@ -89,6 +89,22 @@ __device__ __forceinline__ void chroma_numerators(uint32_t w0, uint32_t e0w, uin
   od[0] = 2 * (a0 + a1) - 512; od[1] = a0 + b0 + a1 + b1 - 512; od[2] = 2 * (b0 + b1) - 512; od[3] = lastcol ? pb : b0 + e0 + b1 + e1 - 512;
   if (lastrow) { od[0] = pa; od[1] = pa; od[2] = pb; od[3] = pb; } // the odd row is the picture's last: no mean of any kind (MD.cs:269)
 }
+// One element of an RGB tensor (mobi_export_rgb.hip, mobi_export_scale.hip) from the byte value v of channel ch (0 R, 1 G, 2 B), as the
+// bits of ESIZE bytes: uint8 is v; float32 is (float)v * sb[ch] + sb[3 + ch]; float16 is that float32 value rounded to nearest-even
+// (v_cvt_f16_f32 in the default rounding mode).
+// a product and a sum, each rounded: written here, under contract(off) -- __fmul_rn / __fadd_rn are plain operators in the HIP headers,
+// compiled where contraction is on, and the backend fused them into one v_fma_f32
+template <int ESIZE>
+__device__ __forceinline__ uint32_t tensor_element(uint32_t v, int ch, const float (&sb)[6]) {
+  if (ESIZE == 1) return v;
+  float f;
+  {
+#pragma clang fp contract(off)
+    const float p = (float)v * sb[ch];
+    f = p + sb[3 + ch];
+  }
+  return ESIZE == 2 ? (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)f) : __float_as_uint(f);
+}
 } // namespace mobi_rgb
 
 #endif

@@ -104,6 +104,8 @@ _SIGS = {
     "mobi_batch_export_query": (C.c_int, [C.c_void_p, C.c_uint64]),
     "mobi_batch_export_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                            C.c_size_t, C.c_void_p]),
+    "mobi_batch_export_device_scaled": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)] + [C.c_int] * 10 + [C.c_void_p, C.c_size_t,
+                                                                                                                       C.c_void_p]),
     "mobi_error_string": (C.c_char_p, [C.c_int]),
     "mobi_build_info": (C.c_char_p, []),
 }
@@ -560,7 +562,7 @@ class MobiclipBatch:
         return h.wait() if wait else h
 
     def export_tensor(self, fmt="rgb", ring_idx=0, n_frames=1, clips=None, layout="nchw", dtype=None, scale=None, bias=None, out=None,
-                      stream=None):
+                      stream=None, crop=None, size=None):
         """Pictures of many clips and frames into a torch tensor on the batch's GPU (mobi_batch_export_device), enqueued on `stream`
         (default: torch.cuda.current_stream of the batch's device) without a host wait: work enqueued on that stream afterwards sees them.
         Frame j = ring index ring_idx - j (oldest first), clips = a range / slice of step 1 (None: all), as in export().
@@ -571,6 +573,10 @@ class MobiclipBatch:
                     torch.float16 or torch.float32: v * scale[ch] + bias[ch] in float32 (a product and a sum, each rounded), float16 rounded
                     from that.  scale, bias: three floats each (default 1 and 0), for float dtypes only.  Normalising with a mean and a
                     standard deviation is scale = 1 / std, bias = -mean / std, rounded to float32 first.
+        crop=(x, y, w, h), size=(out_h, out_w) (fmt="rgb" only; mobi_batch_export_device_scaled): the crop of every picture (default: the
+                    whole picture), area-averaged down to out_h x out_w (default: the crop's size, a pure crop) in one kernel, exactly (the
+                    definition is include/mobiclip_hip.h's); H, W in the shapes above become out_h, out_w.  No upscaling, out_w a multiple
+                    of 4, w * h <= 2**23.  With both None the call is the full-size export.
         out: a contiguous, 16-byte aligned tensor of that shape and dtype on the batch's device to fill (default: a new one, allocated on
         `stream`).  Every argument is checked before the library is called (ValueError); a refused export enqueues nothing."""
         import torch
@@ -611,6 +617,24 @@ class MobiclipBatch:
         if not isinstance(clips, range) or clips.step != 1 or len(clips) < 1 or clips.start < 0 or clips.stop > self.n:
             raise ValueError(f"clips must be a non-empty range / slice of step 1 inside 0..{self.n}, not {clips!r}")
         F, N, W, H = int(n_frames), len(clips), self.Width, self.Height
+        scaled = crop is not None or size is not None
+        if scaled:
+            if fmt != "rgb":
+                raise ValueError(f"crop and size apply to fmt='rgb' only, not {fmt!r}")
+
+            def ints(name, v, n):
+                if not isinstance(v, (tuple, list)) or len(v) != n or any(isinstance(i, bool) or not isinstance(i, (int, np.integer)) for i in v):
+                    raise ValueError(f"{name} must be {n} ints, not {v!r}")
+                return [int(i) for i in v]
+            cx, cy, cw, ch = (0, 0, W, H) if crop is None else ints("crop", crop, 4)
+            if cw < 1 or ch < 1 or cx < 0 or cy < 0 or cx + cw > W or cy + ch > H:
+                raise ValueError(f"crop (x, y, w, h) = {crop!r} is empty or not inside the {W}x{H} picture")
+            oh, ow = (ch, cw) if size is None else ints("size", size, 2)
+            if not (1 <= ow <= cw and 1 <= oh <= ch) or ow % 4:
+                raise ValueError(f"size (out_h, out_w) = {(oh, ow)!r} must be at least 1x1, no larger than the crop ({ch}, {cw}), out_w a multiple of 4")
+            if cw * ch > 1 << 23:
+                raise ValueError(f"crop of {cw}x{ch} pixels: at most 2**23")
+            W, H = ow, oh
         if fmt == "i420":
             shape, tdtype = (F, N, W * H * 3 // 2), torch.uint8
         elif fmt == "argb":
@@ -630,8 +654,12 @@ class MobiclipBatch:
             with torch.cuda.stream(stream):
                 out = torch.empty(shape, dtype=tdtype, device=dev)
         code = DEVICE_EXPORT_FORMATS[(fmt, layout if fmt == "rgb" else None)]
-        rc = self._lib.mobi_batch_export_device(self._h, code, DEVICE_EXPORT_DTYPES[dname], sb, int(ring_idx), F, clips.start, N,
-                                                out.data_ptr(), out.numel() * out.element_size(), stream.cuda_stream)
+        if scaled:
+            rc = self._lib.mobi_batch_export_device_scaled(self._h, code, DEVICE_EXPORT_DTYPES[dname], sb, cx, cy, cw, ch, ow, oh, int(ring_idx), F,
+                                                           clips.start, N, out.data_ptr(), out.numel() * out.element_size(), stream.cuda_stream)
+        else:
+            rc = self._lib.mobi_batch_export_device(self._h, code, DEVICE_EXPORT_DTYPES[dname], sb, int(ring_idx), F, clips.start, N,
+                                                    out.data_ptr(), out.numel() * out.element_size(), stream.cuda_stream)
         if rc != 0:
             raise MobiclipError(error_string(rc))
         return out

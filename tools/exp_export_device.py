@@ -12,6 +12,12 @@ lines.
                    gop_finish reports, (P - 1, P) -- RGB uint8 NCHW, RGB float16 NCHW -- against decode alone, alternating, two rounds
   --nt             (needs --prof) the RGB kernel's stores plain against nontemporal (MOBI_EXPORT_RGB_NT), each export followed at once by a
                    consumer on the same stream (a torch reduction over the tensor): export + consumer time, alternating
+  --scaled         the scaled export (mobi_batch_export_device_scaled): 512 clips x 6 frames of 640x480, centre crop 480x480 -> 224x224,
+                   uint8 and float16 NCHW, three legs alternating over two rounds (HIP events, best of 3): (a) the full-size export plus
+                   torch's crop and adaptive_avg_pool2d on the same stream, (b) the scaled export, (c) the full-size export alone.
+                   --clips N: another batch size (above 512 clips leg (a) hands torch more than 2^31 elements per call: not measured)
+  --scaled --kernels   legs (b) and (c) only, 10 each, nothing timed: for a `rocprofv3 --kernel-trace --stats` run of its own
+  --scaled --e2e   the --e2e run with the scaled export per part against decode alone and the full-size export
   --prof           the -DMOBI_PROFILING twin of the library
 """
 import json
@@ -128,12 +134,16 @@ def from_stats(path, n=4096):
     print(json.dumps(res), flush=True)
 
 
+CROP, SIZE = (80, 0, 480, 480), (224, 224)  # --scaled: the centre square of 640x480, the size a vision model takes
+
+
 def end_to_end(mode, n_clips=4096, G=32, n_groups=3, S=None):
     """decode (+ one device export per part) of groups 1 .. n_groups - 1; group 0 untimed.  -> Gpixels/s of decoded frames"""
     b = m.MobiclipBatch(n_clips, W, H, VER, device_parse=True)
     group = lambda g: [[S[c % len(S)][k] for c in range(n_clips)] for k in range(g * G, (g + 1) * G)]
-    dt = {"u8": torch.uint8, "f16": torch.float16}.get(mode)
-    out = torch.empty((6, n_clips, 3, H, W), dtype=dt, device="cuda") if dt is not None else None
+    dt = {"u8": torch.uint8, "f16": torch.float16}.get(mode.split("_")[0])
+    kw = dict(crop=CROP, size=SIZE) if mode.endswith("_scaled") else {}
+    out = torch.empty((6, n_clips, 3) + (SIZE if kw else (H, W)), dtype=dt, device="cuda") if dt is not None else None
     b.gop_begin(group(0))
     b.gop_begin(group(1))
     while True:
@@ -150,7 +160,7 @@ def end_to_end(mode, n_clips=4096, G=32, n_groups=3, S=None):
             rcs, _ = b.gop_finish()
             P = len(rcs)
             if out is not None:
-                b.export_tensor("rgb", P - 1, P, dtype=dt, out=out[:P])  # the whole part in one call, on the current stream
+                b.export_tensor("rgb", P - 1, P, dtype=dt, out=out[:P], **kw)  # the whole part in one call, on the current stream
             frames += P
             if b.gop_frames_pending() in (0, G):
                 break
@@ -169,6 +179,59 @@ def e2e():
             g = end_to_end(mode, S=S)
             print(json.dumps({"round": rnd, "mode": mode if mode == "decode" else f"decode + rgb nchw {mode} export per part",
                               "clips": 4096, "group": 32, "gpix_s": round(g, 2)}), flush=True)
+
+
+def scaled_legs(b, dt):
+    """the three legs of --scaled for one dtype: name -> a function that enqueues it on the current stream"""
+    x, y, w, h = CROP
+    full = b.export_tensor("rgb", 5, 6, dtype=dt)
+    small = b.export_tensor("rgb", 5, 6, dtype=dt, crop=CROP, size=SIZE)
+
+    def parent_route():  # what a caller did before: full size, then the framework's crop and area average (in float16 for uint8)
+        t = b.export_tensor("rgb", 5, 6, dtype=dt, out=full)[..., y:y + h, x:x + w].flatten(0, 1)
+        return torch.nn.functional.adaptive_avg_pool2d(t if dt != torch.uint8 else t.half(), SIZE)
+    return {"a_full_export_plus_torch_crop_pool": parent_route,
+            "b_scaled_export": lambda: b.export_tensor("rgb", 5, 6, dtype=dt, crop=CROP, size=SIZE, out=small),
+            "c_full_export_alone": lambda: b.export_tensor("rgb", 5, 6, dtype=dt, out=full)}
+
+
+def scaled(n):
+    b = resident(n)
+    s = torch.cuda.current_stream()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for dt in (torch.uint8, torch.float16):
+        legs = scaled_legs(b, dt)
+        if "--kernels" in sys.argv:
+            for k in ("b_scaled_export", "c_full_export_alone"):
+                for _ in range(10):
+                    legs[k]()
+            torch.cuda.synchronize()
+        else:
+            for f in legs.values():  # warm
+                f()
+            for rnd in range(2):
+                for k, f in legs.items():
+                    best = 1e30
+                    for _ in range(3):
+                        e0.record(s)
+                        r = f()
+                        e1.record(s)
+                        e1.synchronize()
+                        best = min(best, e0.elapsed_time(e1))
+                    del r
+                    print(json.dumps({"clips": n, "frames": 6, "crop": CROP, "size": SIZE, "dtype": str(dt).split(".")[-1], "round": rnd,
+                                      "leg": k, "ms": round(best, 4)}), flush=True)
+        del legs
+        torch.cuda.empty_cache()
+    b.close()
+
+
+def scaled_e2e():
+    S = streams(32 * 3, iframe_interval=32)
+    for rnd in range(2):
+        for mode in ("decode", "u8", "u8_scaled", "f16", "f16_scaled"):
+            g = end_to_end(mode, S=S)
+            print(json.dumps({"round": rnd, "mode": mode, "clips": 4096, "group": 32, "gpix_s": round(g, 2)}), flush=True)
 
 
 def nt_ab():
@@ -200,6 +263,11 @@ def nt_ab():
 def main():
     if "--from-stats" in sys.argv:
         from_stats(sys.argv[sys.argv.index("--from-stats") + 1])
+    elif "--scaled" in sys.argv:
+        if "--e2e" in sys.argv:
+            scaled_e2e()
+        else:
+            scaled(int(sys.argv[sys.argv.index("--clips") + 1]) if "--clips" in sys.argv else 512)
     elif "--kernels" in sys.argv:
         kernels()
     elif "--e2e" in sys.argv:
