@@ -334,6 +334,33 @@ int mobi_batch_export_device(mobi_batch *b, int format, int dtype, const float *
 int mobi_batch_export_device_scaled(mobi_batch *b, int format, int dtype, const float *scale_bias, int crop_x, int crop_y, int crop_w, int crop_h,
                                     int out_w, int out_h, int ring_idx, int n_frames, int clip0, int n_clips, void *dst, size_t dst_bytes,
                                     void *stream);
+/* The same export for consumers that want a different box of every clip at one fixed size, larger or smaller, mirrored or not (a training
+ * loader's RandomResizedCrop and horizontal flip): boxes = n_clips rows of {x, y, w, h, flags} in HOST memory; row c - clip0 applies to every
+ * frame of clip c in the call.  boxes is read and copied before the call returns: the caller may reuse it at once.  RGB tensors
+ * (MOBI_EXPORT_RGB_PLANAR / _PACKED only; dtype and scale_bias as above), one kernel.  Picture order, dst indexing, STREAM, SNAPSHOT and
+ * LIFETIME are mobi_batch_export_device_scaled's, with picture_bytes = 3 * out_w * out_h * element size.
+ *   VALUES:   exact, in integers.  v[t][s] is one byte (R, G, B = bytes 2, 1, 0) of the Bitmap's word at picture row y + t, column x + s; the
+ *             chroma neighbours and the last-row / last-column rule are the PICTURE's, not the box's.  Each axis (in_n source samples, out_n
+ *             outputs: w and out_w, h and out_h) has a weight matrix W[o][s] and a denominator d:
+ *               out_n <= in_n (area):   W[o][s] = max(0, min((s + 1) * out_n, (o + 1) * in_n) - max(s * out_n, o * in_n)),  d = in_n
+ *                                       (mobi_batch_export_device_scaled's weights);
+ *               out_n >  in_n (linear, sample centres aligned, clamped at the BOX's edge: crop, then resize):
+ *                                       n = (2 * o + 1) * in_n - out_n,  i0 = floor(n / (2 * out_n)),  f = n - i0 * 2 * out_n;
+ *                                       weight 2 * out_n - f goes to source clamp(i0, 0, in_n - 1), weight f to clamp(i0 + 1, 0, in_n - 1)
+ *                                       (they add when both are one source);  d = 2 * out_n.
+ *             Every row of W sums to d.  S = sum_t sum_s Wy[oy][t] * Wx[ox][s] * v[t][s];  D = dx * dy;  q = (S + D / 2) / D  (floor
+ *             division, D / 2 floored).  With MOBI_BOX_FLIP_X output column ox holds the q of column out_w - 1 - ox.  uint8 stores q;
+ *             float32 (float)q * scale[ch] + bias[ch], a product and a sum each rounded; float16 that value rounded to nearest-even.
+ *             A box at its own size is a pure crop (q = v); where both axes shrink the values are mobi_batch_export_device_scaled's;
+ *             where both grow, S / D is bilinear interpolation with half-pixel centres (align_corners = False) of the box.  The result
+ *             does not depend on the order of execution.
+ *   REFUSED:  every refusal of mobi_batch_export_device, and MOBI_E_ARG for a format other than the two RGB ones, boxes == NULL, a box that
+ *             is empty or not inside the picture, flag bits other than MOBI_BOX_FLIP_X, out_w or out_h below 1, out_w not a multiple of 4,
+ *             and a clip whose D > 2^23 (the sums are 32-bit).  One bad box refuses the whole call; a refused call enqueues nothing. */
+#define MOBI_BOX_FLIP_X 1 /* mirror the output left to right */
+int mobi_batch_export_device_boxes(mobi_batch *b, int format, int dtype, const float *scale_bias,
+                                   const int32_t *boxes /* host, n_clips x 5: x, y, w, h, flags */, int out_w, int out_h, int ring_idx,
+                                   int n_frames, int clip0, int n_clips, void *dst, size_t dst_bytes, void *stream);
 /* Encoder-side analysis: Analyzer.InterPredict2x2 (Analyzer.cs:608-681) for every 2x2 luma block of
  * every macroblock of every clip, as SolveInterPredictionPuzzle calls it (:683-693): three-step search (6, 3, 1 pels) in up
  * to five past frames = ring slots 0..4 of this batch (the encoder's PastFramesY, MobiEncoder.cs:138-144).

@@ -11,6 +11,10 @@
 // Export to device memory (mobi_batch_export_device) has no pipeline: the caller's stream waits for the batch's stream and the kernels
 // write straight into dst.  A batch that only does that creates no streams and allocates no staging (init_events, not init_staging).
 //
+// An export whose kernel needs per-call data in device memory (mobi_batch_export_device_boxes: a record per clip) hands it over as
+// MobiExportParams; it travels in a parameter block of a small pool: filled on the host, copied on the caller's stream in front of the
+// launch, free again when the event recorded behind the launch has completed.
+//
 // The ring-slot guard keeps, per ring slot, the events of the exports that read it and may still run: packs on the pack stream and
 // device exports on callers' streams, which sit behind whatever the caller has enqueued there.  A step that writes the slot waits for
 // all of them (mobi_exporter_guard); finished ones are dropped whenever the set is looked at.
@@ -68,6 +72,34 @@ struct MobiExporter {
   uint64_t next_ticket = 1, retired = 0;  // tickets 1 .. next_ticket - 1 issued; 1 .. retired known to be complete
   std::deque<std::pair<uint64_t, hipEvent_t>> pending;
   std::vector<hipEvent_t> ev_pool;
+  // parameter blocks: `bytes` of pinned host memory, as many of device memory, and the event behind the last launch that read the latter
+  struct ParamBlock { void *host = nullptr, *dev = nullptr; size_t bytes = 0; hipEvent_t ev = nullptr; };
+  std::vector<ParamBlock> params;
+
+  // a block of at least `bytes` that no launch still reads (its event has completed), or a new one.  *out points into `params`: it holds
+  // until the next take_params (a push_back moves the blocks), which is longer than mobi_exporter_run_device, its one caller, keeps it.
+  // The pool grows by a block for every export enqueued while all are still in flight and does not shrink before the exporter goes.
+  int take_params(size_t bytes, ParamBlock **out) {
+    for (auto &pb : params) {
+      if (pb.bytes < bytes) continue;
+      const hipError_t q = hipEventQuery(pb.ev);
+      if (q == hipSuccess) { *out = &pb; return MOBI_OK; }
+      (void)hipGetLastError(); // (hipErrorNotReady stays with the thread otherwise)
+      if (q != hipErrorNotReady) return MOBI_E_DEVICE;
+    }
+    ParamBlock pb;
+    pb.bytes = std::max<size_t>(4096, bytes + bytes / 2); // (a caller whose batches grow a little finds room in the blocks it has)
+    if (hipHostMalloc(&pb.host, pb.bytes, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return MOBI_E_DEVICE; }
+    if (hipMalloc(&pb.dev, pb.bytes) != hipSuccess || hipEventCreateWithFlags(&pb.ev, hipEventDisableTiming) != hipSuccess) {
+      (void)hipGetLastError();
+      if (pb.dev) (void)hipFree(pb.dev);
+      (void)hipHostFree(pb.host);
+      return MOBI_E_DEVICE;
+    }
+    params.push_back(pb);
+    *out = &params.back();
+    return MOBI_OK;
+  }
 
   int get_event(hipEvent_t *e) {
     if (!ev_pool.empty()) { *e = ev_pool.back(); ev_pool.pop_back(); return MOBI_OK; }
@@ -159,6 +191,12 @@ struct MobiExporter {
     drain(); // the copies of outstanding exports still read the staging chunks and write the callers' memory
     for (auto &v : readers) // ... and device exports still read the ring, on the callers' streams
       for (auto e : v) { (void)hipEventSynchronize(e); (void)hipEventDestroy(e); }
+    for (auto &pb : params) { // (behind the readers' events on their streams; a block whose launch failed to be enqueued may be behind none)
+      (void)hipEventSynchronize(pb.ev);
+      (void)hipEventDestroy(pb.ev);
+      (void)hipFree(pb.dev);
+      (void)hipHostFree(pb.host);
+    }
     for (auto &p : pending) (void)hipEventDestroy(p.second);
     for (auto e : ev_pool) (void)hipEventDestroy(e);
     for (auto e : ev_packed) if (e) (void)hipEventDestroy(e);
@@ -273,8 +311,15 @@ int mobi_exporter_run(MobiExporter *x, const MobiExportJob &job, uint64_t *ticke
   return MOBI_OK;
 }
 
-int mobi_exporter_run_device(MobiExporter *x, const MobiExportJob &job, hipStream_t stream, const std::function<int(hipStream_t)> &launch) {
+int mobi_exporter_run_device(MobiExporter *x, const MobiExportJob &job, hipStream_t stream, const std::function<int(hipStream_t)> &launch,
+                             MobiExportParams *params) {
   if (int e = x->init_events()) return e;
+  MobiExporter::ParamBlock *pb = nullptr;
+  if (params) { // (before anything is enqueued: a call that finds no block enqueues nothing)
+    if (int e = x->take_params(params->bytes, &pb)) return e;
+    memcpy(pb->host, params->host, params->bytes);
+    params->dev = pb->dev;
+  }
   // whatever fails once something is enqueued: the kernels of this export have finished when the caller gets the error
   struct Drain {
     hipStream_t s; bool armed = true;
@@ -282,7 +327,11 @@ int mobi_exporter_run_device(MobiExporter *x, const MobiExportJob &job, hipStrea
   } drain{stream};
   if (hipEventRecord(x->ev_src, job.src_stream) != hipSuccess) { drain.armed = false; (void)hipGetLastError(); return MOBI_E_DEVICE; }
   if (hipStreamWaitEvent(stream, x->ev_src, 0) != hipSuccess) return MOBI_E_DEVICE; // the reconstruction of every frame exported is in front
-  if (launch(stream) != 0) return MOBI_E_DEVICE;
+  if (pb && hipMemcpyAsync(pb->dev, pb->host, params->bytes, hipMemcpyHostToDevice, stream) != hipSuccess) return MOBI_E_DEVICE;
+  const int rc = launch(stream);
+  // the block is free once the copy and the kernels behind it have run (also after a launch that failed half way: the drain is behind it)
+  if (pb && hipEventRecord(pb->ev, stream) != hipSuccess) return MOBI_E_DEVICE;
+  if (rc != 0) return MOBI_E_DEVICE;
   for (int j = 0; j < job.n_frames && j < 6; j++) // the guard: a step that will write one of these slots waits for these kernels
     if (int e = x->arm((job.slot0 + j) % 6, stream)) return e;
   drain.armed = false;

@@ -9,6 +9,7 @@
 
 #include <functional>
 
+#include "mobi_export_resample.h"
 #include "mobi_export_scale.h"
 
 // the ring of one batch as the export reads it (MobiReconArgs' layout: [clip][slot 0..5][tiled Y | tiled UV])
@@ -36,6 +37,16 @@ extern "C" int mobi_launch_export_rgb(const MobiExportGeom *g, int version, int 
 extern "C" int mobi_launch_export_scale(const MobiExportGeom *g, int version, int planar, int esize, const MobiScalePlan *plan, int n_frames,
                                         int n_clips, int clip0, int slot0, const MobiRgbAffine *sb, uint8_t *out_dev, hipStream_t s);
 
+// mobi_export_resample.hip: the same pictures, a box per clip resized to ow x oh (mobi_export_resample.h).  clips_dev = n_clips records in
+// DEVICE memory (a parameter block of the exporter); blocks = the largest mobi_resample_blocks, lds_bytes the largest mobi_resample_lds_bytes
+// of them
+struct MobiResampleCall {
+  uint32_t ow, oh, blocks, lds_bytes;
+  const MobiResampleClip *clips_dev;
+};
+extern "C" int mobi_launch_export_resample(const MobiExportGeom *g, int version, int planar, int esize, const MobiResampleCall *call, int n_frames,
+                                           int n_clips, int clip0, int slot0, const MobiRgbAffine *sb, uint8_t *out_dev, hipStream_t s);
+
 #if !defined(__HIPCC__) || !defined(__HIP_DEVICE_COMPILE__)
 struct MobiExporter;
 // one export of a checked request (mobi_batch_export).  slot0 = the ring slot of the OLDEST frame (ring index ring_idx); frame j is slot
@@ -55,7 +66,17 @@ int mobi_exporter_run(MobiExporter *x, const MobiExportJob &job, uint64_t *ticke
 // one export into device memory on the caller's stream (mobi_batch_export_device): `stream` waits for job.src_stream through an event,
 // launch(stream) enqueues the kernels, and every ring slot read is armed in the guard with an event recorded on `stream` behind them.  No
 // staging, no ticket.  On an error after something was enqueued the call waits for `stream` before it returns.
-int mobi_exporter_run_device(MobiExporter *x, const MobiExportJob &job, hipStream_t stream, const std::function<int(hipStream_t)> &launch);
+// params (optional): per-call data the kernels read from device memory.  `bytes` bytes at `host` are copied, before the call returns, into
+// the pinned side of a PARAMETER BLOCK (a pinned host buffer, a device buffer and an event; a small pool, mobi_export.cpp) and from there
+// to the device on `stream`, in front of launch(), which finds the device address in `dev`; the block is taken again once the event
+// recorded behind the launch has completed.  No host wait, and no allocation once the pool has a free block of that size.
+struct MobiExportParams {
+  const void *host;
+  size_t bytes;
+  const void *dev; // set for launch()
+};
+int mobi_exporter_run_device(MobiExporter *x, const MobiExportJob &job, hipStream_t stream, const std::function<int(hipStream_t)> &launch,
+                             MobiExportParams *params = nullptr);
 int mobi_exporter_wait(MobiExporter *x, uint64_t ticket);
 int mobi_exporter_query(MobiExporter *x, uint64_t ticket);
 // the ring-slot guard: before a step that writes ring slot `slot` is enqueued on `stream`, it waits for every export that read that slot

@@ -105,7 +105,7 @@ int mobi_batch_export(mobi_batch *b, int format, int ring_idx, int n_frames, int
 }
 // ---- export into device memory, on the caller's stream (torch tensors, the caller's own HIP allocations) ----
 // The arguments are checked here; the stream order and the ring-slot guard are mobi_export.cpp's, the RGB kernels mobi_export_rgb.hip's and
-// mobi_export_scale.hip's.
+// mobi_export_scale.hip's and mobi_export_resample.hip's.
 namespace {
 // element size of an RGB export's dtype; 0: a combination the RGB formats do not have
 size_t rgb_esize(int dtype, const float *scale_bias) {
@@ -113,9 +113,10 @@ size_t rgb_esize(int dtype, const float *scale_bias) {
   return dtype == MOBI_DTYPE_F16 ? 2 : dtype == MOBI_DTYPE_F32 ? 4 : 0;
 }
 // What every device export checks once its format is known, and the hand-over: pictures of `pic` bytes each, n_frames x n_clips of them
-// into dst on `stream`; launch(job, need, stream) enqueues the kernels (need = the bytes the export writes).
+// into dst on `stream`; launch(job, need, stream) enqueues the kernels (need = the bytes the export writes).  params: what the kernels read
+// from device memory (mobi_exporter.h), or nothing.
 int export_device(mobi_batch *b, int format, size_t pic, int ring_idx, int n_frames, int clip0, int n_clips, void *dst, size_t dst_bytes, void *stream,
-                  const std::function<int(const MobiExportJob &, size_t, hipStream_t)> &launch) {
+                  const std::function<int(const MobiExportJob &, size_t, hipStream_t)> &launch, MobiExportParams *params = nullptr) {
   if (clip0 < 0 || n_clips < 1 || clip0 > b->n - n_clips) return MOBI_E_ARG;
   if (ring_idx < 0 || ring_idx > 5 || n_frames < 1 || ring_idx - n_frames + 1 < 0) return MOBI_E_ARG;
   const size_t need = pic * n_frames * n_clips;
@@ -147,7 +148,7 @@ int export_device(mobi_batch *b, int format, size_t pic, int ring_idx, int n_fra
   job.slot0 = (b->ring_base + 6 - ring_idx) % 6;
   job.dst = dst;
   job.src_stream = b->stream;
-  return mobi_exporter_run_device(b->exporter, job, s, [&](hipStream_t st) { return launch(job, need, st); });
+  return mobi_exporter_run_device(b->exporter, job, s, [&](hipStream_t st) { return launch(job, need, st); }, params);
 }
 } // namespace
 int mobi_batch_export_device(mobi_batch *b, int format, int dtype, const float *scale_bias, int ring_idx, int n_frames, int clip0, int n_clips,
@@ -211,6 +212,41 @@ int mobi_batch_export_device_scaled(mobi_batch *b, int format, int dtype, const 
   };
   return export_device(b, format, mobi_scale_picture_bytes((uint32_t)out_w, (uint32_t)out_h, (uint32_t)esize), ring_idx, n_frames, clip0, n_clips, dst,
                        dst_bytes, stream, launch);
+}
+// A box per clip, resized to out_w x out_h, mirrored or not (mobi_export_resample.h): RGB tensors only.  The boxes are checked and the
+// clips' records made here; they reach the kernel through a parameter block of the exporter.
+int mobi_batch_export_device_boxes(mobi_batch *b, int format, int dtype, const float *scale_bias, const int32_t *boxes, int out_w, int out_h, int ring_idx,
+                                   int n_frames, int clip0, int n_clips, void *dst, size_t dst_bytes, void *stream) {
+  if (!b || !dst || !boxes || (format != MOBI_EXPORT_RGB_PLANAR && format != MOBI_EXPORT_RGB_PACKED)) return MOBI_E_ARG;
+  const size_t esize = rgb_esize(dtype, scale_bias);
+  if (!esize) return MOBI_E_ARG;
+  if (out_w < 1 || out_h < 1 || (out_w & 3)) return MOBI_E_ARG;
+  // The boxes are the caller's memory and have to be copied before the call returns, so they are read here, in front of the shared
+  // checks of export_device: that is why the clip range, which says how many rows `boxes` has, is looked at here as well as there.
+  // Nothing is enqueued and nothing of the batch changes before export_device has accepted the rest.
+  if (n_clips < 1 || clip0 < 0 || clip0 > b->n - n_clips) return MOBI_E_ARG;
+  const int W = (int)b->g.width, H = (int)b->g.height;
+  std::vector<MobiResampleClip> recs((size_t)n_clips);
+  MobiResampleCall call{(uint32_t)out_w, (uint32_t)out_h, 0u, 0u, nullptr};
+  for (int c = 0; c < n_clips; c++) {
+    const int32_t *bx = boxes + 5 * (size_t)c;
+    const int x = bx[0], y = bx[1], w = bx[2], h = bx[3];
+    if (w < 1 || h < 1 || x < 0 || y < 0 || x > W - w || y > H - h || (bx[4] & ~MOBI_BOX_FLIP_X)) return MOBI_E_ARG;
+    if (mobi_resample_den((uint32_t)w, (uint32_t)h, (uint32_t)out_w, (uint32_t)out_h) > ((uint64_t)1 << 23)) return MOBI_E_ARG; // the sums stay below 2^31
+    recs[c] = mobi_resample_plan((uint32_t)x, (uint32_t)y, (uint32_t)w, (uint32_t)h, (uint32_t)bx[4], (uint32_t)out_w, (uint32_t)out_h);
+    call.blocks = std::max(call.blocks, mobi_resample_blocks(&recs[c]));
+    call.lds_bytes = std::max(call.lds_bytes, mobi_resample_lds_bytes(&recs[c]));
+  }
+  MobiRgbAffine sb{{1.f, 1.f, 1.f, 0.f, 0.f, 0.f}};
+  if (scale_bias) memcpy(sb.v, scale_bias, sizeof(sb.v));
+  MobiExportParams params{recs.data(), recs.size() * sizeof(MobiResampleClip), nullptr};
+  auto launch = [&](const MobiExportJob &job, size_t, hipStream_t st) -> int {
+    call.clips_dev = (const MobiResampleClip *)params.dev;
+    return mobi_launch_export_resample(&job.g, b->version, format == MOBI_EXPORT_RGB_PLANAR, (int)esize, &call, n_frames, n_clips, clip0, job.slot0, &sb,
+                                       (uint8_t *)dst, st);
+  };
+  return export_device(b, format, mobi_scale_picture_bytes((uint32_t)out_w, (uint32_t)out_h, (uint32_t)esize), ring_idx, n_frames, clip0, n_clips, dst,
+                       dst_bytes, stream, launch, &params);
 }
 int mobi_batch_export_wait(mobi_batch *b, uint64_t ticket) {
   if (!b || !b->exporter) return MOBI_E_ARG;

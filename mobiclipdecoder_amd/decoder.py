@@ -106,6 +106,8 @@ _SIGS = {
                                            C.c_size_t, C.c_void_p]),
     "mobi_batch_export_device_scaled": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)] + [C.c_int] * 10 + [C.c_void_p, C.c_size_t,
                                                                                                                        C.c_void_p]),
+    "mobi_batch_export_device_boxes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int32)] + [C.c_int] * 6
+                                       + [C.c_void_p, C.c_size_t, C.c_void_p]),
     "mobi_error_string": (C.c_char_p, [C.c_int]),
     "mobi_build_info": (C.c_char_p, []),
 }
@@ -562,7 +564,7 @@ class MobiclipBatch:
         return h.wait() if wait else h
 
     def export_tensor(self, fmt="rgb", ring_idx=0, n_frames=1, clips=None, layout="nchw", dtype=None, scale=None, bias=None, out=None,
-                      stream=None, crop=None, size=None):
+                      stream=None, crop=None, size=None, boxes=None, flip=None):
         """Pictures of many clips and frames into a torch tensor on the batch's GPU (mobi_batch_export_device), enqueued on `stream`
         (default: torch.cuda.current_stream of the batch's device) without a host wait: work enqueued on that stream afterwards sees them.
         Frame j = ring index ring_idx - j (oldest first), clips = a range / slice of step 1 (None: all), as in export().
@@ -577,6 +579,11 @@ class MobiclipBatch:
                     whole picture), area-averaged down to out_h x out_w (default: the crop's size, a pure crop) in one kernel, exactly (the
                     definition is include/mobiclip_hip.h's); H, W in the shapes above become out_h, out_w.  No upscaling, out_w a multiple
                     of 4, w * h <= 2**23.  With both None the call is the full-size export.
+        boxes=(len(clips), 4) ints, rows (x, y, w, h); flip=len(clips) bools or None; size=(out_h, out_w), required (fmt="rgb" only;
+                    mobi_batch_export_device_boxes): clip i's box of every frame, resized to out_h x out_w -- area-averaged where an axis
+                    shrinks, bilinear (half-pixel centres, clamped at the box's edge) where it grows -- and mirrored left to right where
+                    flip[i], in one kernel, exactly (include/mobiclip_hip.h).  out_w a multiple of 4; dx * dy <= 2**23 with d = the box's
+                    side where the axis shrinks, twice the output's where it grows.  Not together with crop.
         out: a contiguous, 16-byte aligned tensor of that shape and dtype on the batch's device to fill (default: a new one, allocated on
         `stream`).  Every argument is checked before the library is called (ValueError); a refused export enqueues nothing."""
         import torch
@@ -617,7 +624,50 @@ class MobiclipBatch:
         if not isinstance(clips, range) or clips.step != 1 or len(clips) < 1 or clips.start < 0 or clips.stop > self.n:
             raise ValueError(f"clips must be a non-empty range / slice of step 1 inside 0..{self.n}, not {clips!r}")
         F, N, W, H = int(n_frames), len(clips), self.Width, self.Height
-        scaled = crop is not None or size is not None
+        box_rows = None
+        if boxes is not None or flip is not None:
+            if boxes is None:
+                raise ValueError("flip applies to boxes only")
+            if crop is not None:
+                raise ValueError("boxes and crop exclude each other")
+            if fmt != "rgb":
+                raise ValueError(f"boxes apply to fmt='rgb' only, not {fmt!r}")
+            if size is None:
+                raise ValueError("boxes need a size (out_h, out_w)")
+            if not isinstance(size, (tuple, list)) or len(size) != 2 or any(isinstance(i, bool) or not isinstance(i, (int, np.integer)) for i in size):
+                raise ValueError(f"size must be 2 ints, not {size!r}")
+            oh, ow = int(size[0]), int(size[1])
+            if oh < 1 or ow < 1 or ow % 4:
+                raise ValueError(f"size (out_h, out_w) = {(oh, ow)!r} must be at least 1x1, out_w a multiple of 4")
+            try:
+                bx = np.asarray(boxes)
+            except (TypeError, ValueError):
+                raise ValueError(f"boxes must be an integer array of shape ({N}, 4)") from None
+            if bx.dtype == np.bool_ or not np.issubdtype(bx.dtype, np.integer) or bx.shape != (N, 4):
+                raise ValueError(f"boxes must be an integer array of shape ({N}, 4), not {bx.dtype} {bx.shape}")
+            bx = bx.astype(np.int64)
+            if flip is None:
+                fl = np.zeros(N, np.int64)
+            else:
+                try:
+                    fl = np.asarray(flip)
+                except (TypeError, ValueError):
+                    raise ValueError(f"flip must be {N} bools") from None
+                if fl.dtype != np.bool_ or fl.shape != (N,):
+                    raise ValueError(f"flip must be {N} bools, not {fl.dtype} {fl.shape}")
+                fl = fl.astype(np.int64)
+            x, y, w, h = bx.T
+            bad = (w < 1) | (h < 1) | (x < 0) | (y < 0) | (x + w > W) | (y + h > H)
+            if bad.any():
+                i = int(np.argmax(bad))
+                raise ValueError(f"boxes[{i}] (x, y, w, h) = {bx[i].tolist()} is empty or not inside the {W}x{H} picture")
+            D = np.where(ow > w, 2 * ow, w) * np.where(oh > h, 2 * oh, h)
+            if (D > 1 << 23).any():
+                i = int(np.argmax(D > 1 << 23))
+                raise ValueError(f"boxes[{i}] = {bx[i].tolist()} to {ow}x{oh}: dx * dy = {int(D[i])}, at most 2**23")
+            box_rows = np.ascontiguousarray(np.concatenate([bx, fl[:, None]], axis=1), dtype=np.int32)
+            W, H = ow, oh
+        scaled = box_rows is None and (crop is not None or size is not None)
         if scaled:
             if fmt != "rgb":
                 raise ValueError(f"crop and size apply to fmt='rgb' only, not {fmt!r}")
@@ -654,7 +704,11 @@ class MobiclipBatch:
             with torch.cuda.stream(stream):
                 out = torch.empty(shape, dtype=tdtype, device=dev)
         code = DEVICE_EXPORT_FORMATS[(fmt, layout if fmt == "rgb" else None)]
-        if scaled:
+        if box_rows is not None:
+            rc = self._lib.mobi_batch_export_device_boxes(self._h, code, DEVICE_EXPORT_DTYPES[dname], sb, box_rows.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                          ow, oh, int(ring_idx), F, clips.start, N, out.data_ptr(),
+                                                          out.numel() * out.element_size(), stream.cuda_stream)
+        elif scaled:
             rc = self._lib.mobi_batch_export_device_scaled(self._h, code, DEVICE_EXPORT_DTYPES[dname], sb, cx, cy, cw, ch, ow, oh, int(ring_idx), F,
                                                            clips.start, N, out.data_ptr(), out.numel() * out.element_size(), stream.cuda_stream)
         else:

@@ -18,6 +18,12 @@ lines.
                    --clips N: another batch size (above 512 clips leg (a) hands torch more than 2^31 elements per call: not measured)
   --scaled --kernels   legs (b) and (c) only, 10 each, nothing timed: for a `rocprofv3 --kernel-trace --stats` run of its own
   --scaled --e2e   the --e2e run with the scaled export per part against decode alone and the full-size export
+  --boxes          the resampled export (mobi_batch_export_device_boxes) at the 512 clips x 6 frames of 640x480 of --scaled (no --clips: the
+                   batch is not made larger), -> 224x224, uint8 and float16 NCHW, legs alternating over two rounds (HIP events, best of 3):
+                   (a) the full-size export plus a per-clip loop of torch's crop, interpolate (area / bilinear, antialias off) and flip on the
+                   same stream, (b) the resampled export with a random box (8 - 100 % of the area, 3:4 .. 4:3) and a random flip per clip,
+                   (c) the resampled export with the centre 480x480 box for every clip, (d) the scaled export at that crop
+  --boxes --kernels    legs (b), (c), (d) only, 10 each, nothing timed: for a `rocprofv3 --kernel-trace --stats` run of its own
   --prof           the -DMOBI_PROFILING twin of the library
 """
 import json
@@ -226,6 +232,72 @@ def scaled(n):
     b.close()
 
 
+def random_boxes(n, seed=7):
+    """n boxes of 8 - 100 % of the picture's area at aspect ratios 3:4 .. 4:3 (log-uniform), cut to the picture, and flips"""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    boxes = []
+    for _ in range(n):
+        a, ar = rng.uniform(0.08, 1.0) * PX, np.exp(rng.uniform(np.log(3 / 4), np.log(4 / 3)))
+        w, h = min(W, int(round((a * ar) ** 0.5))), min(H, int(round((a / ar) ** 0.5)))
+        boxes.append((int(rng.integers(0, W - w + 1)), int(rng.integers(0, H - h + 1)), w, h))
+    return boxes, [bool(v) for v in rng.integers(0, 2, n)]
+
+
+def boxes_legs(b, n, dt):
+    boxes, flips = random_boxes(n)
+    full = b.export_tensor("rgb", 5, 6, dtype=dt)
+    small = b.export_tensor("rgb", 5, 6, dtype=dt, crop=CROP, size=SIZE)
+
+    def torch_route():  # what a caller does without the entry point: full size, then per clip crop, resize, flip
+        t = b.export_tensor("rgb", 5, 6, dtype=dt, out=full)
+        res = torch.empty((6, n, 3) + SIZE, dtype=torch.float16 if dt == torch.uint8 else dt, device=t.device)
+        for c, ((x, y, w, h), fl) in enumerate(zip(boxes, flips)):
+            v = t[:, c, :, y:y + h, x:x + w]
+            v = v.half() if dt == torch.uint8 else v
+            # (one mode per clip, as a loader's resize has: area where the box is no smaller than the output, bilinear otherwise)
+            r = (torch.nn.functional.interpolate(v, size=SIZE, mode="area") if w >= SIZE[1] and h >= SIZE[0]
+                 else torch.nn.functional.interpolate(v, size=SIZE, mode="bilinear", align_corners=False))
+            res[:, c] = torch.flip(r, (3,)) if fl else r
+        return res
+    return {"a_full_export_plus_torch_per_clip_loop": torch_route,
+            "b_boxes_export_random": lambda: b.export_tensor("rgb", 5, 6, dtype=dt, boxes=boxes, flip=flips, size=SIZE, out=small),
+            "c_boxes_export_centre": lambda: b.export_tensor("rgb", 5, 6, dtype=dt, boxes=[CROP] * n, size=SIZE, out=small),
+            "d_scaled_export_centre": lambda: b.export_tensor("rgb", 5, 6, dtype=dt, crop=CROP, size=SIZE, out=small)}
+
+
+def boxes_run():
+    n = 512  # (not larger: DESIGN.md, "Scaled export", records an unexplained memory fault of the 4096-clip run)
+    b = resident(n)
+    s = torch.cuda.current_stream()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for dt in (torch.uint8, torch.float16):
+        legs = boxes_legs(b, n, dt)
+        if "--kernels" in sys.argv:
+            for k in ("b_boxes_export_random", "c_boxes_export_centre", "d_scaled_export_centre"):
+                for _ in range(10):
+                    legs[k]()
+            torch.cuda.synchronize()
+        else:
+            for f in legs.values():  # warm
+                f()
+            for rnd in range(2):
+                for k, f in legs.items():
+                    best = 1e30
+                    for _ in range(3):
+                        e0.record(s)
+                        r = f()
+                        e1.record(s)
+                        e1.synchronize()
+                        best = min(best, e0.elapsed_time(e1))
+                    del r
+                    print(json.dumps({"clips": n, "frames": 6, "size": SIZE, "dtype": str(dt).split(".")[-1], "round": rnd, "leg": k,
+                                      "ms": round(best, 4)}), flush=True)
+        del legs
+        torch.cuda.empty_cache()
+    b.close()
+
+
 def scaled_e2e():
     S = streams(32 * 3, iframe_interval=32)
     for rnd in range(2):
@@ -263,6 +335,8 @@ def nt_ab():
 def main():
     if "--from-stats" in sys.argv:
         from_stats(sys.argv[sys.argv.index("--from-stats") + 1])
+    elif "--boxes" in sys.argv:
+        boxes_run()
     elif "--scaled" in sys.argv:
         if "--e2e" in sys.argv:
             scaled_e2e()
