@@ -1,4 +1,4 @@
-// mobi_export.cpp -- decoded pictures out to host memory (include/mobiclip_hip.h, mobi_batch_export): the pinned-block registry of
+// mobi_export.cpp -- decoded pictures out to host and device memory (include/mobiclip_hip.h, mobi_batch_export*): the pinned-block registry of
 // mobi_host_alloc, the staging pipeline, the tickets and the ring-slot guard.  The C entry points are in mobi_pictures.cpp; what they hand
 // over is mobi_exporter.h's.
 //
@@ -47,6 +47,15 @@ constexpr size_t kChunkBytes = (size_t)64 << 20;
 std::mutex g_reg_mutex;
 std::map<uintptr_t, size_t> g_reg; // mobi_host_alloc blocks: start -> bytes
 
+// has everything in front of event e completed?  1: yes, 0: still running, MOBI_E_DEVICE: the query failed.  No error stays with the
+// thread (hipErrorNotReady would otherwise).
+int event_done(hipEvent_t e) {
+  const hipError_t q = hipEventQuery(e);
+  if (q == hipSuccess) return 1;
+  (void)hipGetLastError();
+  return q == hipErrorNotReady ? 0 : MOBI_E_DEVICE;
+}
+
 } // namespace
 
 bool mobi_host_registered(const void *p, size_t bytes) {
@@ -82,10 +91,9 @@ struct MobiExporter {
   int take_params(size_t bytes, ParamBlock **out) {
     for (auto &pb : params) {
       if (pb.bytes < bytes) continue;
-      const hipError_t q = hipEventQuery(pb.ev);
-      if (q == hipSuccess) { *out = &pb; return MOBI_OK; }
-      (void)hipGetLastError(); // (hipErrorNotReady stays with the thread otherwise)
-      if (q != hipErrorNotReady) return MOBI_E_DEVICE;
+      const int done = event_done(pb.ev);
+      if (done == 1) { *out = &pb; return MOBI_OK; }
+      if (done != 0) return done;
     }
     ParamBlock pb;
     pb.bytes = std::max<size_t>(4096, bytes + bytes / 2); // (a caller whose batches grow a little finds room in the blocks it has)
@@ -109,10 +117,9 @@ struct MobiExporter {
   int prune(int s) {
     auto &v = readers[s];
     for (size_t i = 0; i < v.size();) {
-      const hipError_t q = hipEventQuery(v[i]);
-      if (q == hipSuccess) { ev_pool.push_back(v[i]); v[i] = v.back(); v.pop_back(); continue; }
-      if (q != hipErrorNotReady) { (void)hipGetLastError(); return MOBI_E_DEVICE; }
-      (void)hipGetLastError(); // (hipErrorNotReady stays with the thread otherwise)
+      const int done = event_done(v[i]);
+      if (done == 1) { ev_pool.push_back(v[i]); v[i] = v.back(); v.pop_back(); continue; }
+      if (done != 0) return done;
       i++;
     }
     return MOBI_OK;
@@ -209,6 +216,22 @@ struct MobiExporter {
   }
 };
 
+namespace {
+// Whatever fails once something of an export is enqueued: nothing of it may still run when the caller gets the error.  Unless disarmed,
+// waits for the exporter's streams (x: a host export, which then issues no ticket) or for the caller's stream s (x == nullptr: a device export).
+struct Drain {
+  MobiExporter *x;
+  hipStream_t s;
+  bool armed = true;
+  ~Drain() {
+    if (!armed) return;
+    if (x) x->drain();
+    else (void)hipStreamSynchronize(s);
+    (void)hipGetLastError();
+  }
+};
+} // namespace
+
 MobiExporter *mobi_exporter_new(int device) {
   auto *x = new MobiExporter();
   x->device = device;
@@ -228,8 +251,7 @@ int mobi_exporter_run(MobiExporter *x, const MobiExportJob &job, uint64_t *ticke
   if (int e = x->init_staging()) return e;
   // tickets nobody waits for or asks about: the ones already done give their events back (a caller that never waits holds at most the
   // exports still in flight)
-  while (!x->pending.empty() && hipEventQuery(x->pending.front().second) == hipSuccess) x->retire_upto(x->pending.front().first);
-  (void)hipGetLastError(); // (hipErrorNotReady stays with the thread otherwise)
+  while (!x->pending.empty() && event_done(x->pending.front().second) == 1) x->retire_upto(x->pending.front().first);
   const MobiExportGeom &g = job.g;
   const size_t pic = job.format == MOBI_EXPORT_I420 ? (size_t)mobi_export_i420_bytes((uint32_t)g.width, (uint32_t)g.height)
                                                     : (size_t)g.width * g.height * 4;
@@ -241,11 +263,7 @@ int mobi_exporter_run(MobiExporter *x, const MobiExportJob &job, uint64_t *ticke
   if (!pinned)
     if (int e = x->init_bounce()) return e;
   uint8_t *dst = (uint8_t *)job.dst;
-  // whatever fails once something is enqueued: nothing of this export may still run when the caller gets the error (it issues no ticket)
-  struct Drain {
-    MobiExporter *x; bool armed = true;
-    ~Drain() { if (armed) { x->drain(); (void)hipGetLastError(); } }
-  } drain{x};
+  Drain drain{x, nullptr};
   auto hip = [](hipError_t e) { return e == hipSuccess ? MOBI_OK : MOBI_E_DEVICE; };
   if (int e = hip(hipEventRecord(x->ev_src, job.src_stream))) return e; // the reconstruction of every frame exported is in front of this
   if (int e = hip(hipStreamWaitEvent(x->pack_s, x->ev_src, 0))) return e;
@@ -320,11 +338,7 @@ int mobi_exporter_run_device(MobiExporter *x, const MobiExportJob &job, hipStrea
     memcpy(pb->host, params->host, params->bytes);
     params->dev = pb->dev;
   }
-  // whatever fails once something is enqueued: the kernels of this export have finished when the caller gets the error
-  struct Drain {
-    hipStream_t s; bool armed = true;
-    ~Drain() { if (armed) { (void)hipStreamSynchronize(s); (void)hipGetLastError(); } }
-  } drain{stream};
+  Drain drain{nullptr, stream};
   if (hipEventRecord(x->ev_src, job.src_stream) != hipSuccess) { drain.armed = false; (void)hipGetLastError(); return MOBI_E_DEVICE; }
   if (hipStreamWaitEvent(stream, x->ev_src, 0) != hipSuccess) return MOBI_E_DEVICE; // the reconstruction of every frame exported is in front
   if (pb && hipMemcpyAsync(pb->dev, pb->host, params->bytes, hipMemcpyHostToDevice, stream) != hipSuccess) return MOBI_E_DEVICE;
@@ -355,11 +369,9 @@ int mobi_exporter_query(MobiExporter *x, uint64_t ticket) {
   if (ticket <= x->retired) return 1;
   for (auto &p : x->pending)
     if (p.first >= ticket) {
-      const hipError_t q = hipEventQuery(p.second);
-      if (q == hipSuccess) { x->retire_upto(p.first); return 1; }
-      if (q == hipErrorNotReady) return 0;
-      (void)hipGetLastError();
-      return MOBI_E_DEVICE;
+      const int done = event_done(p.second);
+      if (done == 1) x->retire_upto(p.first);
+      return done;
     }
   return MOBI_E_DEVICE;
 }

@@ -7,7 +7,7 @@
 // A workgroup (4 waves) takes one picture, one band of output rows and one strip of output columns of ITS CLIP's tiling: the record is read
 // once, from device memory, and everything derived from it -- weights, spans, loop counts -- is uniform over the workgroup.  It gathers:
 //   1. a chunk of the source rows and columns that have weight in the tile is converted in the Bitmap kernel's lane shape -- 4 pixels of two
-//      rows per lane, chroma_numerators and convert2 on them -- into RGB words in LDS;
+//      rows per lane, fetch_quad (mobi_export_tensor.h) -- into RGB words in LDS;
 //   2. a lane per (source row, output column) sums its column run of those words, weighted, into sums along x in LDS (a lane owns its sums:
 //      no atomics);
 //   3. a lane per 4 consecutive outputs of a row adds its row run of the sums along x, weighted, to 12 sums in registers.
@@ -18,22 +18,13 @@
 #include <stdint.h>
 
 #include "mobi_export_resample.h"
+#include "mobi_export_tensor.h"
 #include "mobi_exporter.h"
-#include "mobi_rgb.h"
 
 namespace {
-using namespace mobi_rgb;
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+using namespace mobi_export_tensor;
 constexpr uint32_t kLanes = kMobiResampleLanes;
 
-// W words (4 * W bytes, aligned to that) in one store
-template <int W>
-__device__ __forceinline__ void store_words(uint8_t *d, const uint32_t *w) {
-  if (W == 1) *(uint32_t *)d = w[0];
-  else if (W == 2) *(u32x2 *)d = u32x2{w[0], w[1]};
-  else *(u32x4 *)d = u32x4{w[0], w[1], w[2], w[3]};
-}
 // task tid, tid + 256, ... of a list of rows x n tasks as (row, column): the first one, and the step without a division per task
 struct Walk {
   uint32_t row, col, drow, dcol, n;
@@ -58,12 +49,10 @@ __global__ __launch_bounds__(kMobiResampleLanes) void mobi_export_resample(const
                                                                            MobiRgbAffine sb, uint8_t *out) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   const uint32_t p = p0 + blockIdx.y, tid = threadIdx.x;
-  const uint32_t j = p / (uint32_t)n_clips, c = p - j * (uint32_t)n_clips;
-  const MobiResampleClip k = clips[c];
+  const Picture src = picture(planes, clip_bytes, slot_bytes, height, lgS, n_clips, clip0, slot0, p);
+  const MobiResampleClip k = clips[src.c];
   uint32_t r0, r1, c0, c1;
   if (!mobi_resample_tile(&k, ow, oh, blockIdx.x, &r0, &r1, &c0, &c1)) return; // (a smaller clip's tiling: the whole workgroup leaves)
-  const uint8_t *Y = planes + (size_t)(clip0 + c) * clip_bytes + (size_t)((slot0 + j) % 6u) * slot_bytes;
-  const uint8_t *UV = Y + ((size_t)height << lgS);
   uint8_t *pic = out + (size_t)p * mobi_scale_picture_bytes(ow, oh, ESIZE);
   const uint32_t rows = r1 - r0, sw = c1 - c0, nq = sw >> 2;
   u32x4 *coltap = (u32x4 *)lds;                       // [strip_w] first, count, wf, wl of the strip's outputs
@@ -96,26 +85,8 @@ __global__ __launch_bounds__(kMobiResampleLanes) void mobi_export_resample(const
       Walk w1(tid, groups);
       for (uint32_t i = tid; i < (nrows >> 1) * groups; i += kLanes, w1.next()) {
         const uint32_t x0 = ca + 4u * w1.col, y0 = ra + 2u * w1.row; // x0 + 3 < width, y0 + 1 < height: both are multiples of 16
-        const bool lastcol = x0 + 4u >= (uint32_t)width, lastrow = y0 + 2u >= (uint32_t)height;
-        // luma column; chroma: samples a, b under the pixels (two bytes of one tile row) and e right of them (the next tile's for a = 6)
-        const uint32_t ycol = mobi_ty_col(x0), ccol = mobi_tc_x(x0 >> 1), ecol = lastcol ? ccol : mobi_tc_x((x0 >> 1) + 2u);
-        const uint8_t *yp = Y + mobi_ty_row(y0, lgS) + ycol; // rows y0, y0 + 1 are the two rows of one chunk
-        const uint32_t yw0 = *(const uint32_t *)yp, yw1 = *(const uint32_t *)(yp + 8);
-        const uint8_t *c0p = UV + mobi_tc_row(y0 >> 1, lgS), *c1p = lastrow ? c0p : UV + mobi_tc_row((y0 >> 1) + 1u, lgS);
-        const uint32_t u0w = *(const uint16_t *)(c0p + ccol), v0w = *(const uint16_t *)(c0p + ccol + 8);
-        const uint32_t u1w = *(const uint16_t *)(c1p + ccol), v1w = *(const uint16_t *)(c1p + ccol + 8);
-        const uint32_t ue0 = c0p[ecol], ve0 = c0p[ecol + 8], ue1 = c1p[ecol], ve1 = c1p[ecol + 8]; // (not looked at in the last column)
-        int ue[4], uo[4], ve[4], vo[4];
-        chroma_numerators(u0w, ue0, u1w, ue1, lastrow, lastcol, ue, uo);
-        chroma_numerators(v0w, ve0, v1w, ve1, lastrow, lastcol, ve, vo);
         uint32_t pe[4], po[4];
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-          const f32x2 ye = {(float)((yw0 >> (16 * h)) & 0xFF), (float)((yw0 >> (16 * h + 8)) & 0xFF)};
-          const f32x2 yo = {(float)((yw1 >> (16 * h)) & 0xFF), (float)((yw1 >> (16 * h + 8)) & 0xFF)};
-          convert2(version, ye, ue[2 * h], ue[2 * h + 1], ve[2 * h], ve[2 * h + 1], pe[2 * h], pe[2 * h + 1]);
-          convert2(version, yo, uo[2 * h], uo[2 * h + 1], vo[2 * h], vo[2 * h + 1], po[2 * h], po[2 * h + 1]);
-        }
+        fetch_quad(src.Y, src.UV, x0, y0, width, height, lgS, version, pe, po);
         uint32_t *d = rgb + 2u * w1.row * k.chunk_cols + 4u * w1.col;
         *(u32x4 *)d = u32x4{pe[0], pe[1], pe[2], pe[3]};
         *(u32x4 *)(d + k.chunk_cols) = u32x4{po[0], po[1], po[2], po[3]};
@@ -201,32 +172,11 @@ __global__ __launch_bounds__(kMobiResampleLanes) void mobi_export_resample(const
   }
 }
 
-namespace {
-template <int PLANAR, int ESIZE>
-void launch_resample(const MobiExportGeom *g, int version, const MobiResampleCall &k, uint32_t p0, uint32_t n_pics, int n_clips, int clip0, int slot0,
-                     const MobiRgbAffine &sb, uint8_t *out, hipStream_t s) {
-  hipLaunchKernelGGL((mobi_export_resample<PLANAR, ESIZE>), dim3(k.blocks, n_pics), dim3(kLanes), k.lds_bytes, s, g->planes, g->clip_bytes, g->slot_bytes,
-                     g->width, g->height, g->lg, version, n_clips, clip0, slot0, p0, k.ow, k.oh, k.clips_dev, sb, out);
-}
-} // namespace
-
 extern "C" int mobi_launch_export_resample(const MobiExportGeom *g, int version, int planar, int esize, const MobiResampleCall *call, int n_frames,
                                            int n_clips, int clip0, int slot0, const MobiRgbAffine *sb, uint8_t *out_dev, hipStream_t s) {
-  if (esize != 1 && esize != 2 && esize != 4) return (int)hipErrorInvalidValue;
-  const uint32_t n_pics = (uint32_t)n_frames * (uint32_t)n_clips;
-  // pictures go in blockIdx.y: one launch up to 65535 of them (more are several launches of that many)
-  for (uint32_t p0 = 0; p0 < n_pics; p0 += 65535u) {
-    const uint32_t n = n_pics - p0 < 65535u ? n_pics - p0 : 65535u;
-    if (planar) {
-      if (esize == 1) launch_resample<1, 1>(g, version, *call, p0, n, n_clips, clip0, slot0, *sb, out_dev, s);
-      else if (esize == 2) launch_resample<1, 2>(g, version, *call, p0, n, n_clips, clip0, slot0, *sb, out_dev, s);
-      else launch_resample<1, 4>(g, version, *call, p0, n, n_clips, clip0, slot0, *sb, out_dev, s);
-    } else {
-      if (esize == 1) launch_resample<0, 1>(g, version, *call, p0, n, n_clips, clip0, slot0, *sb, out_dev, s);
-      else if (esize == 2) launch_resample<0, 2>(g, version, *call, p0, n, n_clips, clip0, slot0, *sb, out_dev, s);
-      else launch_resample<0, 4>(g, version, *call, p0, n, n_clips, clip0, slot0, *sb, out_dev, s);
-    }
-    if (hipError_t e = hipGetLastError()) return (int)e;
-  }
-  return 0;
+  return launch_pictures(planar, esize, n_frames, n_clips, [&](auto pl, auto es, uint32_t p0, uint32_t n) {
+    hipLaunchKernelGGL((mobi_export_resample<decltype(pl)::value, decltype(es)::value>), dim3(call->blocks, n), dim3(kLanes), call->lds_bytes, s, g->planes,
+                       g->clip_bytes, g->slot_bytes, g->width, g->height, g->lg, version, n_clips, clip0, slot0, p0, call->ow, call->oh, call->clips_dev, *sb,
+                       out_dev);
+  });
 }

@@ -12,12 +12,11 @@
 #include <stdint.h>
 
 #include "mobi_export_rgb.h"
+#include "mobi_export_tensor.h"
 #include "mobi_exporter.h"
-#include "mobi_rgb.h"
 
 namespace {
-using namespace mobi_rgb;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+using namespace mobi_export_tensor;
 
 // Element k (0 .. 11) of the lane's four pixels in output order -- planar: channel ch's pixels t = 0 .. 3 (k = t, per plane); packed:
 // pixel k / 3, channel k % 3 -- as the bits of one element of ESIZE bytes (mobi_rgb.h, tensor_element).
@@ -37,9 +36,8 @@ __global__ __launch_bounds__(64) void mobi_export_rgb(const uint8_t *planes, uin
                                                      uint8_t *out) {
   __shared__ u32x4 stage[48 * ESIZE]; // the unit's output bytes, in output order
   const uint32_t p = p0 + blockIdx.y, lane = threadIdx.x;
-  const uint32_t j = p / (uint32_t)n_clips, c = p - j * (uint32_t)n_clips;
-  const uint8_t *Y = planes + (size_t)(clip0 + c) * clip_bytes + (size_t)((slot0 + j) % 6u) * slot_bytes;
-  const uint8_t *UV = Y + ((size_t)height << lgS);
+  const Picture src = picture(planes, clip_bytes, slot_bytes, height, lgS, n_clips, clip0, slot0, p);
+  const uint8_t *Y = src.Y, *UV = src.UV;
   uint8_t *pic = out + (size_t)p * mobi_rgb_picture_bytes((uint32_t)width, (uint32_t)height, ESIZE);
   const uint32_t u0 = blockIdx.x * kUnitsPerWave, units = mobi_rgb_units((uint32_t)width, (uint32_t)height);
   const uint32_t u1 = u0 + kUnitsPerWave < units ? u0 + kUnitsPerWave : units;
@@ -108,39 +106,13 @@ __global__ __launch_bounds__(64) void mobi_export_rgb(const uint8_t *planes, uin
   }
 }
 
-namespace {
-template <int PLANAR, int ESIZE, bool NT>
-void launch_rgb(const MobiExportGeom *g, int version, uint32_t p0, uint32_t n_pics, int n_clips, int clip0, int slot0,
-                const MobiRgbAffine &sb, uint8_t *out, hipStream_t s) {
-  const uint32_t waves = (mobi_rgb_units((uint32_t)g->width, (uint32_t)g->height) + kUnitsPerWave - 1) / kUnitsPerWave;
-  hipLaunchKernelGGL((mobi_export_rgb<PLANAR, ESIZE, NT>), dim3(waves, n_pics), dim3(64), 0, s, g->planes, g->clip_bytes, g->slot_bytes, g->width, g->height, g->lg, version, n_clips, clip0,
-                     slot0, p0, sb, out);
-}
-template <bool NT>
-void launch_rgb(const MobiExportGeom *g, int version, int planar, int esize, uint32_t p0, uint32_t n_pics, int n_clips, int clip0, int slot0,
-                const MobiRgbAffine &sb, uint8_t *out, hipStream_t s) {
-  if (planar) {
-    if (esize == 1) launch_rgb<1, 1, NT>(g, version, p0, n_pics, n_clips, clip0, slot0, sb, out, s);
-    else if (esize == 2) launch_rgb<1, 2, NT>(g, version, p0, n_pics, n_clips, clip0, slot0, sb, out, s);
-    else launch_rgb<1, 4, NT>(g, version, p0, n_pics, n_clips, clip0, slot0, sb, out, s);
-  } else {
-    if (esize == 1) launch_rgb<0, 1, NT>(g, version, p0, n_pics, n_clips, clip0, slot0, sb, out, s);
-    else if (esize == 2) launch_rgb<0, 2, NT>(g, version, p0, n_pics, n_clips, clip0, slot0, sb, out, s);
-    else launch_rgb<0, 4, NT>(g, version, p0, n_pics, n_clips, clip0, slot0, sb, out, s);
-  }
-}
-} // namespace
-
 extern "C" int mobi_launch_export_rgb(const MobiExportGeom *g, int version, int planar, int esize, int nontemporal, int n_frames, int n_clips,
                                       int clip0, int slot0, const MobiRgbAffine *sb, uint8_t *out_dev, hipStream_t s) {
-  if (esize != 1 && esize != 2 && esize != 4) return (int)hipErrorInvalidValue;
-  const uint32_t n_pics = (uint32_t)n_frames * (uint32_t)n_clips;
-  // pictures go in blockIdx.y: one launch up to 65535 of them (more are several launches of that many)
-  for (uint32_t p0 = 0; p0 < n_pics; p0 += 65535u) {
-    const uint32_t n = n_pics - p0 < 65535u ? n_pics - p0 : 65535u;
-    if (nontemporal) launch_rgb<true>(g, version, planar, esize, p0, n, n_clips, clip0, slot0, *sb, out_dev, s);
-    else launch_rgb<false>(g, version, planar, esize, p0, n, n_clips, clip0, slot0, *sb, out_dev, s);
-    if (hipError_t e = hipGetLastError()) return (int)e;
-  }
-  return 0;
+  const uint32_t waves = (mobi_rgb_units((uint32_t)g->width, (uint32_t)g->height) + kUnitsPerWave - 1) / kUnitsPerWave;
+  return launch_pictures(planar, esize, n_frames, n_clips, [&](auto pl, auto es, uint32_t p0, uint32_t n) {
+    constexpr int PLANAR = decltype(pl)::value, ESIZE = decltype(es)::value;
+    const auto kernel = nontemporal ? mobi_export_rgb<PLANAR, ESIZE, true> : mobi_export_rgb<PLANAR, ESIZE, false>;
+    hipLaunchKernelGGL(kernel, dim3(waves, n), dim3(64), 0, s, g->planes, g->clip_bytes, g->slot_bytes, g->width, g->height, g->lg, version, n_clips, clip0,
+                       slot0, p0, *sb, out_dev);
+  });
 }

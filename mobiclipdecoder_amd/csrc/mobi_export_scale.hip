@@ -4,7 +4,7 @@
 // element (uint8 / float16 / float32), as mobi_export_rgb is.
 //
 // A workgroup (4 waves) takes one picture, one band of output rows and one strip of output columns.  It converts the source pixels that
-// have weight in them in the Bitmap kernel's lane shape -- 4 pixels of two rows per lane, chroma_numerators and convert2 on them -- and adds
+// have weight in them in the Bitmap kernel's lane shape -- 4 pixels of two rows per lane, fetch_quad (mobi_export_tensor.h) -- and adds
 // weight * byte into 32-bit sums [row][channel][column] in LDS.  Integer sums commute: the result does not depend on the order of the adds.
 // A lane is a group of 4 source columns (its column weights are computed once) and a wave walks the row pairs (the row weights are
 // wave-uniform); the two rows of a pair are combined per output row before the column weights are applied.  After a barrier the lanes
@@ -14,24 +14,15 @@
 #include <stdint.h>
 
 #include "mobi_export_scale.h"
+#include "mobi_export_tensor.h"
 #include "mobi_exporter.h"
-#include "mobi_rgb.h"
 
 namespace {
-using namespace mobi_rgb;
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+using namespace mobi_export_tensor;
 constexpr uint32_t kWaves = 4;
 
 __device__ __forceinline__ void lds_add(uint32_t *p, uint32_t v) {
   (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); // ds_add_u32, no return value
-}
-// W words (4 * W bytes, aligned to that) in one store
-template <int W>
-__device__ __forceinline__ void store_words(uint8_t *d, const uint32_t *w) {
-  if (W == 1) *(uint32_t *)d = w[0];
-  else if (W == 2) *(u32x2 *)d = u32x2{w[0], w[1]};
-  else *(u32x4 *)d = u32x4{w[0], w[1], w[2], w[3]};
 }
 } // namespace
 
@@ -44,9 +35,7 @@ __global__ __launch_bounds__(64 * kWaves) void mobi_export_scale(const uint8_t *
   extern __shared__ __attribute__((aligned(16))) uint32_t acc[]; // sums [rows][3][sw]
   const uint32_t p = p0 + blockIdx.y, tid = threadIdx.x, lane = tid & 63u;
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
-  const uint32_t j = p / (uint32_t)n_clips, c = p - j * (uint32_t)n_clips;
-  const uint8_t *Y = planes + (size_t)(clip0 + c) * clip_bytes + (size_t)((slot0 + j) % 6u) * slot_bytes;
-  const uint8_t *UV = Y + ((size_t)height << lgS);
+  const Picture src = picture(planes, clip_bytes, slot_bytes, height, lgS, n_clips, clip0, slot0, p);
   uint8_t *pic = out + (size_t)p * mobi_scale_picture_bytes(k.ow, k.oh, ESIZE);
   const uint32_t band = blockIdx.x / k.n_strips, strip = blockIdx.x - band * k.n_strips;
   uint32_t r0, r1, c0, c1;
@@ -79,29 +68,10 @@ __global__ __launch_bounds__(64 * kWaves) void mobi_export_scale(const uint8_t *
       ib[t] = b_ok ? o + 1u - c0 : 0u;
       wb[t] = b_ok ? k.ow - w : 0u;
     }
-    const bool lastcol = x0 + 4u >= (uint32_t)width;
-    // luma column; chroma: samples a, b under the pixels (two bytes of one tile row) and e right of them (the next tile's for a = 6)
-    const uint32_t ycol = mobi_ty_col(x0), ccol = mobi_tc_x(x0 >> 1), ecol = lastcol ? ccol : mobi_tc_x((x0 >> 1) + 2u);
     for (uint32_t rp = wave; rp < pairs; rp += kWaves) { // (wave-uniform)
       const uint32_t y0 = py0 + 2u * rp; // even; y0 + 1 < height
-      const bool lastrow = y0 + 2u >= (uint32_t)height;
-      const uint8_t *yp = Y + mobi_ty_row(y0, lgS) + ycol; // rows y0, y0 + 1 are the two rows of one chunk
-      const uint32_t yw0 = *(const uint32_t *)yp, yw1 = *(const uint32_t *)(yp + 8);
-      const uint8_t *c0p = UV + mobi_tc_row(y0 >> 1, lgS), *c1p = lastrow ? c0p : UV + mobi_tc_row((y0 >> 1) + 1u, lgS);
-      const uint32_t u0w = *(const uint16_t *)(c0p + ccol), v0w = *(const uint16_t *)(c0p + ccol + 8);
-      const uint32_t u1w = *(const uint16_t *)(c1p + ccol), v1w = *(const uint16_t *)(c1p + ccol + 8);
-      const uint32_t ue0 = c0p[ecol], ve0 = c0p[ecol + 8], ue1 = c1p[ecol], ve1 = c1p[ecol + 8]; // (not looked at in the last column)
-      int ue[4], uo[4], ve[4], vo[4];
-      chroma_numerators(u0w, ue0, u1w, ue1, lastrow, lastcol, ue, uo);
-      chroma_numerators(v0w, ve0, v1w, ve1, lastrow, lastcol, ve, vo);
       uint32_t pe[4], po[4];
-#pragma unroll
-      for (int h = 0; h < 2; h++) {
-        const f32x2 ye = {(float)((yw0 >> (16 * h)) & 0xFF), (float)((yw0 >> (16 * h + 8)) & 0xFF)};
-        const f32x2 yo = {(float)((yw1 >> (16 * h)) & 0xFF), (float)((yw1 >> (16 * h + 8)) & 0xFF)};
-        convert2(version, ye, ue[2 * h], ue[2 * h + 1], ve[2 * h], ve[2 * h + 1], pe[2 * h], pe[2 * h + 1]);
-        convert2(version, yo, uo[2 * h], uo[2 * h + 1], vo[2 * h], vo[2 * h + 1], po[2 * h], po[2 * h + 1]);
-      }
+      fetch_quad(src.Y, src.UV, x0, y0, width, height, lgS, version, pe, po);
       // the rows' weights (wave-uniform): row y has a in sum row R and b in R + 1; a row outside the span has none
       auto row_tap = [&](uint32_t y, uint32_t &R, uint32_t &a, uint32_t &b) {
         const bool in = y >= k.cy + t0 && y < py1;
@@ -179,32 +149,11 @@ __global__ __launch_bounds__(64 * kWaves) void mobi_export_scale(const uint8_t *
   }
 }
 
-namespace {
-template <int PLANAR, int ESIZE>
-void launch_scale(const MobiExportGeom *g, int version, const MobiScalePlan &k, uint32_t p0, uint32_t n_pics, int n_clips, int clip0, int slot0,
-                  const MobiRgbAffine &sb, uint8_t *out, hipStream_t s) {
-  hipLaunchKernelGGL((mobi_export_scale<PLANAR, ESIZE>), dim3(k.n_bands * k.n_strips, n_pics), dim3(64 * kWaves), mobi_scale_lds_bytes(&k), s, g->planes,
-                     g->clip_bytes, g->slot_bytes, g->width, g->height, g->lg, version, n_clips, clip0, slot0, p0, k, sb, out);
-}
-} // namespace
-
 extern "C" int mobi_launch_export_scale(const MobiExportGeom *g, int version, int planar, int esize, const MobiScalePlan *plan, int n_frames,
                                         int n_clips, int clip0, int slot0, const MobiRgbAffine *sb, uint8_t *out_dev, hipStream_t s) {
-  if (esize != 1 && esize != 2 && esize != 4) return (int)hipErrorInvalidValue;
-  const uint32_t n_pics = (uint32_t)n_frames * (uint32_t)n_clips;
-  // pictures go in blockIdx.y: one launch up to 65535 of them (more are several launches of that many)
-  for (uint32_t p0 = 0; p0 < n_pics; p0 += 65535u) {
-    const uint32_t n = n_pics - p0 < 65535u ? n_pics - p0 : 65535u;
-    if (planar) {
-      if (esize == 1) launch_scale<1, 1>(g, version, *plan, p0, n, n_clips, clip0, slot0, *sb, out_dev, s);
-      else if (esize == 2) launch_scale<1, 2>(g, version, *plan, p0, n, n_clips, clip0, slot0, *sb, out_dev, s);
-      else launch_scale<1, 4>(g, version, *plan, p0, n, n_clips, clip0, slot0, *sb, out_dev, s);
-    } else {
-      if (esize == 1) launch_scale<0, 1>(g, version, *plan, p0, n, n_clips, clip0, slot0, *sb, out_dev, s);
-      else if (esize == 2) launch_scale<0, 2>(g, version, *plan, p0, n, n_clips, clip0, slot0, *sb, out_dev, s);
-      else launch_scale<0, 4>(g, version, *plan, p0, n, n_clips, clip0, slot0, *sb, out_dev, s);
-    }
-    if (hipError_t e = hipGetLastError()) return (int)e;
-  }
-  return 0;
+  return launch_pictures(planar, esize, n_frames, n_clips, [&](auto pl, auto es, uint32_t p0, uint32_t n) {
+    hipLaunchKernelGGL((mobi_export_scale<decltype(pl)::value, decltype(es)::value>), dim3(plan->n_bands * plan->n_strips, n), dim3(64 * kWaves),
+                       mobi_scale_lds_bytes(plan), s, g->planes, g->clip_bytes, g->slot_bytes, g->width, g->height, g->lg, version, n_clips, clip0, slot0, p0,
+                       *plan, *sb, out_dev);
+  });
 }

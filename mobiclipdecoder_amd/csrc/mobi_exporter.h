@@ -1,6 +1,7 @@
-// mobi_exporter.h -- interface between the C-ABI layer (mobi_pictures.cpp) and the export of decoded pictures to host memory (mobi_export.cpp,
-// mobi_export.hip; include/mobiclip_hip.h, mobi_batch_export).  The C entry points check their arguments against the batch and hand over
-// what the export needs of it; the export's state (streams, staging chunks, tickets, the ring-slot guard) lives in a MobiExporter.
+// mobi_exporter.h -- interface between the C-ABI layer (mobi_pictures.cpp) and the export of decoded pictures to host and device memory
+// (mobi_export.cpp, mobi_export*.hip; include/mobiclip_hip.h, mobi_batch_export*).  The C entry points check their arguments against the batch
+// and hand over what the export needs of it; the export's state (streams, staging chunks, parameter blocks, tickets, the ring-slot guard)
+// lives in a MobiExporter.
 #ifndef MOBI_EXPORTER_H
 #define MOBI_EXPORTER_H
 #include <hip/hip_runtime_api.h>

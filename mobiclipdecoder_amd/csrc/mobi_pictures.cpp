@@ -70,18 +70,22 @@ int mobi_batch_get_argb_at(mobi_batch *b, int clip, int ring_idx, uint32_t *out)
   HIP_TRY(hipMemcpy(out, b->d_argb, words * 4, hipMemcpyDeviceToHost));
   return MOBI_OK;
 }
-// ---- export of whole batches of pictures to host memory (the converter's decode -> AddFrame loop, MobiConverter/Program.cs:69-76) ----
-// The arguments are checked here against the batch; the pipeline, the tickets and the ring-slot guard are mobi_export.cpp's.
-int mobi_batch_export(mobi_batch *b, int format, int ring_idx, int n_frames, int clip0, int n_clips, void *dst, size_t dst_bytes, uint64_t *ticket_out) {
-  if (!b || !dst || (format != MOBI_EXPORT_I420 && format != MOBI_EXPORT_ARGB)) return MOBI_E_ARG;
-  if (clip0 < 0 || n_clips < 1 || clip0 > b->n - n_clips) return MOBI_E_ARG;
+// ---- what the exports to host and to device memory share ----
+namespace {
+// clips [clip0, clip0 + n_clips) of the batch?
+bool clip_range_ok(const mobi_batch *b, int clip0, int n_clips) { return clip0 >= 0 && n_clips >= 1 && clip0 <= b->n - n_clips; }
+// Frames ring_idx .. ring_idx - n_frames + 1 of those clips: MOBI_OK when they can be exported.  Ranges (`fits`: what the caller knows
+// about dst), then the state of the batch: poisoned, not decoded yet, still in flight.
+int check_export(const mobi_batch *b, int ring_idx, int n_frames, int clip0, int n_clips, bool fits) {
+  if (!clip_range_ok(b, clip0, n_clips)) return MOBI_E_ARG;
   if (ring_idx < 0 || ring_idx > 5 || n_frames < 1 || ring_idx - n_frames + 1 < 0) return MOBI_E_ARG;
-  const size_t px = (size_t)b->g.width * b->g.height, pic = format == MOBI_EXPORT_I420 ? px * 3 / 2 : px * 4;
-  if (dst_bytes < pic * n_frames * n_clips) return MOBI_E_ARG;
-  if (b->poisoned) return MOBI_E_ARG;
+  if (!fits || b->poisoned) return MOBI_E_ARG;
   if (ring_idx >= b->frames_started) return MOBI_E_NULLREF;
   if (ring_idx - n_frames + 1 < b->async_count) return MOBI_E_ARG; // frames of steps not waited for: mobi_batch_wait may still repair them
-  HIP_TRY(hipSetDevice(b->device));
+  return MOBI_OK;
+}
+// the job of a checked request (mobi_exporter.h); makes the batch's exporter at its first export
+MobiExportJob export_job(mobi_batch *b, int format, int ring_idx, int n_frames, int clip0, int n_clips, void *dst) {
   if (!b->exporter) b->exporter = mobi_exporter_new(b->device);
   MobiExportJob job;
   job.g = MobiExportGeom{b->arena + kGuard, b->clip_bytes, (uint32_t)b->slot_bytes, (int)b->g.width, (int)b->g.height, (int)b->g.stride, (int)b->g.mbw, b->g.lg};
@@ -92,6 +96,17 @@ int mobi_batch_export(mobi_batch *b, int format, int ring_idx, int n_frames, int
   job.slot0 = (b->ring_base + 6 - ring_idx) % 6;
   job.dst = dst;
   job.src_stream = b->stream;
+  return job;
+}
+} // namespace
+// ---- export of whole batches of pictures to host memory (the converter's decode -> AddFrame loop, MobiConverter/Program.cs:69-76) ----
+// The arguments are checked here against the batch; the pipeline, the tickets and the ring-slot guard are mobi_export.cpp's.
+int mobi_batch_export(mobi_batch *b, int format, int ring_idx, int n_frames, int clip0, int n_clips, void *dst, size_t dst_bytes, uint64_t *ticket_out) {
+  if (!b || !dst || (format != MOBI_EXPORT_I420 && format != MOBI_EXPORT_ARGB)) return MOBI_E_ARG;
+  const size_t px = (size_t)b->g.width * b->g.height, pic = format == MOBI_EXPORT_I420 ? px * 3 / 2 : px * 4;
+  if (int e = check_export(b, ring_idx, n_frames, clip0, n_clips, dst_bytes >= pic * n_frames * n_clips)) return e;
+  HIP_TRY(hipSetDevice(b->device));
+  MobiExportJob job = export_job(b, format, ring_idx, n_frames, clip0, n_clips, dst);
   job.argb = [b](int c0, int n, int slot, uint32_t *out, hipStream_t s) {
     MobiReconArgs a = b->args(nullptr, nullptr);
     a.ring_base = slot;
@@ -104,26 +119,31 @@ int mobi_batch_export(mobi_batch *b, int format, int ring_idx, int n_frames, int
   return MOBI_OK;
 }
 // ---- export into device memory, on the caller's stream (torch tensors, the caller's own HIP allocations) ----
-// The arguments are checked here; the stream order and the ring-slot guard are mobi_export.cpp's, the RGB kernels mobi_export_rgb.hip's and
-// mobi_export_scale.hip's and mobi_export_resample.hip's.
+// The arguments are checked here; the stream order and the ring-slot guard are mobi_export.cpp's, the RGB kernels mobi_export_rgb.hip's,
+// mobi_export_scale.hip's and mobi_export_resample.hip's (what the three share: mobi_export_tensor.h).
 namespace {
 // element size of an RGB export's dtype; 0: a combination the RGB formats do not have
 size_t rgb_esize(int dtype, const float *scale_bias) {
   if (dtype == MOBI_DTYPE_U8) return scale_bias ? 0 : 1;
   return dtype == MOBI_DTYPE_F16 ? 2 : dtype == MOBI_DTYPE_F32 ? 4 : 0;
 }
+// the same for the entry points that have RGB formats only: 0 for any other format too
+size_t rgb_only_esize(int format, int dtype, const float *scale_bias) {
+  return format == MOBI_EXPORT_RGB_PLANAR || format == MOBI_EXPORT_RGB_PACKED ? rgb_esize(dtype, scale_bias) : 0;
+}
+// scale[3], bias[3] of a call; none: the bytes as they are
+MobiRgbAffine rgb_affine(const float *scale_bias) {
+  MobiRgbAffine sb{{1.f, 1.f, 1.f, 0.f, 0.f, 0.f}};
+  if (scale_bias) memcpy(sb.v, scale_bias, sizeof(sb.v));
+  return sb;
+}
 // What every device export checks once its format is known, and the hand-over: pictures of `pic` bytes each, n_frames x n_clips of them
 // into dst on `stream`; launch(job, need, stream) enqueues the kernels (need = the bytes the export writes).  params: what the kernels read
 // from device memory (mobi_exporter.h), or nothing.
 int export_device(mobi_batch *b, int format, size_t pic, int ring_idx, int n_frames, int clip0, int n_clips, void *dst, size_t dst_bytes, void *stream,
                   const std::function<int(const MobiExportJob &, size_t, hipStream_t)> &launch, MobiExportParams *params = nullptr) {
-  if (clip0 < 0 || n_clips < 1 || clip0 > b->n - n_clips) return MOBI_E_ARG;
-  if (ring_idx < 0 || ring_idx > 5 || n_frames < 1 || ring_idx - n_frames + 1 < 0) return MOBI_E_ARG;
   const size_t need = pic * n_frames * n_clips;
-  if (dst_bytes < need || ((uintptr_t)dst & 15)) return MOBI_E_ARG;
-  if (b->poisoned) return MOBI_E_ARG;
-  if (ring_idx >= b->frames_started) return MOBI_E_NULLREF;
-  if (ring_idx - n_frames + 1 < b->async_count) return MOBI_E_ARG; // frames of steps not waited for: mobi_batch_wait may still repair them
+  if (int e = check_export(b, ring_idx, n_frames, clip0, n_clips, dst_bytes >= need && !((uintptr_t)dst & 15))) return e;
   HIP_TRY(hipSetDevice(b->device));
   // dst: device memory of this batch's device, the whole of [dst, dst + need) inside one allocation
   hipPointerAttribute_t at;
@@ -138,16 +158,7 @@ int export_device(mobi_batch *b, int format, size_t pic, int ring_idx, int n_fra
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(s, &cap) != hipSuccess) { (void)hipGetLastError(); return MOBI_E_ARG; }
   if (cap != hipStreamCaptureStatusNone) return MOBI_E_ARG;
-  if (!b->exporter) b->exporter = mobi_exporter_new(b->device);
-  MobiExportJob job;
-  job.g = MobiExportGeom{b->arena + kGuard, b->clip_bytes, (uint32_t)b->slot_bytes, (int)b->g.width, (int)b->g.height, (int)b->g.stride, (int)b->g.mbw, b->g.lg};
-  job.format = format;
-  job.n_frames = n_frames;
-  job.clip0 = clip0;
-  job.n_clips = n_clips;
-  job.slot0 = (b->ring_base + 6 - ring_idx) % 6;
-  job.dst = dst;
-  job.src_stream = b->stream;
+  const MobiExportJob job = export_job(b, format, ring_idx, n_frames, clip0, n_clips, dst);
   return mobi_exporter_run_device(b->exporter, job, s, [&](hipStream_t st) { return launch(job, need, st); }, params);
 }
 } // namespace
@@ -169,8 +180,7 @@ int mobi_batch_export_device(mobi_batch *b, int format, int dtype, const float *
   }
   const size_t px = (size_t)b->g.width * b->g.height;
   const size_t pic = format == MOBI_EXPORT_I420 ? px * 3 / 2 : format == MOBI_EXPORT_ARGB ? px * 4 : px * 3 * esize;
-  MobiRgbAffine sb{{1.f, 1.f, 1.f, 0.f, 0.f, 0.f}};
-  if (scale_bias) memcpy(sb.v, scale_bias, sizeof(sb.v));
+  const MobiRgbAffine sb = rgb_affine(scale_bias);
   uint8_t *out = (uint8_t *)dst;
   auto launch = [&](const MobiExportJob &job, size_t need, hipStream_t st) -> int {
     if (format == MOBI_EXPORT_I420) return mobi_launch_export_i420(&job.g, 0, n_frames * n_clips, n_clips, clip0, job.slot0, out, st);
@@ -196,16 +206,14 @@ int mobi_batch_export_device(mobi_batch *b, int format, int dtype, const float *
 // The crop, area-averaged down to out_w x out_h (mobi_export_scale.h): RGB tensors only, one crop per call.
 int mobi_batch_export_device_scaled(mobi_batch *b, int format, int dtype, const float *scale_bias, int crop_x, int crop_y, int crop_w, int crop_h,
                                     int out_w, int out_h, int ring_idx, int n_frames, int clip0, int n_clips, void *dst, size_t dst_bytes, void *stream) {
-  if (!b || !dst || (format != MOBI_EXPORT_RGB_PLANAR && format != MOBI_EXPORT_RGB_PACKED)) return MOBI_E_ARG;
-  const size_t esize = rgb_esize(dtype, scale_bias);
-  if (!esize) return MOBI_E_ARG;
+  const size_t esize = rgb_only_esize(format, dtype, scale_bias);
+  if (!b || !dst || !esize) return MOBI_E_ARG;
   const int W = (int)b->g.width, H = (int)b->g.height;
   if (crop_w < 1 || crop_h < 1 || crop_x < 0 || crop_y < 0 || crop_x > W - crop_w || crop_y > H - crop_h) return MOBI_E_ARG;
   if (out_w < 1 || out_h < 1 || out_w > crop_w || out_h > crop_h || (out_w & 3)) return MOBI_E_ARG;
   if ((uint64_t)crop_w * (uint64_t)crop_h > ((uint64_t)1 << 23)) return MOBI_E_ARG; // the sums stay below 2^31
   const MobiScalePlan plan = mobi_scale_plan((uint32_t)crop_x, (uint32_t)crop_y, (uint32_t)crop_w, (uint32_t)crop_h, (uint32_t)out_w, (uint32_t)out_h);
-  MobiRgbAffine sb{{1.f, 1.f, 1.f, 0.f, 0.f, 0.f}};
-  if (scale_bias) memcpy(sb.v, scale_bias, sizeof(sb.v));
+  const MobiRgbAffine sb = rgb_affine(scale_bias);
   auto launch = [&](const MobiExportJob &job, size_t, hipStream_t st) -> int {
     return mobi_launch_export_scale(&job.g, b->version, format == MOBI_EXPORT_RGB_PLANAR, (int)esize, &plan, n_frames, n_clips, clip0, job.slot0, &sb,
                                     (uint8_t *)dst, st);
@@ -217,14 +225,13 @@ int mobi_batch_export_device_scaled(mobi_batch *b, int format, int dtype, const 
 // clips' records made here; they reach the kernel through a parameter block of the exporter.
 int mobi_batch_export_device_boxes(mobi_batch *b, int format, int dtype, const float *scale_bias, const int32_t *boxes, int out_w, int out_h, int ring_idx,
                                    int n_frames, int clip0, int n_clips, void *dst, size_t dst_bytes, void *stream) {
-  if (!b || !dst || !boxes || (format != MOBI_EXPORT_RGB_PLANAR && format != MOBI_EXPORT_RGB_PACKED)) return MOBI_E_ARG;
-  const size_t esize = rgb_esize(dtype, scale_bias);
-  if (!esize) return MOBI_E_ARG;
+  const size_t esize = rgb_only_esize(format, dtype, scale_bias);
+  if (!b || !dst || !boxes || !esize) return MOBI_E_ARG;
   if (out_w < 1 || out_h < 1 || (out_w & 3)) return MOBI_E_ARG;
   // The boxes are the caller's memory and have to be copied before the call returns, so they are read here, in front of the shared
   // checks of export_device: that is why the clip range, which says how many rows `boxes` has, is looked at here as well as there.
   // Nothing is enqueued and nothing of the batch changes before export_device has accepted the rest.
-  if (n_clips < 1 || clip0 < 0 || clip0 > b->n - n_clips) return MOBI_E_ARG;
+  if (!clip_range_ok(b, clip0, n_clips)) return MOBI_E_ARG;
   const int W = (int)b->g.width, H = (int)b->g.height;
   std::vector<MobiResampleClip> recs((size_t)n_clips);
   MobiResampleCall call{(uint32_t)out_w, (uint32_t)out_h, 0u, 0u, nullptr};
@@ -237,8 +244,7 @@ int mobi_batch_export_device_boxes(mobi_batch *b, int format, int dtype, const f
     call.blocks = std::max(call.blocks, mobi_resample_blocks(&recs[c]));
     call.lds_bytes = std::max(call.lds_bytes, mobi_resample_lds_bytes(&recs[c]));
   }
-  MobiRgbAffine sb{{1.f, 1.f, 1.f, 0.f, 0.f, 0.f}};
-  if (scale_bias) memcpy(sb.v, scale_bias, sizeof(sb.v));
+  const MobiRgbAffine sb = rgb_affine(scale_bias);
   MobiExportParams params{recs.data(), recs.size() * sizeof(MobiResampleClip), nullptr};
   auto launch = [&](const MobiExportJob &job, size_t, hipStream_t st) -> int {
     call.clips_dev = (const MobiResampleClip *)params.dev;

@@ -1,6 +1,7 @@
 // mobi_rgb.h -- the per-pixel arithmetic of the Bitmap (MD.cs:260-323), shared by the kernels that compile it: mobi_yuv_to_argb
-// (mobi_rgb.hip, the Bitmap itself) and mobi_export_rgb (mobi_export_rgb.hip, RGB tensors in device memory).  Both therefore compute
-// the same 0xAARRGGBB word for every pixel; the tensor export takes its R, G, B from bytes 2, 1, 0 of that word.
+// (mobi_rgb.hip, the Bitmap itself) and the RGB tensor exports mobi_export_rgb, mobi_export_scale and mobi_export_resample (the .hip
+// files of those names; the latter two through mobi_export_tensor.h).  All therefore compute the same 0xAARRGGBB word for every pixel;
+// the tensor exports take their R, G, B from bytes 2, 1, 0 of that word.
 //
 // Per pixel: Y, plus U and V averaged from up to four chroma neighbours chosen by the pixel's parity (not on the last column / last row,
 // MD.cs:269), then either the float BT.601-like matrix with the 16..255 range stretch (Moflex3DS, :297-305) or the integer Y+U-V / Y+V /
@@ -89,7 +90,23 @@ __device__ __forceinline__ void chroma_numerators(uint32_t w0, uint32_t e0w, uin
   od[0] = 2 * (a0 + a1) - 512; od[1] = a0 + b0 + a1 + b1 - 512; od[2] = 2 * (b0 + b1) - 512; od[3] = lastcol ? pb : b0 + e0 + b1 + e1 - 512;
   if (lastrow) { od[0] = pa; od[1] = pa; od[2] = pb; od[3] = pb; } // the odd row is the picture's last: no mean of any kind (MD.cs:269)
 }
-// One element of an RGB tensor (mobi_export_rgb.hip, mobi_export_scale.hip) from the byte value v of channel ch (0 R, 1 G, 2 B), as the
+// The Bitmap's words of those four pixels in both rows, pe = the even row's, po = the odd row's: yw0, yw1 = their luma bytes, the chroma
+// words and lastrow / lastcol as in chroma_numerators (u.. of the U plane, v.. of the V plane).  The lane shape of mobi_yuv_to_argb and
+// of fetch_quad (mobi_export_tensor.h); how the words are fetched is the caller's.
+__device__ __forceinline__ void convert_quad(int version, uint32_t yw0, uint32_t yw1, uint32_t u0w, uint32_t ue0, uint32_t u1w, uint32_t ue1, uint32_t v0w,
+                                             uint32_t ve0, uint32_t v1w, uint32_t ve1, bool lastrow, bool lastcol, uint32_t (&pe)[4], uint32_t (&po)[4]) {
+  int ue[4], uo[4], ve[4], vo[4];
+  chroma_numerators(u0w, ue0, u1w, ue1, lastrow, lastcol, ue, uo);
+  chroma_numerators(v0w, ve0, v1w, ve1, lastrow, lastcol, ve, vo);
+#pragma unroll
+  for (int k = 0; k < 2; k++) {
+    const f32x2 ye = {(float)((yw0 >> (16 * k)) & 0xFF), (float)((yw0 >> (16 * k + 8)) & 0xFF)};
+    const f32x2 yo = {(float)((yw1 >> (16 * k)) & 0xFF), (float)((yw1 >> (16 * k + 8)) & 0xFF)};
+    convert2(version, ye, ue[2 * k], ue[2 * k + 1], ve[2 * k], ve[2 * k + 1], pe[2 * k], pe[2 * k + 1]);
+    convert2(version, yo, uo[2 * k], uo[2 * k + 1], vo[2 * k], vo[2 * k + 1], po[2 * k], po[2 * k + 1]);
+  }
+}
+// One element of an RGB tensor (the three export kernels) from the byte value v of channel ch (0 R, 1 G, 2 B), as the
 // bits of ESIZE bytes: uint8 is v; float32 is (float)v * sb[ch] + sb[3 + ch]; float16 is that float32 value rounded to nearest-even
 // (v_cvt_f16_f32 in the default rounding mode).
 // a product and a sum, each rounded: written here, under contract(off) -- __fmul_rn / __fadd_rn are plain operators in the HIP headers,

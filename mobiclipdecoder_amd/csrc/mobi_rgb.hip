@@ -1,6 +1,6 @@
 // mobi_rgb.hip -- the Bitmap that MobiclipDecoder.DecodeFrame() returns (MD.cs:260-323), on the GPU.
 //
-// Per pixel: the arithmetic of mobi_rgb.h (shared with the tensor export, mobi_export_rgb.hip).  HBM-bound: 1.5 bytes read, 4 written per
+// Per pixel: the arithmetic of mobi_rgb.h (shared with the tensor exports, mobi_export_*.hip).  HBM-bound: 1.5 bytes read, 4 written per
 // pixel.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -25,7 +25,7 @@ __device__ __forceinline__ uint32_t lane_right(uint32_t v) { // the value of the
 // lane >> 3 the row pair.  The planes are macroblock tiles (mobi_tile.h): a lane's two luma rows are 4 + 4 bytes of one 16-byte chunk, its
 // chroma samples two bytes of one or two tile rows; a row of the wave's output is 128 contiguous bytes.
 //
-// Chroma: mobi_rgb.h (chroma_numerators) on the lane's samples of its two rows.
+// Chroma and conversion: mobi_rgb.h (convert_quad) on the lane's samples of its two rows.
 // r04: 29 vector instructions per pixel instead of 65 (two pixels per floating-point instruction, one conversion instruction per output
 // byte instead of five, half the chroma loads per pixel) -- tools/exp_rgb.py.
 extern "C" __global__ __launch_bounds__(64) void mobi_yuv_to_argb(const uint8_t *planes, uint64_t clip_bytes, uint32_t slot_bytes, int ring_base,
@@ -55,17 +55,8 @@ extern "C" __global__ __launch_bounds__(64) void mobi_yuv_to_argb(const uint8_t 
     const int d0 = (int)(mobi_tile_c((uint32_t)mbx + 1u, 0, lgS)) - (int)(mobi_tile_c((uint32_t)mbx, 0, lgS)) - 6; // first sample of the next tile's row, seen from this lane's pair
     ue0 = c0p[d0]; ve0 = c0p[d0 + 8]; ue1 = c1p[d0]; ve1 = c1p[d0 + 8];
   }
-  int ue[4], uo[4], ve[4], vo[4];
-  chroma_numerators(u0w, ue0, u1w, ue1, lastrow, lastcol, ue, uo);
-  chroma_numerators(v0w, ve0, v1w, ve1, lastrow, lastcol, ve, vo);
   uint32_t pe[4], po[4];
-#pragma unroll
-  for (int k = 0; k < 2; k++) {
-    const f32x2 ye = {(float)((yw0 >> (16 * k)) & 0xFF), (float)((yw0 >> (16 * k + 8)) & 0xFF)};
-    const f32x2 yo = {(float)((yw1 >> (16 * k)) & 0xFF), (float)((yw1 >> (16 * k + 8)) & 0xFF)};
-    convert2(version, ye, ue[2 * k], ue[2 * k + 1], ve[2 * k], ve[2 * k + 1], pe[2 * k], pe[2 * k + 1]);
-    convert2(version, yo, uo[2 * k], uo[2 * k + 1], vo[2 * k], vo[2 * k + 1], po[2 * k], po[2 * k + 1]);
-  }
+  convert_quad(version, yw0, yw1, u0w, ue0, u1w, ue1, v0w, ve0, v1w, ve1, lastrow, lastcol, pe, po);
   if (active) {
     uint32_t *o = out + ((size_t)clip * height + y0) * width + x0;
     // written once, read by nobody on this GPU: past the caches (0.222 -> 0.215 ms per 512 clips of 640x480, A/B on one box)

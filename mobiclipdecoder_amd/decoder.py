@@ -313,6 +313,21 @@ class MobiclipDecoder:
             pass
 
 
+def _check_frames(ring_idx, n_frames):
+    """the frames of an export: ring indices ring_idx .. ring_idx - n_frames + 1"""
+    if isinstance(ring_idx, bool) or not isinstance(ring_idx, (int, np.integer)) or not 0 <= ring_idx <= 5:
+        raise ValueError(f"ring_idx must be an int in 0..5, not {ring_idx!r}")
+    if isinstance(n_frames, bool) or not isinstance(n_frames, (int, np.integer)) or not 1 <= n_frames <= ring_idx + 1:
+        raise ValueError(f"n_frames must be an int in 1..ring_idx + 1 = {ring_idx + 1}, not {n_frames!r}")
+
+
+def _ints(name, v, n):
+    """v, a tuple or list of n ints (no bools), as a list of int"""
+    if not isinstance(v, (tuple, list)) or len(v) != n or any(isinstance(i, bool) or not isinstance(i, (int, np.integer)) for i in v):
+        raise ValueError(f"{name} must be {n} ints, not {v!r}")
+    return [int(i) for i in v]
+
+
 def unpack_motion_search(words):
     """Packed results of mobi_batch_motion_search / the oracle -> dict(dx, dy, frame, score)."""
     w = np.asarray(words, dtype=np.uint32)
@@ -531,6 +546,16 @@ class MobiclipBatch:
             raise MobiclipError(error_string(rc))
         return out
 
+    def _clip_range(self, clips):
+        """the clips argument of the exports as a range: None = all clips, a slice is taken of them"""
+        if clips is None:
+            clips = range(self.n)
+        elif isinstance(clips, slice):
+            clips = range(self.n)[clips]
+        if not isinstance(clips, range) or clips.step != 1 or len(clips) < 1 or clips.start < 0 or clips.stop > self.n:
+            raise ValueError(f"clips must be a non-empty range / slice of step 1 inside 0..{self.n}, not {clips!r}")
+        return clips
+
     def export(self, fmt="i420", ring_idx=0, n_frames=1, clips=None, out=None, wait=True):
         """Pictures of many clips and frames to host memory in one call (mobi_batch_export): frame j = ring index ring_idx - j (oldest first),
         clips = a range / slice of clip numbers (step 1; None: all).  -> (n_frames, n_clips, W*H*3/2) uint8 (fmt="i420"; split_i420) or
@@ -538,16 +563,8 @@ class MobiclipBatch:
         wait=False an ExportHandle is returned at once -- the export runs behind the steps enqueued so far -- when out is host_empty() memory."""
         if fmt not in EXPORT_FORMATS:
             raise ValueError(f"fmt must be one of {sorted(EXPORT_FORMATS)}, not {fmt!r}")
-        if isinstance(ring_idx, bool) or not isinstance(ring_idx, (int, np.integer)) or not 0 <= ring_idx <= 5:
-            raise ValueError(f"ring_idx must be an int in 0..5, not {ring_idx!r}")
-        if isinstance(n_frames, bool) or not isinstance(n_frames, (int, np.integer)) or not 1 <= n_frames <= ring_idx + 1:
-            raise ValueError(f"n_frames must be an int in 1..ring_idx + 1 = {ring_idx + 1}, not {n_frames!r}")
-        if clips is None:
-            clips = range(self.n)
-        elif isinstance(clips, slice):
-            clips = range(self.n)[clips]
-        if not isinstance(clips, range) or clips.step != 1 or len(clips) < 1 or clips.start < 0 or clips.stop > self.n:
-            raise ValueError(f"clips must be a non-empty range / slice of step 1 inside 0..{self.n}, not {clips!r}")
+        _check_frames(ring_idx, n_frames)
+        clips = self._clip_range(clips)
         W, H = self.Width, self.Height
         shape, dtype = ((n_frames, len(clips), W * H * 3 // 2), np.uint8) if fmt == "i420" else ((n_frames, len(clips), H, W), np.uint32)
         if out is None:
@@ -613,78 +630,15 @@ class MobiclipBatch:
                     raise ValueError(f"{name} must be three finite floats, not {v!r}")
                 vals += v
             sb = (C.c_float * 6)(*np.asarray(vals, np.float32).tolist())
-        if isinstance(ring_idx, bool) or not isinstance(ring_idx, (int, np.integer)) or not 0 <= ring_idx <= 5:
-            raise ValueError(f"ring_idx must be an int in 0..5, not {ring_idx!r}")
-        if isinstance(n_frames, bool) or not isinstance(n_frames, (int, np.integer)) or not 1 <= n_frames <= ring_idx + 1:
-            raise ValueError(f"n_frames must be an int in 1..ring_idx + 1 = {ring_idx + 1}, not {n_frames!r}")
-        if clips is None:
-            clips = range(self.n)
-        elif isinstance(clips, slice):
-            clips = range(self.n)[clips]
-        if not isinstance(clips, range) or clips.step != 1 or len(clips) < 1 or clips.start < 0 or clips.stop > self.n:
-            raise ValueError(f"clips must be a non-empty range / slice of step 1 inside 0..{self.n}, not {clips!r}")
+        _check_frames(ring_idx, n_frames)
+        clips = self._clip_range(clips)
         F, N, W, H = int(n_frames), len(clips), self.Width, self.Height
-        box_rows = None
+        box_rows = crop_size = None
         if boxes is not None or flip is not None:
-            if boxes is None:
-                raise ValueError("flip applies to boxes only")
-            if crop is not None:
-                raise ValueError("boxes and crop exclude each other")
-            if fmt != "rgb":
-                raise ValueError(f"boxes apply to fmt='rgb' only, not {fmt!r}")
-            if size is None:
-                raise ValueError("boxes need a size (out_h, out_w)")
-            if not isinstance(size, (tuple, list)) or len(size) != 2 or any(isinstance(i, bool) or not isinstance(i, (int, np.integer)) for i in size):
-                raise ValueError(f"size must be 2 ints, not {size!r}")
-            oh, ow = int(size[0]), int(size[1])
-            if oh < 1 or ow < 1 or ow % 4:
-                raise ValueError(f"size (out_h, out_w) = {(oh, ow)!r} must be at least 1x1, out_w a multiple of 4")
-            try:
-                bx = np.asarray(boxes)
-            except (TypeError, ValueError):
-                raise ValueError(f"boxes must be an integer array of shape ({N}, 4)") from None
-            if bx.dtype == np.bool_ or not np.issubdtype(bx.dtype, np.integer) or bx.shape != (N, 4):
-                raise ValueError(f"boxes must be an integer array of shape ({N}, 4), not {bx.dtype} {bx.shape}")
-            bx = bx.astype(np.int64)
-            if flip is None:
-                fl = np.zeros(N, np.int64)
-            else:
-                try:
-                    fl = np.asarray(flip)
-                except (TypeError, ValueError):
-                    raise ValueError(f"flip must be {N} bools") from None
-                if fl.dtype != np.bool_ or fl.shape != (N,):
-                    raise ValueError(f"flip must be {N} bools, not {fl.dtype} {fl.shape}")
-                fl = fl.astype(np.int64)
-            x, y, w, h = bx.T
-            bad = (w < 1) | (h < 1) | (x < 0) | (y < 0) | (x + w > W) | (y + h > H)
-            if bad.any():
-                i = int(np.argmax(bad))
-                raise ValueError(f"boxes[{i}] (x, y, w, h) = {bx[i].tolist()} is empty or not inside the {W}x{H} picture")
-            D = np.where(ow > w, 2 * ow, w) * np.where(oh > h, 2 * oh, h)
-            if (D > 1 << 23).any():
-                i = int(np.argmax(D > 1 << 23))
-                raise ValueError(f"boxes[{i}] = {bx[i].tolist()} to {ow}x{oh}: dx * dy = {int(D[i])}, at most 2**23")
-            box_rows = np.ascontiguousarray(np.concatenate([bx, fl[:, None]], axis=1), dtype=np.int32)
-            W, H = ow, oh
-        scaled = box_rows is None and (crop is not None or size is not None)
-        if scaled:
-            if fmt != "rgb":
-                raise ValueError(f"crop and size apply to fmt='rgb' only, not {fmt!r}")
-
-            def ints(name, v, n):
-                if not isinstance(v, (tuple, list)) or len(v) != n or any(isinstance(i, bool) or not isinstance(i, (int, np.integer)) for i in v):
-                    raise ValueError(f"{name} must be {n} ints, not {v!r}")
-                return [int(i) for i in v]
-            cx, cy, cw, ch = (0, 0, W, H) if crop is None else ints("crop", crop, 4)
-            if cw < 1 or ch < 1 or cx < 0 or cy < 0 or cx + cw > W or cy + ch > H:
-                raise ValueError(f"crop (x, y, w, h) = {crop!r} is empty or not inside the {W}x{H} picture")
-            oh, ow = (ch, cw) if size is None else ints("size", size, 2)
-            if not (1 <= ow <= cw and 1 <= oh <= ch) or ow % 4:
-                raise ValueError(f"size (out_h, out_w) = {(oh, ow)!r} must be at least 1x1, no larger than the crop ({ch}, {cw}), out_w a multiple of 4")
-            if cw * ch > 1 << 23:
-                raise ValueError(f"crop of {cw}x{ch} pixels: at most 2**23")
-            W, H = ow, oh
+            box_rows, W, H = self._box_geometry(fmt, N, crop, size, boxes, flip)
+        elif crop is not None or size is not None:
+            crop_size = self._crop_geometry(fmt, crop, size)
+            W, H = crop_size[4:]
         if fmt == "i420":
             shape, tdtype = (F, N, W * H * 3 // 2), torch.uint8
         elif fmt == "argb":
@@ -706,10 +660,10 @@ class MobiclipBatch:
         code = DEVICE_EXPORT_FORMATS[(fmt, layout if fmt == "rgb" else None)]
         if box_rows is not None:
             rc = self._lib.mobi_batch_export_device_boxes(self._h, code, DEVICE_EXPORT_DTYPES[dname], sb, box_rows.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                          ow, oh, int(ring_idx), F, clips.start, N, out.data_ptr(),
+                                                          W, H, int(ring_idx), F, clips.start, N, out.data_ptr(),
                                                           out.numel() * out.element_size(), stream.cuda_stream)
-        elif scaled:
-            rc = self._lib.mobi_batch_export_device_scaled(self._h, code, DEVICE_EXPORT_DTYPES[dname], sb, cx, cy, cw, ch, ow, oh, int(ring_idx), F,
+        elif crop_size is not None:
+            rc = self._lib.mobi_batch_export_device_scaled(self._h, code, DEVICE_EXPORT_DTYPES[dname], sb, *crop_size, int(ring_idx), F,
                                                            clips.start, N, out.data_ptr(), out.numel() * out.element_size(), stream.cuda_stream)
         else:
             rc = self._lib.mobi_batch_export_device(self._h, code, DEVICE_EXPORT_DTYPES[dname], sb, int(ring_idx), F, clips.start, N,
@@ -717,6 +671,63 @@ class MobiclipBatch:
         if rc != 0:
             raise MobiclipError(error_string(rc))
         return out
+
+    def _box_geometry(self, fmt, N, crop, size, boxes, flip):
+        """export_tensor's boxes / flip / size, checked -> the (N, 5) int32 rows (x, y, w, h, flip) of the library call, out_w, out_h"""
+        W, H = self.Width, self.Height
+        if boxes is None:
+            raise ValueError("flip applies to boxes only")
+        if crop is not None:
+            raise ValueError("boxes and crop exclude each other")
+        if fmt != "rgb":
+            raise ValueError(f"boxes apply to fmt='rgb' only, not {fmt!r}")
+        if size is None:
+            raise ValueError("boxes need a size (out_h, out_w)")
+        oh, ow = _ints("size", size, 2)
+        if oh < 1 or ow < 1 or ow % 4:
+            raise ValueError(f"size (out_h, out_w) = {(oh, ow)!r} must be at least 1x1, out_w a multiple of 4")
+        try:
+            bx = np.asarray(boxes)
+        except (TypeError, ValueError):
+            raise ValueError(f"boxes must be an integer array of shape ({N}, 4)") from None
+        if bx.dtype == np.bool_ or not np.issubdtype(bx.dtype, np.integer) or bx.shape != (N, 4):
+            raise ValueError(f"boxes must be an integer array of shape ({N}, 4), not {bx.dtype} {bx.shape}")
+        bx = bx.astype(np.int64)
+        if flip is None:
+            fl = np.zeros(N, np.int64)
+        else:
+            try:
+                fl = np.asarray(flip)
+            except (TypeError, ValueError):
+                raise ValueError(f"flip must be {N} bools") from None
+            if fl.dtype != np.bool_ or fl.shape != (N,):
+                raise ValueError(f"flip must be {N} bools, not {fl.dtype} {fl.shape}")
+            fl = fl.astype(np.int64)
+        x, y, w, h = bx.T
+        bad = (w < 1) | (h < 1) | (x < 0) | (y < 0) | (x + w > W) | (y + h > H)
+        if bad.any():
+            i = int(np.argmax(bad))
+            raise ValueError(f"boxes[{i}] (x, y, w, h) = {bx[i].tolist()} is empty or not inside the {W}x{H} picture")
+        D = np.where(ow > w, 2 * ow, w) * np.where(oh > h, 2 * oh, h)
+        if (D > 1 << 23).any():
+            i = int(np.argmax(D > 1 << 23))
+            raise ValueError(f"boxes[{i}] = {bx[i].tolist()} to {ow}x{oh}: dx * dy = {int(D[i])}, at most 2**23")
+        return np.ascontiguousarray(np.concatenate([bx, fl[:, None]], axis=1), dtype=np.int32), ow, oh
+
+    def _crop_geometry(self, fmt, crop, size):
+        """export_tensor's crop / size, checked -> (crop_x, crop_y, crop_w, crop_h, out_w, out_h)"""
+        W, H = self.Width, self.Height
+        if fmt != "rgb":
+            raise ValueError(f"crop and size apply to fmt='rgb' only, not {fmt!r}")
+        cx, cy, cw, ch = (0, 0, W, H) if crop is None else _ints("crop", crop, 4)
+        if cw < 1 or ch < 1 or cx < 0 or cy < 0 or cx + cw > W or cy + ch > H:
+            raise ValueError(f"crop (x, y, w, h) = {crop!r} is empty or not inside the {W}x{H} picture")
+        oh, ow = (ch, cw) if size is None else _ints("size", size, 2)
+        if not (1 <= ow <= cw and 1 <= oh <= ch) or ow % 4:
+            raise ValueError(f"size (out_h, out_w) = {(oh, ow)!r} must be at least 1x1, no larger than the crop ({ch}, {cw}), out_w a multiple of 4")
+        if cw * ch > 1 << 23:
+            raise ValueError(f"crop of {cw}x{ch} pixels: at most 2**23")
+        return cx, cy, cw, ch, ow, oh
 
     def quantizer(self, clip):
         return self._lib.mobi_batch_quantizer(self._h, clip)
