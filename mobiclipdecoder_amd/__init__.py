@@ -17,4 +17,5 @@ from .decoder import (  # noqa: F401
     quant_tables,
     transform_code,
 )
+from .audio import MobiclipAudio  # noqa: F401
 from .streamgen import GenParams, generate_clip, default_params  # noqa: F401
