@@ -381,9 +381,11 @@ namespace {
 //   P_C1  the same for the right half of a LEFT/RIGHT pair.
 // After motion compensation (the windows are dead):
 //   P_OUT  the octet's output samples, luma rows R = 0..15 and chroma rows as R = 16..23 (column = plane * 8 + sample) in ONE formula:
-//          (row R, column c) of macroblock g at (R & 7) * 384 + (R >> 3) * 128 + ((g ^ (R & 7)) * 16) + c.  A row's eight macroblocks are
-//          rotated by the row number, so that the 64 lanes of a motion-compensation store, the eight lanes that add one area's residual
-//          (one row each) and the 16-byte reads of the final copy all spread over the banks; and a coded area's place is one constant
+//          (row R, column c) of macroblock g at (R & 7) * P_PITCH + (R >> 3) * 128 + g * 16 + c.  The pitch is 384 + 16 bytes: 400 r mod 256
+//          = 0, 144, 32, 176, 64, 208, 96, 240, so the eight lanes that add one area's residual (one row each) fall into eight different
+//          16-byte granules of the banks, the 64 lanes of a motion-compensation store cover 256 contiguous bytes, and every address is
+//          a per-lane base plus a constant (r03..r06 kept the pitch at 384 and rotated a row's macroblocks by the row number instead:
+//          one v_xor per stored row, two per residual word); and a coded area's place is one constant
 //          K = (area < 4 ? area >> 1 : 2) * 128 + (area & 1) * 8 whatever the plane (r03 kept chroma in a layout of its own: the residual
 //          add spent 30 instructions per half round choosing between the two).
 enum {
@@ -391,8 +393,9 @@ enum {
   P_C = 5120,
   P_C1 = 7680,
   P_BYTES = 10240,
-  P_OUT = 0,      // 3072 B
-  P_COEF = 3072,  // coefficient tiles of P_TILE words: 8 tiles of int16 PAIRS (two areas each) per packed round, or P_ROUND tiles of int32
+  P_OUT = 0,      // 3200 B
+  P_PITCH = 400,  // of the rows R & 7 of P_OUT
+  P_COEF = 3200,  // coefficient tiles of P_TILE words: 8 tiles of int16 PAIRS (two areas each) per packed round, or P_ROUND tiles of int32
   P_TILE = 72,
 #ifndef MOBI_PK_PAIRS
 #define MOBI_PK_PAIRS 12
@@ -402,13 +405,14 @@ enum {
   P_ROUND = 22,   // 32-bit rounds (the fall-back when some area's coefficients are too large for 16-bit butterflies): three half rounds of eight
   P_SUM = P_COEF + P_PAIRS * P_TILE * 4, // sum of |coefficient| per coded area (48 words), behind the packed tiles; dead before a 32-bit round
   P_SC = 9728,    // dequant scales (320 B): on top of the chroma windows, once the chroma has been interpolated
-  P_TAB = 10048,  // slot -> uint32: [6:4] g, [15:8] area * 8 + g, [31:16] K (above): 48 words
-  P_INV = 9408    // area*8 + g -> uint32: [12:0] where the slot's coefficients start in the packed tiles (byte offset from P_COEF: pair tile
+  P_TAB = 10048,  // slot -> uint32: [15:8] area * 8 + g, [31:16] g * 16 + K (above): 48 words
+  P_INV = 9536    // area*8 + g -> uint32: [12:0] where the slot's coefficients start in the packed tiles (byte offset from P_COEF: pair tile
                   // slot >> 1, half slot & 1), [19:13] slot, [31:23] what selects the dequant scale: 0x0FC (one 8x8 transform: byte offset =
                   // 4 * position) or 0x13C (4x4 blocks: 256 + 4 * (position & 15)), see the scatter.  48 words behind the last coefficient tile.
 };
-static_assert(P_COEF + P_ROUND * P_TILE * 4 <= P_INV && P_INV + 192 <= P_SC && P_TAB + 192 <= P_BYTES && P_SUM + 192 <= P_INV, "inter LDS map");
-__device__ __forceinline__ int out_px(int g, int R, int c) { return P_OUT + (R & 7) * 384 + (R >> 3) * 128 + ((g ^ (R & 7)) << 4) + c; }
+static_assert(P_OUT + 7 * P_PITCH + 384 <= P_COEF && P_COEF + P_ROUND * P_TILE * 4 <= P_INV && P_INV + 192 <= P_SC && P_SC + 320 <= P_TAB && P_TAB + 192 <= P_BYTES && P_SUM + 192 <= P_INV, "inter LDS map");
+static_assert(23 * P_TILE * 4 + 2 < (1 << 13) && (P_PITCH & 15) == 0, "P_INV's offset field (48 slots); 16-byte reads of the output rows");
+__device__ __forceinline__ int out_px(int g, int R, int c) { return P_OUT + (R & 7) * P_PITCH + (R >> 3) * 128 + (g << 4) + c; }
 __device__ __forceinline__ int out_y(int g, int R, int c) { return out_px(g, R, c); }
 __device__ __forceinline__ int out_c(int g, int R, int pl, int x) { return out_px(g, 16 + R, pl * 8 + x); }
 // N output rows of 4 pixels from N + 1 window rows (x0[i], x1[i] = the two aligned dwords holding row i's 5 bytes)
@@ -524,12 +528,34 @@ __device__ __forceinline__ void recon_inter_oct(const MobiReconArgs &A, uint8_t 
     const uint32_t bP = chunk0(colB ? topB : posA, colB ? refB : refA, uP), bB = chunk0(topB, refB, uB);
     // pair p of a window that starts at row 2u: row 2(u + p): tile row (u + p) >> 3, quadrant row ((u + p) >> 2) & 1, rows 2((u + p) & 3)
     auto rowpart = [&](uint32_t v) { return ((v & ~7u) << (lgS + 1)) + (((v & 7u) + (v & 4u)) << 4); };
-    const uint32_t vP = uP + (uint32_t)ph, vB = uB + (uint32_t)ph - 5u; // round t: pair 2t + ph of P, pair 2t + ph - 5 of B
+    // Three chunks two pairs apart from ONE rowpart: rowpart(v + 4) - rowpart(v) is 128 inside a tile row's upper quadrant row and one
+    // tile row less 128 out of the lower one (v & 4), rowpart(v + 2) - rowpart(v) is 32 inside a quadrant row and 64 less than the step
+    // of four out of it (v & 2).  (r03..r06 evaluated rowpart five times per lane and selected base and pair per round.)
+    const uint32_t Tm = (16u << lgS) - 256u; // (wave-uniform)
+    auto rows3 = [&](uint32_t base, uint32_t v, uint32_t (&r)[3]) { // -> the chunks of pairs v, v + 2, v + 4
+      uint32_t h = (v >> 2) & 1u, e = (v >> 1) & 1u;
+      // (as numbers: known to be 0 / 1, each product becomes a comparison, a select and a mask, and the steps save one instruction instead
+      // of twelve.  This is a fact about one compiler's code generation: re-count the vector instructions up to the last window DMA --
+      // profiles/r07_ubench.txt, static counts -- when the compiler changes)
+      asm volatile("" : "+v"(h), "+v"(e));
+      const uint32_t dm = __umul24(h, Tm) + 64u;
+      r[0] = base + rowpart(v);
+      r[1] = __umul24(e, dm) + r[0] + 32u;
+      r[2] = r[0] + 64u + dm;
+    };
+    // A lane's five pairs are two such runs: pairs ph, ph + 2, ph + 4 of P, and then either P's next three (a whole leaf: pairs ph + 4,
+    // ph + 6, ph + 8) or, TOP/BOTTOM, pairs 1 - ph, 3 - ph, 5 - ph of B (which sit at 6 - ph ... of the window).
     // rounds 0, 1: pairs 0..3 (P); round 2: pairs 4, 5 (TOP/BOTTOM: 5 is B's first); rounds 3, 4: pairs 6..9 (TOP/BOTTOM: B's)
-    const bool b2 = tb && ph, b34 = tb;
-    const uint32_t base2 = b2 ? bB : bP, v2 = b2 ? vB : vP, base34 = b34 ? bB : bP, v34 = b34 ? vB : vP;
-    const uint32_t v4 = (!tb && ph) ? v34 - 1u : v34;         // a whole leaf has no tenth pair: the ninth again
-    uint32_t o[5] = {bP + rowpart(vP), bP + rowpart(vP + 2), base2 + rowpart(v2 + 4), base34 + rowpart(v34 + 6), base34 + rowpart(v4 + 8)};
+    const uint32_t vP = uP + (uint32_t)ph;
+    uint32_t r1[3], r2[3];
+    rows3(bP, vP, r1);
+    rows3(tb ? bB : bP, tb ? uB + 1u - (uint32_t)ph : vP + 4u, r2);
+    const bool early = tb && !ph;          // the second run starts in round 3, not in round 2
+    // ... and then has one chunk less to bring; so has the lane of a whole leaf's tenth pair, which does not exist: its eighth again
+    const bool short2 = tb != (ph != 0);
+    const uint32_t o[5] = {r1[0], r1[1], early ? r1[2] : r2[0], early ? r2[0] : r2[1], short2 ? r2[1] : r2[2]};
+    // (a lane with nothing to bring -- short2 above, chroma rows past the window below -- repeats its OWN previous chunk since r07, not
+    // another lane's: already fetched, so in bounds and no new line; its place in LDS, pair 9 or chroma rows 9..11, is never read)
     // (only the lanes of macroblocks fetched this way ask: one execution mask for all eight rounds; the others' places in LDS keep
     // whatever they held -- their motion compensation below runs on it and is overwritten or never stored)
     if (win) {
@@ -546,13 +572,22 @@ __device__ __forceinline__ void recon_inter_oct(const MobiReconArgs &A, uint8_t 
     auto crowpart = [&](uint32_t r) { return ((r & ~7u) << lgS) + ((r & 7u) << 4); };
     uint32_t rA, rB;
     const uint32_t cA = cchunk0(cposA, refA, rA), cB = cchunk0(ctopB, refB, rB);
-    const uint32_t qA = rA + (uint32_t)ch2, qB = rB + (uint32_t)ch2 - 5u; // round t: row 4t + ch2 of A, row 4t + ch2 - 5 of B
-    // round 0: rows 0..3 (A); round 1: rows 4..7 (TOP/BOTTOM: 5.. are B's); round 2: rows 8..11 (TOP/BOTTOM: B's 3, 4; there is no row
-    // past 8 resp. 9: those lanes bring the last one again)
-    const bool cb1 = tb && ch2 >= 1;
-    const uint32_t cbase1 = cb1 ? cB : cA, q1 = cb1 ? qB : qA, cbase2 = tb ? cB : cA;
-    const uint32_t q2 = tb ? qB - (ch2 >= 2 ? (uint32_t)ch2 - 1u : 0u) : qA - (uint32_t)ch2;
-    const uint32_t co[3] = {cA + crowpart(qA), cbase1 + crowpart(q1 + 4), cbase2 + crowpart(q2 + 8)};
+    // crowpart(r + 8) - crowpart(r) is one tile row; crowpart(r + 4) - crowpart(r) is 64 inside the upper half of a tile row and a tile row
+    // less 64 out of the lower one: a lane's rounds are one crowpart and such steps, TOP/BOTTOM a second one for leaf B
+    const uint32_t Tc = 8u << lgS, Tcm = Tc - 128u; // (wave-uniform)
+    auto cstep4 = [&](uint32_t r) {
+      uint32_t h = (r >> 2) & 1u;
+      asm volatile("" : "+v"(h)); // (as in rows3)
+      return __umul24(h, Tcm) + 64u;
+    };
+    // round 0: rows 0..3 (A); round 1: rows 4..7 (TOP/BOTTOM: 5.. are B's rows 0..2); round 2: rows 8..11 (TOP/BOTTOM: B's 3, 4).  There
+    // is no row past 8 resp. 9: those lanes bring their own round 1 chunk again
+    const uint32_t qA = rA + (uint32_t)ch2;
+    const uint32_t c0 = cA + crowpart(qA), cE = c0 + cstep4(qA);
+    const uint32_t cY = cB + crowpart(rB + (uint32_t)((ch2 + 3) & 3)); // B's rows 3 (round 2), 0, 1, 2 (round 1)
+    const uint32_t stB = cstep4(rB);
+    const uint32_t cYd = cY + (ch2 == 1 ? stB : 0u);                    // ... and 4 (round 2)
+    const uint32_t co[3] = {c0, (tb && ch2) ? cY : cE, tb ? cYd : (ch2 ? cE : c0 + Tc)};
     if (win) {
 #pragma unroll
       for (int t = 0; t < 3; t++) dma16_sv(clip_base, co[t], lds0 + P_C + t * 1024);
@@ -560,9 +595,10 @@ __device__ __forceinline__ void recon_inter_oct(const MobiReconArgs &A, uint8_t 
     if (any_lr) { // the right halves of LEFT/RIGHT pairs: rows 0..8 of leaf B's own window
       const uint32_t q3 = rB + (uint32_t)ch2;
       if (lr && win) {
-        dma16_sv(clip_base, cB + crowpart(q3), lds0 + P_C1);
-        dma16_sv(clip_base, cB + crowpart(q3 + 4), lds0 + P_C1 + 1024);
-        dma16_sv(clip_base, cB + crowpart(q3 + 8 - (uint32_t)ch2), lds0 + P_C1 + 2048);
+        const uint32_t z0 = cB + crowpart(q3), z1 = z0 + cstep4(q3);
+        dma16_sv(clip_base, z0, lds0 + P_C1);
+        dma16_sv(clip_base, z1, lds0 + P_C1 + 1024);
+        dma16_sv(clip_base, ch2 ? z1 : z0 + Tc, lds0 + P_C1 + 2048); // row 8; the other lanes their round 1 chunk again
       }
     }
   }
@@ -771,12 +807,12 @@ __device__ __forceinline__ void recon_inter_oct(const MobiReconArgs &A, uint8_t 
   MOBI_STOP(5);
   wave_sync();
   {
-    // out_px with the row's low bits constant: (g ^ k) << 4 = (g << 4) ^ (k << 4), and nothing else of the address lives in bits 4..6
-    const int by = P_OUT + rr * 128 + (g << 4) + 4 * q, bc = P_OUT + 256 + ch * (4 * 384) + ((g << 4) ^ (ch << 6)) + pl * 8 + 4 * qc;
+    // out_px, one base per lane and the row as a constant offset: luma rows 8 * rr + k, chroma rows 4 * ch + k
+    const int by = out_y(g, 8 * rr, 4 * q), bc = out_c(g, 4 * ch, pl, 4 * qc);
 #pragma unroll
-    for (int k = 0; k < 8; k++) *(uint32_t *)(L + ((by ^ (k << 4)) + k * 384)) = mcv[k];            // = out_y(g, 8 * rr + k, 4 * q)
+    for (int k = 0; k < 8; k++) *(uint32_t *)(L + (by + k * P_PITCH)) = mcv[k];
 #pragma unroll
-    for (int k = 0; k < 4; k++) *(uint32_t *)(L + ((bc ^ (k << 4)) + k * 384)) = mcv[8 + k];        // = out_c(g, 4 * ch + k, pl, 4 * qc)
+    for (int k = 0; k < 4; k++) *(uint32_t *)(L + (bc + k * P_PITCH)) = mcv[8 + k];
   }
   if (PROF) pt[3] = prof_stamp();
   MOBI_STOP(6);
@@ -820,7 +856,7 @@ __device__ __forceinline__ void recon_inter_oct(const MobiReconArgs &A, uint8_t 
         const int slot = first + __builtin_popcount(mask & ((1u << kk) - 1u));
         const int a = lane >> 3;
         const uint32_t K = (uint32_t)((a < 4 ? a >> 1 : 2) * 128 + (a & 1) * 8);
-        *(uint32_t *)(L + P_TAB + 4 * slot) = ((uint32_t)(lane & 7) << 4) | ((uint32_t)lane << 8) | (K << 16);
+        *(uint32_t *)(L + P_TAB + 4 * slot) = ((uint32_t)lane << 8) | ((K + ((uint32_t)(lane & 7) << 4)) << 16);
         *(uint32_t *)(L + P_INV + 4 * lane) = (uint32_t)((slot >> 1) * (P_TILE * 4) + (slot & 1) * 2) | ((uint32_t)slot << 13) | ((is8 ? 0x0FCu : 0x13Cu) << 23); // area * 8 + g -> slot, for the scatter
       }
       if (lane < 48) *(uint32_t *)(L + P_SUM + 4 * lane) = 0u;
@@ -877,10 +913,10 @@ __device__ __forceinline__ void recon_inter_oct(const MobiReconArgs &A, uint8_t 
       for (int o = lane * 16; o < n_tiles * P_TILE * 4; o += 1024) *(uint4 *)(L + P_COEF + o) = z;
     };
     // where the lane's two words of an area are: 8x8 -> row r, samples 0..3 and 4..7; 4x4 -> rows i0, i0 + 1 of block r >> 1.
-    // address = C + ((g ^ x) << 4) + K(area) in the layout of out_px
+    // address = C (the lane's) + g * 16 + K(area) (the slot's: one number in P_TAB) in the layout of out_px; the second word is 4 bytes
+    // (8x8) or one row (4x4) behind the first
     const int s4 = r >> 1, rowa4 = (s4 >> 1) * 4 + (r & 1) * 2, cola4 = (s4 & 1) * 4;
-    const int Ca8 = P_OUT + r * 384, Cb8 = Ca8 + 4, x8 = r << 4;
-    const int Ca4 = P_OUT + rowa4 * 384 + cola4, Cb4 = P_OUT + (rowa4 + 1) * 384 + cola4, xa4 = rowa4 << 4, xb4 = (rowa4 + 1) << 4;
+    const int Ca8 = P_OUT + r * P_PITCH, Ca4 = P_OUT + rowa4 * P_PITCH + cola4;
     bool wide = false;  // (wave-uniform) some area's coefficients are too large for the 16-bit butterflies
     for (int base = 0; base < n_slots && !wide; base += 2 * P_PAIRS) {
       zero_tiles(n_slots - base < 2 * P_PAIRS ? (n_slots - base + 1) >> 1 : P_PAIRS);
@@ -902,9 +938,8 @@ __device__ __forceinline__ void recon_inter_oct(const MobiReconArgs &A, uint8_t 
         MOBI_STOP(10);
         if (act) {
           const uint32_t recA = lds32(L, P_TAB + 4 * slot0), recB = actB ? lds32(L, P_TAB + 4 * slot0 + 4) : recA;
-          const int Ca = is8g ? Ca8 : Ca4, Cb = is8g ? Cb8 : Cb4, xa = is8g ? x8 : xa4, xb = is8g ? x8 : xb4;
-          const int gA = (int)(recA & 0x70u), KA = (int)(recA >> 16), gB = (int)(recB & 0x70u), KB = (int)(recB >> 16);
-          uint8_t *wa = L + (Ca + (gA ^ xa) + KA), *wb = L + (Cb + (gA ^ xb) + KA), *wc = L + (Ca + (gB ^ xa) + KB), *wd = L + (Cb + (gB ^ xb) + KB);
+          const int Ca = is8g ? Ca8 : Ca4, dab = is8g ? 4 : P_PITCH;
+          uint8_t *wa = L + (Ca + (int)(recA >> 16)), *wb = wa + dab, *wc = L + (Ca + (int)(recB >> 16)), *wd = wc + dab;
           idct_pass2_pk(tile, is8g, r, wa, wb, wc, wd, actB, lo, hi);
         }
         wave_sync();
@@ -938,9 +973,8 @@ __device__ __forceinline__ void recon_inter_oct(const MobiReconArgs &A, uint8_t 
         for (int h = 0; h < 3; h++) {
           if (actx[h]) {
             const bool is8 = is8x[h];
-            const int Ca = is8 ? Ca8 : Ca4, Cb = is8 ? Cb8 : Cb4, xa = is8 ? x8 : xa4, xb = is8 ? x8 : xb4;
-            const int gg = (int)(recx[h] & 0x70u), KK = (int)(recx[h] >> 16);
-            idct_pass2_q(coef + P_TILE * (8 * h + grp), is8, r, L + (Ca + (gg ^ xa) + KK), L + (Cb + (gg ^ xb) + KK), lo, hi);
+            uint8_t *wa = L + ((is8 ? Ca8 : Ca4) + (int)(recx[h] >> 16));
+            idct_pass2_q(coef + P_TILE * (8 * h + grp), is8, r, wa, wa + (is8 ? 4 : P_PITCH), lo, hi);
           }
         }
         wave_sync();
@@ -1036,7 +1070,8 @@ __device__ __forceinline__ void recon_inter_oct(const MobiReconArgs &A, uint8_t 
 // against 2.696, and 2.81 against 2.50 on 848x480; 5 waves with 96 words (5 spills) 2.84.  Fewer waves do cost (15 per CU +3 %,
 // 12 per CU +12 %, MOBI_LDS_PAD); more do not pay.  Output rows padded in LDS (pitch 144 / 80 instead of 128 / 64, so that the eight
 // lanes of an area do not meet in one bank when they add the residual: 55 % of the LDS cycles are bank conflicts): 2.754 against 2.758 --
-// LDS time is not on the critical path of a kernel that waits for memory requests.
+// LDS time is not on the critical path of a kernel that waits for memory requests.  (That was r02, and a padding for the banks' sake.  The
+// pitch of 400 the output tile has now is there for the instructions it saves, in a kernel bound by their issue: P_OUT above.)
 MOBI_OCT_KERNEL(mobi_recon_inter8, 4, 0, 16)
 #if defined(MOBI_PROFILING)
 MOBI_OCT_KERNEL(mobi_recon_inter8_prof, 4, 1, 16) // (in-kernel cycle records, MOBI_DEBUG=9: the profiling twin of the library only)

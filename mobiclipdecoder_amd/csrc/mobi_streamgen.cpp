@@ -522,19 +522,63 @@ struct Gen {
     if (m.intra) bw.ue(m4 == 0 ? 2 : inv_cbp4_intra[m4]); else bw.ue(inv_cbp4_inter[m4]);
     for (int q = 0; q < 4; q++) if ((m4 >> q) & 1) put_block_scripted(tm.at({m.mb, 4 * k + q}));
   }
-  void gen_pframe_scripted(int dq, const std::map<int, mobi_gen_script_mb> &mbs, const TokMap &tm) {
+  // one scripted leaf: reference and vector as written down (the stream carries the difference to the predictor); false = the script asks
+  // for what the syntax or the planes do not have
+  bool put_leaf_scripted(int s, int x, int y, int w, int h, int io, int ref, int dx, int dy) {
+    const int nref = frames_done < 5 ? frames_done : 5;
+    if (ref < 1 || ref > nref || !pinv[s].nbits[ref] || std::abs(dx) > 63 || std::abs(dy) > 63 || !mv_ok(x, y, w, h, dx, dy)) return false;
+    bw.put(pinv[s].code[ref], pinv[s].nbits[ref]);
+    bw.se(dx - predx);
+    bw.se(dy - predy);
+    mvc[io] = dx; mvc[io + 1] = dy;
+    return true;
+  }
+  bool put_motion_scripted(const mobi_gen_script_mv &v, int x, int y, int io) {
+    switch (v.shape) {
+      case 0: return put_leaf_scripted(0, x, y, 16, 16, io, v.ref[0], v.dx[0], v.dy[0]);
+      case 1:
+        if (!pinv[0].nbits[8]) return false;
+        bw.put(pinv[0].code[8], pinv[0].nbits[8]);
+        return put_leaf_scripted(1, x, y, 16, 8, io, v.ref[0], v.dx[0], v.dy[0]) && put_leaf_scripted(1, x, y + 8, 16, 8, io, v.ref[1], v.dx[1], v.dy[1]);
+      case 2:
+        if (!pinv[0].nbits[9]) return false;
+        bw.put(pinv[0].code[9], pinv[0].nbits[9]);
+        return put_leaf_scripted(4, x, y, 8, 16, io, v.ref[0], v.dx[0], v.dy[0]) && put_leaf_scripted(4, x + 8, y, 8, 16, io, v.ref[1], v.dx[1], v.dy[1]);
+      case 3:
+        if (!pinv[0].nbits[8] || !pinv[1].nbits[9]) return false;
+        bw.put(pinv[0].code[8], pinv[0].nbits[8]);
+        for (int half = 0; half < 2; half++) {
+          bw.put(pinv[1].code[9], pinv[1].nbits[9]);
+          for (int k = 0; k < 2; k++)
+            if (!put_leaf_scripted(5, x + 8 * k, y + 8 * half, 8, 8, io, v.ref[2 * half + k], v.dx[2 * half + k], v.dy[2 * half + k])) return false;
+        }
+        return true;
+    }
+    return false;
+  }
+  bool gen_pframe_scripted(int dq, const std::map<int, mobi_gen_script_mb> &mbs, const TokMap &tm, const std::map<int, mobi_gen_script_mv> &mvs) {
     bw.put(0, 1);
     bw.se(dq);
     if (ver == 0) { if (quant == 0) setup_quant(0); else if (dq) setup_quant(quant + dq); }
     else if (dq) setup_quant(quant + dq);
     vlc_table = 0;
-    for (int mb = 0; mb < mbw * mbh; mb++) { // every vector is (0, 0): so is every predictor
+    std::fill(mvc.begin(), mvc.end(), 0);
+    for (int mb = 0; mb < mbw * mbh; mb++) { // without scripted motion every vector is (0, 0): so is every predictor
       mobi_gen_script_mb none;
       memset(&none, 0, sizeof(none));
       none.mb = mb;
       auto it = mbs.find(mb);
       const mobi_gen_script_mb &m = it == mbs.end() ? none : it->second;
+      const int mx = mb % mbw, my = mb / mbw;
+      int io = 2 * mx; // the predictor and the row cache as gen_pframe keeps them
+      int a[3] = {mvc[io], mvc[io + 2], mvc[io + 4]}, b[3] = {mvc[io + 1], mvc[io + 3], mvc[io + 5]};
+      auto med = [](int *v) { if (v[0] > v[1]) std::swap(v[0], v[1]); if (v[1] > v[2]) std::swap(v[1], v[2]); if (v[0] > v[1]) std::swap(v[0], v[1]); return v[1]; };
+      predx = med(a); predy = med(b);
+      io += 2;
+      mvc[io] = 0; mvc[io + 1] = 0;
+      auto mv = mvs.find(mb);
       if (m.intra) { // DecIntraFullBlockPMode, MD.cs:1759-1786, mode 3 = DC
+        if (mv != mvs.end()) return false;
         bw.put(pinv[0].code[6], pinv[0].nbits[6]);
         bw.ue(inv_cbp_intra[m.cbp]);
         bw.put(3, 3);
@@ -542,13 +586,18 @@ struct Gen {
         bw.put(3, 3);
         for (int k = 4; k < 6; k++) if ((m.cbp >> k) & 1) put_area_scripted(m, k, tm);
       } else {
-        bw.put(pinv[0].code[1], pinv[0].nbits[1]);
-        bw.se(0);
-        bw.se(0);
+        if (mv != mvs.end()) {
+          if (!put_motion_scripted(mv->second, mx * 16, my * 16, io)) return false;
+        } else {
+          bw.put(pinv[0].code[1], pinv[0].nbits[1]);
+          bw.se(0 - predx);
+          bw.se(0 - predy);
+        }
         bw.ue(inv_cbp_inter[m.cbp]);
         for (int k = 0; k < 6; k++) if ((m.cbp >> k) & 1) put_area_scripted(m, k, tm);
       }
     }
+    return true;
   }
 };
 
@@ -595,10 +644,16 @@ extern "C" int64_t mobi_gen_clip(const mobi_gen_params *p, uint8_t *out, size_t 
 
 extern "C" int64_t mobi_gen_clip_scripted(const mobi_gen_params *p, const int32_t *frame_qdelta, const mobi_gen_script_mb *mbs, int32_t n_mbs,
                                           const mobi_gen_script_tok *toks, int32_t n_toks, uint8_t *out, size_t cap, uint32_t *frame_off) {
+  return mobi_gen_clip_scripted_mv(p, frame_qdelta, mbs, n_mbs, toks, n_toks, nullptr, 0, out, cap, frame_off);
+}
+
+extern "C" int64_t mobi_gen_clip_scripted_mv(const mobi_gen_params *p, const int32_t *frame_qdelta, const mobi_gen_script_mb *mbs, int32_t n_mbs,
+                                             const mobi_gen_script_tok *toks, int32_t n_toks, const mobi_gen_script_mv *mvs, int32_t n_mvs,
+                                             uint8_t *out, size_t cap, uint32_t *frame_off) {
   if (!p || p->width == 0 || p->height == 0 || (p->width & 15) || (p->height & 15) || p->width > 1024) return -1;
   if (p->version != 1 && p->version != 2) return -1;
   if (p->quantizer < 12 || p->quantizer > 52 || p->n_frames < 1) return -1;
-  if (n_mbs < 0 || n_toks < 0 || (n_mbs && !mbs) || (n_toks && !toks)) return -1;
+  if (n_mbs < 0 || n_toks < 0 || n_mvs < 0 || (n_mbs && !mbs) || (n_toks && !toks) || (n_mvs && !mvs)) return -1;
   const int n_mb = (int)(p->width / 16) * (int)(p->height / 16);
   auto is_iframe = [&](int f) { return f == 0 || (p->iframe_interval > 0 && f % p->iframe_interval == 0); };
   // the script, frame by frame, checked: a coded block has tokens, a token has a coded block, positions are distinct and in range
@@ -610,6 +665,12 @@ extern "C" int64_t mobi_gen_clip_scripted(const mobi_gen_params *p, const int32_
     for (int k = 0; k < 6; k++)
       if (((m.cbp >> k) & 1) && !((m.t8 >> k) & 1) && (m.cbp4[k] < (m.intra ? 0 : 1) || m.cbp4[k] > 15)) return -1;
     if (!fm[m.frame].emplace(m.mb, m).second) return -1;
+  }
+  std::vector<std::map<int, mobi_gen_script_mv>> fv(p->n_frames);
+  for (int i = 0; i < n_mvs; i++) {
+    const mobi_gen_script_mv &v = mvs[i];
+    if (v.frame < 0 || v.frame >= p->n_frames || is_iframe(v.frame) || v.mb < 0 || v.mb >= n_mb || v.shape < 0 || v.shape > 3) return -1;
+    if (!fv[v.frame].emplace(v.mb, v).second) return -1;
   }
   for (int i = 0; i < n_toks; i++) {
     const mobi_gen_script_tok &t = toks[i];
@@ -650,7 +711,7 @@ extern "C" int64_t mobi_gen_clip_scripted(const mobi_gen_params *p, const int32_
       const int dq = frame_qdelta ? frame_qdelta[f] : 0;
       q += dq;
       if (q < 12 || q > 52) return -1;
-      g.gen_pframe_scripted(dq, fm[f], ft[f]);
+      if (!g.gen_pframe_scripted(dq, fm[f], ft[f], fv[f])) return -1;
     }
     g.bw.align();
     g.frames_done++;

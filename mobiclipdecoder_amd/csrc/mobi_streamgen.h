@@ -84,6 +84,19 @@ typedef struct mobi_gen_script_tok {
 int64_t mobi_gen_clip_scripted(const mobi_gen_params *p, const int32_t *frame_qdelta, const mobi_gen_script_mb *mbs, int32_t n_mbs,
                                const mobi_gen_script_tok *toks, int32_t n_toks, uint8_t *out, size_t cap, uint32_t *frame_off);
 
+/* ---- scripted motion (tests/test_inter_addressing_gpu.py): the partition, reference and vector of an inter macroblock written down ----
+ * As mobi_gen_clip_scripted; a macroblock that mvs names (it must not be intra) is coded with that partition instead of the 16x16 leaf with
+ * vector (0, 0).  Vectors are absolute, in half samples, |component| <= 63: the writer keeps the decoder's predictor and codes the difference.
+ * -1 also for a reference the clip does not have yet, or a window that leaves the picture (edge_mode: the plane's memory). */
+typedef struct mobi_gen_script_mv {
+  int32_t frame, mb;
+  int32_t shape;                 /* 0: one 16x16 leaf; 1: TOP/BOTTOM (two 16x8); 2: LEFT/RIGHT (two 8x16); 3: four 8x8 (TOP/BOTTOM, each half LEFT/RIGHT) */
+  int32_t ref[4], dx[4], dy[4];  /* per leaf in coding order (shape 3: top left, top right, bottom left, bottom right); reference 1..5 */
+} mobi_gen_script_mv;
+int64_t mobi_gen_clip_scripted_mv(const mobi_gen_params *p, const int32_t *frame_qdelta, const mobi_gen_script_mb *mbs, int32_t n_mbs,
+                                  const mobi_gen_script_tok *toks, int32_t n_toks, const mobi_gen_script_mv *mvs, int32_t n_mvs,
+                                  uint8_t *out, size_t cap, uint32_t *frame_off);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,8 @@ def _lib():
         lib.mobi_gen_clip.restype = C.c_int64
         lib.mobi_gen_clip_scripted.argtypes = [C.POINTER(GenParams), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.mobi_gen_clip_scripted.restype = C.c_int64
+        lib.mobi_gen_clip_scripted_mv.argtypes = [C.POINTER(GenParams), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.mobi_gen_clip_scripted_mv.restype = C.c_int64
         _LIB = lib
     return _LIB
 
@@ -71,10 +73,11 @@ def generate_clip(p):
     return buf[: int(n)], fo
 
 
-def generate_scripted(p, mbs, toks, qdelta=None):
+def generate_scripted(p, mbs, toks, qdelta=None, motion=None):
     """A clip whose P-frames are written down instead of drawn (csrc/mobi_streamgen.h, mobi_gen_clip_scripted): exact levels at exact scan
     positions, nothing redrawn.  mbs: rows (frame, mb, intra, cbp, t8, cbp4[0..5]); toks: rows (frame, mb, block = area * 4 + 4x4 block,
-    scan position, level, form); qdelta: None or one quantizer delta per frame.  Macroblocks no row names copy the frame before.
+    scan position, level, form); qdelta: None or one quantizer delta per frame; motion: None or rows (frame, mb, shape, ref[0..3], dx[0..3],
+    dy[0..3]) (mobi_gen_script_mv: the partition, references and vectors of an inter macroblock).  Macroblocks no row names copy the frame before.
     -> (bytes ndarray, frame_off uint32[n_frames+1]); ValueError for a script the writer refuses."""
     lib = _lib()
     mbs = np.ascontiguousarray(np.asarray(mbs, np.int32).reshape(-1, 11))
@@ -83,13 +86,14 @@ def generate_scripted(p, mbs, toks, qdelta=None):
     if qd is not None and qd.shape != (p.n_frames,):
         raise ValueError("qdelta needs one entry per frame")
     fo = np.zeros(p.n_frames + 1, np.uint32)
-    args = (C.byref(p), None if qd is None else qd.ctypes.data, mbs.ctypes.data, len(mbs), toks.ctypes.data, len(toks))
-    need = lib.mobi_gen_clip_scripted(*args, None, 0, fo.ctypes.data)
+    mv = np.ascontiguousarray(np.asarray([] if motion is None else motion, np.int32).reshape(-1, 15))
+    args = (C.byref(p), None if qd is None else qd.ctypes.data, mbs.ctypes.data, len(mbs), toks.ctypes.data, len(toks), mv.ctypes.data, len(mv))
+    need = lib.mobi_gen_clip_scripted_mv(*args, None, 0, fo.ctypes.data)
     if need == -1:
         raise ValueError("bad generator parameters or script")
     n = -need if need < 0 else need
     buf = np.zeros(max(int(n), 2), np.uint8)
-    got = lib.mobi_gen_clip_scripted(*args, buf.ctypes.data, buf.size, fo.ctypes.data)
+    got = lib.mobi_gen_clip_scripted_mv(*args, buf.ctypes.data, buf.size, fo.ctypes.data)
     if got != n:
         raise RuntimeError(f"generator size mismatch {got} != {n}")
     return buf[: int(n)], fo
