@@ -45,14 +45,15 @@ float mobi_debug_stage_ms(const mobi_batch *b) { return b ? b->last_stage_ms : 0
 float mobi_debug_hostparse_ms(const mobi_batch *b) { return b ? b->last_hostparse_ms : 0.f; }
 float mobi_debug_phase_ms(const mobi_batch *b, int k) { return b && k >= 0 && k < 6 ? b->phase_ms[k] : 0.f; } // host-parsed step: where the call's time went
 long long mobi_debug_read_parse(mobi_batch *b, uint32_t *desc_out, uint32_t *items_out, uint32_t *res_out, uint32_t *payload_out, size_t payload_words) {
-  if (!b || !b->d_pres) return MOBI_E_ARG;
+  if (!b || !b->dp.res.p) return MOBI_E_ARG;
+  const DpSet &B = b->dp;
   const size_t n = (size_t)b->n, n_mbs = (size_t)b->g.mbw * b->g.mbh;
   HIP_TRY(hipSetDevice(b->device));
   HIP_TRY(hipStreamSynchronize(b->stream));
-  if (desc_out) HIP_TRY(hipMemcpy(desc_out, b->d_pdesc.p, n * n_mbs * sizeof(MbDesc), hipMemcpyDeviceToHost));
-  if (items_out) HIP_TRY(hipMemcpy(items_out, b->d_pitems.p, n * n_mbs * 4, hipMemcpyDeviceToHost));
-  if (res_out) HIP_TRY(hipMemcpy(res_out, b->d_pres, n * sizeof(MobiDevResult), hipMemcpyDeviceToHost));
-  if (payload_out) HIP_TRY(hipMemcpy(payload_out, b->d_ppay.p, std::min(payload_words * 4, b->d_ppay.cap), hipMemcpyDeviceToHost));
+  if (desc_out) HIP_TRY(hipMemcpy(desc_out, B.desc.p, n * n_mbs * sizeof(MbDesc), hipMemcpyDeviceToHost));
+  if (items_out) HIP_TRY(hipMemcpy(items_out, B.items.p, n * n_mbs * 4, hipMemcpyDeviceToHost));
+  if (res_out) HIP_TRY(hipMemcpy(res_out, B.res.p, n * sizeof(MobiDevResult), hipMemcpyDeviceToHost));
+  if (payload_out) HIP_TRY(hipMemcpy(payload_out, B.pay.p, std::min(payload_words * 4, B.pay.cap), hipMemcpyDeviceToHost));
   return (long long)b->last_pay_cap;
 }
 } // extern "C"
@@ -245,7 +246,7 @@ int mobi_batch_reset_clips(mobi_batch *b, const int32_t *clips, int count) {
   int later = 0;
   for (int i = 0; i < b->gop_count; i++) {
     const mobi_batch::GopSlot &S = b->gslot[(b->gop_head + i) & 1];
-    later += S.K - (S.resolved ? S.done : 0);
+    later += S.H.K - (S.resolved ? S.done : 0);
   }
   for (int j = 0; j < count; j++) {
     const int c = clips[j];
@@ -266,10 +267,10 @@ int mobi_batch_clip_frames(const mobi_batch *b, int32_t *out) {
   std::vector<int32_t> turned(b->idle_count);
   for (int i = 0; i < b->gop_count; i++) {
     const mobi_batch::GopSlot &S = b->gslot[(b->gop_head + i) & 1];
-    if (S.idle_from.empty()) continue;
+    if (S.H.idle_from.empty()) continue;
     const int done = S.resolved ? S.done : 0;
     for (int c = 0; c < b->n; c++)
-      if (!b->stale(S.serial, c)) turned[c] -= S.K - std::max(done, (int)S.idle_from[c]);
+      if (!b->stale(S.serial, c)) turned[c] -= S.H.K - std::max(done, (int)S.H.idle_from[c]);
   }
   for (int c = 0; c < b->n; c++)
     if (b->ended[c]) out[c] = std::max(0, out[c] - std::max(0, turned[c]));

@@ -1,6 +1,7 @@
 // mobi_batch.h -- internal to the C-ABI layer of libmobiclip_hip.so (include/mobiclip_hip.h), never installed: the buffer and handle holders,
-// the host parse pool, the launch plan, struct mobi_batch and the one copy of every idiom a frame step is made of.  The entry points are in
-// mobi_batch.cpp, mobi_step_host.cpp, mobi_step_device.cpp, mobi_step_groups.cpp, mobi_replay.cpp and mobi_pictures.cpp.  There is no CPU
+// the host parse pool, the launch plan, struct mobi_batch and the one copy of every idiom a frame step is made of -- among them what a
+// device-parsed hand-over (a step, an asynchronous step, a group) owns and reports: DpSet, HostShare, and the staged image of mobi_handover.h.
+// The entry points are in mobi_batch.cpp, mobi_step_host.cpp, mobi_step_device.cpp, mobi_step_groups.cpp, mobi_replay.cpp and mobi_pictures.cpp.  There is no CPU
 // reconstruction path: every entry point that produces pixels goes through mobi_launch_inter / mobi_launch_intra.
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -25,6 +26,8 @@
 #include "mobi_exporter.h"
 #define MOBI_GOP_DEVICE_DECLS
 #include "mobi_gop.h"
+#include "mobi_handover.h"
+static_assert(StageImage::kSkip == MOBI_DP_SKIP, "the staged image and the parse kernels name a skipped lane alike");
 #include "mobi_kernels.h"
 #include "mobi_tile.h"
 #include "mobi_parse.h"
@@ -60,6 +63,7 @@ template <bool Pinned> struct GrowBuf { // growable buffer: pinned host staging 
     cap = want;
     return MOBI_OK;
   }
+  int grow(size_t n) { return n <= cap ? MOBI_OK : reserve(n + n / 4); } // growing is slow (pinned memory) or a device-wide stall (hipFree): leave room for the longer frames to come
   ~GrowBuf() { release(); }
 };
 using PinnedBuf = GrowBuf<true>;
@@ -235,6 +239,51 @@ inline int parse_host(MobiStreamParser *p, const uint8_t *data, size_t len, int3
 // a reconstruction fault word behind an rc that is still MOBI_OK (bit 1: an intra dependency never arrived)
 static inline int fault_rc(int rc, int fault) { return rc == MOBI_OK && fault ? ((fault & 2) ? MOBI_E_DEVICE : MOBI_E_CLAMP) : rc; }
 
+// What a device-parsed hand-over of `frames` x n lanes owns: the staged image's two copies, what its parse leaves in HBM ([v][n_mbs] descriptors
+// and items, cap_words payload words per lane, [v] results), the pinned copies of results and fault words, the staging of the host parser's
+// command lists (dp_override) and of states on their way back (dp_return_list), and the events "uploaded" and "parsed".  One in mobi_batch
+// (mobi_batch_decode), one per AsyncSlot, one per GopSlot.
+struct DpSet {
+  DevBuf bits, desc, pay, items, res;
+  PinnedBuf h_stage, h_res, h_fault, h_over, h_ret;
+  Event ev_up, ev_parsed;
+  size_t cap_words = 0, n = 0, n_mbs = 0;
+  int reserve_results(size_t lanes) { if (int e = res.reserve(lanes * sizeof(MobiDevResult))) return e; return h_res.reserve(lanes * sizeof(MobiDevResult)); }
+  // MbDesc.payload_off is relative to the lane's own part of the arena, which may then be as large as HBM lets it (24576 clips of
+  // 640x480 need 13 G words for an I-frame); the host parser's clips write into their own parts like everybody else (dp_override)
+  int reserve_tables(size_t lanes, int n_clips, int mbs, size_t words) {
+    n = (size_t)n_clips; n_mbs = (size_t)mbs; cap_words = words;
+    if (int e = desc.reserve(align_up(lanes * n_mbs * sizeof(MbDesc) + 8 * sizeof(MbDesc), kAlign))) return e;
+    if (int e = pay.reserve(align_up(lanes * cap_words * 4 + kPaySlack, kAlign))) return e;
+    return items.reserve(lanes * n_mbs * 4);
+  }
+  struct Rows { uint8_t *desc, *pay, *items; MobiDevResult *res; };
+  Rows rows(int k) const { const size_t v = (size_t)k * n; return {desc.p + v * n_mbs * sizeof(MbDesc), pay.p + v * cap_words * 4, items.p + v * n_mbs * 4, (MobiDevResult *)res.p + v}; } // frame k's tables
+  const MobiDevResult *results() const { return (const MobiDevResult *)h_res.p; }
+  int *faults() const { return (int *)h_fault.p; }
+};
+// The host parser's share of a hand-over of K frames and what it came to, [v] = [k * n + c]: its own clips when the parse was enqueued (from
+// frame 0) and the clips it took over at the first frame the device parsers could not finish.  A step is K = 1.
+struct HostShare {
+  int K = 0;
+  bool lockstep = false;           // the lock-step parser was in front of THIS hand-over (ls_decide)
+  std::vector<int32_t> offs;       // [v] Offset at submission
+  std::vector<uint8_t> idle_from;  // [c] the clip's first idle frame (K: none; mobi_batch_set_idle); empty: the hand-over has no idle slot
+  std::vector<int> host_from, rc;  // [c] the first frame that is the host parser's (K: none); [v] its rc
+  std::vector<int32_t> off;        // [v] Offset behind a host-parsed frame
+  std::vector<uint32_t> quant, yuv; // [v] Quantizer / YuvFormat behind it (the parser itself may be further by the time of the report)
+  int live_end(int c) const { return idle_from.empty() ? K : idle_from[c]; } // frames [0, live_end) of clip c are live
+  void clear(int n) { const size_t nv = (size_t)n * K; host_from.assign(n, K); rc.assign(nv, MOBI_OK); off.assign(nv, 0); quant.assign(nv, 0); yuv.assign(nv, 0); }
+};
+struct DpSeed { const MobiDevState *state; const MobiDevTail *tail; MobiStreamParser *parser; }; // device addresses of a start state, and whose it becomes (dp_seed_parsers)
+struct ParseTimer { // HIP events around the parse launches (kernel timing on): made on demand
+  Event a, b;
+  bool on(bool timing) { if (timing && !a) { (void)hipEventCreate(&a.h); (void)hipEventCreate(&b.h); } return timing && a && b; }
+  void start(bool timing, hipStream_t s) { if (on(timing)) (void)hipEventRecord(a, s); }
+  void stop(bool timing, hipStream_t s) { if (on(timing)) (void)hipEventRecord(b, s); }
+  void read(bool timing, float &ms_out) { float ms = 0; if (timing && a && b && hipEventElapsedTime(&ms, a, b) == hipSuccess) ms_out = ms; }
+};
+
 struct mobi_batch {
   int n = 0, device = 0, version = 0;
   MobiGeom g{};
@@ -270,14 +319,12 @@ struct mobi_batch {
   int parse_mode = 0; // explicit (env / mobi_batch_set_parse_mode), or by batch size and settled at the first frame (parse_auto)
   bool parse_auto = false;
   int hybrid_host = 0;           // parse mode 2: the last hybrid_host clips are parsed by the host pool while the GPU parses the others
-  Event ev_up;
-  PinnedBuf h_stage2;
-  size_t last_pay_cap = 0;
+  DpSet dp; // mobi_batch_decode's device-parsed steps
+  size_t last_pay_cap = 0; // payload bound of the last step's parse, synchronous or not (mobi_debug_read_parse)
   float last_parse_ms = 0; // duration of the last mobi_parse_frames launch (kernel timing on)
   float last_decode_ms = 0, last_stage_ms = 0; // wall time of the last mobi_batch_decode call / of its host staging part
   float phase_ms[6] = {0, 0, 0, 0, 0, 0};      // (profiling) host-parsed step: parse loop, plan, stage + upload enqueue, launch enqueue, sync; device-parsed step: cumulative ms after gather + upload, parse enqueued, parse done, launches enqueued, all done
   float last_hostparse_ms = 0;                 // ... / of its host parse part (host parse mode)
-  DevBuf d_bits, d_pdesc, d_ppay, d_pitems;
   DevBuf d_src, d_search; // mobi_batch_motion_search: the pictures being analysed, the packed results
   // the decoder state of the device-parsed clips: a ring of three entries (a step reads ps_cur, writes ps_cur + 1), so that the state a frame
   // STARTED from is still there when the host parser has to take the frame over (decode_device_parse, async_repair; mobi_state.h)
@@ -291,7 +338,6 @@ struct mobi_batch {
   unsigned long returns = 0;           // clips handed back to the device parsers so far (dp_return)
   std::vector<uint8_t> host_share;     // [clip] 1: the hybrid mode's share (stays with the host parser by design)
   std::vector<uint16_t> clean_run, clean_need; // [clip] consecutive frames the device parsers could have finished; how many it takes to go back
-  PinnedBuf h_ret;                     // dp_return: states on their way back to the device
   PinnedBuf h_fix;                     // async_repair: one clip's command list
   DevBuf d_fix;
   uint32_t pay_clip_words = 0;         // of the last device-parsed step (MobiReconArgs.pay_clip_words)
@@ -300,69 +346,45 @@ struct mobi_batch {
   bool lockstep = false;               // this step: mobi_parse_frames_ls in front of mobi_parse_frames
   int host_chunk = 256;                // host-parsed steps: clips per chunk of the parse / stage / upload pipeline (mobi_batch_decode)
   size_t fused_mbs = kFusedStepMbs;     // launch_plan: steps of at most this many macroblocks go out as one launch
-  DevArr<MobiDevResult> d_pres;
   DevArr<uint8_t> d_ptables;
-  PinnedBuf h_pres;
   std::vector<uint32_t> dev_quant, dev_yuvfmt;
   // asynchronous steps (mobi_batch_submit / mobi_batch_wait, device parse only): two sets of staging so that the bytes of step
   // n + 1 are gathered and uploaded while the GPU works on step n; everything else follows stream order
   struct AsyncSlot {
-    PinnedBuf h_stage, h_pres, h_fault, h_over, h_ret; // h_over: the command lists of the host parser's clips (dp_override); h_ret: dp_return
-    DevBuf d_bits;
-    // what the parse of this step leaves in HBM: owned by the slot, so that the parse of step n + 1 (on stream_p) may run under the
-    // reconstruction of step n (on stream), which still reads step n's
-    DevBuf d_pdesc, d_ppay, d_pitems, d_pres;
-    Event ev_up, ev_done, ev_parsed;
-    std::vector<int32_t> offs; // Offset of every clip at submission
-    int n_dev = 0;
-    bool lockstep = false;           // the lock-step parser was in front of THIS step (ls_decide at submission)
-    bool parsed_recorded = false;    // ev_parsed has been recorded at least once
+    // (what the parse of this step leaves in HBM is the slot's, so that the parse of step n + 1 -- on stream_p -- may run under the
+    // reconstruction of step n -- on stream --, which still reads step n's)
+    DpSet B;
+    StageImage img;                  // of the staged bitstream (B.h_stage): async_repair parses from it
+    HostShare H;                     // clips whose result is the host parser's (its own clips at submission; clips repaired in mobi_batch_wait)
+    Event ev_done;
+    bool parsed_recorded = false;    // B.ev_parsed has been recorded at least once
     int state_in = 0, ring_base = 0; // the entry of the state ring this step's parse read; the ring position its reconstruction wrote
-    size_t hdr_bytes = 0;            // of the staged bitstream image (h_stage: offsets, lengths, bits)
-    // clips whose result is the host parser's (its own clips at submission; clips repaired in mobi_batch_wait)
-    std::vector<uint8_t> is_host;
-    std::vector<int> host_rc;
-    std::vector<int32_t> host_off;
-    std::vector<uint32_t> host_quant, host_yuv; // Quantizer / YuvFormat behind that frame (the parser itself may be a step further by the time of wait)
     uint64_t serial = 0;             // the step's place among the steps handed over (stream generations: mobi_batch::stale)
-    std::vector<uint8_t> idle;       // [clip] 1: an idle slot of this step (mobi_batch_set_idle); empty: the step has none
-    bool is_idle(int c) const { return !idle.empty() && idle[c] != 0; }
+    bool is_idle(int c) const { return H.live_end(c) == 0; } // an idle slot of this step (mobi_batch_set_idle)
   };
   AsyncSlot aslot[2];
   // frame-parallel groups (mobi_batch_gop_begin / mobi_batch_gop_finish, mobi_gop.h): K frames of every clip parsed side by side as n * K
   // virtual clips (v = k * n + c), reconstructed as K steps.  Two slots: the bytes of group g + 1 are gathered and uploaded, and its parse
   // enqueued, while group g is reconstructed.
   struct GopSlot {
-    PinnedBuf h_stage, h_res, h_fault, h_over[MOBI_GOP_PARSE_MAX], h_seed, h_ret;
-    DevBuf d_bits, d_desc, d_pay, d_items, d_res, d_sin, d_sout, d_sls, d_tails, d_fault;
-    Event ev_up, ev_parsed, ev_recon;
-    int K = 0;
-    size_t hdr_bytes = 0, bytes = 0, max_len = 0, cap_words = 0;
-    int n_iframes = 0;
-    bool parse_enqueued = false, lockstep = false;
+    DpSet B;
+    StageImage img;                  // boff / lens: where the host parser finds its frames (the header's copy says MOBI_DP_SKIP for its clips)
+    HostShare H;                     // host_from ... : what the group's first mobi_batch_gop_finish settles for all K frames (a group of more than six is finished in two calls)
+    PinnedBuf h_over[MOBI_GOP_PARSE_MAX], h_seed;
+    DevBuf d_sin, d_sout, d_sls, d_tails, d_fault;
+    Event ev_recon;
+    bool parse_enqueued = false;
     int ring_in = 0;                 // the state ring entry the group's parse read
     uint64_t serial = 0;             // the group's place among the steps handed over (stream generations: mobi_batch::stale)
-    size_t reset_off = 0;            // clips reset from this group on (mobi_batch_reset_clips): n_reset int32 at d_bits + reset_off, uploaded with
-    int n_reset = 0;                 // the group's bits; mobi_reset_state writes their fresh state in front of the group's parse
-    std::vector<uint64_t> boff;      // [v] where the frame's bytes start in the staged image (behind its header)
-    std::vector<uint32_t> lens;      // [v] their number (the header's copy carries MOBI_DP_SKIP for the host parser's clips)
-    std::vector<int32_t> offs;       // [v] Offset at submission
     std::vector<uint8_t> is_host;    // [c] the host parser's clip when the parse was enqueued
-    // what the group's first mobi_batch_gop_finish settles for all K frames (a group of more than six is finished in two calls)
     bool resolved = false, returned = false; // (returned: the clips that go back to the device parsers have been sent)
     bool sorted = false;             // the group's intra macroblocks were put in wavefront order on the device (mobi_launch_gop_sort)
     DevBuf d_sorted, d_hist;
     uint64_t sorted_off[MOBI_GOP_PARSE_MAX] = {0};
     uint32_t sorted_items[MOBI_GOP_PARSE_MAX] = {0};
     int done = 0;                    // frames reconstructed and reported so far
-    std::vector<int> host_from, hslot, hrc, all_host;
-    std::vector<int32_t> hoff;
-    std::vector<uint32_t> hq, hy;
+    std::vector<int> hslot, all_host;
     std::vector<uint8_t> hready;
-    std::vector<uint8_t> idle_from;  // [c] the clip's first idle frame of the group (K: none; mobi_batch_set_idle); empty: the group has no idle slot
-    size_t idle_off = 0;             // ... in the staged image: n_idle clip indices (int32), then idle_from[n], uploaded with the group's bits
-    int n_idle = 0;
-    int live_end(int c) const { return idle_from.empty() ? K : idle_from[c]; } // frames [0, live_end) of clip c are live
   };
   GopSlot gslot[2];
   int gop_head = 0, gop_count = 0;
@@ -382,7 +404,7 @@ struct mobi_batch {
   bool committed = false;
   // timing
   Event ev_begin, ev_end;
-  Event ev_p0, ev_p1; // around the parse launch (kernel timing on)
+  ParseTimer ptimer;  // around the parse launch (kernel timing on)
   int ktiming = 0; // HIP events around launches: 0 none, 1 the inter launches (the dominant kernel: roofline), 2 every launch
   struct EvPair { hipEvent_t a, b; int kind; };
   std::vector<EvPair> evs;
@@ -545,17 +567,20 @@ void reset_commit(mobi_batch *b, uint64_t serial);
 // a mask of another n_frames, idle slots that are not a suffix, a live frame of an ended clip no pending reset names; changes nothing.
 int idle_check(const mobi_batch *b, int K, std::vector<uint8_t> &from);
 void idle_commit(mobi_batch *b, int K, const std::vector<uint8_t> &from); // the hand-over is made: marks and counts, the mask is consumed; BEFORE reset_commit
-struct DpStaged { // n_dev: clips the GPU parses; n_iframes: of them, I-frames (first bit); reset_off / n_reset: where the clip list of the resets
-  size_t hdr_bytes = 0, bytes = 0, max_len = 0, reset_off = 0; // handed over with this step sits in the image (mobi_batch_reset_clips)
-  int n_dev = 0, n_iframes = 0, n_reset = 0;
-  size_t idle_off = 0; // the step's idle clips (mobi_batch_set_idle), n_idle int32 behind the reset list
-  int n_idle = 0;
-};
-struct DpRows { uint8_t *desc, *pay, *items; MobiDevResult *res; size_t cap_words; };
 int dp_init(mobi_batch *b);
-bool ls_decide(const mobi_batch *b, const DpStaged &st);
-int dp_override(mobi_batch *b, const std::vector<int> &clips, const int *rc, PinnedBuf &stage, const DpRows &d, hipStream_t s,
+bool ls_decide(const mobi_batch *b, const StageImage &img);
+// the staged image of a hand-over (mobi_handover.h; resets: its reset list, img.n_reset clips) gathered into B.h_stage by the pool in `chunks` rounds of tasks of `run` frames; up != nullptr:
+// and sent to B.bits on `up`, each round's bytes while the next is gathered (header_too: the header with the first, else the bits only)
+// t0: when the caller began planning it (last_stage_ms counts from there)
+int dp_stage(mobi_batch *b, const StageImage &img, DpSet &B, const uint8_t *const *data, const int32_t *offsets, const uint8_t *idle_from, const int32_t *resets, int chunks, int run,
+             hipStream_t up, bool header_too, std::chrono::steady_clock::time_point t0);
+size_t dp_cap_words(mobi_batch *b, size_t max_len);
+void dp_parse_args(const mobi_batch *b, const StageImage &img, const DpSet &B, MobiDevParseArgs &pa);
+int dp_idle_rows(mobi_batch *b, const StageImage &img, const DpSet &B, const MobiDevParseArgs &pa, bool carry_state, hipStream_t s);
+int dp_seed_parsers(mobi_batch *b, const std::vector<DpSeed> &seeds, PinnedBuf &stage, hipStream_t s);
+int dp_override(mobi_batch *b, const std::vector<int> &clips, const int *rc, PinnedBuf &stage, const DpSet &B, int k, hipStream_t s,
                 const ParsedFrame *const *frames = nullptr, const int *rcs = nullptr);
-int dp_return_list(mobi_batch *b, const std::vector<int> &back, int entry, PinnedBuf &stage, hipStream_t s);
+int dp_return_list(mobi_batch *b, const std::vector<int> &back, int entry, DpSet &B, hipStream_t s);
+void dp_report(mobi_batch *b, const HostShare &H, const DpSet &B, int k0, int k1, int32_t *offsets_out, int *rc);
 int decode_device_parse(mobi_batch *b, const uint8_t *const *data, const size_t *len, int32_t *offsets, int *rc);
 int ensure_argb(mobi_batch *b, int n_clips);

@@ -1,4 +1,7 @@
-// mobi_step_device.cpp -- device-parsed frame steps: behind mobi_batch_decode, mobi_batch_submit / mobi_batch_wait, and what the groups share with them
+// mobi_step_device.cpp -- device-parsed frame steps: behind mobi_batch_decode, mobi_batch_submit / mobi_batch_wait.  A step is a group of one
+// frame as far as the hand-over goes, and that part is here once, for the groups (mobi_step_groups.cpp) too: gather and upload of the staged
+// image (dp_stage; its layout: mobi_handover.h), the payload bound, the parse arguments and the idle rows (dp_cap_words, dp_parse_args,
+// dp_idle_rows), the host parser's seeds, command lists and way back (dp_seed_parsers, dp_override, dp_return_list), the report (dp_report).
 #include "mobi_batch.h"
 
 // DecodeFrame() of every clip with the bitstream parse on the GPU: upload Data[Offset..) of every clip, one parse launch
@@ -17,13 +20,12 @@ int dp_init(mobi_batch *b) {
   const int n = b->n;
   if (b->d_pstate[0]) return MOBI_OK;
   auto init = [&]() -> int {
-    if (int e = b->d_pres.alloc(n)) return e;
-    HIP_TRY(hipMemset(b->d_pres, 0, sizeof(MobiDevResult) * n));
+    if (int e = b->dp.reserve_results(n)) return e;
+    HIP_TRY(hipMemset(b->dp.res.p, 0, sizeof(MobiDevResult) * n));
     std::vector<uint8_t> blob(MOBI_DT_BYTES);
     mobi_dparse_build_tables(b->version, blob.data());
     if (int e = b->d_ptables.alloc(MOBI_DT_BYTES)) return e;
     HIP_TRY(hipMemcpy(b->d_ptables, blob.data(), MOBI_DT_BYTES, hipMemcpyHostToDevice));
-    if (int e = b->h_pres.reserve(sizeof(MobiDevResult) * n)) return e;
     if (int e = b->d_pstate_ls.alloc(n)) return e;
     for (int k = 0; k < 3; k++) {
       if (int e = b->d_ptail[k].alloc(n)) return e;
@@ -36,7 +38,7 @@ int dp_init(mobi_batch *b) {
     return MOBI_OK;
   };
   if (int e = init()) {
-    b->d_pres.free(); b->d_ptables.free(); b->d_pstate_ls.free();
+    b->dp.res.release(); b->d_ptables.free(); b->d_pstate_ls.free();
     for (int k = 0; k < 3; k++) { b->d_pstate[k].free(); b->d_ptail[k].free(); }
     return e;
   }
@@ -54,158 +56,107 @@ int dp_init(mobi_batch *b) {
 //   I-frames: 1024 clips 23.4 / 11.7, 2048: 30.0 / 11.3, 4096: 30.0 / 16.5, 8192: 54.9 / 23.6
 // -- one wave per clip wins while every clip has a wave slot of its own and the frames are P-frames; an I-frame's macroblocks are all of one
 // kind, which is what lanes in lock step like.
-bool ls_decide(const mobi_batch *b, const DpStaged &st) {
+bool ls_decide(const mobi_batch *b, const StageImage &st) {
   if (b->ls_policy != 2) return b->ls_policy == 1;
   const bool iframe_step = 2 * st.n_iframes > st.n_dev;
   return st.n_dev >= 5120 || (iframe_step && st.n_dev >= 768);
 }
-// stage [bit_off u64 x n][bit_len u32 x n][bits: each clip 8-byte aligned, zero padded] into pinned memory; the host parser's clips
-// (b->on_host) carry MOBI_DP_SKIP for a length and no bits
-// dev != nullptr: the image is also sent to *dev on `up`, chunk by chunk while the next chunk is gathered (one thread of the pool sits in
-// the copy calls, which return when the bus is done: 8 ms for the 370 MB of a step of 24576 clips; the others gather) -- r04: gathering and
-// sending were 12 of the 45 ms of such a step, one after the other.
-// resets != nullptr: these clip indices (int32) ride behind the bits, for mobi_reset_state
-// idle != nullptr: (*idle)[i] == 0 marks clip i's slot idle (idle_check): nothing of it is read, gathered or uploaded, its length says
-// MOBI_DP_SKIP to the parse kernels, and the list of these clips rides behind the resets, for mobi_idle_rows
-static int dp_stage(mobi_batch *b, const uint8_t *const *data, const size_t *len, const int32_t *offsets, PinnedBuf &stage, DpStaged &st,
-                    DevBuf *dev = nullptr, bool dev_headroom = false, hipStream_t up = nullptr, const std::vector<int32_t> *resets = nullptr,
-                    const std::vector<uint8_t> *idle = nullptr) {
-  const int n = b->n, nd = n, n_mbs = b->g.mbw * b->g.mbh;
-  const auto t_stage0 = std::chrono::steady_clock::now();
-  constexpr size_t kBitPad = 32; // the reader runs two 8-byte registers ahead
-  std::vector<uint64_t> boff(nd);
-  std::vector<uint32_t> blen(nd);
-  size_t pos = 0, max_len = 0;
-  const size_t frame_bound = (size_t)n_mbs * 4096 + 64;
-  std::vector<int32_t> idle_list;
-  for (int i = 0; i < n; i++) {
-    if (idle && (*idle)[i] == 0) { boff[i] = pos; blen[i] = MOBI_DP_SKIP; idle_list.push_back(i); continue; }
-    const int64_t o = offsets[i];
-    size_t l = (data[i] && o >= 0 && (uint64_t)o < len[i]) ? len[i] - (size_t)o : 0; // nothing readable: the first ReadU16LE throws
-    // MOC5 callers pass the whole file as Data (Form1.cs:292-302).  The reader advances two bytes per refill and refills at most
-    // once per syntax element: <= ~1450 refills per macroblock (127 partition nodes, 384 levels of up to three reads each), so
-    // bytes beyond 4 KB per macroblock cannot influence the parse of this frame
-    l = std::min(l, frame_bound);
-    max_len = std::max(max_len, l); // (the host parser's clips too: their share of the payload bound counts)
-    boff[i] = pos;
-    if (b->on_host[i]) { blen[i] = MOBI_DP_SKIP; continue; }
-    blen[i] = (uint32_t)l;
-    pos += align_up(l + kBitPad, 8);
-    st.n_dev++;
-    st.n_iframes += l >= 2 && (data[i][o + 1] & 0x80) != 0; // the frame's first bit: the top bit of its first 16-bit little-endian word (MD.cs:110-113)
+// Gather and upload.  With `up`, one thread of the pool sits in the copy calls, which return when the bus is done (8 ms for the 370 MB of a
+// step of 24576 clips), while the others gather the next round -- r04: gathering and sending were 12 of the 45 ms of such a step, one after
+// the other.  `run` frames per task: one per frame has the pool's threads queue at its counter (122 880 frames of 256x192: 8 ms).
+int dp_stage(mobi_batch *b, const StageImage &img, DpSet &B, const uint8_t *const *data, const int32_t *offsets, const uint8_t *idle_from, const int32_t *resets, int chunks, int run,
+             hipStream_t up, bool header_too, std::chrono::steady_clock::time_point t0) {
+  const int nv = (int)img.lanes();
+  uint8_t *hs = B.h_stage.p;
+  img.write_header(hs, resets, idle_from);
+  if (nv < 2048 || !up) chunks = 1;
+  std::atomic<int> up_err{0};
+  auto start_of = [&](int v) { return v < nv ? img.hdr_bytes + (size_t)img.boff[v] : img.bytes; }; // (behind the last lane: the lists)
+  for (int k = 0; k <= chunks; k++) {
+    const int c0 = k < chunks ? (int)((long)nv * k / chunks) : nv, c1 = k < chunks ? (int)((long)nv * (k + 1) / chunks) : nv;
+    const int u0 = k >= 1 ? (int)((long)nv * (k - 1) / chunks) : 0, u1 = k >= 1 ? (int)((long)nv * k / chunks) : 0; // gathered in the round before
+    const int n_up = up && u1 > u0 ? 1 : 0;
+    if (n_up + (c1 - c0) == 0) continue;
+    b->pool->run(n_up + (c1 - c0 + run - 1) / run, [&](int j) {
+      if (j < n_up) {
+        const size_t a = u0 == 0 && header_too ? 0 : start_of(u0), e = start_of(u1);
+        if (e > a && (hipSetDevice(b->device) != hipSuccess || hipMemcpyAsync(B.bits.p + a, hs + a, e - a, hipMemcpyHostToDevice, up) != hipSuccess)) up_err = 1;
+        return;
+      }
+      for (int v = c0 + (j - n_up) * run, e = std::min(c1, v + run); v < e; v++) img.gather(hs, (size_t)v, data, offsets);
+    });
   }
-  pos += 64; // (a skipped clip's offset points at readable bytes too)
-  const size_t list_pos = pos, n_reset = resets ? resets->size() : 0;
-  pos += align_up(n_reset * 4, 16);
-  const size_t idle_pos = pos;
-  pos += align_up(idle_list.size() * 4, 16);
-  const size_t hdr_bytes = align_up((size_t)nd * 12, 16);
-  if (hdr_bytes + pos > stage.cap) // pinned memory is slow to allocate: leave room for the longer frames to come
-    if (int e = stage.reserve(hdr_bytes + pos + (hdr_bytes + pos) / 4)) return e;
-  uint8_t *hs = stage.p;
-  memcpy(hs, boff.data(), (size_t)nd * 8);
-  memcpy(hs + (size_t)nd * 8, blen.data(), (size_t)nd * 4);
-  memset(hs + hdr_bytes + list_pos - 64, 0, 64);
-  if (n_reset) memcpy(hs + hdr_bytes + list_pos, resets->data(), n_reset * 4);
-  st.reset_off = hdr_bytes + list_pos;
-  st.n_reset = (int)n_reset;
-  if (!idle_list.empty()) memcpy(hs + hdr_bytes + idle_pos, idle_list.data(), idle_list.size() * 4);
-  st.idle_off = hdr_bytes + idle_pos;
-  st.n_idle = (int)idle_list.size();
-  auto gather = [&](int i) {
-    if (blen[i] == MOBI_DP_SKIP) return;
-    uint8_t *dst = hs + hdr_bytes + boff[i];
-    if (blen[i]) memcpy(dst, data[i] + offsets[i], blen[i]);
-    memset(dst + blen[i], 0, align_up(blen[i] + kBitPad, 8) - blen[i]);
-  };
-  constexpr int kRun = 32; // frames per pool task (one per frame has the pool's threads queue at its counter: gop_begin measured it)
-  if (!dev) {
-    b->pool->run((nd + kRun - 1) / kRun, [&](int j) { for (int i = j * kRun, e = std::min(nd, i + kRun); i < e; i++) gather(i); });
-  } else {
-    const size_t need = hdr_bytes + pos;
-    if (need > dev->cap) // growing frees and allocates (a device-wide stall): asynchronous steps leave room for the longer frames to come
-      if (int e = dev->reserve(dev_headroom ? need + need / 4 : need)) return e;
-    const int chunks = nd >= 2048 ? 4 : 1;
-    std::atomic<int> up_err{0};
-    auto end_of = [&](int c1) { return c1 < nd ? hdr_bytes + (size_t)boff[c1] : need; }; // byte offset where clip c1's bits start
-    for (int k = 0; k <= chunks; k++) {
-      const int c0 = k < chunks ? (int)((long)nd * k / chunks) : nd, c1 = k < chunks ? (int)((long)nd * (k + 1) / chunks) : nd;
-      const int u0 = k >= 1 ? (int)((long)nd * (k - 1) / chunks) : 0, u1 = k >= 1 ? (int)((long)nd * k / chunks) : 0; // gathered in the round before
-      const int n_up = u1 > u0 ? 1 : 0;
-      if (n_up + (c1 - c0) == 0) continue;
-      b->pool->run(n_up + (c1 - c0 + kRun - 1) / kRun, [&](int j) {
-        if (j < n_up) {
-          const size_t a = u0 == 0 ? 0 : end_of(u0), e = end_of(u1); // (the first chunk takes the header along)
-          if (e > a && (hipSetDevice(b->device) != hipSuccess || hipMemcpyAsync(dev->p + a, hs + a, e - a, hipMemcpyHostToDevice, up) != hipSuccess)) up_err = 1;
-          return;
-        }
-        for (int i = c0 + (j - n_up) * kRun, e = std::min(c1, i + kRun); i < e; i++) gather(i);
-      });
-    }
-    if (up_err) return MOBI_E_DEVICE;
-  }
-  b->last_stage_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_stage0).count();
-  st.hdr_bytes = hdr_bytes;
-  st.bytes = hdr_bytes + pos;
-  st.max_len = max_len;
+  b->last_stage_ms = ms_since(t0);
+  return up_err ? MOBI_E_DEVICE : MOBI_OK;
+}
+// A lane's payload can never exceed 448 words per macroblock, nor 64 per macroblock + one level per THREE bits read (a level word stands for
+// a token with a level, and the shortest of those -- either table, either version -- has two bits and a sign: mobi_dparse_build_tables;
+// tests/test_parse_fallback.py checks the tables for it).  The longest frame of a hand-over varies: the bound follows it upwards in steps
+// of a quarter, so that the payload arena -- gigabytes for thousands of clips -- is not freed and allocated again every few frames.
+size_t dp_cap_words(mobi_batch *b, size_t max_len) {
+  const size_t n_mbs = (size_t)b->g.mbw * b->g.mbh;
+  if (max_len > b->dp_len_hint) b->dp_len_hint = max_len + max_len / 4;
+  return std::min<size_t>(n_mbs * 448 + MOBI_WIDE_PARAMS, n_mbs * 64 + (8 * b->dp_len_hint + 2) / 3) + 448 + 64;
+}
+// what every parse launch is told: the image, the tables the set holds, the picture.  The caller adds the decoder state and the parser in front
+void dp_parse_args(const mobi_batch *b, const StageImage &img, const DpSet &B, MobiDevParseArgs &pa) {
+  memset(&pa, 0, sizeof(pa));
+  pa.bits = B.bits.p + img.hdr_bytes;
+  pa.bit_off = (const uint64_t *)B.bits.p;
+  pa.bit_len = (const uint32_t *)(B.bits.p + img.lanes() * 8);
+  pa.tables = b->d_ptables;
+  pa.scale = b->d_scale;
+  pa.pay_local = 1;
+  pa.desc = (MbDesc *)B.desc.p;
+  pa.payload = (uint32_t *)B.pay.p;
+  pa.items = (uint32_t *)B.items.p;
+  pa.res = (MobiDevResult *)B.res.p;
+  pa.pay_cap = (uint32_t)B.cap_words;
+  pa.n_clips = (int)img.lanes(); pa.version = b->version;
+  pa.width = b->g.width; pa.height = b->g.height; pa.stride = b->g.stride; pa.lg = b->g.lg; pa.mbw = b->g.mbw; pa.mbh = b->g.mbh;
+}
+// the idle slots' empty rows, in front of the parse kernels (mobi_idle.hip).  carry_state (steps): their clips' state goes into the entry the
+// next parse reads; groups: their clips' chains end at idle_from (mobi_gop.h)
+int dp_idle_rows(mobi_batch *b, const StageImage &img, const DpSet &B, const MobiDevParseArgs &pa, bool carry_state, hipStream_t s) {
+  if (!img.n_idle) return MOBI_OK;
+  MobiIdleArgs ia;
+  memset(&ia, 0, sizeof(ia));
+  ia.clips = (const int32_t *)(B.bits.p + img.idle_off); ia.count = img.n_idle;
+  if (img.idle_from_off) ia.idle_from = B.bits.p + img.idle_from_off;
+  ia.n = img.n; ia.K = img.K; ia.n_mbs = b->g.mbw * b->g.mbh;
+  ia.desc = pa.desc; ia.res = pa.res;
+  if (carry_state) { ia.state_in = pa.state_in; ia.state_out = pa.state_out; ia.tail_in = pa.tail_in; ia.tail_out = pa.tail_out; }
+  if (mobi_launch_idle_rows(&ia, s) != 0) return MOBI_E_DEVICE;
+  b->idle_launches++;
   return MOBI_OK;
 }
-// output buffers + the parse launch.  A clip's payload can never exceed 448 words per macroblock, nor 64 per macroblock + one level
-// per THREE bits read (a level word stands for a token with a level, and the shortest of those -- either table, either version -- has two
-// bits and a sign: mobi_dparse_build_tables; tests/test_parse_fallback.py checks the tables for it).  `busy`: earlier steps may still be using the buffers (asynchronous steps): drain the stream before growing one.
-// *state_in: which entry of the state ring the step reads (the state its frames start from).
-struct DpOut { DevBuf *desc, *pay, *items; MobiDevResult *res; hipStream_t stream; bool async = false; };
-static int dp_parse(mobi_batch *b, const uint8_t *d_bits, const DpStaged &st, bool busy, const DpOut &o, int *state_in) {
-  const int n = b->n, n_mbs = b->g.mbw * b->g.mbh;
-  // (the longest frame of a step varies from step to step: the bound follows it upwards in steps of a quarter, so that the payload
-  // arena -- gigabytes for thousands of clips -- is not freed and allocated again every few frames)
-  if (st.max_len > b->dp_len_hint) b->dp_len_hint = st.max_len + st.max_len / 4;
-  const size_t cap_words = std::min<size_t>((size_t)n_mbs * 448 + MOBI_WIDE_PARAMS, (size_t)n_mbs * 64 + (8 * b->dp_len_hint + 2) / 3) + 448 + 64;
-  // MbDesc.payload_off is relative to the clip's own part of the arena, which may then be as large as HBM lets it (24576 clips of
-  // 640x480 need 13 G words for an I-frame); the host parser's clips write into their own parts like everybody else (dp_override)
-  b->pay_clip_words = (uint32_t)cap_words;
-  const size_t want_desc = align_up((size_t)n * n_mbs * sizeof(MbDesc) + 8 * sizeof(MbDesc), kAlign), want_pay = align_up((size_t)n * cap_words * 4 + kPaySlack, kAlign),
-               want_items = (size_t)n * n_mbs * 4;
-  if (busy && (want_desc > (*o.desc).cap || want_pay > (*o.pay).cap || want_items > (*o.items).cap)) HIP_TRY(hipStreamSynchronize(o.stream));
-  if (int e = (*o.desc).reserve(want_desc)) return e;
-  if (int e = (*o.pay).reserve(want_pay)) return e;
-  if (int e = (*o.items).reserve(want_items)) return e;
+// a step's staged image: planned, room made for it (dev_headroom: asynchronous steps leave room in HBM too), gathered -- and with `up` on its way
+static int dp_stage_step(mobi_batch *b, StageImage &img, DpSet &B, const uint8_t *const *data, const size_t *len, const int32_t *offsets, const std::vector<uint8_t> &idle,
+                         bool dev_state, bool dev_headroom, hipStream_t up) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const uint8_t *idle_from = idle.empty() ? nullptr : idle.data();
+  const std::vector<int32_t> none, &resets = dev_state ? b->reset_list : none; // (before dp_init there is nothing on the device to reset)
+  img.plan(b->n, 1, b->g.mbw * b->g.mbh, data, len, offsets, b->on_host.data(), idle_from, resets.size(), false);
+  if (int e = B.h_stage.grow(img.bytes)) return e;
+  if (int e = dev_headroom ? B.bits.grow(img.bytes) : B.bits.reserve(img.bytes)) return e;
+  return dp_stage(b, img, B, data, offsets, idle_from, resets.data(), 4, 32, up, true, t0);
+}
+// output tables + the parse launch of a step on stream s.  *state_in: which entry of the state ring the step reads (the state its frames start from).
+static int dp_parse(mobi_batch *b, const StageImage &img, DpSet &B, hipStream_t s, bool async, int *state_in) {
+  b->last_pay_cap = dp_cap_words(b, img.max_len);
+  b->pay_clip_words = (uint32_t)b->last_pay_cap;
+  if (int e = B.reserve_tables(b->n, b->n, b->g.mbw * b->g.mbh, b->pay_clip_words)) return e;
   MobiDevParseArgs pa;
-  memset(&pa, 0, sizeof(pa));
-  pa.bits = d_bits + st.hdr_bytes;
-  pa.bit_off = (const uint64_t *)d_bits;
-  pa.bit_len = (const uint32_t *)(d_bits + (size_t)n * 8);
-  pa.tables = b->d_ptables;
+  dp_parse_args(b, img, B, pa);
   const int in = b->ps_cur, out = (b->ps_cur + 1) % 3;
   pa.state_in = b->d_pstate[in]; pa.state_out = b->d_pstate[out];
   pa.tail_in = b->d_ptail[in]; pa.tail_out = b->d_ptail[out];
-  pa.scale = b->d_scale;
   pa.state_ls = b->d_pstate_ls;
-  pa.lockstep = b->lockstep ? (o.async ? 2 : 1) : 0; // (2: an asynchronous step; the launch has had one shape for both since r05: mobi_launch_parse_ls)
-  pa.pay_local = 1;
-  pa.desc = (MbDesc *)(*o.desc).p;
-  pa.payload = (uint32_t *)(*o.pay).p;
-  pa.items = (uint32_t *)(*o.items).p;
-  pa.res = o.res;
-  pa.pay_cap = (uint32_t)cap_words;
-  b->last_pay_cap = cap_words;
-  pa.n_clips = n; pa.version = b->version;
-  pa.width = b->g.width; pa.height = b->g.height; pa.stride = b->g.stride; pa.lg = b->g.lg; pa.mbw = b->g.mbw; pa.mbh = b->g.mbh;
-  if (b->ktiming && !b->ev_p0) { (void)hipEventCreate(&b->ev_p0.h); (void)hipEventCreate(&b->ev_p1.h); }
-  const bool ptime = b->ktiming && b->ev_p0 && b->ev_p1;
-  if (st.n_idle) { // the idle slots' empty rows, and their clips' state carried into the entry the next parse reads (in front of the parse kernels: mobi_idle.hip)
-    MobiIdleArgs ia;
-    memset(&ia, 0, sizeof(ia));
-    ia.clips = (const int32_t *)(d_bits + st.idle_off); ia.count = st.n_idle;
-    ia.n = n; ia.K = 1; ia.n_mbs = n_mbs;
-    ia.desc = pa.desc; ia.res = pa.res;
-    ia.state_in = pa.state_in; ia.state_out = pa.state_out; ia.tail_in = pa.tail_in; ia.tail_out = pa.tail_out;
-    if (mobi_launch_idle_rows(&ia, o.stream) != 0) return MOBI_E_DEVICE;
-    b->idle_launches++;
-  }
-  if (ptime) (void)hipEventRecord(b->ev_p0, o.stream);
-  if (mobi_launch_parse(&pa, o.stream) != 0) return MOBI_E_DEVICE;
-  if (ptime) (void)hipEventRecord(b->ev_p1, o.stream);
+  pa.lockstep = b->lockstep ? (async ? 2 : 1) : 0; // (2: an asynchronous step; the launch has had one shape for both since r05: mobi_launch_parse_ls)
+  if (int e = dp_idle_rows(b, img, B, pa, true, s)) return e;
+  b->ptimer.start(b->ktiming, s);
+  if (mobi_launch_parse(&pa, s) != 0) return MOBI_E_DEVICE;
+  b->ptimer.stop(b->ktiming, s);
   b->ps_cur = out;
   *state_in = in;
   return MOBI_OK;
@@ -213,10 +164,10 @@ static int dp_parse(mobi_batch *b, const uint8_t *d_bits, const DpStaged &st, bo
 
 // The command lists of host-parsed clips of a device-parsed step (`clips`, ascending; b->cur[c] holds clip c's frame when rc[c] is MOBI_OK):
 // staged in pinned memory and copied into the clips' own rows of what the parse kernels leave -- descriptor rows, payload parts, item
-// rows, result records -- on stream s.  Runs of neighbouring clips (the hybrid mode's share) go as one copy per table.
+// rows, result records of frame `frame` of the set B -- on stream s.  Runs of neighbouring clips (the hybrid mode's share) go as one copy per table.
 // frames != nullptr: frames[j] is clips[j]'s parsed frame (nullptr: it failed) and rcs[j] its rc -- both by POSITION in `clips` (the
 // frame-parallel path: a clip has K frames); else b->cur[c] and rc[c] by clip.
-int dp_override(mobi_batch *b, const std::vector<int> &clips, const int *rc, PinnedBuf &stage, const DpRows &d, hipStream_t s,
+int dp_override(mobi_batch *b, const std::vector<int> &clips, const int *rc, PinnedBuf &stage, const DpSet &B, int frame, hipStream_t s,
                 const ParsedFrame *const *frames, const int *rcs) {
   const int k = (int)clips.size(), n_mbs = b->g.mbw * b->g.mbh;
   if (k == 0) return MOBI_OK;
@@ -226,7 +177,9 @@ int dp_override(mobi_batch *b, const std::vector<int> &clips, const int *rc, Pin
   for (int j = 0; j < k; j++)
     if (const ParsedFrame *f = frame_of(j)) pitch_w = std::max(pitch_w, f->payload.size());
   pitch_w = align_up(pitch_w + 4, 4);
-  if (pitch_w > d.cap_words) return MOBI_E_DEVICE; // cannot happen: cap_words bounds any clip's payload
+  const DpSet::Rows d = B.rows(frame);
+  const size_t cap_b = B.cap_words * 4;
+  if (pitch_w > B.cap_words) return MOBI_E_DEVICE; // cannot happen: cap_words bounds any clip's payload
   const size_t desc_b = (size_t)n_mbs * sizeof(MbDesc), item_b = (size_t)n_mbs * 4, res_b = sizeof(MobiDevResult), pay_b = pitch_w * 4;
   const size_t o_item = align_up((size_t)k * desc_b, 16), o_res = o_item + align_up((size_t)k * item_b, 16), o_pay = o_res + align_up((size_t)k * res_b, 16);
   if (int e = stage.reserve(o_pay + (size_t)k * pay_b)) return e;
@@ -260,38 +213,42 @@ int dp_override(mobi_batch *b, const std::vector<int> &clips, const int *rc, Pin
     HIP_TRY(hipMemcpyAsync(d.desc + c0 * desc_b, h + (size_t)j0 * desc_b, run * desc_b, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d.items + c0 * item_b, h + o_item + (size_t)j0 * item_b, run * item_b, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync((uint8_t *)(d.res + c0), h + o_res + (size_t)j0 * res_b, run * res_b, hipMemcpyHostToDevice, s));
-    if (run == 1) HIP_TRY(hipMemcpyAsync(d.pay + c0 * d.cap_words * 4, h + o_pay + (size_t)j0 * pay_b, pay_b, hipMemcpyHostToDevice, s));
-    else HIP_TRY(hipMemcpy2DAsync(d.pay + c0 * d.cap_words * 4, d.cap_words * 4, h + o_pay + (size_t)j0 * pay_b, pay_b, pay_b, run, hipMemcpyHostToDevice, s));
+    if (run == 1) HIP_TRY(hipMemcpyAsync(d.pay + c0 * cap_b, h + o_pay + (size_t)j0 * pay_b, pay_b, hipMemcpyHostToDevice, s));
+    else HIP_TRY(hipMemcpy2DAsync(d.pay + c0 * cap_b, cap_b, h + o_pay + (size_t)j0 * pay_b, pay_b, pay_b, run, hipMemcpyHostToDevice, s));
     j0 = j1;
   }
   return MOBI_OK;
 }
-// the decoder state the clips of `cl` had when the step that read ring entry `in` started, into their host parsers: two asynchronous copies per
-// clip into pinned memory, ONE wait, the imports on the pool (r05 issued two blocking copies per clip: a step in which every clip of a large
-// batch is handed over at once -- a ModsDS batch that cuts to a quantiser below 12 -- sat in tens of thousands of them)
-// (into b->parsers, or into ps[j] for clip cl[j] when ps is given: a repair of a stream a reset has ended, mobi_batch::parser_at)
-static int dp_seed_parsers(mobi_batch *b, const std::vector<int> &cl, int in, PinnedBuf &stage, hipStream_t s, const std::vector<MobiStreamParser *> *ps = nullptr) {
-  if (cl.empty()) return MOBI_OK;
+// Decoder states the device holds into host parsers -- the state a frame STARTED from, when the host parser takes the frame over: two asynchronous
+// copies per seed into pinned memory, ONE wait, the imports on the pool (r05 issued two blocking copies per clip: a step in which every clip of a
+// large batch is handed over at once -- a ModsDS batch that cuts to a quantiser below 12 -- sat in tens of thousands of them)
+int dp_seed_parsers(mobi_batch *b, const std::vector<DpSeed> &seeds, PinnedBuf &stage, hipStream_t s) {
+  if (seeds.empty()) return MOBI_OK;
   const size_t rec = sizeof(MobiDevState) + sizeof(MobiDevTail);
-  if (int e = stage.reserve(cl.size() * rec)) return e;
-  for (size_t j = 0; j < cl.size(); j++) {
-    HIP_TRY(hipMemcpyAsync(stage.p + j * rec, b->d_pstate[in] + cl[j], sizeof(MobiDevState), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(stage.p + j * rec + sizeof(MobiDevState), b->d_ptail[in] + cl[j], sizeof(MobiDevTail), hipMemcpyDeviceToHost, s));
+  if (int e = stage.reserve(seeds.size() * rec)) return e;
+  for (size_t j = 0; j < seeds.size(); j++) {
+    HIP_TRY(hipMemcpyAsync(stage.p + j * rec, seeds[j].state, sizeof(MobiDevState), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(stage.p + j * rec + sizeof(MobiDevState), seeds[j].tail, sizeof(MobiDevTail), hipMemcpyDeviceToHost, s));
   }
   HIP_TRY(hipStreamSynchronize(s));
-  b->pool->run((int)cl.size(), [&](int j) {
-    MobiStreamParser *p = ps ? (*ps)[j] : b->parsers[cl[j]].get();
-    p->import_state(*(const MobiDevState *)(stage.p + (size_t)j * rec), *(const MobiDevTail *)(stage.p + (size_t)j * rec + sizeof(MobiDevState)));
+  b->pool->run((int)seeds.size(), [&](int j) {
+    seeds[j].parser->import_state(*(const MobiDevState *)(stage.p + (size_t)j * rec), *(const MobiDevTail *)(stage.p + (size_t)j * rec + sizeof(MobiDevState)));
   });
   return MOBI_OK;
+}
+// (a step's: the clips `cl` from entry `in` of the state ring, into `parser(c)`)
+template <class F> static int dp_seed_step(mobi_batch *b, const std::vector<int> &cl, int in, PinnedBuf &stage, F parser) {
+  std::vector<DpSeed> seeds;
+  for (int c : cl) seeds.push_back({b->d_pstate[in] + c, b->d_ptail[in] + c, parser(c)});
+  return dp_seed_parsers(b, seeds, stage, b->stream);
 }
 
 // A clip the host parser took over goes BACK to the device parsers once its frames are again the kind they finish: `clean_need`
 // consecutive frames without a walk, a token without a level or a value beyond the device parsers' fields (MobiStreamParser::device_ready),
 // doubled with every hand-over (4, 8, ... 256: a clip whose every frame needs the host parser -- a ModsDS stream below quantiser 12 -- costs
 // a wasted device parse every few hundred frames, a glitch in an otherwise clean stream a handful of host-parsed frames).  The parser's state
-// goes into entry `entry` of the state ring -- the one the next step's parse reads -- on stream s, through `stage`.
-static int dp_return(mobi_batch *b, const std::vector<int> &host_clips, const int *rc, int entry, PinnedBuf &stage, hipStream_t s) {
+// goes into entry `entry` of the state ring -- the one the next step's parse reads -- on stream s, through B.h_ret.
+static int dp_return(mobi_batch *b, const std::vector<int> &host_clips, const int *rc, int entry, DpSet &B, hipStream_t s) {
   std::vector<int> back;
   for (int c : host_clips) {
     if (b->host_share[c]) continue;
@@ -299,10 +256,11 @@ static int dp_return(mobi_batch *b, const std::vector<int> &host_clips, const in
     else b->clean_run[c] = 0;
     if (b->clean_run[c] >= b->clean_need[c]) back.push_back(c);
   }
-  return dp_return_list(b, back, entry, stage, s);
+  return dp_return_list(b, back, entry, B, s);
 }
-int dp_return_list(mobi_batch *b, const std::vector<int> &back, int entry, PinnedBuf &stage, hipStream_t s) {
+int dp_return_list(mobi_batch *b, const std::vector<int> &back, int entry, DpSet &B, hipStream_t s) {
   if (back.empty()) return MOBI_OK;
+  PinnedBuf &stage = B.h_ret;
   const size_t rec = sizeof(MobiDevState) + sizeof(MobiDevTail);
   if (int e = stage.reserve(back.size() * rec)) return e;
   for (size_t k = 0; k < back.size(); k++) {
@@ -334,57 +292,54 @@ int decode_device_parse(mobi_batch *b, const uint8_t *const *data, const size_t 
   b->mark_hybrid_share();
   const uint64_t serial = b->handover + 1;
   reset_apply_host(b, serial);
-  const std::vector<int32_t> *resets = dev_state && !b->reset_list.empty() ? &b->reset_list : nullptr;
   std::vector<int> host_clips;
   for (int i = 0; i < n; i++)
     if (b->on_host[i] && !is_idle(i)) host_clips.push_back(i);
-  DpStaged st;
-  using clk = std::chrono::steady_clock;
-  const auto q0 = clk::now();
-  if (int e = dp_stage(b, data, len, offsets, b->h_stage, st, &b->d_bits, false, b->stream, resets, idle.empty() ? nullptr : &idle)) return e; // gathered and on their way
+  DpSet &B = b->dp;
+  StageImage st;
+  const auto q0 = std::chrono::steady_clock::now();
+  if (int e = dp_stage_step(b, st, B, data, len, offsets, idle, dev_state, false, b->stream)) return e; // gathered and on their way
   b->phase_ms[0] = ms_since(q0);
   b->lockstep = ls_decide(b, st);
-  if (st.n_reset && mobi_launch_reset_state((const int32_t *)(b->d_bits.p + st.reset_off), st.n_reset, n, b->d_pstate[b->ps_cur], b->d_ptail[b->ps_cur], b->stream) != 0)
+  if (st.n_reset && mobi_launch_reset_state((const int32_t *)(B.bits.p + st.reset_off), st.n_reset, n, b->d_pstate[b->ps_cur], b->d_ptail[b->ps_cur], b->stream) != 0)
     return MOBI_E_DEVICE;
   int state_in = 0;
-  if (int e = dp_parse(b, b->d_bits.p, st, false, DpOut{&b->d_pdesc, &b->d_ppay, &b->d_pitems, b->d_pres, b->stream}, &state_in)) return e;
+  if (int e = dp_parse(b, st, B, b->stream, false, &state_in)) return e;
   idle_commit(b, 1, idle);
   reset_commit(b, serial);
   b->phase_ms[1] = ms_since(q0);
-  const size_t cap_words = b->last_pay_cap;
-  const DpRows rows{b->d_pdesc.p, b->d_ppay.p, b->d_pitems.p, b->d_pres, cap_words};
-  const bool ptime = b->ktiming && b->ev_p0 && b->ev_p1;
-  MobiDevResult *res = (MobiDevResult *)b->h_pres.p;
-  HIP_TRY(hipMemcpyAsync(res, b->d_pres, sizeof(MobiDevResult) * n, hipMemcpyDeviceToHost, b->stream));
+  const MobiDevResult *res = B.results(), *d_res = (const MobiDevResult *)B.res.p;
+  HIP_TRY(hipMemcpyAsync(B.h_res.p, d_res, sizeof(MobiDevResult) * n, hipMemcpyDeviceToHost, b->stream));
   auto host_parse = [&](const std::vector<int> &cl) {
     b->pool->run((int)cl.size(), [&](int j) { const int i = cl[j]; rc[i] = parse_host(b->parsers[i].get(), data[i], len[i], &offsets[i], b->cur[i]); });
   };
   if (!host_clips.empty()) { // while the GPU parses its clips, the host pool parses its own and sends their command lists up beside it
     if (int e = ensure_stream(b->stream2)) return e;
-    if (int e = ensure_event(b->ev_up)) return e;
+    if (int e = ensure_event(B.ev_up)) return e;
     host_parse(host_clips);
-    if (int e = dp_override(b, host_clips, rc, b->h_stage2, rows, b->stream2)) return e; // (no kernel touches these clips' rows: MOBI_DP_SKIP)
-    HIP_TRY(hipEventRecord(b->ev_up, b->stream2));
-    HIP_TRY(hipStreamWaitEvent(b->stream, b->ev_up, 0));
+    if (int e = dp_override(b, host_clips, rc, B.h_over, B, 0, b->stream2)) return e; // (no kernel touches these clips' rows: MOBI_DP_SKIP)
+    HIP_TRY(hipEventRecord(B.ev_up, b->stream2));
+    HIP_TRY(hipStreamWaitEvent(b->stream, B.ev_up, 0));
     HIP_TRY(hipStreamSynchronize(b->stream2));
   }
   HIP_TRY(hipStreamSynchronize(b->stream)); // the launch sizes below depend on what the parse found
   b->phase_ms[2] = ms_since(q0);
-  if (ptime) { float ms = 0; if (hipEventElapsedTime(&ms, b->ev_p0, b->ev_p1) == hipSuccess) b->last_parse_ms = ms; }
+  b->ptimer.read(b->ktiming, b->last_parse_ms);
   // frames the device parsers could not finish: the host parser takes them over from the state they started with
   std::vector<int> fb;
   for (int i = 0; i < n; i++)
     if (!b->on_host[i] && !is_idle(i) && res[i].rc != MOBI_OK) fb.push_back(i);
   if (!fb.empty()) {
-    if (int e = dp_seed_parsers(b, fb, state_in, b->h_ret, b->stream)) return e; // (the stream is idle: it was waited for above)
+    if (int e = dp_seed_step(b, fb, state_in, B.h_ret, [&](int c) { return b->parsers[c].get(); })) return e; // (the stream is idle: it was waited for above)
     host_parse(fb);
     for (int c : fb) {
       b->route_to_host(c);
       host_clips.push_back(c);
     }
     b->fallbacks += fb.size();
-    if (int e = dp_override(b, fb, rc, b->h_stage2, rows, b->stream)) return e; // (behind the parse kernels, which blanked these clips' rows)
+    if (int e = dp_override(b, fb, rc, B.h_over, B, 0, b->stream)) return e; // (behind the parse kernels, which blanked these clips' rows)
   }
+  // (dp_report's loop over the caller's own arrays: rc[] and offsets[] already hold the host parser's results, where dp_report wants a copy of them)
   uint32_t K = 0;
   b->ls_finished = b->lockstep ? 0 : -1;
   for (int i = 0; i < n; i++) {
@@ -405,15 +360,15 @@ int decode_device_parse(mobi_batch *b, const uint8_t *const *data, const size_t 
   // 3. reconstruction straight from what the parse left in HBM
   FailAll fail_all{rc, n, b->stream}; // rc[], Offset, the ring and the decoder state have advanced: the launches below must complete
   if (int e = b->begin_step()) return e;
-  MobiReconArgs a = b->args(b->d_pdesc.p, b->d_ppay.p);
+  MobiReconArgs a = b->args(B.desc.p, B.pay.p);
   a.pay_clip_words = b->pay_clip_words;
   a.done = b->d_done;
   if (mobi_launch_inter(&a, b->stream) != 0) return MOBI_E_DEVICE;
-  if (K && mobi_launch_intra_cl(&a, (const uint32_t *)b->d_pitems.p, &b->d_pres[0].n_intra, (int)(sizeof(MobiDevResult) / 4), (int)K, 0, b->stream) != 0)
+  if (K && mobi_launch_intra_cl(&a, (const uint32_t *)B.items.p, &d_res[0].n_intra, (int)(sizeof(MobiDevResult) / 4), (int)K, 0, b->stream) != 0)
     return MOBI_E_DEVICE;
   if (int e = b->read_faults(b->h_fault.data())) return e;
   if (!host_clips.empty())
-    if (int e = dp_return(b, host_clips, rc, b->ps_cur, b->h_ret, b->stream)) return e; // (ps_cur: what the next step's parse reads)
+    if (int e = dp_return(b, host_clips, rc, b->ps_cur, B, b->stream)) return e; // (ps_cur: what the next step's parse reads)
   b->phase_ms[3] = ms_since(q0);
   HIP_TRY(hipStreamSynchronize(b->stream));
   b->phase_ms[4] = ms_since(q0);
@@ -503,50 +458,42 @@ int mobi_batch_submit(mobi_batch *b, const uint8_t *const *data, const size_t *l
   b->mark_hybrid_share();
   const uint64_t serial = b->handover + 1;
   reset_apply_host(b, serial); // (before the staging: the routing decides which clips the device parses)
-  const std::vector<int32_t> *resets = dev_state && !b->reset_list.empty() ? &b->reset_list : nullptr;
   mobi_batch::AsyncSlot &S = b->aslot[(b->async_head + b->async_count) & 1];
-  for (Event *ev : {&S.ev_up, &S.ev_done, &S.ev_parsed})
+  DpSet &B = S.B;
+  HostShare &H = S.H;
+  StageImage &st = S.img;
+  for (Event *ev : {&B.ev_up, &S.ev_done, &B.ev_parsed})
     if (int e = ensure_event(*ev)) return e;
   if (int e = ensure_stream(b->stream2)) return e;
   if (int e = ensure_stream(b->stream_p)) return e;
-  DpStaged st;
-  if (int e = dp_stage(b, data, len, offsets, S.h_stage, st, nullptr, false, nullptr, resets, idle.empty() ? nullptr : &idle)) return e; // (this slot's previous step was waited for: its upload is done)
-  if (int e = S.d_pres.reserve(sizeof(MobiDevResult) * n)) return e;
-  if (st.bytes > S.d_bits.cap) // growing frees and allocates (a device-wide stall): leave room for the longer frames to come
-    if (int e = S.d_bits.reserve(st.bytes + st.bytes / 4)) return e;
-  if (int e = S.h_pres.reserve(sizeof(MobiDevResult) * n)) return e;
-  if (int e = S.h_fault.reserve(sizeof(int) * n)) return e;
-  S.offs.assign(offsets, offsets + n);
-  S.n_dev = n;
+  if (int e = dp_stage_step(b, st, B, data, len, offsets, idle, dev_state, true, nullptr)) return e; // (this slot's previous step was waited for: its upload is done)
+  if (int e = B.reserve_results(n)) return e;
+  if (int e = B.h_fault.reserve(sizeof(int) * n)) return e;
   S.serial = serial;
-  b->lockstep = S.lockstep = ls_decide(b, st);
-  S.hdr_bytes = st.hdr_bytes;
-  S.is_host.assign(n, 0);
-  S.host_rc.assign(n, MOBI_OK);
-  S.host_off.assign(n, 0);
-  S.host_quant.assign(n, 0);
-  S.host_yuv.assign(n, 0);
-  S.idle.clear();
-  if (!idle.empty()) { S.idle.resize(n); for (int i = 0; i < n; i++) S.idle[i] = idle[i] == 0; }
+  b->lockstep = H.lockstep = ls_decide(b, st);
+  H.K = 1;
+  H.offs.assign(offsets, offsets + n);
+  H.idle_from = idle;
+  H.clear(n);
   // the host parser's clips: parsed now (the caller's bytes are only good during this call), their command lists staged for the copy below
   std::vector<int> host_clips;
   for (int i = 0; i < n; i++)
     if (b->on_host[i] && !S.is_idle(i)) host_clips.push_back(i);
   if (!host_clips.empty()) {
-    for (int i : host_clips) { S.is_host[i] = 1; S.host_off[i] = offsets[i]; }
+    for (int i : host_clips) { H.host_from[i] = 0; H.off[i] = offsets[i]; }
     b->pool->run((int)host_clips.size(), [&](int j) {
       const int i = host_clips[j];
-      S.host_rc[i] = parse_host(b->parsers[i].get(), data[i], len[i], &S.host_off[i], b->cur[i]);
-      S.host_quant[i] = b->parsers[i]->quantizer();
-      S.host_yuv[i] = b->parsers[i]->yuv_format();
+      H.rc[i] = parse_host(b->parsers[i].get(), data[i], len[i], &H.off[i], b->cur[i]);
+      H.quant[i] = b->parsers[i]->quantizer();
+      H.yuv[i] = b->parsers[i]->yuv_format();
     });
   }
   // Everything that can fail without touching the device is behind us.  From the first enqueue on, a failure leaves work in flight
   // that reads this slot's pinned memory and (later) a ring that has turned without a step to wait for: the batch is drained and
   // POISONED -- every later call reports MOBI_E_DEVICE -- rather than left in a state where the next submit reuses the slot.
   Poison poison{b};
-  HIP_TRY(hipMemcpyAsync(S.d_bits.p, S.h_stage.p, st.bytes, hipMemcpyHostToDevice, b->stream2)); // beside whatever the step before is doing
-  HIP_TRY(hipEventRecord(S.ev_up, b->stream2));
+  HIP_TRY(hipMemcpyAsync(B.bits.p, B.h_stage.p, st.bytes, hipMemcpyHostToDevice, b->stream2)); // beside whatever the step before is doing
+  HIP_TRY(hipEventRecord(B.ev_up, b->stream2));
   // Three streams: the upload (stream2), the parse (stream_p: after the upload; the decoder state goes from parse to parse in its order)
   // and the reconstruction (stream: after this step's parse; the ring goes from step to step in its order).  The parse of this step
   // runs under the reconstruction of the one before -- the lock-step parser leaves most of the chip idle -- because what it writes
@@ -554,35 +501,35 @@ int mobi_batch_submit(mobi_batch *b, const uint8_t *const *data, const size_t *l
   // (Only the lock-step parser gets the stream of its own: the one-wave-per-clip parser fills every wave slot of the chip with 122-register
   // waves, and a reconstruction launched beside it waits for them to leave anyway -- 20.5 instead of 13.2 ms per step of 4096 clips.)
   hipStream_t ps = b->lockstep ? b->stream_p : b->stream;
-  HIP_TRY(hipStreamWaitEvent(ps, S.ev_up, 0));
+  HIP_TRY(hipStreamWaitEvent(ps, B.ev_up, 0));
   { // the parser in front is chosen step by step (ls_decide), and with it the stream: the state this parse reads is the one the step before wrote
     mobi_batch::AsyncSlot &prev = b->aslot[(b->async_head + b->async_count + 1) & 1];
-    if (b->async_seq > 0 && prev.ev_parsed && prev.parsed_recorded) HIP_TRY(hipStreamWaitEvent(ps, prev.ev_parsed, 0));
+    if (b->async_seq > 0 && prev.B.ev_parsed && prev.parsed_recorded) HIP_TRY(hipStreamWaitEvent(ps, prev.B.ev_parsed, 0));
   }
-  MobiDevResult *d_res = (MobiDevResult *)S.d_pres.p;
+  const MobiDevResult *d_res = (const MobiDevResult *)B.res.p;
   // clips reset from this step on: a new decoder's state into the entry the parse reads, behind whatever the step before wrote there
-  if (st.n_reset && mobi_launch_reset_state((const int32_t *)(S.d_bits.p + st.reset_off), st.n_reset, n, b->d_pstate[b->ps_cur], b->d_ptail[b->ps_cur], ps) != 0)
+  if (st.n_reset && mobi_launch_reset_state((const int32_t *)(B.bits.p + st.reset_off), st.n_reset, n, b->d_pstate[b->ps_cur], b->d_ptail[b->ps_cur], ps) != 0)
     return MOBI_E_DEVICE;
-  if (int e = dp_parse(b, S.d_bits.p, st, false, DpOut{&S.d_pdesc, &S.d_ppay, &S.d_pitems, d_res, ps, true}, &S.state_in)) return e;
+  if (int e = dp_parse(b, st, B, ps, true, &S.state_in)) return e;
   if (!host_clips.empty()) {
-    if (int e = dp_override(b, host_clips, S.host_rc.data(), S.h_over, DpRows{S.d_pdesc.p, S.d_ppay.p, S.d_pitems.p, d_res, b->last_pay_cap}, ps)) return e;
-    if (int e = dp_return(b, host_clips, S.host_rc.data(), b->ps_cur, S.h_ret, ps)) return e; // (the parse kernels skip these clips: their entries are free to write)
+    if (int e = dp_override(b, host_clips, H.rc.data(), B.h_over, B, 0, ps)) return e;
+    if (int e = dp_return(b, host_clips, H.rc.data(), b->ps_cur, B, ps)) return e; // (the parse kernels skip these clips: their entries are free to write)
   }
-  HIP_TRY(hipMemcpyAsync(S.h_pres.p, d_res, sizeof(MobiDevResult) * n, hipMemcpyDeviceToHost, ps));
-  HIP_TRY(hipEventRecord(S.ev_parsed, ps));
+  HIP_TRY(hipMemcpyAsync(B.h_res.p, d_res, sizeof(MobiDevResult) * n, hipMemcpyDeviceToHost, ps));
+  HIP_TRY(hipEventRecord(B.ev_parsed, ps));
   S.parsed_recorded = true;
-  if (ps != b->stream) HIP_TRY(hipStreamWaitEvent(b->stream, S.ev_parsed, 0));
+  if (ps != b->stream) HIP_TRY(hipStreamWaitEvent(b->stream, B.ev_parsed, 0));
   // reconstruction straight from what the parse leaves in HBM (failed clips: blank descriptors, no items)
   if (int e = b->begin_step()) return e;
   S.ring_base = b->ring_base;
-  MobiReconArgs a = b->args(S.d_pdesc.p, S.d_ppay.p);
+  MobiReconArgs a = b->args(B.desc.p, B.pay.p);
   a.pay_clip_words = b->pay_clip_words;
   a.done = b->d_done;
   if (mobi_launch_inter(&a, b->stream) != 0) return MOBI_E_DEVICE;
   // the parse has not run yet, so nobody knows how many intra macroblocks the longest list will have: MOBI_ASYNC_INTRA_SLOTS slots are launched
   // (a P-frame's lists are shorter), and a second launch (mobi_recon_intra_walk, one workgroup per four clips) goes through the rest of theirs (an I-frame: every macroblock)
-  if (mobi_launch_intra_cl(&a, (const uint32_t *)S.d_pitems.p, &d_res[0].n_intra, (int)(sizeof(MobiDevResult) / 4), std::min(n_mbs, MOBI_ASYNC_INTRA_SLOTS), 1, b->stream) != 0) return MOBI_E_DEVICE;
-  if (int e = b->read_faults((int *)S.h_fault.p)) return e;
+  if (mobi_launch_intra_cl(&a, (const uint32_t *)B.items.p, &d_res[0].n_intra, (int)(sizeof(MobiDevResult) / 4), std::min(n_mbs, MOBI_ASYNC_INTRA_SLOTS), 1, b->stream) != 0) return MOBI_E_DEVICE;
+  if (int e = b->read_faults(B.faults())) return e;
   HIP_TRY(hipEventRecord(S.ev_done, b->stream));
   poison.armed = false;
   idle_commit(b, 1, idle);
@@ -600,7 +547,7 @@ static int async_repair(mobi_batch *b, mobi_batch::AsyncSlot &S, const std::vect
   if (b->stream_p) HIP_TRY(hipStreamSynchronize(b->stream_p));
   HIP_TRY(hipStreamSynchronize(b->stream));
   mobi_batch::AsyncSlot *S1 = b->async_count == 2 ? &b->aslot[(b->async_head + 1) & 1] : nullptr;
-  const int n = b->n, k = (int)failed.size(), nT = S1 ? 2 : 1;
+  const int k = (int)failed.size(), nT = S1 ? 2 : 1;
   mobi_batch::AsyncSlot *const T[2] = {&S, S1};
   // A clip reset between the two steps (mobi_batch_reset_clips) has its new stream's first frame in S1, parsed from a new decoder's state: the
   // repair stays in S, with the parser of the stream S belongs to (mobi_batch::parser_at), and leaves the clip's current state alone.
@@ -613,20 +560,20 @@ static int async_repair(mobi_batch *b, mobi_batch::AsyncSlot &S, const std::vect
   // r06: a batch operation.  The start states in one go, the parses on the pool (a clip's two frames in order), then per affected step ONE
   // reconstruction of the failed clips (recon_clips) -- r05 did all of it clip by clip on the calling thread: a GOP damaged in every clip of a
   // batch, or a ModsDS batch that cuts to a quantiser below 12 in one frame, stalled mobi_batch_wait for ~1.5 ms x 2 x clips.
-  if (int e = dp_seed_parsers(b, failed, S.state_in, S.h_ret, b->stream, &parser)) return e;
+  if (int e = dp_seed_step(b, failed, S.state_in, S.B.h_ret, [&](int c) { return b->parser_at(S.serial, c); })) return e;
   if (b->gop_frames.size() < (size_t)k * 2) b->gop_frames.resize((size_t)k * 2);
   std::vector<int> prc((size_t)k * 2, MOBI_OK);
   b->pool->run(k, [&](int j) {
     const int c = failed[j];
     for (int t = 0; t < (cascade[j] ? 2 : 1); t++) {
-      const uint64_t boff = ((const uint64_t *)T[t]->h_stage.p)[c];
-      const uint32_t blen = ((const uint32_t *)(T[t]->h_stage.p + (size_t)n * 8))[c];
+      const StageImage &img = T[t]->img;
+      HostShare &H = T[t]->H;
       int32_t off = 0;
-      prc[(size_t)j * 2 + t] = parser[j]->parse_frame(T[t]->h_stage.p + T[t]->hdr_bytes + boff, blen, &off, b->gop_frames[(size_t)j * 2 + t]);
-      T[t]->is_host[c] = 1;
-      T[t]->host_off[c] = T[t]->offs[c] + off;
-      T[t]->host_quant[c] = parser[j]->quantizer();
-      T[t]->host_yuv[c] = parser[j]->yuv_format();
+      prc[(size_t)j * 2 + t] = parser[j]->parse_frame(T[t]->B.h_stage.p + img.hdr_bytes + img.boff[c], img.lens[c], &off, b->gop_frames[(size_t)j * 2 + t]);
+      H.host_from[c] = 0;
+      H.off[c] = H.offs[c] + off;
+      H.quant[c] = parser[j]->quantizer();
+      H.yuv[c] = parser[j]->yuv_format();
     }
   });
   for (int t = 0; t < nT; t++) {
@@ -642,8 +589,8 @@ static int async_repair(mobi_batch *b, mobi_batch::AsyncSlot &S, const std::vect
     std::vector<int> fault(cl.size());
     if (int e = recon_clips(b, cl, fr.data(), T[t]->ring_base, fault.data())) return e;
     for (size_t i = 0; i < cl.size(); i++) {
-      T[t]->host_rc[cl[i]] = fault_rc(prc[(size_t)js[i] * 2 + t], fault[i]);
-      ((int *)T[t]->h_fault.p)[cl[i]] = 0;
+      T[t]->H.rc[cl[i]] = fault_rc(prc[(size_t)js[i] * 2 + t], fault[i]);
+      T[t]->B.faults()[cl[i]] = 0;
     }
   }
   for (int c : failed) {
@@ -660,35 +607,40 @@ int mobi_batch_wait(mobi_batch *b, int32_t *offsets_out, int *rc) {
   if (b->async_count == 0) return MOBI_E_ARG;
   mobi_batch::AsyncSlot &S = b->aslot[b->async_head & 1];
   HIP_TRY(hipEventSynchronize(S.ev_done));
-  const MobiDevResult *res = (const MobiDevResult *)S.h_pres.p;
-  const int *fault = (const int *)S.h_fault.p;
+  const MobiDevResult *res = S.B.results();
   std::vector<int> failed;
-  for (int i = 0; i < S.n_dev; i++)
-    if (!S.is_host[i] && !S.is_idle(i) && res[i].rc != MOBI_OK) failed.push_back(i);
+  for (int i = 0; i < b->n; i++)
+    if (S.H.host_from[i] && !S.is_idle(i) && res[i].rc != MOBI_OK) failed.push_back(i);
   if (!failed.empty())
     if (int e = async_repair(b, S, failed)) { b->poisoned = true; return e; }
-  b->ls_finished = S.lockstep ? 0 : -1; // (of the step being reported, not of the one submitted last: ADVICE r05)
-  for (int i = 0; i < S.n_dev; i++) {
-    if (S.is_idle(i)) { // (Offset as handed in; Quantizer / YuvFormat stay the last live frame's)
-      rc[i] = MOBI_IDLE;
-      if (offsets_out) offsets_out[i] = S.offs[i];
-      continue;
-    }
-    if (S.is_host[i]) {
-      rc[i] = S.host_rc[i];
-      if (offsets_out) offsets_out[i] = S.host_off[i];
-      b->dev_quant[i] = S.host_quant[i];
-      b->dev_yuvfmt[i] = S.host_yuv[i];
-    } else {
-      if (S.lockstep && res[i].pad == MOBI_LS_MAGIC) b->ls_finished++;
-      rc[i] = res[i].rc;
-      if (offsets_out) offsets_out[i] = S.offs[i] + (int32_t)res[i].consumed;
-      b->dev_quant[i] = res[i].quant;
-      b->dev_yuvfmt[i] = res[i].yuvfmt;
-    }
-    rc[i] = fault_rc(rc[i], fault[i]);
-  }
+  dp_report(b, S.H, S.B, 0, 1, offsets_out, rc); // (ls_finished: of the step being reported, not of the one submitted last: ADVICE r05)
   b->async_head ^= 1;
   b->async_count--;
   return MOBI_OK;
+}
+// What frames k0 .. k1 - 1 of a hand-over came to, in rc / offsets_out [(k - k0) * n + c]: rc and Offset, the host parser's where the frame was
+// its, and Quantizer / YuvFormat behind each clip's last LIVE frame among them.  An idle slot: MOBI_IDLE, Offset as handed in, Quantizer /
+// YuvFormat stay the last live frame's.
+void dp_report(mobi_batch *b, const HostShare &H, const DpSet &B, int k0, int k1, int32_t *offsets_out, int *rc) {
+  const int n = b->n;
+  const MobiDevResult *res = B.results();
+  const int *fault = B.faults();
+  if (k0 == 0) b->ls_finished = H.lockstep ? 0 : -1;
+  for (int k = k0; k < k1; k++)
+    for (int c = 0; c < n; c++) {
+      const size_t v = (size_t)k * n + c, o = (size_t)(k - k0) * n + c;
+      if (k >= H.live_end(c)) {
+        rc[o] = MOBI_IDLE;
+        if (offsets_out) offsets_out[o] = H.offs[v];
+        continue;
+      }
+      const bool host = k >= H.host_from[c];
+      if (!host && H.lockstep && res[v].pad == MOBI_LS_MAGIC) b->ls_finished++;
+      rc[o] = fault_rc(host ? H.rc[v] : res[v].rc, fault[v]);
+      if (offsets_out) offsets_out[o] = host ? H.off[v] : H.offs[v] + (int32_t)res[v].consumed;
+      if (k == std::min(k1, H.live_end(c)) - 1) {
+        b->dev_quant[c] = host ? H.quant[v] : res[v].quant;
+        b->dev_yuvfmt[c] = host ? H.yuv[v] : res[v].yuvfmt;
+      }
+    }
 }

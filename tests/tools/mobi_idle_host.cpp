@@ -66,7 +66,7 @@ int mobi_idle_chain_run(uint32_t w, uint32_t h, int version, const uint8_t *data
   for (size_t v = 0; v < nv; v++) {
     const int k = (int)(v / n), c = (int)(v % n);
     boff[v] = bits.size();
-    if (idle_from && k >= idle_from[c]) { blen[v] = MOBI_DP_SKIP; bits.resize(bits.size() + 32, 0); continue; }
+    if (idle_from && k >= idle_from[c]) { blen[v] = MOBI_DP_SKIP; continue; } // (an idle lane has no bytes: csrc/mobi_handover.h)
     const uint32_t l = frame_off[pre + k + 1] - frame_off[pre + k];
     blen[v] = l;
     bits.insert(bits.end(), data + frame_off[pre + k], data + frame_off[pre + k] + l);
