@@ -368,8 +368,13 @@ __device__ __forceinline__ void idct_pass2_pk(const uint32_t *t, bool is8, int r
 //   C. residual on packed int16, the same row of TWO coded areas per lane, sixteen areas per round (r04); 32-bit rounds behind a guard.
 //   D. the octet's tiles are contiguous: whole-line stores.
 // The integer VALU is not one machine (tools/ubench/oprate.hip: two-operand adds / shifts / logic ops issue in ~2.7 cycles per wave,
-// everything with three operands, byte selects, compares, SDWA, DPP and 16-bit packed forms in ~4.3), and the kernel is bound by its
-// vector instruction count: tools/exp_stages.sh counts it stage by stage (MOBI_STOP).
+// everything with three operands, byte selects, compares, SDWA, DPP and 16-bit packed forms in ~4.3).  What bounds the kernel, as measured
+// (profiles/octet_serial_path.txt): the vector pipe is busy about 85 % of the time (0.85 vector instructions per CU clock, four waves
+// per SIMD), and a stage's share of a wave's life is its share of the vector count (residual: 39 % of the life, 42 % of the vector
+// instructions) -- except for the two waits on memory, for the wave's own descriptors and for its windows, 18 % of a life between them.
+// So a vector instruction that no longer runs still buys the most (tools/exp_stages.sh counts them stage by stage, MOBI_STOP); scalar
+// instructions, branches and waits taken out of the wave's serial path buy little (stage 9 in batches: two LDS round trips per batch
+// instead of two per word, -0.8 %); a vector instruction ADDED to save scalar ones loses; and what shortens a wait on memory pays its share.
 namespace {
 // LDS of one octet (10 KB: sixteen waves per CU).  While the windows are in flight / being interpolated:
 //   P_L   luma windows: chunk (row pair p = 0..9, quadrant column s = 0..3) of macroblock g at p * 512 + s * 128 + g * 16; a chunk =
@@ -400,6 +405,7 @@ enum {
 #ifndef MOBI_PK_PAIRS
 #define MOBI_PK_PAIRS 12
 #endif
+  P_TOUCH = 1024, // workgroups between a wave and the one whose descriptors it touches (stage A)
   P_PAIRS = MOBI_PK_PAIRS, // packed round: the level words are scattered ONCE for up to 24 coded areas (an octet has 14 on average in the generator's
                   // mix, more than 16 in one out of five: r04 scattered twice for those); the transforms take the pair tiles eight at a time
   P_ROUND = 22,   // 32-bit rounds (the fall-back when some area's coefficients are too large for 16-bit butterflies): three half rounds of eight
@@ -411,6 +417,7 @@ enum {
                   // 4 * position) or 0x13C (4x4 blocks: 256 + 4 * (position & 15)), see the scatter.  48 words behind the last coefficient tile.
 };
 static_assert(P_OUT + 7 * P_PITCH + 384 <= P_COEF && P_COEF + P_ROUND * P_TILE * 4 <= P_INV && P_INV + 192 <= P_SC && P_SC + 320 <= P_TAB && P_TAB + 192 <= P_BYTES && P_SUM + 192 <= P_INV, "inter LDS map");
+static_assert(P_INV + 4 * 63 < P_BYTES && P_SC + 0x1FC < P_BYTES, "what a lane without a word may read in a batch of the scatter");
 static_assert(23 * P_TILE * 4 + 2 < (1 << 13) && (P_PITCH & 15) == 0, "P_INV's offset field (48 slots); 16-byte reads of the output rows");
 __device__ __forceinline__ int out_px(int g, int R, int c) { return P_OUT + (R & 7) * P_PITCH + (R >> 3) * 128 + (g << 4) + c; }
 __device__ __forceinline__ int out_y(int g, int R, int c) { return out_px(g, R, c); }
@@ -465,6 +472,24 @@ __device__ __forceinline__ void recon_inter_oct(const MobiReconArgs &A, uint8_t 
   // ---- stage A: descriptor, then every global read of the octet ----
   const uint4 *dp = (const uint4 *)(A.desc + (clip * (uint32_t)A.n_mbs + mby * mbw + mbx0) + g); // the table has slack past the last octet
   const uint4 d = dp[0], d2 = dp[1];
+  // One load nobody looks at, beside the wave's own: the two lines of the descriptors that the octet P_TOUCH workgroups later on this XCD
+  // will ask for (octets are numbered along an XCD: workgroup + 8 = octet + 1; 8 macroblocks per octet where the width is a multiple of
+  // 128, near enough elsewhere).  A wave waits a tenth of its life for its own descriptors (MOBI_DEBUG=9); with the lines already in this
+  // XCD's L2 the launch is 0.5 - 1.0 % shorter at 512, 1024 and 2048 workgroups alike (profiles/octet_serial_path.txt).  r02 had measured
+  // the same idea as a loss: as a DMA of two lines into LDS, in a kernel that was bound by its requests.  The address is a scalar base and
+  // the lane's four bytes of the 256 (one vector instruction: computed per lane it cost nine).  Not in the one-launch step (FUSED: small
+  // batches, whose table ends within P_TOUCH workgroups; not measured there).  The wait for the windows below waits for these lines too
+  // (fetch wait 1221 -> 1407 clocks in the cycle records): as the LAST request with a wait for all but one it would not; written, not
+  // yet run on a GPU (HISTORY.md).
+  uint32_t touch = 0;
+  if (!FUSED) {
+    const uint32_t own = clip * (uint32_t)A.n_mbs + mby * mbw + mbx0, total = (uint32_t)A.n_clips * (uint32_t)A.n_mbs; // (wave-uniform)
+    uint32_t room = max(total, 8u); // (the table's slack covers an octet's eight from any macroblock)
+    asm volatile("" : "+s"(room)); // (kept on the scalar unit: as total > 8 ? total - 8 : 0 it became a saturating subtraction, which only the vector unit has, and took the address with it)
+    const uint32_t later = min(own + (uint32_t)P_TOUCH, room - 8u);
+    const uint8_t *tb = (const uint8_t *)A.desc + (size_t)later * sizeof(MbDesc);
+    touch = *(const uint32_t *)(tb + (uint32_t)lane * 4u);
+  }
   if (PROF) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); pb = prof_stamp(); }
   const bool valid = g < nmb && (d.y & 1) == MOBI_MB_INTER;
   const int nl = (d.y >> 1) & 0x7F, kind2 = (d.y >> 26) & 3;
@@ -643,6 +668,7 @@ __device__ __forceinline__ void recon_inter_oct(const MobiReconArgs &A, uint8_t 
   if (PROF) pt[1] = prof_stamp();
   MOBI_STOP(2);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (!FUSED) asm volatile("" : : "v"(touch)); // (the load has come back with everything else; nobody looks at it)
   wave_sync();
   if (PROF) pt[2] = prof_stamp();
 
@@ -867,10 +893,10 @@ __device__ __forceinline__ void recon_inter_oct(const MobiReconArgs &A, uint8_t 
     const int r = lane & 7, grp = lane >> 3;
     // one pass over the macroblock's level words: PK = into the int16 pair tiles of slots [base, base + 16) (and, in the first round, the
     // per-area sums of |coefficient|), else into the int32 tiles of slots [base, base + P_ROUND)
-    auto scatter_all = [&](auto pk, int base) {
+    auto scatter_one = [&](auto pk, int base, uint32_t e) {
       constexpr bool PK = decltype(pk)::value;
       const int base_off = PK ? (base >> 1) * (P_TILE * 4) : 0; // (wave-uniform)
-      auto scatter = [&](uint32_t e) {
+      {
         const uint32_t t = e & 0x1FF, t4 = t << 2, p4 = t4 & 0xFCu, kk4 = ((t >> 6) * 8 + (uint32_t)g) << 2;
         const int level = (int32_t)e >> 16;
         const uint32_t inv = lds32(L, P_INV + (int)kk4);
@@ -887,7 +913,21 @@ __device__ __forceinline__ void recon_inter_oct(const MobiReconArgs &A, uint8_t 
           const int slot = (int)((inv >> 13) & 0x7Fu) - base;
           if ((unsigned)slot < (unsigned)P_ROUND) *(int *)(L + P_COEF + slot * (P_TILE * 4) + p4) = v;
         }
-      };
+      }
+    };
+    // beyond the registers (dense macroblocks): 64 more words of a macroblock per round trip, eight loads in flight per lane
+    auto scatter_rest = [&](auto pk, int base) {
+      for (uint32_t i = 8u * CWR + (uint32_t)j; __builtin_amdgcn_ballot_w64(i < ncoef) != 0; i += 64) {
+        uint32_t tw[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) tw[k] = i + 8u * k < ncoef ? cw[i + 8u * k] : 0u;
+#pragma unroll
+        for (int k = 0; k < 8; k++)
+          if (i + 8u * k < ncoef) scatter_one(pk, base, tw[k]);
+      }
+    };
+    auto scatter_all = [&](auto pk, int base) {
+      auto scatter = [&](uint32_t e) { scatter_one(pk, base, e); };
 #pragma unroll
       for (int k = 0; k < CWR; k++) {
         int lf = left;
@@ -898,16 +938,72 @@ __device__ __forceinline__ void recon_inter_oct(const MobiReconArgs &A, uint8_t 
         asm volatile("" : "+v"(e));
         if (mine) scatter(e);
       }
-      // beyond the registers (dense macroblocks): 64 more words of a macroblock per round trip, eight loads in flight per lane
-      for (uint32_t i = 8u * CWR + (uint32_t)j; __builtin_amdgcn_ballot_w64(i < ncoef) != 0; i += 64) {
-        uint32_t tw[8];
+      scatter_rest(pk, base);
+    };
+    static_assert(CWR == 16, "scatter_first's batches: words 0 .. 127 in registers");
+    // The same pass when ONE packed round holds every coded area (n_slots <= 2 * P_PAIRS: all but one octet in a thousand of the
+    // generator's mix) -- no range test, every sum wanted -- as batches of B words per lane: B reads of P_INV, one wait, B reads of P_SC, one
+    // wait, then the products; only a word's store and sum sit inside the execution mask of the lanes that have the word.  (Word by word,
+    // each word was two dependent LDS round trips inside its own execution mask, behind its own ballot and branch: nine scalar
+    // instructions and two waits per word and pass.)  A lane without a word in the batch reads with whatever its register holds: any
+    // 9-bit position reads inside P_INV .. P_SC, any selector inside P_SC .. P_TAB.  The batches are chosen once per octet from the largest
+    // ncoef (wave-uniform ballots).  Without the range test a word's store goes wherever its area's P_INV entry says: this relies on the
+    // parsers never writing a level word for an area that is not coded (a word belongs to a coded block by the bitstream's syntax),
+    // so that every entry a word reads was written at set-up for THIS octet; a stale
+    // entry could point anywhere in the 8 KB its offset field spans (LDS drops a store beyond the allocation).
+    const int g4 = 4 * g;
+    auto batch = [&](auto k0c, auto bc) {
+      constexpr int K0 = decltype(k0c)::value, B = decltype(bc)::value;
+      uint32_t e[B], t4[B], kk[B], inv[B];
+      int sc[B];
+      int lf = left;
+      asm volatile("" : "+v"(lf)); // (compared in its batch, as in scatter_all)
 #pragma unroll
-        for (int k = 0; k < 8; k++) tw[k] = i + 8u * k < ncoef ? cw[i + 8u * k] : 0u;
+      for (int i = 0; i < B; i++) {
+        e[i] = cwr[K0 + i];
+        asm volatile("" : "+v"(e[i])); // (a word's arithmetic stays in its batch: hoisted out of the loop over the rounds, all sixteen words' ran for every octet)
+        t4[i] = e[i] << 2;
+        kk[i] = (((e[i] >> 6) & 7u) << 5) + (uint32_t)g4; // 4 * (area * 8 + g)
+        inv[i] = lds32(L, P_INV + (int)kk[i]);
+      }
 #pragma unroll
-        for (int k = 0; k < 8; k++)
-          if (i + 8u * k < ncoef) scatter(tw[k]);
+      for (int i = 0; i < B; i++) sc[i] = (int)lds32(L, P_SC + (int)((t4[i] | 0x100u) & (inv[i] >> 23)));
+      int v[B];
+      uint32_t at[B], av[B];
+#pragma unroll
+      for (int i = 0; i < B; i++) {
+        v[i] = __mul24(sc[i], (int32_t)e[i] >> 16);
+        at[i] = (inv[i] & 0x1FFFu) + (t4[i] & 0xFCu);
+        const int a = v[i] < 0 ? -v[i] : v[i];
+        av[i] = (uint32_t)(a > 0xFFFF ? 0xFFFF : a);
+        asm volatile("" : "+v"(v[i]), "+v"(at[i]), "+v"(av[i])); // (computed for the batch: sunk into the mask below, a word's second read waited there)
+      }
+#pragma unroll
+      for (int i = 0; i < B; i++) {
+        if (lf > 8 * (K0 + i)) {
+          *(int16_t *)(L + P_COEF + at[i]) = (int16_t)v[i];
+          __hip_atomic_fetch_add((uint32_t *)(L + P_SUM + kk[i]), av[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+        }
       }
     };
+#define MOBI_BATCH(K0, B) batch(std::integral_constant<int, K0>{}, std::integral_constant<int, B>{})
+    auto scatter_first = [&]() {
+      // (the word counts are looked at as far as the octet goes: two octets out of three stop at the first test)
+      if (__builtin_amdgcn_ballot_w64(ncoef > 16) == 0) MOBI_BATCH(0, 2);
+      else if (__builtin_amdgcn_ballot_w64(ncoef > 24) == 0) MOBI_BATCH(0, 3);
+      else {
+        MOBI_BATCH(0, 4);
+        if (__builtin_amdgcn_ballot_w64(ncoef > 32) != 0) {
+          if (CWR > 4) MOBI_BATCH(4, 4);
+          if (CWR > 8 && __builtin_amdgcn_ballot_w64(ncoef > 64) != 0) {
+            MOBI_BATCH(8, 4);
+            if (CWR > 12 && __builtin_amdgcn_ballot_w64(ncoef > 96) != 0) MOBI_BATCH(12, 4);
+          }
+          scatter_rest(std::true_type{}, 0);
+        }
+      }
+    };
+#undef MOBI_BATCH
     auto zero_tiles = [&](int n_tiles) { // (wave-uniform: only the tiles in use)
       const uint4 z = uint4{0, 0, 0, 0};
       for (int o = lane * 16; o < n_tiles * P_TILE * 4; o += 1024) *(uint4 *)(L + P_COEF + o) = z;
@@ -921,7 +1017,8 @@ __device__ __forceinline__ void recon_inter_oct(const MobiReconArgs &A, uint8_t 
     for (int base = 0; base < n_slots && !wide; base += 2 * P_PAIRS) {
       zero_tiles(n_slots - base < 2 * P_PAIRS ? (n_slots - base + 1) >> 1 : P_PAIRS);
       wave_sync();
-      scatter_all(std::true_type{}, base);
+      if (n_slots <= 2 * P_PAIRS) scatter_first();
+      else scatter_all(std::true_type{}, base);
       wave_sync();
       if (base == 0) {
         const uint32_t sm = lane < 48 ? lds32(L, P_SUM + 4 * lane) : 0u;
@@ -1053,7 +1150,8 @@ __device__ __forceinline__ void recon_inter_oct(const MobiReconArgs &A, uint8_t 
 // life waiting for its own, MOBI_DEBUG=9): the loop around this much inlined code spills (24 VGPRs, 26 SGPRs at best: the kernel
 // arguments stay live across it), and as a real function the callee-saved registers go through scratch.  Not kept.  Touching the
 // descriptors of the octet an XCD starts 512 ... 8192 workgroups later (a DMA of two lines into unused LDS): 2.81 against 2.71 ms per
-// 8192 clips -- two more requests per wave in a kernel bound by requests cost more than the shorter wait gives.
+// 8192 clips -- two more requests per wave in a kernel bound by requests cost more than the shorter wait gives.  (That was r02.  Since the
+// kernel is bound by its vector pipe the same touch pays, as one plain load: stage A of recon_inter_oct, P_TOUCH.)
 #define MOBI_OCT_KERNEL(NAME, WAVES, PROF, NCWR)                                                      \
   extern "C" __global__ __launch_bounds__(64, WAVES) void NAME(MobiReconArgs A) {                      \
     __shared__ __attribute__((aligned(16))) uint8_t lds[P_BYTES];                                      \
