@@ -119,10 +119,7 @@ inline void step_write(const std::vector<const ParsedFrame *> &frames, int n_mbs
 }
 
 struct LevelPlan { // launch plan of one frame step: the intra macroblocks of all clips, sorted by dependency level
-  // One item = MOBI_INTRA_ITEM_WORDS words, everything a wave needs to start (mobi_recon_intra): (clip << 13 | mb), MbDesc.w1,
-  // MbDesc.payload_off inside the step's arena, and flags: [0] 16x16 plane, [1] has intra dependencies (must poll their tags),
-  // [2] has intra dependents (must publish its own), [14:5] number of level words,
-  // [31:16] plane parameter.
+  // One item = MOBI_INTRA_ITEM_WORDS words, everything a wave needs to start (mobi_recon_intra); its layout: mobi_cmd.h, the intra launch item
   std::vector<uint32_t> items;
   uint32_t n_items = 0;         // launch items, padding included
   uint32_t n_intra = 0;         // intra macroblocks among them
@@ -172,8 +169,8 @@ struct LevelPlan { // launch plan of one frame step: the intra macroblocks of al
           if (!f || L > f->hdr.n_levels) continue;
           for (uint32_t i = f->class_start[(size_t)L * MOBI_INTRA_CLASSES + k]; i < f->class_start[(size_t)L * MOBI_INTRA_CLASSES + k + 1]; i++) {
             const uint32_t *it = &f->intra_items[(size_t)i * 4];
-            intra_cmd_bytes += sizeof(MbDesc) + 4 * (MOBI_INTRA_RECORDS + ((it[3] >> 5) & 0x3FFu));
-            const uint32_t item[4] = {MOBI_ITEM(c, it[0]), it[1], it[2] + (uint32_t)base[c], it[3] & ~8u};
+            intra_cmd_bytes += sizeof(MbDesc) + 4 * (MOBI_INTRA_RECORDS + mobi_item_coefs(it[3]));
+            const uint32_t item[4] = {MOBI_ITEM(c, it[0]), it[1], it[2] + (uint32_t)base[c], mobi_item_shipped(it[3])};
             items.insert(items.end(), item, item + 4);
             n_intra++;
             for (int q = 1; q < 4 && sparse; q++) items.insert(items.end(), none, none + 4);

@@ -1,7 +1,7 @@
 // mobi_dparse.hip -- device-side bitstream parser for gfx950: one wave per clip.
 //
-// Same syntax walk as mobi_parse.cpp (which cites MobiclipDecoder.cs, "MD.cs", line by line; what both know about the format's leaves and
-// the command list's words is mobi_syntax.h): bit reader (:2970-3015),
+// Same syntax walk as mobi_parse.cpp (which cites MobiclipDecoder.cs, "MD.cs", line by line; what both know about the format's leaves is mobi_syntax.h,
+// the command list's words are mobi_cmd.h's): bit reader (:2970-3015),
 // frame headers (:113-143, :224-236), MV prediction (:163-208), partition tree (:469-1746), residual CBP/VLC
 // (:1818-1833, :2909-2968, :3330-3432), intra macroblock syntax (:1759-1880, :2776-2902).  The parse of one clip is a
 // chain of data-dependent reads, so a wave runs it on ONE lane; the machine is filled by clips instead (8 waves per SIMD
@@ -98,7 +98,7 @@ __device__ __noinline__ ResidOut resid_block_fn(BitR r, uint32_t n_coefs, lds_u8
     if (p >= N) { r.fail(MOBI_E_UNSUPPORTED); break; } // the reference would walk past the dequant words (Internal[] aliasing)
     const int idx = (flags & 4) ? zz[p] : 0; // low byte of the dequant word = zigzag target (MD.cs:3426); all zero before the first SetupQuantTables
     p++;
-    if (value != 0) out[n_coefs++] = (uint32_t)(tile + idx) | ((uint32_t)(int)(int16_t)value << 16);
+    if (value != 0) out[n_coefs++] = mobi_level_word(tile + idx, (int16_t)value);
     else r.fail(MOBI_E_UNSUPPORTED); // a token without a level: the frame's command list would not name every token (mobi_state.h): the host parser's
     if (last) break;
   }
@@ -185,8 +185,8 @@ struct DP {
         #pragma nounroll
         for (int i = 0; i + 1 < n_leaf_words; i += 2) {
           const uint32_t w0 = L->leaves[i], mv = L->leaves[i + 1];
-          const int x = (int)(w0 & 15) * 2, y = (int)((w0 >> 4) & 15) * 2, w = 16 >> ((w0 >> 8) & 3), h = 16 >> ((w0 >> 10) & 3);
-          const uint32_t cell = mobi_cell((int16_t)(mv & 0xFFFF), (int16_t)(mv >> 16), (int)((w0 >> 12) & 7));
+          const int x = mobi_leaf_x(w0), y = mobi_leaf_y(w0), w = 16 >> mobi_leaf_wi(w0), h = 16 >> mobi_leaf_hi(w0);
+          const uint32_t cell = mobi_cell(mobi_leaf_dx(mv), mobi_leaf_dy(mv), mobi_leaf_ref(w0));
           #pragma nounroll
           for (int cy = y >> 1; cy < (y + h) >> 1; cy++)
             #pragma nounroll
@@ -354,7 +354,7 @@ struct DP {
       const int p = se();
       check_intra_reads(2, cur_off);
       if (p < -32768 || p > 32767) { fail(MOBI_E_UNSUPPORTED); return; }
-      w3 = 1u | ((uint32_t)(uint16_t)(int16_t)p << 16);
+      w3 = mobi_w3_plane16(p);
     }
     #pragma nounroll
     for (int k = 0; k < 4; k++) {

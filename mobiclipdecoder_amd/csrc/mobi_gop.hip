@@ -40,7 +40,7 @@ __device__ __forceinline__ void sort_count(const MobiGopSortArgs &A, int k, int 
     const uint32_t ni = A.res[v].n_intra;
     const uint32_t *items = A.items + v * A.n_mbs;
     for (uint32_t i = lane; i < ni; i += 64) {
-      const uint32_t mb = items[i] & 0x1FFFu, my = mb / (uint32_t)A.mbw;
+      const uint32_t mb = MOBI_ITEM_MB(items[i]), my = mb / (uint32_t)A.mbw;
       atomicAdd(&cnt[(mb - my * A.mbw) + 2 * my], 1u);
     }
   }
@@ -85,11 +85,11 @@ extern "C" __global__ __launch_bounds__(256) void mobi_gop_scatter(MobiGopSortAr
     const MbDesc *desc = A.desc + v * A.n_mbs;
     const uint32_t *items = A.items + v * A.n_mbs;
     for (uint32_t i = lane; i < ni; i += 64) {
-      const uint32_t mb = items[i] & 0x1FFFu, my = mb / (uint32_t)A.mbw, l = (mb - my * A.mbw) + 2 * my;
+      const uint32_t mb = MOBI_ITEM_MB(items[i]), my = mb / (uint32_t)A.mbw, l = (mb - my * A.mbw) + 2 * my;
       const uint4 d = *(const uint4 *)(desc + mb); // payload_off, w1, w2, w3
       const uint32_t pos = base[l] + atomicAdd(&cnt[l], 1u);
       if (pos < A.sorted_cap[k]) // (always: the caller sized the room from the same counts)
-        out[pos] = uint4{MOBI_ITEM((uint32_t)(c0 + j), mb), d.y, d.x, (d.w & (0xFFFF0007u | MOBI_W3_WIDE)) | ((d.z & 0x3FFu) << 5)};
+        out[pos] = uint4{MOBI_ITEM((uint32_t)(c0 + j), mb), d.y, d.x, MOBI_ITEM_FLAGS(d.w, d.z)};
     }
   }
 }

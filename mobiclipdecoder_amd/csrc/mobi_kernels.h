@@ -5,7 +5,6 @@
 #include <stdint.h>
 
 #include "mobi_cmd.h"
-#include "mobi_syntax.h"
 
 // Everything one reconstruction launch needs.  HBM layout:
 //   planes : [clip][slot 0..5][ Y: stride*height | UV: stride*height/2 ], each plane as macroblock TILES (mobi_tile.h): a
@@ -37,7 +36,7 @@ static_assert(sizeof(MobiReconArgs) == 128, "kernarg block layout");
 
 // mobi_recon_inter8: every inter macroblock of the step, one wave per octet of macroblocks
 extern "C" int mobi_launch_inter(const MobiReconArgs *a, hipStream_t s);
-// items_dev: n_items launch items of 16 bytes (MOBI_INTRA_ITEM_WORDS words), sorted by dependency level -- see LevelPlan in mobi_batch.h
+// items_dev: n_items launch items of 16 bytes (mobi_cmd.h: MOBI_INTRA_ITEM_WORDS words), sorted by dependency level -- see LevelPlan in mobi_batch.h
 extern "C" int mobi_launch_intra(const MobiReconArgs *a, const uint32_t *items_dev, int n_items, hipStream_t s);
 // small batches: both of the above in one launch (mobi_recon_step: the intra fours wait for the inter macroblocks their halo reads)
 extern "C" int mobi_launch_step(const MobiReconArgs *a, const uint32_t *items_dev, int n_items, hipStream_t s);
@@ -57,7 +56,4 @@ extern "C" int mobi_launch_fwd_dct(int n, const int32_t *in_dev, int32_t *out_de
 extern "C" int mobi_launch_compare_clips(const MobiReconArgs *a, int modulus, uint32_t *out_dev, hipStream_t s);
 // slot (tiled Y + UV planes of one frame) -> lin_dev: the same frame as the reference's row-major Y[stride*height] then UV[stride*height/2]
 extern "C" int mobi_launch_untile(const uint8_t *slot, uint8_t *lin_dev, int stride, int height, hipStream_t s);
-// intra launch item: word 0 = MOBI_ITEM(clip, mb) (mobi_syntax.h); words 1..3: MbDesc.w1, MbDesc.payload_off, flags (mobi_recon_intra in mobi_kernels.hip)
-#define MOBI_INTRA_ITEM_WORDS 4
-#define MOBI_ITEM_NONE 0xFFFFFFFFu /* padding: every dependency level starts on a wave of four items */
 #endif

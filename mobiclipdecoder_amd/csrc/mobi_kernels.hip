@@ -144,21 +144,24 @@ __device__ __forceinline__ void idct_pass1(const int *c, int *t, bool is8, int r
     for (int m = 0; m < 4; m++) { t[16 * s + 4 * m + k0] = out[m]; t[16 * s + 4 * m + k0 + 1] = out[4 + m]; }
   }
 }
-// pass 2 whose eight residuals stay with the lane, as four int16 pairs (saturated): 8x8 -> row r; 4x4 -> rows i0, i0 + 1 of block r >> 1
-__device__ __forceinline__ uint4 idct_pass2_pk(const int *t, bool is8, int r) {
-  int in[8], out[8];
-  if (is8) {
-#pragma unroll
-    for (int m = 0; m < 8; m++) in[m] = t[8 * r + m];
-    mobi_bfly8(in, out);
-  } else {
-    const int s = r >> 1, i0 = (r & 1) * 2;
-#pragma unroll
-    for (int m = 0; m < 8; m++) in[m] = t[16 * s + 4 * i0 + m]; // groups i0 and i0 + 1
-    mobi_bfly4(in, out);
-    mobi_bfly4(in + 4, out + 4);
+// pass 2 of area t by lane r, the butterflies: 8x8 -> row r; 4x4 -> rows i0, i0 + 1 of block r >> 1.  Either way eight residuals (<< 6).
+// (As text, not as a function: as an inlined function with out[] as its result every kernel compiled differently, and with out[] as a
+// pointer argument it went through scratch.)
+#define MOBI_IDCT_PASS2(t, is8, r, in, out)                                                       \
+  if (is8) {                                                                                      \
+    _Pragma("unroll") for (int m = 0; m < 8; m++) in[m] = t[8 * r + m];                           \
+    mobi_bfly8(in, out);                                                                          \
+  } else {                                                                                        \
+    const int s = r >> 1, i0 = (r & 1) * 2;                                                       \
+    _Pragma("unroll") for (int m = 0; m < 8; m++) in[m] = t[16 * s + 4 * i0 + m]; /* groups i0 and i0 + 1 */ \
+    mobi_bfly4(in, out);                                                                          \
+    mobi_bfly4(in + 4, out + 4);                                                                  \
   }
-  typedef short s16x2 __attribute__((ext_vector_type(2)));
+typedef short s16x2 __attribute__((ext_vector_type(2)));
+// ... whose eight residuals stay with the lane, as four int16 pairs (saturated)
+__device__ __forceinline__ uint4 idct_pass2_res16(const int *t, bool is8, int r) {
+  int in[8], out[8];
+  MOBI_IDCT_PASS2(t, is8, r, in, out)
   union { s16x2 v; uint32_t u; } p0, p1, p2, p3;
   p0.v = __builtin_amdgcn_cvt_pk_i16(out[0] >> 6, out[1] >> 6);
   p1.v = __builtin_amdgcn_cvt_pk_i16(out[2] >> 6, out[3] >> 6);
@@ -166,7 +169,6 @@ __device__ __forceinline__ uint4 idct_pass2_pk(const int *t, bool is8, int r) {
   p3.v = __builtin_amdgcn_cvt_pk_i16(out[6] >> 6, out[7] >> 6);
   return uint4{p0.u, p1.u, p2.u, p3.u};
 }
-} // namespace
 
 // q = x / d, r = x % d with magic = floor(2^32 / d): the estimate is at most one short
 __device__ __forceinline__ uint32_t fastdiv(uint32_t x, uint32_t d, uint32_t magic, uint32_t &r) {
@@ -187,7 +189,6 @@ __device__ __forceinline__ uint32_t fastdiv(uint32_t x, uint32_t d, uint32_t mag
 #define MOBI_STOP(n) do { } while (0)
 #define MOBI_ISTOP(n) do { } while (0)
 #endif
-namespace {
 typedef const void __attribute__((address_space(1))) *gptr_t;
 typedef void __attribute__((address_space(3))) *lptr_t;
 // lane i lands at dst + IMM + i*16; dst must be wave-uniform (it travels in M0); IMM = constant byte offset added to BOTH
@@ -206,7 +207,6 @@ __device__ __forceinline__ uint32_t lds32(const uint8_t *L, int byte_off) { retu
 // butterflies differ between one 8x8 transform (lane r = pixel row r) and four 4x4s (lane r = rows (r&1)*2, +1 of
 // sub-block r>>1): both leave 8 residuals for two 4-pixel words, so the pixel update is one shared instruction stream
 // (the 8 lanes of an area agree on the kind, the lanes of a wave do not).
-typedef short s16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint32_t sat_pk_u8(s16x2 v) { // two int16 -> two bytes, each clamped to 0..255 (the clamp table's identity range, MobiConst.cs:587)
 #if defined(__HIP_DEVICE_COMPILE__)
   uint32_t d;
@@ -223,17 +223,7 @@ __device__ __forceinline__ uint32_t sat_pk_u8(s16x2 v) { // two int16 -> two byt
 // saturated sums.
 __device__ __forceinline__ void idct_pass2_q(const int *t, bool is8, int r, uint8_t *wa, uint8_t *wb, s16x2 &lo, s16x2 &hi) {
   int in[8], out[8]; // wa, wb: the two 4-pixel words (4-byte aligned) the lane's eight residuals belong to
-  if (is8) {
-#pragma unroll
-    for (int m = 0; m < 8; m++) in[m] = t[8 * r + m];
-    mobi_bfly8(in, out);
-  } else {
-    const int s = r >> 1, i0 = (r & 1) * 2;
-#pragma unroll
-    for (int m = 0; m < 8; m++) in[m] = t[16 * s + 4 * i0 + m]; // groups i0 and i0 + 1
-    mobi_bfly4(in, out);
-    mobi_bfly4(in + 4, out + 4);
-  }
+  MOBI_IDCT_PASS2(t, is8, r, in, out)
   const uint32_t pw[2] = {*(const uint32_t *)wa, *(const uint32_t *)wb};
   uint32_t res[2];
 #pragma unroll
@@ -250,7 +240,6 @@ __device__ __forceinline__ void idct_pass2_q(const int *t, bool is8, int r, uint
   *(uint32_t *)wa = res[0];
   *(uint32_t *)wb = res[1];
 }
-} // namespace
 
 // ---- 16-bit packed transforms (r04): one lane carries the same row of TWO coded areas, one in each half of a dword ----
 // The octet kernel is bound by vector instruction issue, and 44 % of its instructions were the residual stage: two passes of the 8-point
@@ -267,7 +256,6 @@ __device__ __forceinline__ void idct_pass2_q(const int *t, bool is8, int r, uint
 // (r05, measured and not kept: the same bound says when the clamp table CANNOT be left -- sums below 1700 give |x >> 6| <= 64 -- and an octet
 // of such areas could run its pixel update without the sixteen packed min / max per lane that track the range; with the second copy of the
 // pixel update and the ballot that picks it the launch was no faster: profiles/r05_experiments.txt.)
-namespace {
 __device__ __forceinline__ void bfly8_pk(const s16x2 in[8], s16x2 out[8]) { // mobi_bfly8, two at a time
   const s16x2 a0 = in[0] + in[4], a1 = in[0] - in[4];
   const s16x2 a2 = in[2] + (in[6] >> (short)1), a3 = (in[2] >> (short)1) - in[6];
@@ -353,7 +341,6 @@ __device__ __forceinline__ void idct_pass2_pk(const uint32_t *t, bool is8, int r
     *(uint32_t *)wbB = resB[1];
   }
 }
-} // namespace
 
 // =====================================================================================================
 // mobi_recon_inter8: one wavefront per octet (Kernels; how it got here: HISTORY.md)
@@ -375,7 +362,6 @@ __device__ __forceinline__ void idct_pass2_pk(const uint32_t *t, bool is8, int r
 // So a vector instruction that no longer runs still buys the most (tools/exp_stages.sh counts them stage by stage, MOBI_STOP); scalar
 // instructions, branches and waits taken out of the wave's serial path buy little (stage 9 in batches: two LDS round trips per batch
 // instead of two per word, -0.8 %); a vector instruction ADDED to save scalar ones loses; and what shortens a wait on memory pays its share.
-namespace {
 // LDS of one octet (10 KB: sixteen waves per CU).  While the windows are in flight / being interpolated:
 //   P_L   luma windows: chunk (row pair p = 0..9, quadrant column s = 0..3) of macroblock g at p * 512 + s * 128 + g * 16; a chunk =
 //         two rows x 8 samples of one quadrant (mobi_tile.h).  A whole leaf's window is 9 pairs x 3 columns (17 rows x 17..24 samples
@@ -420,7 +406,6 @@ static_assert(P_OUT + 7 * P_PITCH + 384 <= P_COEF && P_COEF + P_ROUND * P_TILE *
 static_assert(P_INV + 4 * 63 < P_BYTES && P_SC + 0x1FC < P_BYTES, "what a lane without a word may read in a batch of the scatter");
 static_assert(23 * P_TILE * 4 + 2 < (1 << 13) && (P_PITCH & 15) == 0, "P_INV's offset field (48 slots); 16-byte reads of the output rows");
 __device__ __forceinline__ int out_px(int g, int R, int c) { return P_OUT + (R & 7) * P_PITCH + (R >> 3) * 128 + (g << 4) + c; }
-__device__ __forceinline__ int out_y(int g, int R, int c) { return out_px(g, R, c); }
 __device__ __forceinline__ int out_c(int g, int R, int pl, int x) { return out_px(g, 16 + R, pl * 8 + x); }
 // N output rows of 4 pixels from N + 1 window rows (x0[i], x1[i] = the two aligned dwords holding row i's 5 bytes)
 template <int N>
@@ -440,7 +425,6 @@ __device__ __forceinline__ void mc_rows(const uint32_t (&x0)[N + 1], const uint3
 #pragma unroll
   for (int i = 0; i < N; i++) out[i] = __builtin_amdgcn_lerp(m[i], ver ? m[i + 1] : m[i], 0u);
 }
-} // namespace
 
 __device__ __forceinline__ unsigned long long prof_stamp() { // shader clock, pinned: nothing is scheduled across it
   __builtin_amdgcn_sched_barrier(0);
@@ -450,6 +434,8 @@ __device__ __forceinline__ unsigned long long prof_stamp() { // shader clock, pi
   __builtin_amdgcn_sched_barrier(0);
   return t;
 }
+} // namespace
+
 template <int PROF, int CWR, int FUSED>
 __device__ __forceinline__ void recon_inter_oct(const MobiReconArgs &A, uint8_t *L, uint32_t clip, uint32_t mby, uint32_t ox, int lane) {
   unsigned long long pt[7] = {0, 0, 0, 0, 0, 0, 0};
@@ -491,18 +477,18 @@ __device__ __forceinline__ void recon_inter_oct(const MobiReconArgs &A, uint8_t 
     touch = *(const uint32_t *)(tb + (uint32_t)lane * 4u);
   }
   if (PROF) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); pb = prof_stamp(); }
-  const bool valid = g < nmb && (d.y & 1) == MOBI_MB_INTER;
-  const int nl = (d.y >> 1) & 0x7F, kind2 = (d.y >> 26) & 3;
+  const bool valid = g < nmb && mobi_w1_type(d.y) == MOBI_MB_INTER;
+  const int nl = mobi_w1_leaves(d.y), kind2 = MOBI_GET(d.y, MOBI_W1_DUAL); // (kind2 as an expression: through mobi_w1_dual() three s_and_b64 swap their sources)
   const bool leaves = valid && (nl == 1 || kind2 != 0);       // whole leaves (16x16, two 16x8, two 8x16)
   const bool multi = valid && nl > 1 && kind2 == 0;           // deeper tree: MV cell map in the payload
   const bool tb = leaves && kind2 == MOBI_DUAL_TB, lr = leaves && kind2 == MOBI_DUAL_LR;
-  const uint32_t cbp6 = valid ? (d.y >> 8) & 0x3F : 0, ncoef = cbp6 ? d.z & 0x3FF : 0;
+  const uint32_t cbp6 = valid ? mobi_w1_cbp6(d.y) : 0, ncoef = cbp6 ? mobi_w2_coefs(d.z) : 0;
   // (wave masks as ballots of ONE comparison each, combined on the scalar unit: a ballot of a compound condition goes through a 0 / 1
   // register and a second comparison)
-  const unsigned long long v64 = __builtin_amdgcn_ballot_w64(g < nmb) & __builtin_amdgcn_ballot_w64((d.y & 1) == MOBI_MB_INTER); // = ballot(valid)
+  const unsigned long long v64 = __builtin_amdgcn_ballot_w64(g < nmb) & __builtin_amdgcn_ballot_w64(mobi_w1_type(d.y) == MOBI_MB_INTER); // = ballot(valid)
   const unsigned long long six = 0x0000FFFFFFFFFFFFull; // lanes with j < 6
-  const unsigned long long mb64 = __builtin_amdgcn_ballot_w64(((d.y >> (8 + j)) & 1) != 0) & v64 & six;   // bit area*8 + g: the area is coded
-  const unsigned long long tb64 = __builtin_amdgcn_ballot_w64(((d.y >> (14 + j)) & 1) != 0) & six;        // ... with one 8x8 transform
+  const unsigned long long mb64 = __builtin_amdgcn_ballot_w64(((d.y >> (MOBI_W1_CBP_S + j)) & 1) != 0) & v64 & six;   // bit area*8 + g: the area is coded
+  const unsigned long long tb64 = __builtin_amdgcn_ballot_w64(((d.y >> (MOBI_W1_T8_S + j)) & 1) != 0) & six;        // ... with one 8x8 transform
   const uint32_t m_lo = (uint32_t)mb64, m_hi = (uint32_t)(mb64 >> 32), t_lo = (uint32_t)tb64, t_hi = (uint32_t)(tb64 >> 32);
   const uint32_t inter_mask = (uint32_t)v64 & 0xFFu;
   const uint32_t multi_mask = (uint32_t)(v64 & __builtin_amdgcn_ballot_w64(nl > 1) & __builtin_amdgcn_ballot_w64(kind2 == 0)) & 0xFFu;
@@ -512,9 +498,9 @@ __device__ __forceinline__ void recon_inter_oct(const MobiReconArgs &A, uint8_t 
     sl = sl < 0 ? sl + 6 : sl;
     return __umul24((uint32_t)sl, A.slot_bytes); // slot_bytes < 2^24: checked by mobi_launch_inter
   };
-  const uint32_t refA = slot_off((d.z >> 10) & 7), refB = slot_off((d.z >> 13) & 7);
+  const uint32_t refA = slot_off(mobi_w2_ref(d.z, 0)), refB = slot_off(mobi_w2_ref(d.z, 1));
   const int posA = (int)d.w, cposA = (int)d2.x, posB = (int)d2.y, cposB = (int)d2.z;
-  const int phA = (d.z >> 16) & 3, cphA = (d.z >> 18) & 3, phB = (d.z >> 20) & 3, cphB = (d.z >> 22) & 3;
+  const int phA = mobi_w2_phase(d.z, 0), cphA = mobi_w2_cphase(d.z, 0), phB = mobi_w2_phase(d.z, 1), cphB = mobi_w2_cphase(d.z, 1);
   // A leaf's window starts at its first sample's position: leaf B's is row 8 (TOP/BOTTOM) or column 8 (LEFT/RIGHT) of the macroblock
   const int topB = tb ? posB + (8 << lgS) : posB + 8, ctopB = tb ? cposB + (4 << lgS) : cposB + 4;
   // What is fetched is a fixed shape, not the window's exact needs (the kernel is bound by instruction issue since the planes are
@@ -628,7 +614,7 @@ __device__ __forceinline__ void recon_inter_oct(const MobiReconArgs &A, uint8_t 
     }
   }
   MOBI_STOP(1);
-  const int quant = __builtin_amdgcn_readfirstlane((int)((d.y >> 20) & 63));
+  const int quant = __builtin_amdgcn_readfirstlane((int)mobi_w1_quant(d.y));
   const uint32_t *pay = A.payload + (size_t)clip * A.pay_clip_words; // (wave-uniform)
   const uint32_t *cw = pay + d.x + (multi ? MOBI_MV_CELLS : 0);
   uint32_t cwr[CWR]; // lane (g, j) scatters words j, j+8, j+16, ... of macroblock g; the first 8*CWR of them travel in registers
@@ -735,15 +721,15 @@ __device__ __forceinline__ void recon_inter_oct(const MobiReconArgs &A, uint8_t 
       const uint32_t w1m = __builtin_amdgcn_readlane(d.y, gm), w2m = __builtin_amdgcn_readlane(d.z, gm);
       const int pAm = (int)__builtin_amdgcn_readlane(d.w, gm), cAm = (int)__builtin_amdgcn_readlane(d2.x, gm);
       const int pBm = (int)__builtin_amdgcn_readlane(d2.y, gm), cBm = (int)__builtin_amdgcn_readlane(d2.z, gm);
-      const int k2 = (w1m >> 26) & 3;
+      const int k2 = mobi_w1_dual(w1m);
       const bool yBm = k2 == MOBI_DUAL_TB ? yrow >= 8 : k2 == MOBI_DUAL_LR ? yc4 >= 8 : false;
       const bool cBl2 = k2 == MOBI_DUAL_TB ? crow >= 4 : k2 == MOBI_DUAL_LR ? cc4 >= 4 : false;
       const int la = (yBm ? pBm : pAm) + (yrow << lgS) + yc4;
-      D.pha = (w2m >> (yBm ? 20 : 16)) & 3;
-      const uint32_t sa = slot_off((w2m >> (yBm ? 13 : 10)) & 7);
+      D.pha = (w2m >> (yBm ? MOBI_W2_PHB_S : MOBI_W2_PHA_S)) & MOBI_MASK(MOBI_W2_PHA);
+      const uint32_t sa = slot_off((w2m >> (yBm ? MOBI_W2_REFB_S : MOBI_W2_REFA_S)) & MOBI_MASK(MOBI_W2_REFA));
       const int lq = (cBl2 ? cBm : cAm) + cv * (S >> 1) + (crow << lgS) + cc4;
-      D.phq = (w2m >> (cBl2 ? 22 : 18)) & 3;
-      const uint32_t sq = slot_off((w2m >> (cBl2 ? 13 : 10)) & 7);
+      D.phq = (w2m >> (cBl2 ? MOBI_W2_CPHB_S : MOBI_W2_CPHA_S)) & MOBI_MASK(MOBI_W2_CPHA);
+      const uint32_t sq = slot_off((w2m >> (cBl2 ? MOBI_W2_REFB_S : MOBI_W2_REFA_S)) & MOBI_MASK(MOBI_W2_REFA));
       // some lane's window within 8 bytes of the end of a plane row (chroma: of a plane's half): every dword is mapped on its own
       const bool gen = (((uint32_t)la & (uint32_t)(S - 1)) >= (uint32_t)(S - 8)) || (((uint32_t)lq & (uint32_t)((S >> 1) - 1)) >= (uint32_t)((S >> 1) - 8));
       const bool general = __builtin_amdgcn_ballot_w64(gen) != 0;
@@ -769,8 +755,8 @@ __device__ __forceinline__ void recon_inter_oct(const MobiReconArgs &A, uint8_t 
         const uint32_t v = ((a[k] >> 1) & M) + ((a[k + 1] >> 1) & M), p3 = ((h[k] >> 1) & M) + ((h[k + 1] >> 1) & M);
         yo[k] = D.yph == 0 ? a[k] : D.yph == 1 ? h[k] : D.yph == 2 ? v : p3;
       }
-      *(uint16_t *)(L + out_y(gm, 2 * cy, 2 * cx)) = (uint16_t)yo[0];
-      *(uint16_t *)(L + out_y(gm, 2 * cy + 1, 2 * cx)) = (uint16_t)yo[1];
+      *(uint16_t *)(L + out_px(gm, 2 * cy, 2 * cx)) = (uint16_t)yo[0];
+      *(uint16_t *)(L + out_px(gm, 2 * cy + 1, 2 * cx)) = (uint16_t)yo[1];
       // chroma: the U sample in byte 0, the V sample in byte 1 of every operand
       const uint32_t au = cut(D.ur[0], D.csh), bu = cut1(D.ur[0], D.csh), cu = cut(D.ur[1], D.csh), du = cut1(D.ur[1], D.csh);
       const uint32_t av = cut(D.vr[0], D.csh), bv = cut1(D.vr[0], D.csh), cvv = cut(D.vr[1], D.csh), dv = cut1(D.vr[1], D.csh);
@@ -783,7 +769,7 @@ __device__ __forceinline__ void recon_inter_oct(const MobiReconArgs &A, uint8_t 
       L[out_c(gm, cy, 1, cx)] = (uint8_t)(uvp >> 8);
     } else {
       const uint32_t va = mc4_select(D.wa, D.pha), cpred = mc4_select(D.wq, D.phq);
-      *(uint32_t *)(L + out_y(gm, yrow, yc4)) = va;
+      *(uint32_t *)(L + out_px(gm, yrow, yc4)) = va;
       if (lane < 32) *(uint32_t *)(L + out_c(gm, crow, cv, cc4)) = cpred;
     }
   };
@@ -834,7 +820,7 @@ __device__ __forceinline__ void recon_inter_oct(const MobiReconArgs &A, uint8_t 
   wave_sync();
   {
     // out_px, one base per lane and the row as a constant offset: luma rows 8 * rr + k, chroma rows 4 * ch + k
-    const int by = out_y(g, 8 * rr, 4 * q), bc = out_c(g, 4 * ch, pl, 4 * qc);
+    const int by = out_px(g, 8 * rr, 4 * q), bc = out_c(g, 4 * ch, pl, 4 * qc);
 #pragma unroll
     for (int k = 0; k < 8; k++) *(uint32_t *)(L + (by + k * P_PITCH)) = mcv[k];
 #pragma unroll
@@ -897,8 +883,8 @@ __device__ __forceinline__ void recon_inter_oct(const MobiReconArgs &A, uint8_t 
       constexpr bool PK = decltype(pk)::value;
       const int base_off = PK ? (base >> 1) * (P_TILE * 4) : 0; // (wave-uniform)
       {
-        const uint32_t t = e & 0x1FF, t4 = t << 2, p4 = t4 & 0xFCu, kk4 = ((t >> 6) * 8 + (uint32_t)g) << 2;
-        const int level = (int32_t)e >> 16;
+        const uint32_t t = mobi_level_pos(e), t4 = t << 2, p4 = t4 & 0xFCu, kk4 = ((t >> MOBI_LEVEL_AREA_S) * 8 + (uint32_t)g) << 2;
+        const int level = mobi_level_value(e);
         const uint32_t inv = lds32(L, P_INV + (int)kk4);
         const int scale = (int)lds32(L, P_SC + (int)((t4 | 0x100u) & (inv >> 23))); // scale8[p] or scale4[p & 15] (80 words: 64 + 16)
         const int v = __mul24(scale, level);
@@ -963,7 +949,7 @@ __device__ __forceinline__ void recon_inter_oct(const MobiReconArgs &A, uint8_t 
         e[i] = cwr[K0 + i];
         asm volatile("" : "+v"(e[i])); // (a word's arithmetic stays in its batch: hoisted out of the loop over the rounds, all sixteen words' ran for every octet)
         t4[i] = e[i] << 2;
-        kk[i] = (((e[i] >> 6) & 7u) << 5) + (uint32_t)g4; // 4 * (area * 8 + g)
+        kk[i] = (mobi_level_area(e[i]) << 5) + (uint32_t)g4; // 4 * (area * 8 + g)
         inv[i] = lds32(L, P_INV + (int)kk[i]);
       }
 #pragma unroll
@@ -972,7 +958,7 @@ __device__ __forceinline__ void recon_inter_oct(const MobiReconArgs &A, uint8_t 
       uint32_t at[B], av[B];
 #pragma unroll
       for (int i = 0; i < B; i++) {
-        v[i] = __mul24(sc[i], (int32_t)e[i] >> 16);
+        v[i] = __mul24(sc[i], mobi_level_value(e[i]));
         at[i] = (inv[i] & 0x1FFFu) + (t4[i] & 0xFCu);
         const int a = v[i] < 0 ? -v[i] : v[i];
         av[i] = (uint32_t)(a > 0xFFFF ? 0xFFFF : a);
@@ -1101,7 +1087,7 @@ __device__ __forceinline__ void recon_inter_oct(const MobiReconArgs &A, uint8_t 
 #pragma unroll
       for (int it = 0; it < 2; it++) {
         const int i = lane + 64 * it, gq = i >> 4, quad = (i >> 2) & 3, R0 = (quad >> 1) * 8 + 2 * (i & 3), c0 = (quad & 1) * 8;
-        const uint2 v0 = *(const uint2 *)(L + out_y(gq, R0, c0)), v1 = *(const uint2 *)(L + out_y(gq, R0 + 1, c0));
+        const uint2 v0 = *(const uint2 *)(L + out_px(gq, R0, c0)), v1 = *(const uint2 *)(L + out_px(gq, R0 + 1, c0));
         const u32x4 v = {v0.x, v0.y, v1.x, v1.y};
         const uint8_t *dst = ty0 + i * 16;
         if ((inter_mask >> gq) & 1) asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(dst), "v"(v) : "memory");
@@ -1120,7 +1106,7 @@ __device__ __forceinline__ void recon_inter_oct(const MobiReconArgs &A, uint8_t 
 #pragma unroll
     for (int it = 0; it < 2; it++) {
       const int i = lane + 64 * it, gq = i >> 4, quad = (i >> 2) & 3, R0 = (quad >> 1) * 8 + 2 * (i & 3), c0 = (quad & 1) * 8;
-      const uint2 v0 = *(const uint2 *)(L + out_y(gq, R0, c0)), v1 = *(const uint2 *)(L + out_y(gq, R0 + 1, c0));
+      const uint2 v0 = *(const uint2 *)(L + out_px(gq, R0, c0)), v1 = *(const uint2 *)(L + out_px(gq, R0 + 1, c0));
       if (full) *(uint4 *)(ty0 + i * 16) = uint4{v0.x, v0.y, v1.x, v1.y};
       else *(uint4 *)(ty0 + i * 16) = gq < nmb ? uint4{v0.x, v0.y, v1.x, v1.y} : uint4{0, 0, 0, 0};
     }
@@ -1152,15 +1138,22 @@ __device__ __forceinline__ void recon_inter_oct(const MobiReconArgs &A, uint8_t 
 // descriptors of the octet an XCD starts 512 ... 8192 workgroups later (a DMA of two lines into unused LDS): 2.81 against 2.71 ms per
 // 8192 clips -- two more requests per wave in a kernel bound by requests cost more than the shorter wait gives.  (That was r02.  Since the
 // kernel is bound by its vector pipe the same touch pays, as one plain load: stage A of recon_inter_oct, P_TOUCH.)
+// workgroup -> its octet, f(clip, mby, ox): octets are numbered along an XCD (workgroup b runs on XCD b & 7); nothing is called past the
+// last one (the grid is a whole number of workgroups per XCD).  qpr / qpc: octets per macroblock row / per clip (inter_grid below).
+// (f instead of a bool and three results: that form compiled to other branches in both kernels.)
+template <class F>
+__device__ __forceinline__ void block_octet(const MobiReconArgs &A, uint32_t block, F f) {
+  const uint32_t oi = (block & 7) * A.inter_per_xcd + (block >> 3);
+  if (oi >= A.qpc * (uint32_t)A.n_clips) return;
+  uint32_t rem, ox;
+  const uint32_t clip = fastdiv(oi, A.qpc, A.magic_qpc, rem);
+  const uint32_t mby = fastdiv(rem, A.qpr, A.magic_qpr, ox);
+  f(clip, mby, ox);
+}
 #define MOBI_OCT_KERNEL(NAME, WAVES, PROF, NCWR)                                                      \
   extern "C" __global__ __launch_bounds__(64, WAVES) void NAME(MobiReconArgs A) {                      \
     __shared__ __attribute__((aligned(16))) uint8_t lds[P_BYTES];                                      \
-    const uint32_t oi = (blockIdx.x & 7) * A.inter_per_xcd + (blockIdx.x >> 3);                        \
-    if (oi >= A.qpc * (uint32_t)A.n_clips) return;                                                     \
-    uint32_t rem, ox;                                                                                  \
-    const uint32_t clip = fastdiv(oi, A.qpc, A.magic_qpc, rem); /* qpr / qpc: octets per macroblock row / per clip */ \
-    const uint32_t mby = fastdiv(rem, A.qpr, A.magic_qpr, ox);                                         \
-    recon_inter_oct<PROF, NCWR, 0>(A, lds, clip, mby, ox, (int)threadIdx.x);                              \
+    block_octet(A, blockIdx.x, [&](uint32_t clip, uint32_t mby, uint32_t ox) { recon_inter_oct<PROF, NCWR, 0>(A, lds, clip, mby, ox, (int)threadIdx.x); }); \
   }
 // 4 waves per SIMD (108 VGPRs, no spills; 5 waves = 96 VGPRs spill 5 registers since the windows became 16-byte aligned and
 // measure the same) with 128 level words per macroblock in registers (96: 848x480 with its dense blocks 8 % slower; 192: no better).
@@ -1284,7 +1277,7 @@ struct QItem {
   uint32_t clip, mb;
   uint32_t w1;       // MbDesc.w1
   uint32_t pay;      // MbDesc.payload_off
-  uint32_t w3;       // MbDesc.w3: [0] 16x16 plane present, [4] its parameter is a wide one, [31:16] its parameter
+  uint32_t w3;       // MbDesc.w3, the 16x16 plane's bits of it (mobi_item_w3)
   uint32_t ncoef;
   bool has_deps;     // some macroblock its halo reads is an intra one of this step: poll the tags, read the halo afterwards
   bool publish;      // an intra macroblock of this step may read these pixels: write through, drain, publish the tag
@@ -1301,7 +1294,7 @@ __device__ __forceinline__ void recon_intra_quad(const MobiReconArgs &A, uint32_
   uint8_t *Gb = (uint8_t *)G;
   const int S = A.stride, lgS = 31 - __builtin_clz((unsigned)S), mbw = A.mbw;
   const uint32_t clip = I.clip, mb = I.mb, w1 = I.w1, w3 = I.w3, ncoef = I.ncoef;
-  const int t8 = (w1 >> 14) & 0x3F;
+  const int t8 = mobi_w1_t8mask(w1);
   const uint32_t *rec = A.payload + (size_t)I.clip * A.pay_clip_words + I.pay;
   const int mby = (int)(((float)mb + 0.5f) / (float)mbw), mbx = (int)mb - mby * mbw; // mb < 8192: the quotient is never within rounding of an integer
   const int off = ((mby * 16) << lgS) + mbx * 16;                                       // < 2^20: the macroblock's linear offset (MD.cs:212-217)
@@ -1313,7 +1306,7 @@ __device__ __forceinline__ void recon_intra_quad(const MobiReconArgs &A, uint32_
   __builtin_amdgcn_s_setprio(3); // (as in the inter kernel: requests first; 1.173 -> 1.162 ms)
   // ---- everything that can be asked for at once: block records, dequant scales, the first 64 level words, the halo ----
   const uint32_t recA = I.valid ? rec[l] : 0u, recB = I.valid && l < MOBI_INTRA_RECORDS - 16 ? rec[16 + l] : 0u;
-  const uint4 *sc_g = (const uint4 *)(A.scale + ((w1 >> 20) & 63) * MOBI_SCALE_STRIDE);
+  const uint4 *sc_g = (const uint4 *)(A.scale + mobi_w1_quant(w1) * MOBI_SCALE_STRIDE);
   const uint4 sc0 = sc_g[l], sc1 = sc_g[16 + (l & 3)];
   uint32_t cw[8]; // the first 128 level words of the macroblock
 #pragma unroll
@@ -1375,8 +1368,8 @@ __device__ __forceinline__ void recon_intra_quad(const MobiReconArgs &A, uint32_
   // ---- dequantise and scatter the level words ----
   wave_sync();
   auto scatter = [&](uint32_t e) {
-    const int t = e & 0x1FF, level = (int32_t)e >> 16, p = t & 63;
-    const int si = ((t8 >> (t >> 6)) & 1) ? p : 64 + (p & 15);
+    const int t = mobi_level_pos(e), level = mobi_level_value(e), p = mobi_pos_p(t);
+    const int si = ((t8 >> mobi_pos_area(t)) & 1) ? p : 64 + mobi_pos_p4(p);
     coef[t] = __mul24((int)G[IQ_SCALE + si], level);
   };
 #pragma unroll
@@ -1400,7 +1393,7 @@ __device__ __forceinline__ void recon_intra_quad(const MobiReconArgs &A, uint32_
   // round" took; an I-frame's ~3: two).  Pass 1 in place; pass 2 leaves int16 residuals (saturated: whatever does not fit is a
   // clamp-table fault anyway) in registers until every round has read its coefficients, then over the words of areas 0..2 ----
   {
-    const uint32_t cb = (I.valid && !(dbg & 1)) ? (w1 >> 8) & 0x3Fu : 0u;
+    const uint32_t cb = (I.valid && !(dbg & 1)) ? mobi_w1_cbp6(w1) : 0u;
     const uint32_t M = (uint32_t)__builtin_amdgcn_readlane((int)cb, 0) | ((uint32_t)__builtin_amdgcn_readlane((int)cb, 16) << 6) |
                        ((uint32_t)__builtin_amdgcn_readlane((int)cb, 32) << 12) | ((uint32_t)__builtin_amdgcn_readlane((int)cb, 48) << 18); // bit mb * 6 + area
     const int n_act = __builtin_popcount(M);
@@ -1426,7 +1419,7 @@ __device__ __forceinline__ void recon_intra_quad(const MobiReconArgs &A, uint32_
         if (act) idct_pass1(cx, cx, is8a, r);
         wave_sync();
         if (act) {
-          q[rd] = idct_pass2_pk(cx, is8a, r);
+          q[rd] = idct_pass2_res16(cx, is8a, r);
           idx[rd] = id;
           is8r[rd] = is8a;
         }
@@ -1466,8 +1459,8 @@ __device__ __forceinline__ void recon_intra_quad(const MobiReconArgs &A, uint32_
   // (area a, block s); its place in the list follows from how many areas before a are split. ----
   int n_iter;
   {
-    const uint64_t balA = __builtin_amdgcn_ballot_w64(((recA >> 5) & 1) != 0 && (l & 3) == 0);          // areas 0..3: lanes 0, 4, 8, 12 of the row
-    const uint64_t balB = __builtin_amdgcn_ballot_w64(((recB >> 5) & 1) != 0 && (l & 3) == 0 && l < 8); // areas 4, 5: lanes 0, 4
+    const uint64_t balA = __builtin_amdgcn_ballot_w64(mobi_rec_split(recA) && (l & 3) == 0);          // areas 0..3: lanes 0, 4, 8, 12 of the row
+    const uint64_t balB = __builtin_amdgcn_ballot_w64(mobi_rec_split(recB) && (l & 3) == 0 && l < 8); // areas 4, 5: lanes 0, 4
     const uint32_t mA = (uint32_t)(balA >> (lane & 48)) & 0x1111u, mB = (uint32_t)(balB >> (lane & 48)) & 0x11u;
     const uint32_t splits = (mA & 1) | ((mA >> 3) & 2) | ((mA >> 6) & 4) | ((mA >> 9) & 8) | ((mB & 1) << 4) | ((mB >> 4) << 5);
     const int nst = 6 + 3 * __builtin_popcount(splits);
@@ -1483,16 +1476,16 @@ __device__ __forceinline__ void recon_intra_quad(const MobiReconArgs &A, uint32_
     wave_sync();
     auto build = [=](int t, uint32_t rown, uint32_t r0, int &pos) -> uint2 {
       const int a = t >> 2, s = t & 3;
-      const bool split = (r0 >> 5) & 1, pre = (r0 >> 6) & 1;
+      const bool split = mobi_rec_split(r0), pre = mobi_rec_pre_plane(r0);
       pos = (s == 0 || split) ? a + 3 * __builtin_popcount(splits & ((1u << a) - 1u)) + s : -1;
       const uint32_t rs = split ? rown : r0;
-      const int mode = (int)(rs & 15);
-      const bool coded = (rs >> 4) & 1, luma = a < 4;
+      const int mode = mobi_rec_mode(rs);
+      const bool coded = mobi_rec_coded(rs), luma = a < 4;
       const int by = (luma ? (a >> 1) * 8 : 0) + (split ? (s >> 1) * 4 : 0), bx = (luma ? (a & 1) * 8 : 0) + (split ? (s & 1) * 4 : 0);
       const int o_blk = (luma ? 0 : a == 4 ? IQ_TCU : IQ_TCV) + (by + 1) * TP + 4 + bx;
       const bool k_dc = mode == 3, k_tap = mode < 2 || (mode >= 4 && mode <= 8);
       const bool plane_blk = mode == 2, plane_pre = pre && s == 0;
-      const uint32_t param = plane_blk ? rs >> 16 : r0 >> 16;
+      const uint32_t param = plane_blk ? rs >> MOBI_REC_PARAM_S : r0 >> MOBI_REC_PARAM_S; // (an expression: a reader function here changes the kernel's code)
       const int mi = !k_tap ? 0 : mode < 2 ? mode : mode - 2;
       const int tapbase = split ? MOBI_TAP_4X4 + mi * 16 : mi * 64;
       const int boff = (luma ? off : (off >> 1) + (a - 4) * (S >> 1)) + by * S + bx;
@@ -1530,9 +1523,9 @@ __device__ __forceinline__ void recon_intra_quad(const MobiReconArgs &A, uint32_
   uint32_t b0 = b0_early, b1 = b1_early;
   if (__builtin_amdgcn_ballot_w64(waits) != 0) {
     if (waits && l < MOBI_INTRA_DEPS) {
-      const uint32_t dep = (wd >> (16 * (l & 1))) & 0xFFFFu;
+      const uint32_t dep = (wd >> (MOBI_DEP_N * (l & 1))) & MOBI_MASK(MOBI_DEP); // (= mobi_dep_of_pair(wd, l & 1): through it mobi_recon_intra_walk gains an instruction)
       if (dep != MOBI_DEP_NONE && (FUSED || !(dep & MOBI_DEP_INTER))) { // (two launches: the inter macroblocks ran in the one before)
-        const uint32_t *f = A.done + (size_t)clip * A.n_mbs + (dep & 0x1FFFu);
+        const uint32_t *f = A.done + (size_t)clip * A.n_mbs + mobi_dep_mb(dep);
         int spins = 0;
         while (__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != A.step_tag) {
           __builtin_amdgcn_s_sleep(4);
@@ -1604,10 +1597,10 @@ __device__ __forceinline__ void recon_intra_quad(const MobiReconArgs &A, uint32_
   wave_sync();
 
   // ---- 16x16 plane (MD.cs:3017-3166): 64 words, four per lane ----
-  if (__builtin_amdgcn_ballot_w64((w3 & 1) != 0) != 0) {
-    if (w3 & 1) {
+  if (__builtin_amdgcn_ballot_w64(mobi_w3_has_plane16(w3)) != 0) {
+    if (mobi_w3_has_plane16(w3)) {
       const QNb nb{tile, TP + 4};
-      const int param = (w3 & MOBI_W3_WIDE) ? (int)rec[MOBI_INTRA_RECORDS + ncoef + 24] : (int)(int16_t)(w3 >> 16);
+      const int param = mobi_w3_wide(w3) ? (int)rec[MOBI_INTRA_RECORDS + ncoef + MOBI_WIDE_PLANE16] : mobi_w3_param(w3);
 #pragma unroll
       for (int u = 0; u < 4; u++) {
         const int w = u * 16 + l, yy = w >> 2, x0 = (w & 3) * 4;
@@ -1739,19 +1732,17 @@ __device__ __forceinline__ void recon_intra_quad(const MobiReconArgs &A, uint32_
   }
 }
 
-// Launch list built on the host (mobi_batch.h, LevelPlan): 16 bytes per intra macroblock, sorted by dependency level, every level
-// padded to a whole number of waves with null items (x = ~0).
-//   x = clip << 13 | mb   y = MbDesc.w1   z = MbDesc.payload_off (inside this step's arena)
-//   w = [0] 16x16 plane present  [1] has intra dependencies  [2] has intra dependents  [3] unused (r02: the left neighbour's last
-//       column is in the edge side buffer)  [14:5] number of level words  [31:16] plane parameter
+// Launch list built on the host (mobi_batch.h, LevelPlan) or by the group sort (mobi_gop.hip): 16 bytes per intra macroblock (mobi_cmd.h,
+// the intra launch item), sorted by dependency level, every level padded to a whole number of waves with MOBI_ITEM_NONE items.
+__device__ __forceinline__ QItem item_qitem(const uint4 item) {
+  const bool valid = item.x != MOBI_ITEM_NONE;
+  return QItem{valid, valid ? mobi_item_clip(item.x) : 0u, valid ? MOBI_ITEM_MB(item.x) : 0u, item.y, item.z, mobi_item_w3(item.w), mobi_item_coefs(item.w),
+               mobi_item_has_deps(item.w), mobi_item_publishes(item.w)};
+}
 extern "C" __global__ __launch_bounds__(64) void mobi_recon_intra(MobiReconArgs A, const uint4 *items, int n_items, int dbg) {
   __shared__ __attribute__((aligned(16))) uint32_t lds[4 * IQ_WORDS];
   const int lane = threadIdx.x;
-  const uint4 item = items[blockIdx.x * 4 + (lane >> 4)];
-  const bool valid = item.x != 0xFFFFFFFFu;
-  const QItem I{valid, valid ? item.x >> 13 : 0u, valid ? item.x & 0x1FFFu : 0u, item.y, item.z, item.w & (0xFFFF0001u | MOBI_W3_WIDE), (item.w >> 5) & 0x3FFu,
-                (item.w & 2) != 0, (item.w & 4) != 0};
-  recon_intra_quad(A, lds, I, lane, dbg);
+  recon_intra_quad(A, lds, item_qitem(items[blockIdx.x * 4 + (lane >> 4)]), lane, dbg);
 }
 
 // Small batches: the whole frame step in ONE launch.  Workgroups [0, n_inter) are octets of inter macroblocks, the rest fours of intra
@@ -1767,27 +1758,30 @@ extern "C" __global__ __launch_bounds__(64, 4) void mobi_recon_step(MobiReconArg
   __shared__ __attribute__((aligned(16))) uint8_t lds[P_BYTES];
   static_assert(P_BYTES >= 4 * IQ_WORDS * 4, "the intra fours fit the octet's LDS");
   if (blockIdx.x < n_inter) {
-    const uint32_t oi = (blockIdx.x & 7) * A.inter_per_xcd + (blockIdx.x >> 3);
-    if (oi >= A.qpc * (uint32_t)A.n_clips) return;
-    uint32_t rem, ox;
-    const uint32_t clip = fastdiv(oi, A.qpc, A.magic_qpc, rem);
-    const uint32_t mby = fastdiv(rem, A.qpr, A.magic_qpr, ox);
-    recon_inter_oct<0, 16, 1>(A, lds, clip, mby, ox, (int)threadIdx.x);
+    block_octet(A, blockIdx.x, [&](uint32_t clip, uint32_t mby, uint32_t ox) { recon_inter_oct<0, 16, 1>(A, lds, clip, mby, ox, (int)threadIdx.x); });
     return;
   }
   const int lane = threadIdx.x;
-  const uint4 item = items[(blockIdx.x - n_inter) * 4 + (lane >> 4)];
-  const bool valid = item.x != 0xFFFFFFFFu;
-  const QItem I{valid, valid ? item.x >> 13 : 0u, valid ? item.x & 0x1FFFu : 0u, item.y, item.z, item.w & (0xFFFF0001u | MOBI_W3_WIDE), (item.w >> 5) & 0x3FFu,
-                (item.w & 2) != 0, (item.w & 4) != 0};
-  recon_intra_quad<1>(A, (uint32_t *)lds, I, lane);
+  recon_intra_quad<1>(A, (uint32_t *)lds, item_qitem(items[(blockIdx.x - n_inter) * 4 + (lane >> 4)]), lane);
 }
 
 // Items as the device-side parser leaves them (mobi_dparse.hip): per clip, raster order, n_intra[clip] of them at a stride of
 // n_mbs.  Workgroup = slot * ceil(n_clips / 4) + clip quad: the four rows of a wave are the same slot of four clips, neighbours in
 // the dispatch order belong to different clips, so every clip advances along its own dependency chain at the same time, and what
 // a row waits for (raster-earlier, same clip) always sits in an earlier slot, i.e. was dispatched before it.  Who has to poll and
-// who has to publish is in the descriptor (w3 bits 1 and 2: the parsers set them where they list the dependencies).
+// who has to publish is in the descriptor (MOBI_W3_HAS_*: the parsers set them where they list the dependencies).
+__device__ __forceinline__ bool list_reaches(const MobiReconArgs &A, const uint32_t *n_intra, uint32_t n_intra_stride, uint32_t clip, uint32_t slot) {
+  const bool inb = clip < (uint32_t)A.n_clips;
+  const uint32_t ni = inb ? n_intra[(size_t)clip * n_intra_stride] : 0u;
+  return slot < ni;
+}
+// (the item itself is read by the caller: with that line in here mobi_recon_intra_cl computes the descriptor's address twice)
+__device__ __forceinline__ QItem list_qitem(const MobiReconArgs &A, uint32_t clip, uint32_t mb, bool valid) { // valid = list_reaches()
+  const MbDesc *desc = A.desc + (size_t)(valid ? clip : 0) * A.n_mbs + mb;
+  const uint32_t w3 = valid ? desc->w3 : 0u;
+  return QItem{valid, valid ? clip : 0u, mb, valid ? desc->w1 : 0u, valid ? desc->payload_off : 0u, mobi_item_w3(w3),
+               valid ? mobi_w2_coefs(desc->w2) : 0u, (w3 & MOBI_W3_HAS_INTRA_DEPS) != 0, (w3 & MOBI_W3_HAS_DEPENDENTS) != 0};
+}
 extern "C" __global__ __launch_bounds__(64) void mobi_recon_intra_cl(MobiReconArgs A, const uint32_t *items, const uint32_t *n_intra, uint32_t n_intra_stride,
                                                                       uint32_t quads, uint32_t magic_quads) {
   __shared__ __attribute__((aligned(16))) uint32_t lds[4 * IQ_WORDS];
@@ -1795,16 +1789,10 @@ extern "C" __global__ __launch_bounds__(64) void mobi_recon_intra_cl(MobiReconAr
   uint32_t cq;
   const uint32_t slot = fastdiv(blockIdx.x, quads, magic_quads, cq);
   const uint32_t clip = 4 * cq + (uint32_t)(lane >> 4);
-  const bool inb = clip < (uint32_t)A.n_clips;
-  const uint32_t ni = inb ? n_intra[(size_t)clip * n_intra_stride] : 0u;
-  const bool valid = slot < ni;
+  const bool valid = list_reaches(A, n_intra, n_intra_stride, clip, slot);
   if (__builtin_amdgcn_ballot_w64(valid) == 0) return;
-  const uint32_t mb = valid ? items[(size_t)clip * A.n_mbs + slot] & 0x1FFFu : 0u;
-  const MbDesc *desc = A.desc + (size_t)(valid ? clip : 0) * A.n_mbs + mb;
-  const uint32_t w3 = valid ? desc->w3 : 0u; // [1] has intra dependencies: poll their tags; [2] has intra dependents: publish its own
-  const QItem I{valid, valid ? clip : 0u, mb, valid ? desc->w1 : 0u, valid ? desc->payload_off : 0u, w3 & (0xFFFF0001u | MOBI_W3_WIDE),
-                valid ? desc->w2 & 0x3FFu : 0u, (w3 & 2u) != 0, (w3 & 4u) != 0};
-  recon_intra_quad(A, lds, I, lane);
+  const uint32_t mb = valid ? MOBI_ITEM_MB(items[(size_t)clip * A.n_mbs + slot]) : 0u;
+  recon_intra_quad(A, lds, list_qitem(A, clip, mb, valid), lane);
 }
 // When the host does not know the longest list (a step submitted before its parse has run: mobi_batch_submit launches
 // MOBI_ASYNC_INTRA_SLOTS slots, not one per macroblock of the picture), this launch follows: one workgroup per clip quad walks through
@@ -1819,16 +1807,10 @@ extern "C" __global__ __launch_bounds__(64) void mobi_recon_intra_walk(MobiRecon
     int lane = threadIdx.x;
     asm volatile("" : "+v"(lane)); // (opaque: nothing derived from the lane number is carried from round to round)
     const uint32_t clip = 4 * blockIdx.x + (uint32_t)(lane >> 4);
-    const bool inb = clip < (uint32_t)A.n_clips;
-    const uint32_t ni = inb ? n_intra[(size_t)clip * n_intra_stride] : 0u;
-    const bool valid = slot < ni;
+    const bool valid = list_reaches(A, n_intra, n_intra_stride, clip, slot);
     if (__builtin_amdgcn_ballot_w64(valid) == 0) return;
-    const uint32_t mb = valid ? items[(size_t)clip * A.n_mbs + slot] & 0x1FFFu : 0u;
-    const MbDesc *desc = A.desc + (size_t)(valid ? clip : 0) * A.n_mbs + mb;
-    const uint32_t w3 = valid ? desc->w3 : 0u;
-    const QItem I{valid, valid ? clip : 0u, mb, valid ? desc->w1 : 0u, valid ? desc->payload_off : 0u, w3 & (0xFFFF0001u | MOBI_W3_WIDE),
-                  valid ? desc->w2 & 0x3FFu : 0u, (w3 & 2u) != 0, (w3 & 4u) != 0};
-    recon_intra_quad(A, lds, I, lane);
+    const uint32_t mb = valid ? MOBI_ITEM_MB(items[(size_t)clip * A.n_mbs + slot]) : 0u;
+    recon_intra_quad(A, lds, list_qitem(A, clip, mb, valid), lane);
     wave_sync();
   }
 }
@@ -1856,6 +1838,20 @@ static int prof_env(const char *name) { const char *v = getenv(name); return v ?
 #else
 static int prof_env(const char *) { return 0; }
 #endif
+static uint32_t fastdiv_magic(uint32_t d) { // floor(2^32 / d), the divisor 1 saturated: fastdiv's estimate is then one short and corrected
+  const uint64_t m = ((uint64_t)1 << 32) / d;
+  return (uint32_t)(m > 0xFFFFFFFFull ? 0xFFFFFFFFull : m);
+}
+// the octet kernel's view of the batch (what block_octet reads); returns the grid: one workgroup per octet, a whole number per XCD
+static unsigned inter_grid(MobiReconArgs &b) {
+  b.qpr = ((uint32_t)b.mbw + 7) / 8;                    // octets per macroblock row
+  b.qpc = b.qpr * (uint32_t)(b.n_mbs / b.mbw);          // ... per clip
+  b.magic_qpr = fastdiv_magic(b.qpr);
+  b.magic_qpc = fastdiv_magic(b.qpc);
+  const unsigned g8 = (unsigned)(((long)b.qpc * b.n_clips + 7) / 8 * 8);
+  b.inter_per_xcd = g8 / 8;
+  return g8;
+}
 extern "C" int mobi_launch_inter(const MobiReconArgs *a, hipStream_t s) {
   if (a->n_clips <= 0) return 0;
   if (a->slot_bytes >= (1u << 24)) return (int)hipErrorInvalidValue; // 24-bit multiply in the kernel
@@ -1863,13 +1859,7 @@ extern "C" int mobi_launch_inter(const MobiReconArgs *a, hipStream_t s) {
   static const int lds_pad = prof_env("MOBI_LDS_PAD");
   static const int stop_stage = prof_env("MOBI_STOP_STAGE"); // (--profiling builds only: tools/exp_stages.sh)
   b.reserved21 = (uint32_t)stop_stage;
-  b.qpr = ((uint32_t)b.mbw + 7) / 8;                    // octets per macroblock row
-  b.qpc = b.qpr * (uint32_t)(b.n_mbs / b.mbw);          // ... per clip
-  auto magic = [](uint32_t d) { uint64_t m = ((uint64_t)1 << 32) / d; return (uint32_t)(m > 0xFFFFFFFFull ? 0xFFFFFFFFull : m); };
-  b.magic_qpr = magic(b.qpr);
-  b.magic_qpc = magic(b.qpc);
-  const unsigned g8 = (unsigned)(((long)b.qpc * b.n_clips + 7) / 8 * 8); // whole number of workgroups per XCD
-  b.inter_per_xcd = g8 / 8;
+  const unsigned g8 = inter_grid(b);
 #if defined(MOBI_PROFILING)
   if (b.prof) hipLaunchKernelGGL(mobi_recon_inter8_prof, dim3(g8), dim3(64), lds_pad, s, b);
   else
@@ -1890,13 +1880,7 @@ extern "C" int mobi_launch_step(const MobiReconArgs *a, const uint32_t *items_de
   if (a->slot_bytes >= (1u << 24)) return (int)hipErrorInvalidValue;
   MobiReconArgs b = *a;
   b.reserved21 = 0;
-  b.qpr = ((uint32_t)b.mbw + 7) / 8;
-  b.qpc = b.qpr * (uint32_t)(b.n_mbs / b.mbw);
-  auto magic = [](uint32_t d) { uint64_t m = ((uint64_t)1 << 32) / d; return (uint32_t)(m > 0xFFFFFFFFull ? 0xFFFFFFFFull : m); };
-  b.magic_qpr = magic(b.qpr);
-  b.magic_qpc = magic(b.qpc);
-  const unsigned g8 = (unsigned)(((long)b.qpc * b.n_clips + 7) / 8 * 8);
-  b.inter_per_xcd = g8 / 8;
+  const unsigned g8 = inter_grid(b);
   hipLaunchKernelGGL(mobi_recon_step, dim3(g8 + (unsigned)n_items / 4), dim3(64), 0, s, b, (const uint4 *)items_dev, (uint32_t)g8);
   return (int)hipGetLastError();
 }
@@ -1904,9 +1888,8 @@ extern "C" int mobi_launch_step(const MobiReconArgs *a, const uint32_t *items_de
 extern "C" int mobi_launch_intra_cl(const MobiReconArgs *a, const uint32_t *items_dev, const uint32_t *n_intra_dev, int n_intra_stride_words, int K, int walk, hipStream_t s) {
   if (K <= 0 || a->n_clips <= 0) return 0;
   const uint32_t quads = ((uint32_t)a->n_clips + 3) / 4;
-  const uint64_t m = ((uint64_t)1 << 32) / quads;
   hipLaunchKernelGGL(mobi_recon_intra_cl, dim3((unsigned)K * quads), dim3(64), 0, s, *a, items_dev, n_intra_dev, (uint32_t)n_intra_stride_words, quads,
-                     (uint32_t)(m > 0xFFFFFFFFull ? 0xFFFFFFFFull : m));
+                     fastdiv_magic(quads));
   if (walk && K < a->n_mbs)
     hipLaunchKernelGGL(mobi_recon_intra_walk, dim3(quads), dim3(64), 0, s, *a, items_dev, n_intra_dev, (uint32_t)n_intra_stride_words, (uint32_t)K);
   return (int)hipGetLastError();

@@ -22,7 +22,7 @@
 // of bits consumed: it refills lazily, one 16-bit word whenever fewer than 16 bits remain, so after c bits it has fetched 1 + ceil(c / 16)
 // words (every syntax element that consumes more than 16 bits between two of its checks is a bail-out here).
 //
-// What this walk shares with the other two -- geometry, the descriptor's words, the window and mode rules, the codes -- is mobi_syntax.h.
+// What this walk shares with the other two -- geometry, the window and mode rules, the codes -- is mobi_syntax.h; the descriptor's words are mobi_cmd.h's.
 // Host-compilable: tests/tools/mobi_lsparse_host.cpp runs the same functions lane by lane on the CPU against mobi_parse.cpp.
 #ifndef MOBI_LSPARSE_H
 #define MOBI_LSPARSE_H
@@ -285,8 +285,7 @@ LS_FN void ls_leaf(LsLane &s, S &m, const LsCtx &c, int wi, int hi, int x, int y
 #endif
       for (int k = 0; k < 2; k++) {
         const uint32_t a = k ? s.l1a : s.l0a, b = k ? s.l1b : s.l0b;
-        ls_cells(s, (int)(a & 15) * 2, (int)((a >> 4) & 15) * 2, (int)((a >> 8) & 3), (int)((a >> 10) & 3),
-                 mobi_cell((int)(int16_t)(b & 0xFFFF), (int)(int16_t)(b >> 16), (int)((a >> 12) & 7)));
+        ls_cells(s, mobi_leaf_x(a), mobi_leaf_y(a), mobi_leaf_wi(a), mobi_leaf_hi(a), mobi_cell(mobi_leaf_dx(b), mobi_leaf_dy(b), mobi_leaf_ref(a)));
       }
     }
     ls_cells(s, x, y, wi, hi, mobi_cell(dx, dy, ref));
@@ -343,7 +342,7 @@ LS_FN void ls_token(LsLane &s, S &m, const LsCtx &c) {
       else {
         const int idx = (s.blk_flags & 4) ? T[((s.blk_flags & 1) ? MOBI_DT_ZZ8 : MOBI_DT_ZZ4) + s.blk_p] : 0;
         s.blk_p++;
-        if (value != 0) s.pay[s.pay_base + s.mb_pay + s.hdr_words + s.n_coefs++] = (uint32_t)(s.blk_tile + idx) | ((uint32_t)(int)(int16_t)value << 16);
+        if (value != 0) s.pay[s.pay_base + s.mb_pay + s.hdr_words + s.n_coefs++] = mobi_level_word(s.blk_tile + idx, (int16_t)value);
         if (last & 1) {
           s.st = s.ret;
           if (s.st == LS_NEXT && !s.sub_mask && !s.area_mask) s.st = LS_MB_END;
@@ -474,7 +473,7 @@ LS_FN void ls_token_fast(LsLane &s, S &m, const LsCtx &c) {
       ls_take(s, pre + len);
       const int idx = (s.blk_flags & 4) ? T[((s.blk_flags & 1) ? MOBI_DT_ZZ8 : MOBI_DT_ZZ4) + p] : 0;
       s.blk_p = p + 1;
-      s.pay[s.pay_base + s.mb_pay + s.hdr_words + s.n_coefs++] = (uint32_t)(s.blk_tile + idx) | ((uint32_t)(int)(int16_t)value << 16);
+      s.pay[s.pay_base + s.mb_pay + s.hdr_words + s.n_coefs++] = mobi_level_word(s.blk_tile + idx, (int16_t)value);
       if (last & 1) {
         s.st = (s.ret == LS_NEXT && !s.sub_mask && !s.area_mask) ? LS_MB_END : (s.ret == LS_I_FSUB && !s.sub_mask) ? LS_I_FIXED : s.ret;
 #ifndef LS_NO_FOLD
@@ -550,7 +549,7 @@ LS_FN void ls_step_main(LsLane &s, S &m, const LsCtx &c) {
     } else {
       uint32_t *rec_out = s.pay + s.pay_base + s.mb_pay;
       for (int i = 0; i < MOBI_INTRA_RECORDS; i++) rec_out[i] = m.rec(i);
-      w4 = w5 = w6 = w7 = MOBI_DEP_NONE | (MOBI_DEP_NONE << 16); // ls_intra_deps fills them in
+      w4 = w5 = w6 = w7 = mobi_dep_pair(MOBI_DEP_NONE, MOBI_DEP_NONE); // ls_intra_deps fills them in
       s.items[s.n_items++] = MOBI_ITEM(s.clip, s.mb);
     }
     MbDesc d;
@@ -722,7 +721,7 @@ LS_FN void ls_step_intra(LsLane &s, S &m, const LsCtx &c) {
             const int p = ls_se(s);
             ls_check_intra_reads(s, c, 2, s.cur_off);
             if (p < -32768 || p > 32767) ls_bail(s, 13);
-            s.w3 = 1u | ((uint32_t)(uint16_t)(int16_t)p << 16);
+            s.w3 = mobi_w3_plane16(p);
           }
           s.i_mode = md;
           s.st = LS_I_FIXED;

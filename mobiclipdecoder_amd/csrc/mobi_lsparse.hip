@@ -211,7 +211,7 @@ extern "C" __global__ __launch_bounds__(64) void mobi_ls_deps(MobiDevParseArgs A
   const uint32_t idx = chunk * 64 + threadIdx.x, n_mbs = (uint32_t)(A.mbw * A.mbh);
   if (idx >= r->n_intra) return;
   const LsGeom g{A.width, A.height, A.stride, A.lg, A.mbw};
-  const uint32_t mb = A.items[(size_t)clip * n_mbs + idx] & 0x1FFFu;
+  const uint32_t mb = MOBI_ITEM_MB(A.items[(size_t)clip * n_mbs + idx]);
   if (!ls_intra_deps(g, A.desc + (size_t)clip * n_mbs, (int)mb)) A.res[clip].pad = 0; // more than eight: mobi_parse_frames refuses the stream; let it
 }
 

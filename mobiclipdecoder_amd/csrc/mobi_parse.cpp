@@ -194,8 +194,8 @@ void MobiStreamParser::mc_leaf(int wi, int hi, int x, int y, int ref, int dx, in
 void MobiStreamParser::build_cells() {
   for (int i = 0; i + 1 < n_leaf_words_; i += 2) {
     const uint32_t w0 = leaves_[i], mv = leaves_[i + 1];
-    const int x = (int)(w0 & 15) * 2, y = (int)((w0 >> 4) & 15) * 2, w = 16 >> ((w0 >> 8) & 3), h = 16 >> ((w0 >> 10) & 3);
-    const uint32_t cell = mobi_cell((int16_t)(mv & 0xFFFF), (int16_t)(mv >> 16), (int)((w0 >> 12) & 7));
+    const int x = mobi_leaf_x(w0), y = mobi_leaf_y(w0), w = 16 >> mobi_leaf_wi(w0), h = 16 >> mobi_leaf_hi(w0);
+    const uint32_t cell = mobi_cell(mobi_leaf_dx(mv), mobi_leaf_dy(mv), mobi_leaf_ref(w0));
     for (int cy = y >> 1; cy < (y + h) >> 1; cy++)
       for (int cx = x >> 1; cx < (x + w) >> 1; cx++) cells_[cy * 8 + cx] = cell;
   }
@@ -292,7 +292,7 @@ void MobiStreamParser::resid_block(int area, int sub, bool is8) {
       // The reference picks a reduced IDCT from the final scan index (MD.cs:2939-2942, 2954-2955); the reduced transforms only
       // look at part of the block, but for q >= 12 nothing they skip can be nonzero: scan positions 0, 0..2, 0..9 map inside the
       // respective regions (tests/test_oracle_identities.py pins that property of the zigzag tables), so every level is kept.
-      if (value != 0) coefs_[n_coefs_++] = (uint32_t)(tile + (int)(word & 0xFF)) | ((uint32_t)(int)(int16_t)value << 16); // = mobi_coef()
+      if (value != 0) coefs_[n_coefs_++] = mobi_level_word(tile + (int)(word & 0xFF), (int16_t)value);
       else frame_host_only_ = true; // (a token without a level: the device parsers stop there, mobi_state.h)
     } else { // MD.cs:3424-3429 as written
       odd = true;
@@ -319,7 +319,7 @@ void MobiStreamParser::resid_block(int area, int sub, bool is8) {
         frame_fault_ = true; // (the frame is rejected at its end, as a fault the kernels find is; the word itself no longer matters)
         continue;
       }
-      coefs_[n_coefs_++] = (uint32_t)(tile + p) | 0x8000u | ((uint32_t)v << 16); // bit 15: a value, not a level (literal_frame clears it)
+      coefs_[n_coefs_++] = mobi_level_word(tile + p, v) | MOBI_LEVEL_IS_VALUE; // a value, not a level (literal_frame clears the mark)
     }
   }
   if (big && !odd && !surely_faults(is8, variant)) big_unsure_ = true;
@@ -389,18 +389,18 @@ void MobiStreamParser::literal_frame(ParsedFrame &out) {
     const uint32_t t8 = mobi_w1_t8mask(d.w1);
     uint32_t *w = out.payload.data() + d.payload_off + mobi_levels_offset(d.w1);
     for (uint32_t i = 0, n = mobi_w2_coefs(d.w2); i < n; i++) {
-      if (w[i] & 0x8000u) { w[i] &= ~0x8000u; continue; }
-      const int t = (int)(w[i] & 0x1FF), p = t & 63;
-      const int32_t v = sc[((t8 >> (t >> 6)) & 1) ? p : 64 + (p & 15)] * (int32_t)(int16_t)(w[i] >> 16);
+      if (w[i] & MOBI_LEVEL_IS_VALUE) { w[i] &= ~MOBI_LEVEL_IS_VALUE; continue; }
+      const int t = (int)mobi_level_pos(w[i]), p = mobi_pos_p(t);
+      const int32_t v = sc[((t8 >> mobi_pos_area(t)) & 1) ? p : 64 + mobi_pos_p4(p)] * mobi_level_value(w[i]);
       if (v != (int16_t)v) { // an ordinary block with a coefficient beyond int16: resid_block looked at its transform (big_unsure_)
         if (big_unsure_) refuse(MOBI_REFUSE_RUN);
         frame_fault_ = true;
-        w[i] = (uint32_t)t; // (level 0: the frame is rejected, the word no longer matters)
+        w[i] = mobi_level_word(t, 0); // (level 0: the frame is rejected, the word no longer matters)
         continue;
       }
-      w[i] = (uint32_t)t | ((uint32_t)v << 16);
+      w[i] = mobi_level_word(t, v);
     }
-    d.w1 = (d.w1 & ~(63u << 20)) | ((uint32_t)MOBI_SCALE_LITERAL << 20);
+    d.w1 = mobi_w1_with_quant(d.w1, MOBI_SCALE_LITERAL);
   }
 }
 void MobiStreamParser::resid_area(int area) { // loc_11652C, MD.cs:2909-2929
@@ -439,9 +439,9 @@ int MobiStreamParser::pmode(int ci, bool four) {
   return mode;
 }
 // A plane parameter for record r (24: the 16x16 plane's): the record's 16-bit field, or -- a code of 33 bits and more -- a wide parameter
-// behind the macroblock's level words (mobi_cmd.h).  Returns the bits to OR into the record (MbDesc.w3 for r = 24: shifted by the caller).
+// behind the macroblock's level words (mobi_cmd.h).  Returns the bits to OR into the record (r = MOBI_WIDE_PLANE16: see intra_full).
 uint32_t MobiStreamParser::plane_param(int p, int r) {
-  if (p >= -32768 && p <= 32767) return (uint32_t)(uint16_t)(int16_t)p << 16;
+  if (p >= -32768 && p <= 32767) return mobi_rec_param_bits(p);
   if (!any_wide_) memset(wide_, 0, sizeof(wide_));
   any_wide_ = true;
   frame_host_only_ = true;
@@ -502,8 +502,7 @@ void MobiStreamParser::intra_full() { // DecIntraFullBlockPMode, MD.cs:1759-1786
     m = 9;
     const int p = se();
     check_intra_reads(2, cur_off_);
-    const uint32_t pp = plane_param(p, 24);
-    w3_ = 1u | (pp == MOBI_REC_WIDE ? MOBI_W3_WIDE : pp);
+    w3_ = plane_param(p, MOBI_WIDE_PLANE16) == MOBI_REC_WIDE ? mobi_w3_plane16_wide() : mobi_w3_plane16(p);
   }
   for (int k = 0; k < 4; k++) intra_area_fixed(k, m, (cbp >> k) & 1);
   intra_chroma(cbp);
@@ -611,10 +610,10 @@ void MobiStreamParser::finish_levels(ParsedFrame &out) {
   const int n = (int)out.desc.size();
   const long S = g_.stride;
   std::vector<uint16_t> level(n, 0);
-  std::vector<uint8_t> flag(n, 0); // launch-item flags: 2 = has intra dependencies, 4 = has intra dependents
+  std::vector<uint8_t> flag(n, 0); // MOBI_W3_HAS_INTRA_DEPS | MOBI_W3_HAS_DEPENDENTS, until every macroblock's dependents are known
   int maxl = 0, n_intra = 0;
   for (int mb = 0; mb < n; mb++) {
-    if ((out.desc[mb].w1 & 1) != MOBI_MB_INTRA) continue;
+    if (!mobi_w1_intra(out.desc[mb].w1)) continue;
     n_intra++;
     long off = (long)(mb / g_.mbw) * 16 * S + (mb % g_.mbw) * 16;
     int lv = 0;
@@ -625,7 +624,7 @@ void MobiStreamParser::finish_levels(ParsedFrame &out) {
       // ... but the dependency list names every raster-earlier owner: in a one-launch step the inter quads run alongside
       const int added = mobi_dep_add(deps, n_deps, mb, o, [&](int k) { return level[k] != 0; });
       if (added == MOBI_DEP_FULL) fail(MOBI_E_UNSUPPORTED);
-      if (added == MOBI_DEP_ADDED_INTRA) { flag[mb] |= 2; flag[o] |= 4; }
+      if (added == MOBI_DEP_ADDED_INTRA) { flag[mb] |= MOBI_W3_HAS_INTRA_DEPS; flag[o] |= MOBI_W3_HAS_DEPENDENTS; }
     };
     mobi_halo_owners(g_.width, g_.height, g_.stride, g_.lg, g_.mbw, off, dep); // (the probes and their order: mobi_syntax.h)
     level[mb] = (uint16_t)(lv + 1);
@@ -640,10 +639,10 @@ void MobiStreamParser::finish_levels(ParsedFrame &out) {
   auto klass = [&](int mb) {
     const MbDesc &d = out.desc[mb];
     int splits = 0;
-    for (int a = 0; a < 6; a++) splits += (out.payload[d.payload_off + 4 * a] >> 5) & 1; // the area's first block record, bit 5 (mobi_kernels.hip, the schedule)
+    for (int a = 0; a < 6; a++) splits += mobi_rec_split(out.payload[d.payload_off + 4 * a]); // the area's first block record (mobi_kernels.hip, the schedule)
     const int mbx = mb % g_.mbw;
     const bool interior = mbx >= 1 && mbx + 1 < g_.mbw && mb >= g_.mbw;
-    return (interior ? 0 : 8) + ((flag[mb] & 4) ? 4 : 0) + std::min(splits, 3);
+    return (interior ? 0 : 8) + ((flag[mb] & MOBI_W3_HAS_DEPENDENTS) ? 4 : 0) + std::min(splits, 3);
   };
   out.class_start.assign((size_t)(maxl + 1) * MOBI_INTRA_CLASSES + 1, 0); // [L * MOBI_INTRA_CLASSES + class] -> first index into intra_mbs / intra_items; [.. + 1] = its end
   std::vector<uint8_t> kl(n, 0);
@@ -662,13 +661,13 @@ void MobiStreamParser::finish_levels(ParsedFrame &out) {
     if (level[mb]) {
       const uint32_t at = cursor[(size_t)level[mb] * MOBI_INTRA_CLASSES + kl[mb]]++;
       out.intra_mbs[at] = (uint32_t)mb;
+      out.desc[mb].w3 |= flag[mb]; // (the device parsers' item lists carry no flags: mobi_recon_intra_cl reads these two bits from the descriptor)
       const MbDesc d = out.desc[mb];
       uint32_t *it = &out.intra_items[(size_t)at * 4];
       it[0] = (uint32_t)mb;
       it[1] = d.w1;
       it[2] = d.payload_off;
-      it[3] = (d.w3 & (0xFFFF0001u | MOBI_W3_WIDE)) | flag[mb] | (kl[mb] >= 8 ? 8u : 0u) | ((d.w2 & 0x3FFu) << 5);
-      out.desc[mb].w3 |= flag[mb]; // (the device parsers' item lists carry no flags: mobi_recon_intra_cl reads these two bits from the descriptor)
+      it[3] = MOBI_ITEM_FLAGS(d.w3, d.w2) | (kl[mb] >= 8 ? MOBI_ITEM_EDGE : 0u);
     }
   out.hdr.n_mbs = (uint32_t)n;
   out.hdr.n_intra = (uint32_t)n_intra;

@@ -102,16 +102,16 @@ MOBI_ST_FN void mobi_tail_scan_init(MobiTailScan &s) { s.last = s.last8 = s.last
 MOBI_ST_FN void mobi_tail_scan_mb(MobiTailScan &s, const uint32_t *w, int n, uint32_t woff, uint32_t t8, const uint8_t *izz8, const uint8_t *izz4) {
   int end = n;
   while (end > 0 && !s.done) { // blocks from the last to the first: a block = a run of words of one (area, 4x4 sub-block)
-    const uint32_t t = w[end - 1] & 0x1FF, area = t >> 6;
+    const uint32_t t = mobi_level_pos(w[end - 1]), area = mobi_pos_area(t);
     const bool is8 = (t8 >> area) & 1;
-    const uint32_t key = is8 ? area << 2 : (area << 2) | ((t >> 4) & 3);
+    const uint32_t key = is8 ? area << 2 : (area << 2) | mobi_pos_sub(t);
     int beg = end - 1;
     while (beg > 0) {
-      const uint32_t u = w[beg - 1] & 0x1FF, ua = u >> 6;
-      if ((is8 ? ua << 2 : (ua << 2) | ((u >> 4) & 3)) != key) break;
+      const uint32_t u = mobi_level_pos(w[beg - 1]), ua = mobi_pos_area(u);
+      if ((is8 ? ua << 2 : (ua << 2) | mobi_pos_sub(u)) != key) break;
       beg--;
     }
-    const int p = (is8 ? izz8[t & 63] : izz4[t & 15]) + 1, variant = mobi_variant(is8, p);
+    const int p = (is8 ? izz8[mobi_pos_p(t)] : izz4[mobi_pos_p4(t)]) + 1, variant = mobi_variant(is8, p);
     const uint32_t rec = 0x80000000u | ((uint32_t)(end - beg) << 22) | (woff + (uint32_t)beg);
     if (!s.last) { s.last = rec; s.last_is8 = is8; s.last_variant = (uint32_t)variant; }
     if (is8) {
@@ -127,8 +127,8 @@ MOBI_ST_FN void mobi_tail_store(uint32_t *c, int n_zero, uint32_t rec, const uin
   for (int i = 0; i < n_zero; i++) c[i] = 0;
   const uint32_t *w = pay + (rec & 0x3FFFFFu);
   for (uint32_t i = 0, n = (rec >> 22) & 0x7F; i < n; i++) {
-    const uint32_t p = is8 ? w[i] & 63 : w[i] & 15;
-    c[p] = (uint32_t)scale[is8 ? p : 64 + p] * (uint32_t)(int32_t)(int16_t)(w[i] >> 16); // (dequant word >> 8) * level, MD.cs:3427-3429
+    const uint32_t p = is8 ? mobi_pos_p(w[i]) : mobi_pos_p4(w[i]);
+    c[p] = (uint32_t)scale[is8 ? p : 64 + p] * (uint32_t)mobi_level_value(w[i]); // (dequant word >> 8) * level, MD.cs:3427-3429
   }
 }
 MOBI_ST_FN void mobi_tail_finish(const MobiTailScan &s, const uint32_t *pay, const int32_t *scale, const MobiDevTail &in, MobiDevTail &out) {

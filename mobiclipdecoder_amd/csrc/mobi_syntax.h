@@ -1,4 +1,4 @@
-// mobi_syntax.h -- what the parsers know about the bitstream's leaves and about the command list's words, ONCE.
+// mobi_syntax.h -- what the parsers know about the bitstream's leaves, ONCE.
 //
 // Three walks read the same grammar -- mobi_parse.cpp (recursion, exceptions), mobi_dparse.hip (a work stack, a sticky error code),
 // mobi_lsparse.h (a state machine that bails out) -- and mobi_gop.h reads the frame header a fourth time.  Their control flow differs for
@@ -6,8 +6,8 @@
 // every error policy (throw, fail, bail) stays with the caller, which gets a bool or a code to act on.
 //
 // One copy is NOT here: mobi_kernels.hip's Geo has its own owner_luma / owner_chroma.  That file is one of the four whose hash says whether
-// the recorded memory-traffic profile still belongs to the kernels (bench.py), so it does not take a new include for two functions.  For the
-// same reason the command-list words are packed and read here and not in mobi_cmd.h, which only describes them.
+// the recorded memory-traffic profile still belongs to the kernels (bench.py), so it does not take a new include for two functions.
+// The command list's words -- every position, width, reader and writer -- are mobi_cmd.h's; nothing here knows where a field sits.
 #ifndef MOBI_SYNTAX_H
 #define MOBI_SYNTAX_H
 #include <stdint.h>
@@ -81,7 +81,7 @@ MOBI_CMD_FN int mobi_dep_add(uint32_t *deps, int &n, int mb, int o, I is_intra) 
   if (o < 0 || o >= mb) return MOBI_DEP_SKIP;
   MOBI_SYN_NOUNROLL
   for (int k = 0; k < n; k++)
-    if ((int)(deps[k] & 0x1FFF) == o) return MOBI_DEP_SKIP;
+    if ((int)mobi_dep_mb(deps[k]) == o) return MOBI_DEP_SKIP;
   if (n == MOBI_INTRA_DEPS) return MOBI_DEP_FULL;
   const bool intra = is_intra(o);
   deps[n++] = (uint32_t)o | (intra ? 0u : MOBI_DEP_INTER);
@@ -91,14 +91,11 @@ MOBI_CMD_FN int mobi_dep_add(uint32_t *deps, int &n, int mb, int o, I is_intra) 
 MOBI_CMD_FN void mobi_deps_pack(uint32_t *deps, int n, uint32_t &w4, uint32_t &w5, uint32_t &w6, uint32_t &w7) {
   MOBI_SYN_NOUNROLL
   for (int k = n; k < MOBI_INTRA_DEPS; k++) deps[k] = MOBI_DEP_NONE;
-  w4 = deps[0] | (deps[1] << 16);
-  w5 = deps[2] | (deps[3] << 16);
-  w6 = deps[4] | (deps[5] << 16);
-  w7 = deps[6] | (deps[7] << 16);
+  w4 = mobi_dep_pair(deps[0], deps[1]);
+  w5 = mobi_dep_pair(deps[2], deps[3]);
+  w6 = mobi_dep_pair(deps[4], deps[5]);
+  w7 = mobi_dep_pair(deps[6], deps[7]);
 }
-// MbDesc.w3 of an intra macroblock, bits the dependency lists set: some dependency is intra / some intra macroblock depends on this one
-#define MOBI_W3_HAS_INTRA_DEPS 2u
-#define MOBI_W3_HAS_DEPENDENTS 4u
 
 // ---------------------------------------------------------------- motion (MD.cs:400-456)
 // Would CopyBlock throw?  Rows are visited top to bottom, so first row / last row bound the rest.  One w x h window at `pos` with
@@ -125,41 +122,24 @@ MOBI_CMD_FN bool mobi_mc_windows_ok(A S, int height, A off, int w, int h, int dx
 }
 // an inter macroblock of exactly two leaves (their mobi_leaf_w0 words, in stream order): two 16x8 halves, two 8x16 halves, or neither
 MOBI_CMD_FN int mobi_dual_kind(uint32_t w0a, uint32_t w0b) {
-  const uint32_t a = w0a & 0xFFF, b = w0b & 0xFFF; // x/2 | y/2 << 4 | wi << 8 | hi << 10
-  if (a == (0u | (1u << 10)) && b == ((4u << 4) | (1u << 10))) return MOBI_DUAL_TB;
-  if (a == (0u | (1u << 8)) && b == (4u | (1u << 8))) return MOBI_DUAL_LR;
+  const uint32_t a = mobi_leaf_shape(w0a), b = mobi_leaf_shape(w0b); // position and size, whatever the ref slot
+  if (a == mobi_leaf_w0(0, 0, 0, 1, 0) && b == mobi_leaf_w0(0, 8, 0, 1, 0)) return MOBI_DUAL_TB;
+  if (a == mobi_leaf_w0(0, 0, 1, 0, 0) && b == mobi_leaf_w0(8, 0, 1, 0, 0)) return MOBI_DUAL_LR;
   return MOBI_DUAL_NONE;
 }
 // Leaf record i (0: leaf A, 1: leaf B) of a macroblock that travels without a cell map: positions and phases instead of a motion vector
 // (MD.cs:400-416).  pos_y / pos_c: MbDesc.w3 / w4 (A) or w5 / w6 (B); returns the bits of MbDesc.w2.
 template <class A>
 MOBI_CMD_FN uint32_t mobi_leaf_record(int i, uint32_t w0, uint32_t w1, A cur_off, A S, uint32_t &pos_y, uint32_t &pos_c) {
-  const int ref = (w0 >> 12) & 7;
-  const int dx = (int16_t)(w1 & 0xFFFF), dy = (int16_t)(w1 >> 16), cdx = dx >> 1, cdy = dy >> 1;
+  const int ref = mobi_leaf_ref(w0);
+  // (dx, dy as expressions: through mobi_leaf_dy() the device parser's kernel compiles to other instructions)
+  const int dx = (int16_t)(w1 & MOBI_MASK(MOBI_LEAF_DX)), dy = (int16_t)(w1 >> MOBI_LEAF_DY_S), cdx = dx >> 1, cdy = dy >> 1;
   pos_y = (uint32_t)(int32_t)(cur_off + (A)(dy >> 1) * S + (dx >> 1));
   pos_c = (uint32_t)(int32_t)(cur_off / 2 + (A)(cdy >> 1) * S + (cdx >> 1));
-  return ((uint32_t)ref << (10 + 3 * i)) | ((uint32_t)((dx & 1) | ((dy & 1) << 1)) << (16 + 4 * i)) | ((uint32_t)((cdx & 1) | ((cdy & 1) << 1)) << (18 + 4 * i));
+  // = mobi_w2_leaf(i, ref, phase, chroma phase), spelled out (through the function mobi_parse_frames_ls compiles to another order)
+  return ((uint32_t)ref << (MOBI_W2_REFA_S + MOBI_W2_REF_STEP * i)) | ((uint32_t)((dx & 1) | ((dy & 1) << 1)) << (MOBI_W2_PHA_S + MOBI_W2_PH_STEP * i)) |
+         ((uint32_t)((cdx & 1) | ((cdy & 1) << 1)) << (MOBI_W2_CPHA_S + MOBI_W2_PH_STEP * i));
 }
-
-// ---------------------------------------------------------------- command-list words (layout: mobi_cmd.h)
-MOBI_CMD_FN uint32_t mobi_desc_w1(int type, uint32_t n_leaves, uint32_t cbp6, uint32_t t8mask, uint32_t quant, int dual) {
-  return (uint32_t)type | (n_leaves << 1) | (cbp6 << 8) | (t8mask << 14) | ((quant & 63) << 20) | ((uint32_t)dual << 26);
-}
-MOBI_CMD_FN bool mobi_w1_intra(uint32_t w1) { return (w1 & 1) == MOBI_MB_INTRA; }
-MOBI_CMD_FN uint32_t mobi_w1_leaves(uint32_t w1) { return (w1 >> 1) & 0x7F; }
-MOBI_CMD_FN uint32_t mobi_w1_t8mask(uint32_t w1) { return (w1 >> 14) & 0x3F; }
-MOBI_CMD_FN uint32_t mobi_w1_quant(uint32_t w1) { return (w1 >> 20) & 63; }
-MOBI_CMD_FN uint32_t mobi_w1_dual(uint32_t w1) { return (w1 >> 26) & 3; }
-MOBI_CMD_FN uint32_t mobi_w2_coefs(uint32_t w2) { return w2 & 0x3FF; }
-// what an inter macroblock's payload starts with: nothing when its one or two leaves ride in the descriptor, else the MV cell map
-MOBI_CMD_FN uint32_t mobi_inter_hdr_words(uint32_t n_leaves, int dual) { return (n_leaves > 1 && !dual) ? MOBI_MV_CELLS : 0; }
-// where a macroblock's level words start inside its payload
-MOBI_CMD_FN uint32_t mobi_levels_offset(uint32_t w1) {
-  return mobi_w1_intra(w1) ? MOBI_INTRA_RECORDS : mobi_inter_hdr_words(mobi_w1_leaves(w1), (int)mobi_w1_dual(w1));
-}
-// intra launch item, word 0; words 1..3: MbDesc.w1, MbDesc.payload_off, flags (mobi_recon_intra in mobi_kernels.hip)
-#define MOBI_ITEM(clip, mb) (((uint32_t)(clip) << 13) | (uint32_t)(mb))
-#define MOBI_ITEM_MB(item) ((item) & 0x1FFFu)
 
 // ---------------------------------------------------------------- intra syntax
 // Reads PredictIntra (MD.cs:1883-2774) / the plane predictors (:3017-3327) make outside the block at plane offset `off`: the row above needs
@@ -234,7 +214,7 @@ MOBI_CMD_FN int mobi_rd_se(R &r) { return mobi_gamma_signed(mobi_rd_ue(r)); }
 // level << 4 | run << 9 | last << 15), B: its escape table; TA / TB are the caller's pointer types (the device keeps them in LDS).
 // Returns the token's "last" bit.
 template <class R, class TA, class TB>
-MOBI_CMD_FN uint32_t mobi_rd_token(R &r, TA A, TB B, int &skip, int &value) {
+MOBI_CMD_RT uint32_t mobi_rd_token(R &r, TA A, TB B, int &skip, int &value) {
   uint32_t e;
   if ((r.win >> 25) == 3) { // escape prefix 0000011
     r.win <<= 7;

@@ -47,8 +47,8 @@ void dequant_into(int q, const uint32_t *coefs, int n, uint32_t t8mask, int coef
   mobi_build_scale_table(q, sc);
   for (int i = 0; i < n; i++) {
     uint32_t e = coefs[i];
-    int t = e & 0x1FF, level = (int32_t)e >> 16, area = t >> 6, p = t & 63;
-    int scale = ((t8mask >> area) & 1) ? sc[p] : sc[64 + (p & 15)];
+    int t = (int)mobi_level_pos(e), level = mobi_level_value(e), area = (int)mobi_level_area(e), p = mobi_pos_p(t);
+    int scale = ((t8mask >> area) & 1) ? sc[p] : sc[64 + mobi_pos_p4(p)];
     coef_tile[t] = scale * level;
   }
 }
@@ -90,7 +90,7 @@ void exec_inter(Interp &I, int mb, const MbDesc &d) {
   const MobiGeom &g = I.g;
   const long S = g.stride;
   const uint32_t *pl = I.pf.payload.data() + d.payload_off;
-  const int nl = (int)mobi_w1_leaves(d.w1), cbp6 = (d.w1 >> 8) & 0x3F, t8 = (int)mobi_w1_t8mask(d.w1), ncoef = (int)mobi_w2_coefs(d.w2);
+  const int nl = (int)mobi_w1_leaves(d.w1), cbp6 = (int)mobi_w1_cbp6(d.w1), t8 = (int)mobi_w1_t8mask(d.w1), ncoef = (int)mobi_w2_coefs(d.w2);
   const long off = (long)(mb / g.mbw) * 16 * S + (mb % g.mbw) * 16;
   uint8_t ty[16 * TP], tc[2][8 * TP]; // prediction tiles (interior only; pitch TP, origin at byte 0)
   // per pixel group: the leaf record of the descriptor (single / two halves) or the MV cell under it (deeper trees).
@@ -101,11 +101,11 @@ void exec_inter(Interp &I, int mb, const MbDesc &d) {
     Src s;
     if (nl == 1 || dual) {
       const int i = dual && (dual == MOBI_DUAL_TB ? celly >= 4 : cellx >= 4) ? 1 : 0;
-      s.ref = (d.w2 >> (10 + 3 * i)) & 7;
+      s.ref = (int)mobi_w2_ref(d.w2, i);
       s.ypos = (int32_t)(i ? d.w5 : d.w3);
       s.cpos = (int32_t)(i ? d.w6 : d.w4);
-      s.yph = (d.w2 >> (16 + 4 * i)) & 3;
-      s.cph = (d.w2 >> (18 + 4 * i)) & 3;
+      s.yph = (int)mobi_w2_phase(d.w2, i);
+      s.cph = (int)mobi_w2_cphase(d.w2, i);
     } else {
       const uint32_t c = pl[celly * 8 + cellx];
       const int dx = mobi_cell_dx(c), dy = mobi_cell_dy(c), cdx = dx >> 1, cdy = dy >> 1;
@@ -149,9 +149,9 @@ void exec_inter(Interp &I, int mb, const MbDesc &d) {
     int coef[6 * 64];
     dequant_into(mobi_w1_quant(d.w1), cw, ncoef, t8, coef);
     for (int a = 0; a < 6; a++) {
-      if (!((cbp6 >> a) & 1)) continue;
+      if (!mobi_w1_area_coded(d.w1, a)) continue;
       uint8_t *t = a < 4 ? ty + (a >> 1) * 8 * TP + (a & 1) * 8 : tc[a - 4];
-      resid_area(coef + 64 * a, (t8 >> a) & 1, 0xF, t, TP, &I.fault);
+      resid_area(coef + 64 * a, mobi_w1_area_is8(d.w1, a), 0xF, t, TP, &I.fault);
     }
   }
   uint8_t *y0 = I.Y(0), *uv0 = I.UV(0);
@@ -221,22 +221,22 @@ void exec_intra(Interp &I, int mb, const MbDesc &d) {
   int coef[6 * 64];
   dequant_into(mobi_w1_quant(d.w1), rec + mobi_levels_offset(d.w1), ncoef, t8, coef);
   const int32_t *wide = (const int32_t *)rec + MOBI_INTRA_RECORDS + ncoef; // parameters that do not fit a record's 16 bits (mobi_cmd.h)
-  auto param_of = [&](uint32_t r, int idx) { return (r & MOBI_REC_WIDE) ? wide[idx] : (int)(int16_t)(r >> 16); };
-  if (d.w3 & 1) run_block(I, ty, 0, 0, 16, 2, (d.w3 & MOBI_W3_WIDE) ? wide[24] : (int16_t)(d.w3 >> 16), false, nullptr, false, 0, off, false);
+  auto param_of = [&](uint32_t r, int idx) { return mobi_rec_wide(r) ? wide[idx] : mobi_rec_param(r); };
+  if (mobi_w3_has_plane16(d.w3)) run_block(I, ty, 0, 0, 16, 2, mobi_w3_wide(d.w3) ? wide[MOBI_WIDE_PLANE16] : mobi_w3_param(d.w3), false, nullptr, false, 0, off, false);
   for (int a = 0; a < 6; a++) {
     uint8_t *tile = a < 4 ? ty : tc[a - 4];
     int ay = a < 4 ? (a >> 1) * 8 : 0, ax = a < 4 ? (a & 1) * 8 : 0;
     long aoff = a < 4 ? off + (long)ay * S + ax : off / 2 + (a - 4) * (S / 2);
     uint32_t r0 = rec[a * 4];
-    if ((r0 >> 6) & 1) run_block(I, tile, ay, ax, 8, 2, param_of(r0, a * 4), false, nullptr, false, 0, aoff, a >= 4);
-    if (!((r0 >> 5) & 1)) {
-      run_block(I, tile, ay, ax, 8, r0 & 15, ((r0 >> 6) & 1) ? 0 : param_of(r0, a * 4), (r0 >> 4) & 1, coef + 64 * a, true, 0, aoff, a >= 4);
+    if (mobi_rec_pre_plane(r0)) run_block(I, tile, ay, ax, 8, 2, param_of(r0, a * 4), false, nullptr, false, 0, aoff, a >= 4);
+    if (!mobi_rec_split(r0)) {
+      run_block(I, tile, ay, ax, 8, mobi_rec_mode(r0), mobi_rec_pre_plane(r0) ? 0 : param_of(r0, a * 4), mobi_rec_coded(r0), coef + 64 * a, true, 0, aoff, a >= 4);
     } else {
       for (int s = 0; s < 4; s++) {
         uint32_t r = rec[a * 4 + s];
         int sy = (s >> 1) * 4, sx = (s & 1) * 4;
-        int param = (s == 0 && ((r >> 6) & 1)) ? 0 : param_of(r, a * 4 + s);
-        run_block(I, tile, ay + sy, ax + sx, 4, r & 15, param, (r >> 4) & 1, coef + 64 * a, false, s, aoff + (long)sy * S + sx, a >= 4);
+        int param = (s == 0 && mobi_rec_pre_plane(r)) ? 0 : param_of(r, a * 4 + s);
+        run_block(I, tile, ay + sy, ax + sx, 4, mobi_rec_mode(r), param, mobi_rec_coded(r), coef + 64 * a, false, s, aoff + (long)sy * S + sx, a >= 4);
       }
     }
   }
@@ -277,7 +277,7 @@ int mobi_cmdinterp_decode(void *p, const uint8_t *data, size_t len, int32_t *off
   I.fault = 0;
   const int n = (int)I.pf.desc.size();
   for (int mb = n - 1; mb >= 0; mb--)
-    if ((I.pf.desc[mb].w1 & 1) == MOBI_MB_INTER) exec_inter(I, mb, I.pf.desc[mb]);
+    if (!mobi_w1_intra(I.pf.desc[mb].w1)) exec_inter(I, mb, I.pf.desc[mb]);
   for (uint32_t L = 1; L <= I.pf.hdr.n_levels; L++)
     for (int i = (int)I.pf.level_start[L + 1] - 1; i >= (int)I.pf.level_start[L]; i--) {
       int mb = (int)I.pf.intra_mbs[i];

@@ -333,7 +333,7 @@ int mobi_lshost_compare(uint32_t w, uint32_t h, int version, const uint8_t *data
         uint32_t da[8], db[8];
         for (int k = 0; k < 4; k++) {
           const uint32_t wa = (&a.w4)[k], wb = (&b.w4)[k];
-          da[2 * k] = wa & 0xFFFF; da[2 * k + 1] = wa >> 16; db[2 * k] = wb & 0xFFFF; db[2 * k + 1] = wb >> 16;
+          da[2 * k] = mobi_dep_of_pair(wa, 0); da[2 * k + 1] = mobi_dep_of_pair(wa, 1); db[2 * k] = mobi_dep_of_pair(wb, 0); db[2 * k + 1] = mobi_dep_of_pair(wb, 1);
         }
         for (int k = 0; k < 8; k++) {
           bool fa = da[k] == MOBI_DEP_NONE, fb = db[k] == MOBI_DEP_NONE;
@@ -352,7 +352,7 @@ int mobi_lshost_compare(uint32_t w, uint32_t h, int version, const uint8_t *data
     // the intra list: the host's is sorted by level, this one in raster order -- the same set
     if (same) {
       std::vector<uint32_t> x(C->items.begin(), C->items.begin() + n_intra), y(pf.intra_mbs.begin(), pf.intra_mbs.end());
-      for (auto &v : x) v &= 0x1FFF;
+      for (auto &v : x) v = MOBI_ITEM_MB(v);
       std::sort(x.begin(), x.end());
       std::sort(y.begin(), y.end());
       if (x != y) { fprintf(stderr, "frame %d: intra lists differ\n", f); same = false; }
