@@ -6,7 +6,7 @@
  *   PCM16       interleaved little-endian samples (Program.cs:152-156)
  *   framings    the converter's loops around them: Moflex (Program.cs:75-157), Mods (Program.cs:248-319)
  *
- * Bit-exact with the reference, its wrapping int32 arithmetic included.  Sx (Mods audio_codec 1) is not built: MOBI_E_UNSUPPORTED.
+ * Bit-exact with the reference, its wrapping int32 arithmetic included.  Sx (Mods audio_codec 1) needs the file's codebooks: mobiclip_sx.h.
  * The packets come from host memory (what mobi_moflex_pop_frame / mobi_mods_read_frame hand out), the samples go to device memory on the
  * caller's stream; one lane per (stream, channel) decodes on the GPU, the decoder states live there.  Error codes: mobiclip_hip.h.
  */
@@ -31,7 +31,7 @@ typedef struct mobi_audio mobi_audio;
 #define MOBI_AUDIO_FASTAUDIO 0
 #define MOBI_AUDIO_IMA 1
 #define MOBI_AUDIO_PCM16 2 /* Moflex framing only */
-#define MOBI_AUDIO_SX 3    /* refused: MOBI_E_UNSUPPORTED */
+#define MOBI_AUDIO_SX 3    /* planned and created through mobiclip_sx.h; refused here: MOBI_E_UNSUPPORTED / NULL */
 
 #define MOBI_AUDIO_S16 0 /* int16 */
 #define MOBI_AUDIO_F32 1 /* float32 = sample / 32768, exact */
@@ -62,7 +62,7 @@ typedef struct {
  *   n_samples    [n_channels]: samples per channel (PCM16: len - len % (2 C) bytes' worth, the appended zeros included where they fit)
  * Returns MOBI_OK; MOBI_E_INDEX where the reference would throw -- a block or header that does not fit in len (a Moflex FastAudio
  * iteration that starts with fewer than 40 C bytes left is one), an IMA header index above 88 -- with n_blocks and n_samples zero and
- * the cursor unchanged; MOBI_E_UNSUPPORTED for Sx; MOBI_E_ARG for bad arguments (framing, codec, PCM16 in Mods framing, channels outside
+ * the cursor unchanged; MOBI_E_UNSUPPORTED for Sx (mobi_sx_plan); MOBI_E_ARG for bad arguments (framing, codec, PCM16 in Mods framing, channels outside
  * [1, 8], a cursor outside [0, C), data NULL with len > 0).  len == 0 (and, in Mods framing, n_packets == 0) yields nothing: MOBI_OK. */
 int mobi_audio_plan(int framing, int codec, int n_channels, const uint8_t *data, size_t len, size_t offset, uint32_t n_packets, int *cursor,
                     const uint8_t *fresh, mobi_audio_block *blocks, size_t max_blocks, size_t *n_blocks, int32_t *n_samples);
@@ -73,7 +73,7 @@ int mobi_audio_plan(int framing, int codec, int n_channels, const uint8_t *data,
 int mobi_audio_table(int which, int32_t *out);
 
 /* n_streams decoders of n_channels channels each on `device`, all new: states zero, Mods cursors 0.  NULL for bad arguments (as
- * mobi_audio_plan's; Sx; n_streams < 1 or n_streams * n_channels >= 2^24) or when the device cannot be used. */
+ * mobi_audio_plan's; Sx, which mobi_sx_create makes; n_streams < 1 or n_streams * n_channels >= 2^24) or when the device cannot be used. */
 mobi_audio *mobi_audio_create(int device, int framing, int codec, int n_streams, int n_channels);
 void mobi_audio_destroy(mobi_audio *a);
 

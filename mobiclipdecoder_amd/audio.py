@@ -1,7 +1,7 @@
-"""Batched audio decode (include/mobiclip_audio.h): the FastAudio, IMA-ADPCM and PCM16 sound of many .moflex / .mods streams into one
-torch tensor on the GPU, bit-exact with LibMobiclip's FastAudioDecoder and the converter's IMAADPCMDecoder.  The packets come from the
-container readers (demux.MoLiveDemux frames with chunk_id 2, demux.ModsDemuxer.ReadFrame); samples are only ever produced by the HIP
-kernels (mobi_audio.hip)."""
+"""Batched audio decode (include/mobiclip_audio.h, include/mobiclip_sx.h): the FastAudio, IMA-ADPCM, PCM16 and Sx sound of many .moflex /
+.mods streams into one torch tensor on the GPU, bit-exact with LibMobiclip's FastAudioDecoder and SxDecoder and the converter's
+IMAADPCMDecoder.  The packets come from the container readers (demux.MoLiveDemux frames with chunk_id 2, demux.ModsDemuxer.ReadFrame),
+Sx's codebooks from demux.ModsDemuxer.AudioCodebooks; samples are only ever produced by the HIP kernels (mobi_audio.hip, mobi_sx.hip)."""
 import ctypes as C
 
 import numpy as np
@@ -38,6 +38,15 @@ _SIGS = {
                                     C.POINTER(C.c_uint32), C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_int32),
                                     C.POINTER(C.c_int)]),
 }
+# names must match include/mobiclip_sx.h (tests/test_sx_model.py checks header, library and this table)
+_SX_SIGS = {
+    "mobi_sx_plan": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32, C.POINTER(C.c_int), C.POINTER(AudioBlock), C.c_size_t,
+                               C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]),
+    "mobi_sx_create": (C.c_void_p, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "mobi_sx_reset": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_void_p)]),
+}
+SX_PACKET_SAMPLES = 128
+SX_CODEBOOK_BYTES = 0xC34  # MOBI_MODS_CODEBOOK_BYTES
 _BOUND = False
 
 
@@ -45,7 +54,7 @@ def _lib():
     global _BOUND
     lib = load_library()
     if not _BOUND:
-        for name, (res, args) in _SIGS.items():
+        for name, (res, args) in list(_SIGS.items()) + list(_SX_SIGS.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _BOUND = True
@@ -106,12 +115,51 @@ def plan(framing, codec, n_channels, data, offset=0, n_packets=0, cursor=0, fres
     return rc, [(b.offset, b.channel, b.header, b.header_offset) for b in blocks[:n.value]], ns, cur.value
 
 
+def sx_plan(n_channels, data, offset=0, n_packets=0, cursor=0):
+    """mobi_sx_plan: the Sx packets one Mods frame of one stream yields.  Needs no device.
+    -> (rc, packets as a list of (offset, channel), samples per channel as an int32 array, the cursor afterwards)."""
+    nc = _framing_codec_channels("mods", "sx", n_channels)[2]
+    buf = _as_u8(data)
+    lib = _lib()
+    ptr = buf.ctypes.data if buf.size else None
+    cur, n, ns = C.c_int(int(cursor)), C.c_size_t(), np.zeros(nc, np.int32)
+    rc = lib.mobi_sx_plan(nc, ptr, buf.size, int(offset), int(n_packets), C.byref(cur), None, 0, C.byref(n), ns.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc != 0:
+        return rc, [], ns, cur.value
+    blocks = (AudioBlock * max(1, n.value))()
+    cur = C.c_int(int(cursor))
+    rc = lib.mobi_sx_plan(nc, ptr, buf.size, int(offset), int(n_packets), C.byref(cur), blocks, n.value, C.byref(n), ns.ctypes.data_as(C.POINTER(C.c_int32)))
+    return rc, [(b.offset, b.channel) for b in blocks[:n.value]], ns, cur.value
+
+
+def _codebook_rows(codebooks, n_rows, n_channels, what):
+    """`codebooks` as n_rows * n_channels contiguous uint8 arrays of SX_CODEBOOK_BYTES each, or ValueError"""
+    try:
+        rows = [list(r) for r in codebooks]
+    except TypeError:
+        raise ValueError(f"codebooks must be a sequence of {what} sequences of {n_channels} buffers") from None
+    if len(rows) != n_rows or any(len(r) != n_channels for r in rows):
+        raise ValueError(f"codebooks must hold {n_rows} ({what}) sequences of {n_channels} buffers each")
+    flat = []
+    for r in rows:
+        for b in r:
+            try:
+                a = _as_u8(b)
+            except (TypeError, ValueError):
+                raise ValueError("a codebook must be a byte buffer") from None
+            if a.size != SX_CODEBOOK_BYTES:
+                raise ValueError(f"a codebook is {SX_CODEBOOK_BYTES} bytes, not {a.size}")
+            flat.append(np.ascontiguousarray(a))
+    return flat
+
+
 class MobiclipAudio:
     """n_streams decoders of n_channels channels each, decoded side by side on one GPU: one lane per (stream, channel), the decoder states
     in device memory.  codec: "fastaudio", "ima", "pcm16", or the container's number (Moflex codec_id / Mods audio_codec); framing:
-    "moflex" (frames of MoLiveDemux with chunk_id 2) or "mods" (ModsDemuxer.ReadFrame packets)."""
+    "moflex" (frames of MoLiveDemux with chunk_id 2) or "mods" (ModsDemuxer.ReadFrame packets).  "sx" (Mods audio_codec 1) needs
+    codebooks: n_streams sequences of n_channels buffers of 0xC34 bytes (per stream: ModsDemuxer.AudioCodebooks)."""
 
-    def __init__(self, n_streams, n_channels, codec, framing, device=None):
+    def __init__(self, n_streams, n_channels, codec, framing, device=None, codebooks=None):
         self.framing = framing
         fr, self.codec, self.n_channels = _framing_codec_channels(framing, codec, n_channels)
         if isinstance(n_streams, bool) or not isinstance(n_streams, (int, np.integer)) or int(n_streams) < 1 \
@@ -119,16 +167,27 @@ class MobiclipAudio:
             raise ValueError(f"n_streams must be a positive int with n_streams * n_channels < 2**24, not {n_streams!r}")
         self.n_streams = int(n_streams)
         self._lib = _lib()
+        if self.codec != "sx" and codebooks is not None:
+            raise ValueError("codebooks belong to codec 'sx' only")
         if self.codec == "sx":
-            raise MobiclipError(f"Sx audio is not built: {error_string(MOBI_E_UNSUPPORTED)}")
+            if framing != "mods":
+                raise ValueError("sx exists in Mods framing only")
+            if codebooks is None:
+                raise MobiclipError("Sx audio needs the file's codebooks (codebooks=[ModsDemuxer.AudioCodebooks, ...])")
+            books = _codebook_rows(codebooks, self.n_streams, self.n_channels, "n_streams")
         self.device = int(default_device() if device is None else device)
-        self._h = self._lib.mobi_audio_create(self.device, fr, CODECS[self.codec], self.n_streams, self.n_channels)
+        if self.codec == "sx":
+            ptrs = (C.c_void_p * len(books))(*[b.ctypes.data for b in books])
+            self._h = self._lib.mobi_sx_create(self.device, self.n_streams, self.n_channels, ptrs)
+        else:
+            self._h = self._lib.mobi_audio_create(self.device, fr, CODECS[self.codec], self.n_streams, self.n_channels)
         if not self._h:
-            raise MobiclipError(f"mobi_audio_create failed: {error_string(-8)}")
+            raise MobiclipError(f"mobi_{'sx' if self.codec == 'sx' else 'audio'}_create failed: {error_string(-8)}")
 
-    def reset(self, streams, keep_cursor=False):
+    def reset(self, streams, keep_cursor=False, codebooks=None):
         """New decoders for the listed streams (a refilled slot; a Mods key frame with codec 3: keep_cursor=True).  Takes effect in the next
-        decode(), on its stream; waits for nothing."""
+        decode(), on its stream; waits for nothing.  Sx: codebooks = one sequence of n_channels buffers per listed stream gives them new
+        codebooks as well (mobi_sx_reset; the cursor goes to 0); without, the decoders keep theirs."""
         try:
             idx = [int(s) for s in streams]
         except (TypeError, ValueError):
@@ -136,6 +195,17 @@ class MobiclipAudio:
         if any(s < 0 or s >= self.n_streams for s in idx):
             raise ValueError(f"streams must lie in [0, {self.n_streams})")
         arr = (C.c_int32 * max(1, len(idx)))(*idx)
+        if codebooks is not None:
+            if self.codec != "sx":
+                raise ValueError("codebooks belong to codec 'sx' only")
+            if keep_cursor:
+                raise ValueError("new codebooks set the cursor to 0: keep_cursor does not go with codebooks")
+            books = _codebook_rows(codebooks, len(idx), self.n_channels, "len(streams)")
+            ptrs = (C.c_void_p * max(1, len(books)))(*[b.ctypes.data for b in books])
+            rc = self._lib.mobi_sx_reset(self._h, arr, len(idx), ptrs)
+            if rc != 0:
+                raise MobiclipError(error_string(rc))
+            return
         rc = self._lib.mobi_audio_reset(self._h, arr, len(idx), int(bool(keep_cursor)))
         if rc != 0:
             raise MobiclipError(error_string(rc))
@@ -221,10 +291,11 @@ class MobiclipAudio:
 
     def _longest_row(self, bufs, n_packets):
         """the samples of the longest row of a call: Moflex by the framing itself (mobi_audio_plan, counting only; a frame it rejects
-        has none), Mods from the round robin (ceil(n_packets / C) blocks for some channel, whatever the cursor)"""
+        has none), Mods from the round robin (ceil(n_packets / C) blocks -- Sx: packets of 128 samples -- for some channel, whatever the cursor)"""
         nc = self.n_channels
         if self.framing == "mods":
-            return max(-(-n // nc) * 256 if b.size else 0 for b, n in zip(bufs, n_packets))
+            per = SX_PACKET_SAMPLES if self.codec == "sx" else 256
+            return max(-(-n // nc) * per if b.size else 0 for b, n in zip(bufs, n_packets))
         longest, n, ns = 0, C.c_size_t(), np.zeros(nc, np.int32)
         for b in bufs:
             if b.size and self._lib.mobi_audio_plan(FRAMINGS["moflex"], CODECS[self.codec], nc, b.ctypes.data, b.size, 0, 0, None, None, None,

@@ -8,6 +8,7 @@
   tests/tools/libmobi_lsparse_host.so  lock-step parser's lane functions on the CPU = TEST TOOL (g++)
   tests/tools/libmobi_idle_host.so  the frame-parallel chain's kernel bodies on the CPU, idle slots = TEST TOOL (g++)
   tests/tools/libmobi_audio_host.so  the audio arithmetic header (csrc/mobi_audio.h) on the CPU = TEST TOOL (g++)
+  tests/tools/libmobi_sx_host.so  the Sx arithmetic header (csrc/mobi_sx.h) on the CPU = TEST TOOL (g++)
   tests/tools/abi_caller            plain-C caller of the product's C ABI = TEST TOOL (gcc)
 
 hipcc cross-compiles gfx950 without a GPU.  The built .so files are git-ignored but travel to the
@@ -32,11 +33,12 @@ LIB_INTERP = os.path.join(ROOT, "tests", "tools", "libmobi_cmdinterp.so")
 LIB_LSHOST = os.path.join(ROOT, "tests", "tools", "libmobi_lsparse_host.so")  # the lock-step parser's lane functions on the CPU (test tool)
 LIB_IDLEHOST = os.path.join(ROOT, "tests", "tools", "libmobi_idle_host.so")  # mobi_gop_prepare / mobi_gop_chain bodies on the CPU (test tool)
 LIB_AUDIOHOST = os.path.join(ROOT, "tests", "tools", "libmobi_audio_host.so")  # csrc/mobi_audio.h's per-sample arithmetic on the CPU (test tool)
+LIB_SXHOST = os.path.join(ROOT, "tests", "tools", "libmobi_sx_host.so")  # csrc/mobi_sx.h's packet arithmetic on the CPU (test tool)
 ABI_CALLER = os.path.join(ROOT, "tests", "tools", "abi_caller")  # plain-C caller of the product library (test tool)
 
 
 # the sources of libmobiclip_hip.so: *.cpp are host objects (g++), *.hip kernel objects (hipcc --offload-arch=gfx950); linked in this order
-HIP_SOURCES = ("mobi_batch.cpp", "mobi_step_host.cpp", "mobi_step_device.cpp", "mobi_step_groups.cpp", "mobi_replay.cpp", "mobi_pictures.cpp", "mobi_parse.cpp", "mobi_demux.cpp", "mobi_moflex.cpp", "mobi_export.cpp", "mobi_txcode.cpp", "mobi_audio_plan.cpp", "mobi_audio.cpp", "mobi_kernels.hip", "mobi_rgb.hip", "mobi_dparse.hip", "mobi_lsparse.hip", "mobi_gop.hip", "mobi_analysis.hip", "mobi_export.hip", "mobi_txcode.hip", "mobi_export_rgb.hip", "mobi_export_scale.hip", "mobi_export_resample.hip", "mobi_reset.hip", "mobi_idle.hip", "mobi_audio.hip")
+HIP_SOURCES = ("mobi_batch.cpp", "mobi_step_host.cpp", "mobi_step_device.cpp", "mobi_step_groups.cpp", "mobi_replay.cpp", "mobi_pictures.cpp", "mobi_parse.cpp", "mobi_demux.cpp", "mobi_moflex.cpp", "mobi_export.cpp", "mobi_txcode.cpp", "mobi_audio_plan.cpp", "mobi_audio.cpp", "mobi_kernels.hip", "mobi_rgb.hip", "mobi_dparse.hip", "mobi_lsparse.hip", "mobi_gop.hip", "mobi_analysis.hip", "mobi_export.hip", "mobi_txcode.hip", "mobi_export_rgb.hip", "mobi_export_scale.hip", "mobi_export_resample.hip", "mobi_reset.hip", "mobi_idle.hip", "mobi_audio.hip", "mobi_sx.hip")
 
 
 def hip_objects(profiling=False):
@@ -65,7 +67,7 @@ def header_symbols():
     """every function include/*.h declares (the C ABI)"""
     import re
     names = []
-    for h in ("mobiclip_hip.h", "mobiclip_demux.h", "mobiclip_audio.h"):
+    for h in ("mobiclip_hip.h", "mobiclip_demux.h", "mobiclip_audio.h", "mobiclip_sx.h"):
         text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", h)).read(), flags=re.S)
         names += re.findall(r"\b(mobi_\w+)\s*\(", text)
     return sorted(set(names))
@@ -77,7 +79,7 @@ def build_hip(force=False, profiling=False):
     MOBI_DEBUG=9) and the mobi_debug_* test hooks.  The product library has none of them; tools select the other one with MOBI_LIB."""
     srcs = [os.path.join(CSRC, f) for f in HIP_SOURCES]
     deps = srcs + _hdrs(CSRC) + [os.path.join(ROOT, "include", "mobiclip_hip.h"), os.path.join(ROOT, "include", "mobiclip_demux.h"), os.path.join(ROOT, "include", "mobiclip_audio.h"),
-                                  os.path.abspath(__file__)]
+                                  os.path.join(ROOT, "include", "mobiclip_sx.h"), os.path.abspath(__file__)]
     lib = LIB_HIP_PROF if profiling else LIB_HIP
     if not force and not _newer(lib, deps):
         return lib
@@ -157,6 +159,15 @@ def build_audiohost(force=False):
     return LIB_AUDIOHOST
 
 
+def build_sxhost(force=False):
+    src = os.path.join(ROOT, "tests", "tools", "mobi_sx_host.cpp")
+    plan = os.path.join(CSRC, "mobi_audio_plan.cpp")
+    hdrs = [os.path.join(CSRC, "mobi_sx.h"), os.path.join(CSRC, "mobi_audio.h"), os.path.join(ROOT, "include", "mobiclip_sx.h"), os.path.join(ROOT, "include", "mobiclip_audio.h")]
+    if force or _newer(LIB_SXHOST, [src, plan] + hdrs):
+        _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-I" + CSRC, src, plan, "-o", LIB_SXHOST])
+    return LIB_SXHOST
+
+
 def build_caller(force=False):
     src = os.path.join(ROOT, "tests", "tools", "abi_caller.c")
     if force or _newer(ABI_CALLER, [src, os.path.join(ROOT, "include", "mobiclip_hip.h"), LIB_HIP]):
@@ -165,7 +176,7 @@ def build_caller(force=False):
 
 
 def build_all(force=False):
-    return [build_hip(force), build_hip(force, profiling=True), build_gen(force), build_oracle(force), build_interp(force), build_lshost(force), build_idlehost(force), build_audiohost(force), build_caller(force)]
+    return [build_hip(force), build_hip(force, profiling=True), build_gen(force), build_oracle(force), build_interp(force), build_lshost(force), build_idlehost(force), build_audiohost(force), build_sxhost(force), build_caller(force)]
 
 
 if __name__ == "__main__":

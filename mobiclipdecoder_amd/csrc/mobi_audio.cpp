@@ -2,11 +2,16 @@
 // mobi_audio_decode: plan every stream (mobi_audio_plan.cpp), gather the audio bytes into pinned staging, one copy, one launch
 // (mobi_audio.hip).  The decoder states live in device memory; what the host keeps per stream is what the framing needs to plan the next
 // frame: the Mods channel cursor, which IMA decoders are new, and which streams were reset since the last launch.
+// Sx (include/mobiclip_sx.h, mobi_sx.hip) shares the handle and the call: its packets have their own lengths, its lanes their codebooks in
+// device memory, and a stream refilled by mobi_sx_reset gets its new codebooks behind the packets of the next call's one copy.
 #include "../../include/mobiclip_audio.h"
+#include "../../include/mobiclip_sx.h"
 #include "mobi_audio.h"
 #include "mobi_batch.h"
+#include "mobi_sx.h"
 
 extern "C" int mobi_launch_audio(const MobiAudioArgs *a, hipStream_t s);
+extern "C" int mobi_launch_sx(const MobiAudioArgs *a, const uint8_t *books, hipStream_t s);
 bool mobi_audio_args_ok(int framing, int codec, int n_channels); // mobi_audio_plan.cpp
 
 namespace {
@@ -55,7 +60,10 @@ struct mobi_audio {
   std::vector<uint8_t> fresh; // [n_streams * C]: IMA in Mods framing, the channel's decoder is new (its next packet carries the header)
   std::vector<uint8_t> zero;  // [n_streams]: reset since the last launch: the kernel zeroes the states first
   MobiAudioConst *k = nullptr;
-  DevArr<int32_t> state;      // [MOBI_AU_STATE_WORDS][n_streams * C]
+  DevArr<int32_t> state;      // [MOBI_AU_STATE_WORDS][n_streams * C]; Sx: [MOBI_SX_STATE_WORDS][n_streams * C]
+  DevArr<uint8_t> books;      // Sx: [n_streams * C][MOBI_SX_BOOK_PITCH], the codebooks as the kernel reads them
+  std::vector<uint8_t> pend;  // Sx: [n_streams * C][MOBI_SX_BOOK_PITCH], codebooks of mobi_sx_reset that the next launch's copy takes along
+  std::vector<uint8_t> has_pend; // Sx: [n_streams]
   // two staging pairs: while the kernel of one call reads dev[i], the next call fills pin[i ^ 1]; ev[i] = the end of the kernel that read dev[i]
   PinnedBuf pin[2];
   DevBuf dev[2];
@@ -67,13 +75,18 @@ struct mobi_audio {
   std::vector<size_t> first, count;   // [n_streams]: the stream's blocks in `blocks`
   std::vector<int> new_cursor;        // [n_streams]
   std::vector<uint32_t> lane_blocks;  // [n_streams * C]
-  std::vector<uint32_t> lane_fill;    // [n_streams * C]: blocks gathered so far
+  std::vector<uint32_t> lane_fill;    // [n_streams * C]: blocks gathered so far (Sx: bytes)
+  std::vector<uint32_t> lane_bytes;   // Sx: [n_streams * C], the bytes of the lane's packets
 };
 
-mobi_audio *mobi_audio_create(int device, int framing, int codec, int n_streams, int n_channels) {
-  if (device < 0 || !mobi_audio_args_ok(framing, codec, n_channels) || codec == MOBI_AUDIO_SX || n_streams < 1 ||
+// codebooks == nullptr: every codec but Sx
+static mobi_audio *audio_create(int device, int framing, int codec, int n_streams, int n_channels, const uint8_t *const *codebooks) {
+  if (device < 0 || !mobi_audio_args_ok(framing, codec, n_channels) || (codec == MOBI_AUDIO_SX) != (codebooks != nullptr) || n_streams < 1 ||
       (int64_t)n_streams * n_channels >= (1 << 24))
     return nullptr;
+  if (codebooks)
+    for (int64_t g = 0; g < (int64_t)n_streams * n_channels; g++)
+      if (!codebooks[g]) return nullptr;
   if (hipSetDevice(device) != hipSuccess) {
     (void)hipGetLastError();
     return nullptr;
@@ -86,11 +99,28 @@ mobi_audio *mobi_audio_create(int device, int framing, int codec, int n_streams,
   a->zero.assign(n_streams, 1); // the first launch zeroes the states on its own stream, as one after a reset does
   a->first.resize(n_streams), a->count.resize(n_streams), a->new_cursor.resize(n_streams);
   a->lane_blocks.resize(lanes), a->lane_fill.resize(lanes);
-  if (!(a->k = device_const(device))) return nullptr;
-  if (a->state.alloc(lanes * MOBI_AU_STATE_WORDS) != MOBI_OK) return nullptr;
+  if (codebooks) {
+    a->lane_bytes.resize(lanes);
+    a->has_pend.assign(n_streams, 0);
+    std::vector<uint8_t> h(lanes * MOBI_SX_BOOK_PITCH, 0);
+    for (size_t g = 0; g < lanes; g++) memcpy(h.data() + g * MOBI_SX_BOOK_PITCH, codebooks[g], MOBI_SX_CODEBOOK);
+    if (a->books.alloc(h.size()) != MOBI_OK || hipMemcpy(a->books, h.data(), h.size(), hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipGetLastError();
+      return nullptr;
+    }
+  } else if (!(a->k = device_const(device))) return nullptr;
+  if (a->state.alloc(lanes * (codebooks ? (size_t)MOBI_SX_STATE_WORDS : (size_t)MOBI_AU_STATE_WORDS)) != MOBI_OK) return nullptr;
   for (auto &e : a->ev)
     if (ensure_event(e) != MOBI_OK) return nullptr;
   return a.release();
+}
+
+mobi_audio *mobi_audio_create(int device, int framing, int codec, int n_streams, int n_channels) {
+  return codec == MOBI_AUDIO_SX ? nullptr : audio_create(device, framing, codec, n_streams, n_channels, nullptr); // Sx: mobi_sx_create
+}
+
+mobi_audio *mobi_sx_create(int device, int n_streams, int n_channels, const uint8_t *const *codebooks) {
+  return codebooks ? audio_create(device, MOBI_AUDIO_FRAMING_MODS, MOBI_AUDIO_SX, n_streams, n_channels, codebooks) : nullptr;
 }
 
 void mobi_audio_destroy(mobi_audio *a) {
@@ -115,11 +145,28 @@ int mobi_audio_reset(mobi_audio *a, const int32_t *streams, int count, int keep_
   return MOBI_OK;
 }
 
+int mobi_sx_reset(mobi_audio *a, const int32_t *streams, int count, const uint8_t *const *codebooks) {
+  if (!a || a->codec != MOBI_AUDIO_SX || count < 0 || (count && (!streams || !codebooks))) return MOBI_E_ARG;
+  for (int i = 0; i < count; i++) {
+    if (streams[i] < 0 || streams[i] >= a->n_streams) return MOBI_E_ARG;
+    for (int c = 0; c < a->C; c++)
+      if (!codebooks[(size_t)i * a->C + c]) return MOBI_E_ARG;
+  }
+  std::lock_guard<std::mutex> l(a->mutex);
+  if (count && a->pend.empty()) a->pend.assign((size_t)a->n_streams * a->C * MOBI_SX_BOOK_PITCH, 0);
+  for (int i = 0; i < count; i++) {
+    const int s = streams[i];
+    a->zero[s] = 1, a->has_pend[s] = 1, a->cursor[s] = 0;
+    for (int c = 0; c < a->C; c++) memcpy(&a->pend[((size_t)s * a->C + c) * MOBI_SX_BOOK_PITCH], codebooks[(size_t)i * a->C + c], MOBI_SX_CODEBOOK);
+  }
+  return MOBI_OK;
+}
+
 int mobi_audio_decode(mobi_audio *a, void *stream, const uint8_t *const *data, const size_t *len, const size_t *offsets,
                       const uint32_t *n_packets, int dtype, int layout, void *dst, size_t dst_bytes, size_t max_samples,
                       int32_t *n_samples_out, int *rc) {
   if (!a || !data || !len || !dst || !n_samples_out || !rc) return MOBI_E_ARG;
-  const bool mods = a->framing == MOBI_AUDIO_FRAMING_MODS, pcm = a->codec == MOBI_AUDIO_PCM16;
+  const bool mods = a->framing == MOBI_AUDIO_FRAMING_MODS, pcm = a->codec == MOBI_AUDIO_PCM16, sx = a->codec == MOBI_AUDIO_SX;
   if (mods && (!offsets || !n_packets)) return MOBI_E_ARG;
   if ((dtype != MOBI_AUDIO_S16 && dtype != MOBI_AUDIO_F32) || (layout != MOBI_AUDIO_PLANAR && layout != MOBI_AUDIO_INTERLEAVED)) return MOBI_E_ARG;
   const int S = a->n_streams, C = a->C;
@@ -128,7 +175,8 @@ int mobi_audio_decode(mobi_audio *a, void *stream, const uint8_t *const *data, c
   std::lock_guard<std::mutex> l(a->mutex);
 
   // ---- plan every stream; nothing of the handle changes before the whole call is known to be good ----
-  const size_t blk = a->codec == MOBI_AUDIO_FASTAUDIO ? MOBI_FA_BLOCK_BYTES : MOBI_IMA_BLOCK_BYTES;
+  const size_t blk = sx ? 10 /* the shortest packet */ : a->codec == MOBI_AUDIO_FASTAUDIO ? MOBI_FA_BLOCK_BYTES : MOBI_IMA_BLOCK_BYTES;
+  const uint32_t block_samples = sx ? MOBI_SX_SAMPLES : MOBI_AU_BLOCK_SAMPLES;
   size_t bound = 0;
   for (int s = 0; s < S; s++) {
     if (!data[s] && len[s]) return MOBI_E_ARG;
@@ -142,17 +190,24 @@ int mobi_audio_decode(mobi_audio *a, void *stream, const uint8_t *const *data, c
     int cur = a->cursor[s];
     size_t n = 0;
     int32_t *ns = n_samples_out + (size_t)s * C;
-    rc[s] = mobi_audio_plan(a->framing, a->codec, C, data[s], len[s], mods ? offsets[s] : 0, mods ? n_packets[s] : 0, &cur,
-                            &a->fresh[(size_t)s * C], a->blocks.data() + total_blocks, bound - total_blocks, &n, ns);
+    rc[s] = sx ? mobi_sx_plan(C, data[s], len[s], offsets[s], n_packets[s], &cur, a->blocks.data() + total_blocks, bound - total_blocks, &n, ns)
+               : mobi_audio_plan(a->framing, a->codec, C, data[s], len[s], mods ? offsets[s] : 0, mods ? n_packets[s] : 0, &cur,
+                                 &a->fresh[(size_t)s * C], a->blocks.data() + total_blocks, bound - total_blocks, &n, ns);
     if (rc[s] != MOBI_OK && rc[s] != MOBI_E_INDEX) return rc[s];
     a->first[s] = total_blocks, a->count[s] = n, a->new_cursor[s] = cur;
     total_blocks += n;
     for (int c = 0; c < C; c++) {
       if ((size_t)ns[c] > max_samples) return MOBI_E_ARG;
       if (layout == MOBI_AUDIO_INTERLEAVED && ns[c] != ns[0]) return MOBI_E_ARG;
-      a->lane_blocks[(size_t)s * C + c] = (uint32_t)ns[c] / MOBI_AU_BLOCK_SAMPLES;
+      a->lane_blocks[(size_t)s * C + c] = (uint32_t)ns[c] / block_samples;
       if (!pcm && a->lane_blocks[(size_t)s * C + c] > 0xFFFF) return MOBI_E_ARG;
+      if (sx) a->lane_bytes[(size_t)s * C + c] = 0;
     }
+    if (sx) // a packet's length is in its second word (the plan has checked that it fits)
+      for (size_t i = 0; i < n; i++) {
+        const mobi_audio_block &b = a->blocks[a->first[s] + i];
+        a->lane_bytes[(size_t)s * C + b.channel] += (uint32_t)mobi_sx_packet_bytes((uint32_t)data[s][b.offset + 3] << 8);
+      }
     if (pcm) {
       pcm_bytes += align_up((size_t)ns[0] * 2 * C, kAlign);
       pcm_max = std::max(pcm_max, (uint32_t)ns[0]);
@@ -161,12 +216,18 @@ int mobi_audio_decode(mobi_audio *a, void *stream, const uint8_t *const *data, c
   }
   if (pcm ? pcm_max == 0 : (total_blocks == 0 && !any_zero)) return MOBI_OK; // nothing to enqueue
 
-  // ---- the staged bytes: [one MobiAudioLane per lane (PCM16: per stream)][every lane's blocks back to back, each lane on 16 bytes] ----
+  // ---- the staged bytes: [one MobiAudioLane per lane (PCM16: per stream)][every lane's blocks back to back, each lane on 16 bytes]
+  //      [Sx: the codebooks of the streams mobi_sx_reset refilled, MOBI_SX_BOOK_PITCH each] ----
   const size_t n_desc = pcm ? (size_t)S : lanes, head = align_up(n_desc * sizeof(MobiAudioLane), kAlign);
+  auto lane_size = [&](size_t g) { return sx ? (size_t)a->lane_bytes[g] : a->lane_blocks[g] * blk; };
   size_t total = head + pcm_bytes;
   if (!pcm)
-    for (size_t g = 0; g < lanes; g++) total += align_up(a->lane_blocks[g] * blk, kAlign);
+    for (size_t g = 0; g < lanes; g++) total += align_up(lane_size(g), kAlign);
   if (total - head > 0xFFFFFFFFull) return MOBI_E_ARG;
+  const size_t books_at = total;
+  if (sx)
+    for (int s = 0; s < S; s++)
+      if (a->has_pend[s]) total += (size_t)C * MOBI_SX_BOOK_PITCH;
 
   HIP_TRY(hipSetDevice(a->device));
   hipPointerAttribute_t at;
@@ -207,7 +268,7 @@ int mobi_audio_decode(mobi_audio *a, void *stream, const uint8_t *const *data, c
       desc[g].nblk = (uint16_t)a->lane_blocks[g];
       desc[g].flags = a->zero[g / C] ? MOBI_AU_ZERO : 0;
       a->lane_fill[g] = 0;
-      at_byte += align_up(a->lane_blocks[g] * blk, kAlign);
+      at_byte += align_up(lane_size(g), kAlign);
     }
     for (int s = 0; s < S; s++) {
       const mobi_audio_block *b = a->blocks.data() + a->first[s];
@@ -218,13 +279,34 @@ int mobi_audio_decode(mobi_audio *a, void *stream, const uint8_t *const *data, c
           desc[g].hdr_index = (uint8_t)(s16le(data[s] + b[i].header_offset) & 0x7F);
           desc[g].hdr_last = s16le(data[s] + b[i].header_offset + 2);
         }
-        memcpy(h + head + desc[g].off + a->lane_fill[g]++ * blk, data[s] + b[i].offset, blk);
+        if (sx) {
+          const size_t n = (size_t)mobi_sx_packet_bytes((uint32_t)data[s][b[i].offset + 3] << 8);
+          memcpy(h + head + desc[g].off + a->lane_fill[g], data[s] + b[i].offset, n);
+          a->lane_fill[g] += (uint32_t)n;
+        } else
+          memcpy(h + head + desc[g].off + a->lane_fill[g]++ * blk, data[s] + b[i].offset, blk);
       }
     }
+  }
+  if (sx) {
+    size_t at = books_at;
+    for (int s = 0; s < S; s++)
+      if (a->has_pend[s]) {
+        memcpy(h + at, &a->pend[(size_t)s * C * MOBI_SX_BOOK_PITCH], (size_t)C * MOBI_SX_BOOK_PITCH);
+        at += (size_t)C * MOBI_SX_BOOK_PITCH;
+      }
   }
 
   HIP_TRY(hipMemcpyAsync(a->dev[t].p, h, total, hipMemcpyHostToDevice, st));
   a->busy[t] = true; // from here on the buffers are in use, whatever follows
+  if (sx) {
+    size_t at = books_at;
+    for (int s = 0; s < S; s++)
+      if (a->has_pend[s]) {
+        HIP_TRY(hipMemcpyAsync(a->books + (size_t)s * C * MOBI_SX_BOOK_PITCH, a->dev[t].p + at, (size_t)C * MOBI_SX_BOOK_PITCH, hipMemcpyDeviceToDevice, st));
+        at += (size_t)C * MOBI_SX_BOOK_PITCH;
+      }
+  }
   MobiAudioArgs k;
   memset(&k, 0, sizeof k);
   k.k = a->k;
@@ -237,7 +319,7 @@ int mobi_audio_decode(mobi_audio *a, void *stream, const uint8_t *const *data, c
   k.n_channels = (uint32_t)C;
   k.pcm_max = pcm_max;
   k.codec = a->codec, k.dtype = dtype, k.layout = layout;
-  const int launched = mobi_launch_audio(&k, st);
+  const int launched = sx ? mobi_launch_sx(&k, a->books, st) : mobi_launch_audio(&k, st);
   HIP_TRY(hipEventRecord(a->ev[t], st));
   a->turn = t ^ 1;
   if (launched != 0) return MOBI_E_DEVICE;
@@ -245,6 +327,7 @@ int mobi_audio_decode(mobi_audio *a, void *stream, const uint8_t *const *data, c
   // ---- the call is enqueued: the framing state moves on for the streams that decoded ----
   for (int s = 0; s < S; s++) {
     a->zero[s] = 0;
+    if (sx) a->has_pend[s] = 0;
     if (rc[s] != MOBI_OK) continue;
     a->cursor[s] = a->new_cursor[s];
     for (int c = 0; c < C; c++)

@@ -1,12 +1,14 @@
 // mobi_audio_plan.cpp -- the host-only part of the audio decode (include/mobiclip_audio.h): the framing rules of the reference's converter
-// (mobi_audio_plan: which bytes of a frame are which channel's blocks) and the tables' getter.  No HIP: the CPU tests and a stand-alone
+// (mobi_audio_plan, and mobi_sx_plan of include/mobiclip_sx.h: which bytes of a frame are which channel's blocks) and the tables' getter.  No HIP: the CPU tests and a stand-alone
 // host program call these without a GPU; mobi_audio_decode (mobi_audio.cpp) plans every stream with the same function.
 #include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/mobiclip_audio.h"
 #include "../../include/mobiclip_hip.h"
+#include "../../include/mobiclip_sx.h"
 #include "mobi_audio.h"
+#include "mobi_sx.h"
 
 bool mobi_audio_args_ok(int framing, int codec, int C) {
   if (framing != MOBI_AUDIO_FRAMING_MOFLEX && framing != MOBI_AUDIO_FRAMING_MODS) return false;
@@ -81,6 +83,37 @@ int mobi_audio_plan(int framing, int codec, int n_channels, const uint8_t *data,
   }
   *n_blocks = n;
   if (mods) *cursor = cur;
+  return MOBI_OK;
+}
+
+// Sx in Mods framing (Program.cs:275-288): one packet per channel, round robin from the cursor; SxDecoder.Decode reads two words, then the
+// pulse words its rate asks for, and throws where they end behind the buffer
+int mobi_sx_plan(int n_channels, const uint8_t *data, size_t len, size_t offset, uint32_t n_packets, int *cursor, mobi_audio_block *blocks,
+                 size_t max_blocks, size_t *n_blocks, int32_t *n_samples) {
+  const int C = n_channels;
+  if (C < 1 || C > MOBI_AUDIO_MAX_CHANNELS || !n_blocks || !n_samples || (!data && len) || (!blocks && max_blocks) || len >= 0xFFFFFFFFull ||
+      !cursor || *cursor < 0 || *cursor >= C)
+    return MOBI_E_ARG;
+  *n_blocks = 0;
+  for (int c = 0; c < C; c++) n_samples[c] = 0;
+  if (len == 0 || n_packets == 0) return MOBI_OK;
+  uint32_t per[MOBI_AUDIO_MAX_CHANNELS] = {0};
+  size_t off = offset;
+  int cur = *cursor;
+  for (uint32_t i = 0; i < n_packets; i++) {
+    if (off > len || len - off < 4) return MOBI_E_INDEX;
+    const size_t need = (size_t)mobi_sx_packet_bytes((uint32_t)data[off + 3] << 8);
+    if (need > len - off) return MOBI_E_INDEX;
+    if (i < max_blocks) blocks[i] = mobi_audio_block{(uint32_t)off, 0, (uint16_t)cur, 0};
+    per[cur]++;
+    off += need;
+    cur = cur + 1 >= C ? 0 : cur + 1;
+  }
+  for (int c = 0; c < C; c++)
+    if ((uint64_t)per[c] * MOBI_SX_SAMPLES > 0x7FFFFFFFull) return MOBI_E_ARG;
+  for (int c = 0; c < C; c++) n_samples[c] = (int32_t)(per[c] * MOBI_SX_SAMPLES);
+  *n_blocks = n_packets;
+  *cursor = cur;
   return MOBI_OK;
 }
 

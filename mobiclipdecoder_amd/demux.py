@@ -7,6 +7,9 @@ import numpy as np
 from .decoder import load_library
 
 
+CODEBOOK_BYTES = 0xC34  # MOBI_MODS_CODEBOOK_BYTES
+
+
 class _ModsHeader(C.Structure):
     _fields_ = [("mods_string", C.c_char * 4), ("tag_id", C.c_uint16), ("tag_id_size_dword", C.c_uint16),
                 ("frame_count", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("fps", C.c_uint32),
@@ -75,6 +78,11 @@ class ModsDemuxer:
             fn, off = C.c_uint32(), C.c_uint32()
             self._lib.mobi_mods_keyframe(self._h, k, C.byref(fn), C.byref(off))
             self.KeyFrames.append((fn.value, off.value))
+        # AudioCodebooks[channel] (ModsDemuxer.cs:20-29): 0xC34 bytes each where the header has an AudioOffset, else None
+        self.AudioCodebooks = None
+        if self.Header.audio_offset != 0:
+            self.AudioCodebooks = [C.string_at(self._lib.mobi_mods_audio_codebook(self._h, c), CODEBOOK_BYTES)
+                                   for c in range(self.Header.nb_channel)]
 
     def JumpToKeyFrame(self, k):
         self._lib.mobi_mods_jump_to_keyframe(self._h, int(k))

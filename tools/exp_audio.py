@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Throughput of the batched audio decode on one GPU (MobiclipAudio.decode, Moflex framing, int16 planar, output allocated once, torch's
-current stream); prints ONE JSON line and writes it to --out.
+"""Throughput of the batched audio decode on one GPU (MobiclipAudio.decode, int16 planar, output allocated once, torch's current stream;
+FastAudio and IMA in Moflex framing, Sx in Mods framing); prints ONE JSON line and writes it to --out.
 
-Per codec (FastAudio, IMA): 4096 streams x 2 channels x 4 blocks per call (--streams, --channels, --blocks).
+Per codec (FastAudio, IMA, Sx; --codecs): 4096 streams x 2 channels x 4 blocks per call (--streams, --channels, --blocks; an Sx "block" is
+a packet of 128 samples, of random rate and lag, every sixth a reset packet, over eight random codebooks).
   call_ms      wall time per call over --iters back-to-back calls ended by one synchronise: plan + gather + one copy + launch on the host,
                overlapped with the previous calls' kernels (a call does not wait for its own) -- what a loader sees
   device_ms    HIP events around ONE call's device work, its copy (h2d_bytes) and kernel, enqueued while the stream is held busy so that
@@ -12,12 +13,13 @@ Per codec (FastAudio, IMA): 4096 streams x 2 channels x 4 blocks per call (--str
   device_share_of_call = device_ms_median / call_ms: near 1 the calls are bound by the device, below by the host (Python's per-stream
                handling, plan and gather)
   blocks_per_s, samples_per_s   from call_ms
-  ns_per_sample_per_lane = kernel_ms / (256 * blocks): what one lane's dependent chain takes per sample, write-out included
+  ns_per_sample_per_lane = kernel_ms / (256 * blocks) (Sx: 128 * blocks): what one lane's dependent chain takes per sample, write-out and,
+               for Sx, the load and store of its 546-word state included
   variants     device_ms_median of the same call as float32 planar (twice the bytes stored), int16 interleaved, and with 2 and 4 times the
                streams (int16 planar): a kernel bound by each lane's dependent chain takes the same time until the SIMDs fill up; one
                bound by its stores takes longer with float32
 For scale: --bench-ms takes the project's reconstruction step time of the same session's `python bench.py` (ms per step) into the record.
-For `rocprofv3 --kernel-trace --stats -- python tools/exp_audio.py` the kernels are mobi_audio_blocks<0> (FastAudio) and <1> (IMA).
+For `rocprofv3 --kernel-trace --stats -- python tools/exp_audio.py` the kernels are mobi_audio_blocks<0> (FastAudio), <1> (IMA) and mobi_sx_packets.
 """
 import argparse
 import json
@@ -47,6 +49,35 @@ def frames_for(codec, streams, channels, blocks):
         head = b"".join(bytes([(k * 11 + c) % 89, 0, 0, 0]) for c in range(channels)) if codec == "ima" else b""
         distinct.append(head + lcg(size * channels * blocks, 1 + k) + b"\0\0")
     return [distinct[s % 8] for s in range(streams)]
+
+
+def sx_setup(streams, channels, blocks):
+    """eight distinct (codebook, packets of one lane and call); a stream's frame deals its lanes' packets round robin"""
+    lanes = []
+    for k in range(8):
+        packets = []
+        for b in range(blocks):
+            p = bytearray(lcg(20, 100 + 8 * b + k))
+            p[1] = 0xFE | (p[1] & 1) if (b + k) % 6 == 0 else (p[1] if p[1] >> 1 != 0x7F else p[1] & ~2)
+            packets.append(bytes(p[:(20, 14, 12, 10)[(p[3] >> 4) & 3]]))
+        lanes.append((lcg(0xC34, 50 + k), packets))
+    frames, books = [], []
+    for s in range(streams):
+        mine = [lanes[(s * channels + c) % 8] for c in range(channels)]
+        frames.append(b"".join(mine[c][1][b] for b in range(blocks) for c in range(channels)))
+        books.append([mine[c][0] for c in range(channels)])
+    return frames, books
+
+
+def setup(codec, streams, a, dev):
+    """-> (decoder, frames, decode()'s framing arguments, samples per block, staged bytes: the blocks and a 16-byte descriptor per lane)"""
+    if codec == "sx":
+        frames, books = sx_setup(streams, a.channels, a.blocks)
+        au = m.MobiclipAudio(streams, a.channels, "sx", "mods", device=dev.index, codebooks=books)
+        return au, frames, dict(offsets=[0] * streams, n_packets=[a.channels * a.blocks] * streams), 128, sum(len(f) for f in frames) + 16 * streams * a.channels
+    au = m.MobiclipAudio(streams, a.channels, codec, "moflex", device=dev.index)
+    h2d = streams * a.channels * a.blocks * (40 if codec == "fastaudio" else 128) + 16 * streams * a.channels
+    return au, frames_for(codec, streams, a.channels, a.blocks), {}, 256, h2d
 
 
 _BLOCKER = {}
@@ -104,43 +135,40 @@ def copy_ms(n, iters, dev):
 
 
 def variant(codec, a, dev, streams, dtype, layout):
-    au = m.MobiclipAudio(streams, a.channels, codec, "moflex", device=dev.index)
-    frames = frames_for(codec, streams, a.channels, a.blocks)
-    shape = (streams, a.channels, 256 * a.blocks) if layout == "planar" else (streams, 256 * a.blocks, a.channels)
+    au, frames, kw, spb, _ = setup(codec, streams, a, dev)
+    shape = (streams, a.channels, spb * a.blocks) if layout == "planar" else (streams, spb * a.blocks, a.channels)
     out = torch.empty(shape, dtype=dtype, device=dev)
     for _ in range(a.warmup):
-        au.decode(frames, out=out, dtype=dtype, layout=layout)
+        au.decode(frames, out=out, dtype=dtype, layout=layout, **kw)
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
-    au.decode(frames, out=out, dtype=dtype, layout=layout)
+    au.decode(frames, out=out, dtype=dtype, layout=layout, **kw)
     torch.cuda.synchronize(dev)
-    med = device_ms(au, frames, out, a.iters, dev, (time.perf_counter() - t0) * 1e3, dtype=dtype, layout=layout)[0]
+    med = device_ms(au, frames, out, a.iters, dev, (time.perf_counter() - t0) * 1e3, dtype=dtype, layout=layout, **kw)[0]
     au.close()
     return med
 
 
 def run(codec, a):
     dev = torch.device("cuda", torch.cuda.current_device())
-    au = m.MobiclipAudio(a.streams, a.channels, codec, "moflex", device=dev.index)
-    frames = frames_for(codec, a.streams, a.channels, a.blocks)
-    out = torch.empty((a.streams, a.channels, 256 * a.blocks), dtype=torch.int16, device=dev)
+    au, frames, kw, spb, h2d = setup(codec, a.streams, a, dev)
+    out = torch.empty((a.streams, a.channels, spb * a.blocks), dtype=torch.int16, device=dev)
     for _ in range(a.warmup):
-        au.decode(frames, out=out)
+        au.decode(frames, out=out, **kw)
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     for _ in range(a.iters):
-        au.decode(frames, out=out)
+        au.decode(frames, out=out, **kw)
     torch.cuda.synchronize(dev)
     call = (time.perf_counter() - t0) / a.iters
-    med, low = device_ms(au, frames, out, a.iters, dev, call * 1e3)
+    med, low = device_ms(au, frames, out, a.iters, dev, call * 1e3, **kw)
     n_blocks = a.streams * a.channels * a.blocks
     au.close()
-    h2d = n_blocks * (40 if codec == "fastaudio" else 128) + 16 * a.streams * a.channels  # the staged bytes: the blocks and a 16-byte descriptor per lane
     cp = copy_ms(h2d, a.iters, dev)
     res = {"call_ms": call * 1e3, "device_ms_median": med, "device_ms_min": low, "h2d_bytes": h2d, "copy_ms": cp, "kernel_ms": med - cp,
            "kernel_share_of_call": (med - cp) / (call * 1e3), "device_share_of_call": med / (call * 1e3),
-           "ns_per_sample_per_lane": (med - cp) * 1e6 / (256 * a.blocks),
-           "blocks_per_s": n_blocks / call, "samples_per_s": n_blocks * 256 / call}
+           "ns_per_sample_per_lane": (med - cp) * 1e6 / (spb * a.blocks),
+           "blocks_per_s": n_blocks / call, "samples_per_s": n_blocks * spb / call}
     if a.variants:
         res["device_ms_float32"] = variant(codec, a, dev, a.streams, torch.float32, "planar")
         res["device_ms_interleaved"] = variant(codec, a, dev, a.streams, torch.int16, "interleaved")
@@ -158,10 +186,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--bench-ms", type=float, default=None, help="ms per reconstruction step from the same session's python bench.py")
     ap.add_argument("--no-variants", dest="variants", action="store_false", help="the headline configuration only")
+    ap.add_argument("--codecs", default="fastaudio,ima,sx", help="comma-separated: fastaudio, ima, sx")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     res = {"streams": a.streams, "channels": a.channels, "blocks_per_call": a.blocks, "iters": a.iters, "dtype": "int16", "layout": "planar"}
-    for codec in ("fastaudio", "ima"):
+    for codec in a.codecs.split(","):
         for k, v in run(codec, a).items():
             res[f"{codec}_{k}"] = round(v, 4) if isinstance(v, float) and v < 1e6 else (float("%.4g" % v) if isinstance(v, float) else v)
     if a.bench_ms is not None:
