@@ -347,7 +347,9 @@ __device__ __forceinline__ void idct_pass2_pk(const uint32_t *t, bool is8, int r
 // =====================================================================================================
 //   A. every lane decodes its macroblock's descriptor; ONE fetch path for every macroblock with whole leaves (16x16, two 16x8, two
 //      8x16): DMA rounds with a per-lane source address (global_load_lds_dwordx4), so the rows of a top/bottom pair and the halves of a
-//      left/right pair simply come from the other leaf's position; level words travel in registers.
+//      left/right pair simply come from the other leaf's position; level words travel in registers.  With every request out, and before
+//      it waits for them, the wave works out what B, C and D need of its OWN descriptors and the lane number -- window addresses, byte
+//      selectors, masks, slot records, store bases -- and carries it across the wait in registers: a wave that waits issues nothing.
 //   B. a lane owns 8 consecutive luma rows x 4 pixels (4 chroma rows x 4): it lies inside one leaf whatever the split.  CopyBlock
 //      (MD.cs:424-452) by v_perm_b32 (byte window out of two dwords) and v_lerp_u8: (a>>1)+(b>>1) per byte is the byte average of
 //      a & 0xFE and b & 0xFE; phase 0 uses the same instructions with mask 0xFF and b = a.
@@ -408,19 +410,24 @@ static_assert(23 * P_TILE * 4 + 2 < (1 << 13) && (P_PITCH & 15) == 0, "P_INV's o
 __device__ __forceinline__ int out_px(int g, int R, int c) { return P_OUT + (R & 7) * P_PITCH + (R >> 3) * 128 + (g << 4) + c; }
 __device__ __forceinline__ int out_c(int g, int R, int pl, int x) { return out_px(g, 16 + R, pl * 8 + x); }
 // N output rows of 4 pixels from N + 1 window rows (x0[i], x1[i] = the two aligned dwords holding row i's 5 bytes)
-template <int N>
-__device__ __forceinline__ void mc_rows(const uint32_t (&x0)[N + 1], const uint32_t (&x1)[N + 1], uint32_t sh, int phase, uint32_t *out) {
-  // CopyBlock (MD.cs:424-452) as two stages that every phase runs: h = (a >> 1) + (b >> 1) per byte with b = a and no masking when the
-  // phase has no horizontal half-pel ((a + a) >> 1 = a), then the same between a row and the row below it (or itself).
-  // (x >> 1) + (y >> 1) per byte = v_lerp_u8(x & 0xFE, y & 0xFE): the byte average of the two, which cannot carry once the low bits are gone.
+// CopyBlock (MD.cs:424-452) as two stages that every phase runs: h = (a >> 1) + (b >> 1) per byte with b = a and no masking when the
+// phase has no horizontal half-pel ((a + a) >> 1 = a), then the same between a row and the row below it (or itself).
+// (x >> 1) + (y >> 1) per byte = v_lerp_u8(x & 0xFE, y & 0xFE): the byte average of the two, which cannot carry once the low bits are gone.
+// What of that depends on the leaf alone -- the byte selectors of the window's shift, the masks of the two half-pel stages -- is prepared
+// while the windows are in flight (McSel, stage A's set-up); the vertical half-pel travels as a wave mask.
+struct McSel { uint32_t selA, selB, Mh, Mv; };
+__device__ __forceinline__ McSel mc_prepare(uint32_t sh, int phase) {
   const bool hor = (phase & 1) != 0, ver = (phase & 2) != 0;
-  const uint32_t selA = 0x03020100u + sh * 0x01010101u, selB = hor ? selA + 0x01010101u : selA;
-  const uint32_t Mh = hor ? 0xFEFEFEFEu : 0xFFFFFFFFu, Mv = ver ? 0xFEFEFEFEu : 0xFFFFFFFFu;
+  const uint32_t selA = 0x03020100u + sh * 0x01010101u;
+  return McSel{selA, hor ? selA + 0x01010101u : selA, hor ? 0xFEFEFEFEu : 0xFFFFFFFFu, ver ? 0xFEFEFEFEu : 0xFFFFFFFFu};
+}
+template <int N>
+__device__ __forceinline__ void mc_rows(const uint32_t (&x0)[N + 1], const uint32_t (&x1)[N + 1], const McSel &s, bool ver, uint32_t *out) {
   uint32_t m[N + 1];
 #pragma unroll
   for (int i = 0; i <= N; i++) {
-    const uint32_t a = __builtin_amdgcn_perm(x1[i], x0[i], selA) & Mh, b = __builtin_amdgcn_perm(x1[i], x0[i], selB) & Mh;
-    m[i] = __builtin_amdgcn_lerp(a, b, 0u) & Mv;
+    const uint32_t a = __builtin_amdgcn_perm(x1[i], x0[i], s.selA) & s.Mh, b = __builtin_amdgcn_perm(x1[i], x0[i], s.selB) & s.Mh;
+    m[i] = __builtin_amdgcn_lerp(a, b, 0u) & s.Mv;
   }
 #pragma unroll
   for (int i = 0; i < N; i++) out[i] = __builtin_amdgcn_lerp(m[i], ver ? m[i + 1] : m[i], 0u);
@@ -465,8 +472,9 @@ __device__ __forceinline__ void recon_inter_oct(const MobiReconArgs &A, uint8_t 
   // the same idea as a loss: as a DMA of two lines into LDS, in a kernel that was bound by its requests.  The address is a scalar base and
   // the lane's four bytes of the 256 (one vector instruction: computed per lane it cost nine).  Not in the one-launch step (FUSED: small
   // batches, whose table ends within P_TOUCH workgroups; not measured there).  The wait for the windows below waits for these lines too
-  // (fetch wait 1221 -> 1407 clocks in the cycle records): as the LAST request with a wait for all but one it would not; written, not
-  // yet run on a GPU (HISTORY.md).
+  // (fetch wait 1221 -> 1407 clocks in the cycle records).  As the LAST request, behind the level words, with a wait for all but one it
+  // is not waited for -- and the step is 0.03 ms SLOWER than with the touch here (three runs each, alternating: HISTORY.md, "set-up in
+  // the wait for the windows"): not kept.
   uint32_t touch = 0;
   if (!FUSED) {
     const uint32_t own = clip * (uint32_t)A.n_mbs + mby * mbw + mbx0, total = (uint32_t)A.n_clips * (uint32_t)A.n_mbs; // (wave-uniform)
@@ -652,8 +660,74 @@ __device__ __forceinline__ void recon_inter_oct(const MobiReconArgs &A, uint8_t 
     if (m2) load_cell(__builtin_ctz(m2), cell1);
   }
   if (PROF) pt[1] = prof_stamp();
+  // ---- set-up of stages B, C and D while the windows are in flight ----
+  // Every request of the octet is out; until the windows are here the wave holds its place and used to issue nothing.  What stages
+  // B and C need besides the windows is a function of the wave's OWN descriptors, the ballots above and the lane number, so it is worked
+  // out here, in the shadow of the wait, and crosses it (and the deep trees' fetch behind it) in registers: the windows' LDS addresses, the
+  // byte selectors and masks of both mc_rows, the vertical half-pel conditions as wave masks, the lane's slot record of stage C as the two
+  // words it writes to P_TAB / P_INV (LDS is full of windows until the motion compensation is over: nothing goes there early) and the
+  // bases of the output rows.  Lane (g, rr = j >> 2, q = j & 3) = luma rows 8rr..8rr+7, pixels 4q..4q+3; lane (g, pl = j >> 2,
+  // ch = (j >> 1) & 1, qc = j & 1) = plane pl, chroma rows 4ch..4ch+3, samples 4qc..4qc+3: either lies inside one leaf whatever the split.
+  // (The values are operands of the empty asm statements in front of the wait: the compiler would sink them to their first use.)
+  __builtin_amdgcn_s_setprio(0); // (the set-up yields to the other waves' requests like stage B's arithmetic: at priority 3 it gave half the gain)
+  const int rr = j >> 2, q = j & 3;
+  const int pl = j >> 2, ch = (j >> 1) & 1, qc = j & 1;
+  // out_px, one base per lane and the row as a constant offset: luma rows 8 * rr + k, chroma rows 4 * ch + k
+  int by = out_px(g, 8 * rr, 4 * q), bc = out_c(g, 4 * ch, pl, 4 * qc);
+  const int cl = P_C + 4 * ch * 256 + g * 16 + pl * 8, yl = P_L + 4 * rr * 512 + g * 16; // the lane's chroma / luma window rows outside a pair
+  McSel csel, ysel;
+  int ca0, ca1, ya0e, ya0o, ya1e, ya1o;
+  unsigned long long cver, yver;
+  {
+    const bool cBl = (tb && ch) || (lr && qc);
+    const int ctop = cBl ? ctopB : cposA, cph = cBl ? cphB : cphA;
+    const int cxo = ctop & 7, d0 = (cxo + (lr ? 0 : 4 * qc)) >> 2, d1 = d0 + 1;
+    const int base = cl + ((lr && qc) ? P_C1 - P_C : 0) + ((tb && ch) ? 256 : 0); // (TOP/BOTTOM: leaf B's rows from 5, not 4)
+    ca0 = base + (d0 >> 1) * 128 + (d0 & 1) * 4;
+    ca1 = base + (d1 >> 1) * 128 + (d1 & 1) * 4;
+    csel = mc_prepare((uint32_t)cxo & 3u, cph);
+    cver = __builtin_amdgcn_ballot_w64((cph & 2) != 0);
+  }
+  {
+    // window row w of the lane's leaf sits in pair (yo + w) >> 1, row (yo + w) & 1 of it (yo = the window's first row is odd): the even
+    // rows of the lane's nine at one address + (k >> 1) * 512, the odd ones at another
+    const bool rB = tb && rr, qB = lr && q >= 2;
+    const int ytop = rB || qB ? topB : posA, yph = rB || qB ? phB : phA;
+    const int yo = (ytop >> lgS) & 1, xo = ytop & 7;
+    const int d0 = (xo + 4 * (qB ? q - 2 : q)) >> 2, d1 = d0 + 1;
+    const int base = yl + (rB ? 512 : 0) + (qB ? 256 : 0); // (TOP/BOTTOM: leaf B's pairs from 5, not 4)
+    const int a0 = base + (d0 >> 1) * 128 + (d0 & 1) * 4, a1 = base + (d1 >> 1) * 128 + (d1 & 1) * 4;
+    const int ev = yo * 8, od = yo ? 512 : 8;
+    ya0e = a0 + ev; ya0o = a0 + od; ya1e = a1 + ev; ya1o = a1 + od;
+    ysel = mc_prepare((uint32_t)xo & 3u, yph);
+    yver = __builtin_amdgcn_ballot_w64((yph & 2) != 0);
+  }
+  // stage C's slots: the 8x8 areas first, then -- from an even slot, so that the two areas of a packed pair are of one kind -- the areas
+  // made of 4x4 blocks; inside a kind by area, then macroblock.  (n8 odd: slot n8 stays empty.)  Lane area * 8 + g owns that area's record.
+  const uint32_t m8_lo = m_lo & t_lo, m8_hi = m_hi & t_hi, m4_lo = m_lo & ~t_lo, m4_hi = m_hi & ~t_hi;
+  const int n8_lo = __builtin_popcount(m8_lo), n8 = n8_lo + __builtin_popcount(m8_hi);
+  const int n4_lo = __builtin_popcount(m4_lo), first4 = (n8 + 1) & ~1, n_slots = first4 + n4_lo + __builtin_popcount(m4_hi);
+  uint32_t slot4, tab_w, inv_w;
+  {
+    const bool hi = lane >= 32;
+    const uint32_t below = (1u << (lane & 31)) - 1u;
+    const bool is8 = __builtin_amdgcn_inverse_ballot_w64(tb64);
+    const uint32_t flip = is8 ? 0u : 0xFFFFFFFFu;
+    const uint32_t mask = hi ? m_hi & (t_hi ^ flip) : m_lo & (t_lo ^ flip);
+    const int first = (is8 ? 0 : first4) + (hi ? (is8 ? n8_lo : n4_lo) : 0);
+    const int slot = first + __builtin_popcount(mask & below);
+    const int a = lane >> 3;
+    const uint32_t K = (uint32_t)((a < 4 ? a >> 1 : 2) * 128 + (a & 1) * 8);
+    slot4 = 4u * (uint32_t)slot;
+    tab_w = ((uint32_t)lane << 8) | ((K + ((uint32_t)(lane & 7) << 4)) << 16);
+    inv_w = (uint32_t)((slot >> 1) * (P_TILE * 4) + (slot & 1) * 2) | ((uint32_t)slot << 13) | ((is8 ? 0x0FCu : 0x13Cu) << 23); // area * 8 + g -> slot, for the scatter
+  }
+  asm volatile("" : "+v"(ca0), "+v"(ca1), "+v"(csel.selA), "+v"(csel.selB), "+v"(csel.Mh), "+v"(csel.Mv), "+s"(cver));
+  asm volatile("" : "+v"(ya0e), "+v"(ya0o), "+v"(ya1e), "+v"(ya1o), "+v"(ysel.selA), "+v"(ysel.selB), "+v"(ysel.Mh), "+v"(ysel.Mv), "+s"(yver));
+  asm volatile("" : "+v"(slot4), "+v"(tab_w), "+v"(inv_w), "+v"(by), "+v"(bc));
   MOBI_STOP(2);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_setprio(3); // (the deep trees' requests below)
   if (!FUSED) asm volatile("" : : "v"(touch)); // (the load has come back with everything else; nobody looks at it)
   wave_sync();
   if (PROF) pt[2] = prof_stamp();
@@ -778,49 +852,31 @@ __device__ __forceinline__ void recon_inter_oct(const MobiReconArgs &A, uint8_t 
 
   __builtin_amdgcn_s_setprio(0); // (behind the deep trees' requests too: 7.17 -> 7.10 ms; priority during the motion compensation costs: 7.27)
   MOBI_STOP(3);
-  // ---- stage B: motion compensation.  Lane (g, rr = j >> 2, q = j & 3) = luma rows 8rr..8rr+7, pixels 4q..4q+3; lane (g, pl = j >> 2,
-  // ch = (j >> 1) & 1, qc = j & 1) = plane pl, chroma rows 4ch..4ch+3, samples 4qc..4qc+3: either lies inside one leaf whatever the split ----
+  // ---- stage B: motion compensation, from the addresses, selectors and masks prepared behind stage A's requests ----
   uint32_t mcv[12];
-  const int rr = j >> 2, q = j & 3;
-  const int pl = j >> 2, ch = (j >> 1) & 1, qc = j & 1;
   {
     // chroma first: its windows make room for the dequant scales
-    const bool cBl = (tb && ch) || (lr && qc);
-    const int ctop = cBl ? ctopB : cposA, cph = cBl ? cphB : cphA;
-    const int cxo = ctop & 7, d0 = (cxo + (lr ? 0 : 4 * qc)) >> 2, d1 = d0 + 1;
-    const int base = ((lr && qc) ? P_C1 : P_C) + ((tb && ch) ? 5 : 4 * ch) * 256 + g * 16 + pl * 8;
-    const int a0 = base + (d0 >> 1) * 128 + (d0 & 1) * 4, a1 = base + (d1 >> 1) * 128 + (d1 & 1) * 4;
     uint32_t x0[5], x1[5];
 #pragma unroll
-    for (int k = 0; k < 5; k++) { x0[k] = lds32(L, a0 + k * 256); x1[k] = lds32(L, a1 + k * 256); }
-    mc_rows<4>(x0, x1, (uint32_t)cxo & 3u, cph, mcv + 8);
+    for (int k = 0; k < 5; k++) { x0[k] = lds32(L, ca0 + k * 256); x1[k] = lds32(L, ca1 + k * 256); }
+    mc_rows<4>(x0, x1, csel, __builtin_amdgcn_inverse_ballot_w64(cver), mcv + 8);
   }
   MOBI_STOP(4);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   if (lane < MOBI_SCALE_STRIDE / 4) MOBI_DMA16((const uint8_t *)(A.scale + quant * MOBI_SCALE_STRIDE) + lane * 16, L + P_SC, 0);
   {
-    // window row w of the lane's leaf sits in pair (yo + w) >> 1, row (yo + w) & 1 of it (yo = the window's first row is odd)
-    const bool rB = tb && rr, qB = lr && q >= 2;
-    const int ytop = rB || qB ? topB : posA, yph = rB || qB ? phB : phA;
-    const int yo = (ytop >> lgS) & 1, xo = ytop & 7;
-    const int d0 = (xo + 4 * (qB ? q - 2 : q)) >> 2, d1 = d0 + 1;
-    const int base = P_L + (rB ? 5 : 4 * rr) * 512 + g * 16 + (qB ? 256 : 0);
-    const int a0 = base + (d0 >> 1) * 128 + (d0 & 1) * 4, a1 = base + (d1 >> 1) * 128 + (d1 & 1) * 4;
-    const int ev = yo * 8, od = yo ? 512 : 8;
     uint32_t x0[9], x1[9];
 #pragma unroll
     for (int k = 0; k < 9; k++) {
-      const int o = (k >> 1) * 512 + ((k & 1) ? od : ev);
-      x0[k] = lds32(L, a0 + o);
-      x1[k] = lds32(L, a1 + o);
+      const int o = (k >> 1) * 512;
+      x0[k] = lds32(L, ((k & 1) ? ya0o : ya0e) + o);
+      x1[k] = lds32(L, ((k & 1) ? ya1o : ya1e) + o);
     }
-    mc_rows<8>(x0, x1, (uint32_t)xo & 3u, yph, mcv);
+    mc_rows<8>(x0, x1, ysel, __builtin_amdgcn_inverse_ballot_w64(yver), mcv);
   }
   MOBI_STOP(5);
   wave_sync();
   {
-    // out_px, one base per lane and the row as a constant offset: luma rows 8 * rr + k, chroma rows 4 * ch + k
-    const int by = out_px(g, 8 * rr, 4 * q), bc = out_c(g, 4 * ch, pl, 4 * qc);
 #pragma unroll
     for (int k = 0; k < 8; k++) *(uint32_t *)(L + (by + k * P_PITCH)) = mcv[k];
 #pragma unroll
@@ -852,24 +908,11 @@ __device__ __forceinline__ void recon_inter_oct(const MobiReconArgs &A, uint8_t 
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the scales
   wave_sync();
   if (m_lo | m_hi) {
-    // slots: the 8x8 areas first, then -- from an even slot, so that the two areas of a packed pair are of one kind -- the areas made of
-    // 4x4 blocks; inside a kind by area, then macroblock.  (n8 odd: slot n8 stays empty.)
-    const uint32_t m8_lo = m_lo & t_lo, m8_hi = m_hi & t_hi, m4_lo = m_lo & ~t_lo, m4_hi = m_hi & ~t_hi;
-    const int n8_lo = __builtin_popcount(m8_lo), n8 = n8_lo + __builtin_popcount(m8_hi);
-    const int n4_lo = __builtin_popcount(m4_lo), first4 = (n8 + 1) & ~1, n_slots = first4 + n4_lo + __builtin_popcount(m4_hi);
+    // the slot records (prepared behind stage A's requests): the lanes of the coded areas write theirs
     {
-      const bool hi = lane >= 32;
-      const int kk = lane & 31;
-      if (((hi ? m_hi : m_lo) >> kk) & 1) {
-        const bool is8 = ((hi ? t_hi : t_lo) >> kk) & 1;
-        const uint32_t flip = is8 ? 0u : 0xFFFFFFFFu;
-        const uint32_t mask = hi ? m_hi & (t_hi ^ flip) : m_lo & (t_lo ^ flip);
-        const int first = (is8 ? 0 : first4) + (hi ? (is8 ? n8_lo : n4_lo) : 0);
-        const int slot = first + __builtin_popcount(mask & ((1u << kk) - 1u));
-        const int a = lane >> 3;
-        const uint32_t K = (uint32_t)((a < 4 ? a >> 1 : 2) * 128 + (a & 1) * 8);
-        *(uint32_t *)(L + P_TAB + 4 * slot) = ((uint32_t)lane << 8) | ((K + ((uint32_t)(lane & 7) << 4)) << 16);
-        *(uint32_t *)(L + P_INV + 4 * lane) = (uint32_t)((slot >> 1) * (P_TILE * 4) + (slot & 1) * 2) | ((uint32_t)slot << 13) | ((is8 ? 0x0FCu : 0x13Cu) << 23); // area * 8 + g -> slot, for the scatter
+      if (__builtin_amdgcn_inverse_ballot_w64(mb64)) {
+        *(uint32_t *)(L + P_TAB + slot4) = tab_w;
+        *(uint32_t *)(L + P_INV + 4 * lane) = inv_w;
       }
       if (lane < 48) *(uint32_t *)(L + P_SUM + 4 * lane) = 0u;
     }

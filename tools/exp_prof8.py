@@ -30,7 +30,9 @@ def run(tag, clips=int(os.environ.get("CLIPS", "2048")), **kw):
     rec = recs.sum(0)
     w = float(live.sum())
     print(f"    inside A: kernel arguments {float(((extra >> 8) & 0xFFFFFF).sum()) / w:.0f}  descriptor {float((extra >> 32).sum()) / w:.0f}")
-    names = ["A issue", "fetch wait", "MC", "deep", "residual", "store issue"]
+    # "set-up + fetch wait": the stamps around the wait for the windows also enclose the set-up of stages B, C and D that runs in its shadow
+    # (recon_inter_oct); up to the serial-path work the interval held the wait alone and was printed as "fetch wait"
+    names = ["A issue", "set-up + fetch wait", "MC", "deep", "residual", "store issue"]
     tot = sum(float(rec[k]) for k in range(6))
     print(f"{tag}: {int(w)} waves, {tot / w:.0f} cycles per wave; " + "  ".join(f"{names[k]} {float(rec[k]) / w:.0f}" for k in range(6)) + f"; coded areas per octet {float(rec[7]) / w:.1f}", flush=True)
     b.close()

@@ -2,6 +2,7 @@
 # usage (GPU box): tools/exp_stages.sh <tag> [clips]  -- dynamic instruction counts of mobi_recon_inter8 stage by stage: the profiling twin of the
 # library leaves the kernel after stage n (MOBI_STOP_STAGE=n, decided at run time so nothing is optimised away); the difference of two
 # runs' SQ_INSTS_* per wave is that stage's share.  Stages: 1 descriptor decode + window DMA issue, 2 level words + MV cells asked for,
+# (since the set-up in the wait for the windows: + the window addresses, selectors, masks, slot records and store bases of stages 4 - 8),
 # 3 waited + deep fetch issued, 4 chroma MC, 5 luma MC, 6 MC stored, 7 slow path done, 8 residual set-up, 9 tiles zeroed + scattered,
 # 10 pass 1, 11 pass 2 of the first round, 12 all rounds, 0 whole kernel (with stores).
 TAG=${1:-stages}; CLIPS=${2:-4096}; REPO=${GRAFT_REPO_ROOT:-$(pwd)}; OUT=$REPO/gpurun_out/$TAG; mkdir -p "$OUT"
