@@ -361,6 +361,44 @@ int mobi_batch_export_device_scaled(mobi_batch *b, int format, int dtype, const 
 int mobi_batch_export_device_boxes(mobi_batch *b, int format, int dtype, const float *scale_bias,
                                    const int32_t *boxes /* host, n_clips x 5: x, y, w, h, flags */, int out_w, int out_h, int ring_idx,
                                    int n_frames, int clip0, int n_clips, void *dst, size_t dst_bytes, void *stream);
+/* ---- the motion the stream carries: the decoder's motion field and macroblock data as device tensors -------------------------------
+ * What a decoder knows besides the pictures: the motion vector and reference of every 2x2 luma cell, which macroblocks are intra, the
+ * quantiser and how much residual was coded.  (mobi_batch_motion_search below is the encoder's side: it ESTIMATES motion of new pictures.)
+ * mobi_batch_set_motion(b, 1) allocates a motion ring of six slots per clip beside the picture ring (288 bytes per macroblock and slot);
+ * from then on every frame step -- decode, submit / wait, groups, replay, the repair of a clip in mobi_batch_wait -- writes its slot with
+ * one more kernel (mobi_motion_field) that reads the step's command list in HBM.  mobi_batch_set_motion(b, 0) frees the ring.  Allowed only
+ * with nothing in flight: MOBI_E_ARG while a submitted step or a group is outstanding or an export (host or device) may still be running;
+ * setting the state the batch is in is a no-op.  A batch that never switches motion on runs the code it ran before: no allocation, no launch
+ * (mobi_batch_motion_bytes and mobi_batch_motion_launches stay 0).
+ *   VECTORS:  (dx, dy) in half samples, pointing from the block to its source in the reference picture (the decoder's sign); ref = 1..5,
+ *             frames back; ref 0 = an intra macroblock (dx = dy = 0).  The reference decoder addresses its planes linearly, so
+ *             (dx - 4 t Stride, dy + 4 t) is the same copy for every t; the vector exported is the member of that class with
+ *             -2 Stride <= dx < 2 Stride, however the macroblock was partitioned.  Stride >= Width: every vector that moves by less than a
+ *             picture width is exported as the stream codes it.
+ *   A clip whose frame was refused or idle: the content of its slot is unspecified, as its picture's is.
+ * mobi_batch_export_motion follows mobi_batch_export_device in every respect -- picture order and dst + (j * n_clips + (c - clip0)) *
+ * picture_bytes, STREAM, SNAPSHOT (a later step that writes a motion slot waits for the kernels reading it), LIFETIME, and its refusals --
+ * and refuses with MOBI_E_ARG when motion is not enabled or format / dtype / block / scale are outside the list below, and with
+ * MOBI_E_NULLREF a ring index whose frame was decoded before motion was switched on.  W, H = the picture's width and height:
+ *   MOBI_MOTION_CELLS  dtype MOBI_DTYPE_I16, block 2: per picture int16 [3][H/2][W/2], row-major: dx, dy, ref of every cell.
+ *   MOBI_MOTION_MB     dtype MOBI_DTYPE_I32, block 16: per picture int32 [5][H/16][W/16]: type (0 inter, 1 intra); the quantiser field of the
+ *                      command list (63: the frame's residual words are literal coefficient values, 62: no quantiser table was ever set
+ *                      up); cbp6 (coded 8x8 areas: bits 0-3 luma, 4 U, 5 V); the number of coded levels; the sum of their magnitudes.
+ *   MOBI_MOTION_FLOW   dtype MOBI_DTYPE_F32 or MOBI_DTYPE_F16, block 2, 4, 8 or 16: per picture [2][H/block][W/block]: x, y.  Per cell
+ *                      nx = dx * (60 / ref), ny = dy * (60 / ref) (integers), 0 for intra cells; Sx, Sy = their int32 sums over the block's
+ *                      cells = (block / 2)^2 cells; k = (float)((double)scale / (120.0 * cells)); float32 = (float)Sx * k, one conversion and
+ *                      one product, each rounded once; float16 = that value rounded to nearest-even.  scale = 1: the mean displacement in
+ *                      pixels per frame, pointing from the block to its source.  scale must be finite; the other formats ignore it. */
+#define MOBI_MOTION_CELLS 0
+#define MOBI_MOTION_MB 1
+#define MOBI_MOTION_FLOW 2
+#define MOBI_DTYPE_I16 3 /* int16 */
+#define MOBI_DTYPE_I32 4 /* int32 */
+int mobi_batch_set_motion(mobi_batch *b, int on);
+long mobi_batch_motion_launches(const mobi_batch *b); /* launches of mobi_motion_field so far */
+size_t mobi_batch_motion_bytes(const mobi_batch *b);  /* device memory the motion ring holds (0: motion is off) */
+int mobi_batch_export_motion(mobi_batch *b, int format, int dtype, int block, float scale, int ring_idx, int n_frames, int clip0, int n_clips,
+                             void *dst, size_t dst_bytes, void *stream);
 /* Encoder-side analysis: Analyzer.InterPredict2x2 (Analyzer.cs:608-681) for every 2x2 luma block of
  * every macroblock of every clip, as SolveInterPredictionPuzzle calls it (:683-693): three-step search (6, 3, 1 pels) in up
  * to five past frames = ring slots 0..4 of this batch (the encoder's PastFramesY, MobiEncoder.cs:138-144).

@@ -9,6 +9,7 @@
   tests/tools/libmobi_idle_host.so  the frame-parallel chain's kernel bodies on the CPU, idle slots = TEST TOOL (g++)
   tests/tools/libmobi_audio_host.so  the audio arithmetic header (csrc/mobi_audio.h) on the CPU = TEST TOOL (g++)
   tests/tools/libmobi_sx_host.so  the Sx arithmetic header (csrc/mobi_sx.h) on the CPU = TEST TOOL (g++)
+  tests/tools/libmobi_motionhost.so  "command list -> motion" (csrc/mobi_motion.h) on the CPU = TEST TOOL (g++)
   tests/tools/abi_caller            plain-C caller of the product's C ABI = TEST TOOL (gcc)
 
 hipcc cross-compiles gfx950 without a GPU.  The built .so files are git-ignored but travel to the
@@ -34,11 +35,12 @@ LIB_LSHOST = os.path.join(ROOT, "tests", "tools", "libmobi_lsparse_host.so")  # 
 LIB_IDLEHOST = os.path.join(ROOT, "tests", "tools", "libmobi_idle_host.so")  # mobi_gop_prepare / mobi_gop_chain bodies on the CPU (test tool)
 LIB_AUDIOHOST = os.path.join(ROOT, "tests", "tools", "libmobi_audio_host.so")  # csrc/mobi_audio.h's per-sample arithmetic on the CPU (test tool)
 LIB_SXHOST = os.path.join(ROOT, "tests", "tools", "libmobi_sx_host.so")  # csrc/mobi_sx.h's packet arithmetic on the CPU (test tool)
+LIB_MOTIONHOST = os.path.join(ROOT, "tests", "tools", "libmobi_motionhost.so")  # csrc/mobi_motion.h's reading of a command list on the CPU (test tool)
 ABI_CALLER = os.path.join(ROOT, "tests", "tools", "abi_caller")  # plain-C caller of the product library (test tool)
 
 
 # the sources of libmobiclip_hip.so: *.cpp are host objects (g++), *.hip kernel objects (hipcc --offload-arch=gfx950); linked in this order
-HIP_SOURCES = ("mobi_batch.cpp", "mobi_step_host.cpp", "mobi_step_device.cpp", "mobi_step_groups.cpp", "mobi_replay.cpp", "mobi_pictures.cpp", "mobi_parse.cpp", "mobi_demux.cpp", "mobi_moflex.cpp", "mobi_export.cpp", "mobi_txcode.cpp", "mobi_audio_plan.cpp", "mobi_audio.cpp", "mobi_kernels.hip", "mobi_rgb.hip", "mobi_dparse.hip", "mobi_lsparse.hip", "mobi_gop.hip", "mobi_analysis.hip", "mobi_export.hip", "mobi_txcode.hip", "mobi_export_rgb.hip", "mobi_export_scale.hip", "mobi_export_resample.hip", "mobi_reset.hip", "mobi_idle.hip", "mobi_audio.hip", "mobi_sx.hip")
+HIP_SOURCES = ("mobi_batch.cpp", "mobi_step_host.cpp", "mobi_step_device.cpp", "mobi_step_groups.cpp", "mobi_replay.cpp", "mobi_pictures.cpp", "mobi_parse.cpp", "mobi_demux.cpp", "mobi_moflex.cpp", "mobi_export.cpp", "mobi_txcode.cpp", "mobi_audio_plan.cpp", "mobi_audio.cpp", "mobi_kernels.hip", "mobi_rgb.hip", "mobi_dparse.hip", "mobi_lsparse.hip", "mobi_gop.hip", "mobi_analysis.hip", "mobi_export.hip", "mobi_txcode.hip", "mobi_export_rgb.hip", "mobi_export_scale.hip", "mobi_export_resample.hip", "mobi_reset.hip", "mobi_idle.hip", "mobi_audio.hip", "mobi_sx.hip", "mobi_motion.hip")
 
 
 def hip_objects(profiling=False):
@@ -168,6 +170,13 @@ def build_sxhost(force=False):
     return LIB_SXHOST
 
 
+def build_motionhost(force=False):
+    src = os.path.join(ROOT, "tests", "tools", "mobi_motion_host.cpp")
+    if force or _newer(LIB_MOTIONHOST, [src] + [os.path.join(CSRC, h) for h in ("mobi_motion.h", "mobi_syntax.h", "mobi_cmd.h")]):
+        _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-fwrapv", "-I" + CSRC, src, "-o", LIB_MOTIONHOST])
+    return LIB_MOTIONHOST
+
+
 def build_caller(force=False):
     src = os.path.join(ROOT, "tests", "tools", "abi_caller.c")
     if force or _newer(ABI_CALLER, [src, os.path.join(ROOT, "include", "mobiclip_hip.h"), LIB_HIP]):
@@ -176,7 +185,7 @@ def build_caller(force=False):
 
 
 def build_all(force=False):
-    return [build_hip(force), build_hip(force, profiling=True), build_gen(force), build_oracle(force), build_interp(force), build_lshost(force), build_idlehost(force), build_audiohost(force), build_sxhost(force), build_caller(force)]
+    return [build_hip(force), build_hip(force, profiling=True), build_gen(force), build_oracle(force), build_interp(force), build_lshost(force), build_idlehost(force), build_audiohost(force), build_sxhost(force), build_motionhost(force), build_caller(force)]
 
 
 if __name__ == "__main__":

@@ -293,6 +293,29 @@ int mobi_batch_clip_idle(const mobi_batch *b, int32_t *out) {
   return MOBI_OK;
 }
 int mobi_batch_idle_launches(const mobi_batch *b) { return b ? b->idle_launches : 0; }
+// ---- the motion ring (mobi_motion_ring.h): switched on and off with nothing in flight, so that no step is half with and half without ----
+int mobi_batch_set_motion(mobi_batch *b, int on) {
+  if (!b) return MOBI_E_ARG;
+  if (b->poisoned) return MOBI_E_DEVICE;
+  if ((on != 0) == b->motion_on) return MOBI_OK; // (a batch that never asked for motion: nothing at all)
+  if (b->async_count || b->gop_count || (b->exporter && mobi_exporter_busy(b->exporter))) return MOBI_E_ARG;
+  HIP_TRY(hipSetDevice(b->device));
+  HIP_TRY(hipStreamSynchronize(b->stream)); // (synchronous steps may have left launches behind the caller's last wait: mobi_batch_replay)
+  if (!on) {
+    b->motion_on = false;
+    b->d_mcells.free();
+    b->d_mmbs.free();
+    return MOBI_OK;
+  }
+  const size_t mbs = (size_t)b->n * 6 * b->g.mbw * b->g.mbh;
+  if (int e = b->d_mcells.alloc(mbs * MOBI_MV_CELLS)) return e;
+  if (int e = b->d_mmbs.alloc(mbs * MOBI_MOTION_MB_WORDS)) { b->d_mcells.free(); return e; }
+  b->motion_on = true;
+  b->motion_from = b->frames_started;
+  return MOBI_OK;
+}
+long mobi_batch_motion_launches(const mobi_batch *b) { return b ? b->motion_launches : 0; }
+size_t mobi_batch_motion_bytes(const mobi_batch *b) { return b ? b->motion_bytes() : 0; }
 int idle_check(const mobi_batch *b, int K, std::vector<uint8_t> &from) {
   from.clear();
   if (!b->idle_frames && !b->n_ended) return MOBI_OK; // (a caller that never sets a mask: no per-clip work)

@@ -29,6 +29,7 @@
 #include "mobi_handover.h"
 static_assert(StageImage::kSkip == MOBI_DP_SKIP, "the staged image and the parse kernels name a skipped lane alike");
 #include "mobi_kernels.h"
+#include "mobi_motion_ring.h"
 #include "mobi_tile.h"
 #include "mobi_parse.h"
 
@@ -432,6 +433,28 @@ struct mobi_batch {
   int n_ended = 0;                     // clips with the mark
   std::vector<int32_t> idle_count;     // [clip] idle slots handed over since the clip's last live frame or reset
   int idle_launches = 0;               // launches of mobi_idle_rows so far (mobi_batch_idle_launches)
+  // the motion ring (mobi_batch_set_motion; mobi_motion_ring.h): six slots per clip beside the picture ring's, the slot index is ring_base.
+  // A batch that never asks for motion has motion_on == false: no allocation, and motion_step below returns at its first test.
+  bool motion_on = false;
+  DevArr<uint32_t> d_mcells;           // [clip][slot][mb][64]
+  DevArr<int32_t> d_mmbs;              // [clip][slot][mb][MOBI_MOTION_MB_WORDS]
+  int motion_from = 0;                 // frames_started when motion was switched on: frames after that one have a motion slot
+  long motion_launches = 0;            // launches of mobi_motion_field so far (mobi_batch_motion_launches)
+  size_t motion_bytes() const { return motion_on ? (size_t)n * 6 * g.mbw * g.mbh * (64 + MOBI_MOTION_MB_WORDS) * 4 : 0; }
+  bool motion_has(int ring_idx) const { return motion_on && frames_started - ring_idx > motion_from; }
+  // The hook of every place that launches reconstruction: the step's command list -> its motion slot, directly behind the step's inter launch
+  // on the batch's stream, i.e. before whatever lets the next parse reuse the list's tables.  a = the step's own arguments (a partial launch
+  // carries its first clip in `planes`).  The slot is the step's, which begin_step has guarded; a repair writes the slot of an earlier
+  // step (recon_clips) and takes the guard here.  Idempotent: a step launched twice writes the same words twice.
+  int motion_step(const MobiReconArgs &a) {
+    if (!motion_on) return MOBI_OK;
+    if (a.ring_base != ring_base)
+      if (int e = exporter ? mobi_exporter_guard(exporter, a.ring_base, stream) : MOBI_OK) return e;
+    const MobiMotionRing ring{d_mcells, d_mmbs};
+    if (mobi_launch_motion_field(&a, (int)((size_t)(a.planes - (arena + kGuard)) / clip_bytes), &ring, stream) != 0) return MOBI_E_DEVICE;
+    motion_launches++;
+    return MOBI_OK;
+  }
 
   // The ring-slot guard, called by every step that writes a ring slot, right after the ring has turned and before anything of the step is
   // enqueued: the slot the step writes (ring_base) may still be read by the pack of an export; the batch's stream then waits for it.  With no
@@ -496,7 +519,7 @@ struct mobi_batch {
       if (ktiming) { ep.a = get_event(); ep.b = get_event(); (void)hipEventRecord(ep.a, stream); }
       if (mobi_launch_step(&a, items_dev, (int)plan.n_items, stream) != 0) return MOBI_E_DEVICE;
       if (ktiming) { (void)hipEventRecord(ep.b, stream); evs.push_back(ep); }
-      return MOBI_OK;
+      return motion_step(a);
     }
     if (plan.any_inter) {
       EvPair ep{nullptr, nullptr, 0};
@@ -504,6 +527,7 @@ struct mobi_batch {
       if (mobi_launch_inter(&a, stream) != 0) return MOBI_E_DEVICE;
       if (ktiming) { (void)hipEventRecord(ep.b, stream); evs.push_back(ep); }
     }
+    if (int e = motion_step(a)) return e;
     if (plan.n_items) {
       EvPair ep{nullptr, nullptr, 1};
       if (ktiming >= 2) { ep.a = get_event(); ep.b = get_event(); (void)hipEventRecord(ep.a, stream); }

@@ -247,6 +247,15 @@ int mobi_exporter_guard(MobiExporter *x, int slot, hipStream_t stream) {
   return MOBI_OK;
 }
 
+bool mobi_exporter_busy(MobiExporter *x) {
+  if (!x) return false;
+  while (!x->pending.empty() && event_done(x->pending.front().second) == 1) x->retire_upto(x->pending.front().first);
+  if (!x->pending.empty()) return true;
+  for (int s = 0; s < 6; s++)
+    if (x->prune(s) != MOBI_OK || !x->readers[s].empty()) return true; // (a query that failed: not known to be idle)
+  return false;
+}
+
 int mobi_exporter_run(MobiExporter *x, const MobiExportJob &job, uint64_t *ticket_out) {
   if (int e = x->init_staging()) return e;
   // tickets nobody waits for or asks about: the ones already done give their events back (a caller that never waits holds at most the

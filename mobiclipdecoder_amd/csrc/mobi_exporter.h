@@ -84,6 +84,8 @@ int mobi_exporter_query(MobiExporter *x, uint64_t ticket);
 // and may still be running -- host exports' packs and device exports on callers' streams alike.  No export outstanding: nothing at all
 // (no event, no wait).
 int mobi_exporter_guard(MobiExporter *x, int slot, hipStream_t stream);
+// is any export outstanding: a ticket not complete yet, or a ring slot some export may still be reading?  (mobi_batch_set_motion)
+bool mobi_exporter_busy(MobiExporter *x);
 // is [p, p + bytes) inside one block of mobi_host_alloc?
 bool mobi_host_registered(const void *p, size_t bytes);
 #endif

@@ -254,6 +254,45 @@ int mobi_batch_export_device_boxes(mobi_batch *b, int format, int dtype, const f
   return export_device(b, format, mobi_scale_picture_bytes((uint32_t)out_w, (uint32_t)out_h, (uint32_t)esize), ring_idx, n_frames, clip0, n_clips, dst,
                        dst_bytes, stream, launch, &params);
 }
+// ---- the motion ring into device memory (mobi_motion_ring.h): mobi_batch_export_device's checks, stream order and guard, the ring's kernels ----
+int mobi_batch_export_motion(mobi_batch *b, int format, int dtype, int block, float scale, int ring_idx, int n_frames, int clip0, int n_clips,
+                             void *dst, size_t dst_bytes, void *stream) {
+  if (!b || !dst) return MOBI_E_ARG;
+  const size_t n_mbs = (size_t)b->g.mbw * b->g.mbh;
+  size_t pic = 0, esize = 0;
+  float k = 0.f;
+  switch (format) {
+  case MOBI_MOTION_CELLS:
+    if (dtype != MOBI_DTYPE_I16 || block != 2) return MOBI_E_ARG;
+    pic = 3 * n_mbs * MOBI_MV_CELLS * sizeof(int16_t);
+    break;
+  case MOBI_MOTION_MB:
+    if (dtype != MOBI_DTYPE_I32 || block != 16) return MOBI_E_ARG;
+    pic = MOBI_MB_VALUES * n_mbs * sizeof(int32_t);
+    break;
+  case MOBI_MOTION_FLOW: {
+    esize = dtype == MOBI_DTYPE_F32 ? 4 : dtype == MOBI_DTYPE_F16 ? 2 : 0;
+    if (!esize || (block != 2 && block != 4 && block != 8 && block != 16) || !(scale - scale == 0.f)) return MOBI_E_ARG; // (a finite scale)
+    const int cells = (block / 2) * (block / 2);
+    k = (float)((double)scale / (120.0 * cells));
+    pic = 2 * n_mbs * (256 / (size_t)(block * block)) * esize;
+    break;
+  }
+  default:
+    return MOBI_E_ARG;
+  }
+  if (!b->motion_on) return MOBI_E_ARG;
+  // (the ranges first, as everywhere: then "this frame has no motion slot", the NULLREF of a picture never produced)
+  if (int e = check_export(b, ring_idx, n_frames, clip0, n_clips, dst_bytes >= pic * n_frames * n_clips && !((uintptr_t)dst & 15))) return e;
+  if (!b->motion_has(ring_idx)) return MOBI_E_NULLREF;
+  auto launch = [&](const MobiExportJob &job, size_t, hipStream_t st) -> int {
+    const MobiMotionExport x{{b->d_mcells, b->d_mmbs}, b->g.mbw, b->g.mbh, n_frames, n_clips, clip0, job.slot0};
+    if (format == MOBI_MOTION_CELLS) return mobi_launch_motion_cells(&x, (int16_t *)dst, st);
+    if (format == MOBI_MOTION_MB) return mobi_launch_motion_mb(&x, (int32_t *)dst, st);
+    return mobi_launch_motion_flow(&x, block, (int)esize, k, dst, st);
+  };
+  return export_device(b, format, pic, ring_idx, n_frames, clip0, n_clips, dst, dst_bytes, stream, launch);
+}
 int mobi_batch_export_wait(mobi_batch *b, uint64_t ticket) {
   if (!b || !b->exporter) return MOBI_E_ARG;
   HIP_TRY(hipSetDevice(b->device));

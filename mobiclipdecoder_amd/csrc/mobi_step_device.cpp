@@ -364,6 +364,7 @@ int decode_device_parse(mobi_batch *b, const uint8_t *const *data, const size_t 
   a.pay_clip_words = b->pay_clip_words;
   a.done = b->d_done;
   if (mobi_launch_inter(&a, b->stream) != 0) return MOBI_E_DEVICE;
+  if (int e = b->motion_step(a)) return e;
   if (K && mobi_launch_intra_cl(&a, (const uint32_t *)B.items.p, &d_res[0].n_intra, (int)(sizeof(MobiDevResult) / 4), (int)K, 0, b->stream) != 0)
     return MOBI_E_DEVICE;
   if (int e = b->read_faults(b->h_fault.data())) return e;
@@ -526,6 +527,7 @@ int mobi_batch_submit(mobi_batch *b, const uint8_t *const *data, const size_t *l
   a.pay_clip_words = b->pay_clip_words;
   a.done = b->d_done;
   if (mobi_launch_inter(&a, b->stream) != 0) return MOBI_E_DEVICE;
+  if (int e = b->motion_step(a)) return e;
   // the parse has not run yet, so nobody knows how many intra macroblocks the longest list will have: MOBI_ASYNC_INTRA_SLOTS slots are launched
   // (a P-frame's lists are shorter), and a second launch (mobi_recon_intra_walk, one workgroup per four clips) goes through the rest of theirs (an I-frame: every macroblock)
   if (mobi_launch_intra_cl(&a, (const uint32_t *)B.items.p, &d_res[0].n_intra, (int)(sizeof(MobiDevResult) / 4), std::min(n_mbs, MOBI_ASYNC_INTRA_SLOTS), 1, b->stream) != 0) return MOBI_E_DEVICE;

@@ -278,6 +278,7 @@ static int gop_recon_part(mobi_batch *b, mobi_batch::GopSlot &S, int k0, int k1)
     if (b->ktiming) { ep.a = b->get_event(); ep.b = b->get_event(); (void)hipEventRecord(ep.a, b->stream); }
     if (mobi_launch_inter(&a, b->stream) != 0) return MOBI_E_DEVICE;
     if (b->ktiming) { (void)hipEventRecord(ep.b, b->stream); b->evs.push_back(ep); }
+    if (int e = b->motion_step(a)) return e;
     if (S.sorted) {
       if (S.sorted_items[k] && mobi_launch_intra(&a, (const uint32_t *)S.d_sorted.p + S.sorted_off[k] * 4, (int)S.sorted_items[k], b->stream) != 0) return MOBI_E_DEVICE;
     } else if (Kint && mobi_launch_intra_cl(&a, (const uint32_t *)rows.items, &rows.res->n_intra, (int)(sizeof(MobiDevResult) / 4), (int)Kint, 0, b->stream) != 0)

@@ -108,6 +108,11 @@ _SIGS = {
                                                                                                                        C.c_void_p]),
     "mobi_batch_export_device_boxes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int32)] + [C.c_int] * 6
                                        + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mobi_batch_set_motion": (C.c_int, [C.c_void_p, C.c_int]),
+    "mobi_batch_motion_launches": (C.c_long, [C.c_void_p]),
+    "mobi_batch_motion_bytes": (C.c_size_t, [C.c_void_p]),
+    "mobi_batch_export_motion": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                           C.c_size_t, C.c_void_p]),
     "mobi_error_string": (C.c_char_p, [C.c_int]),
     "mobi_build_info": (C.c_char_p, []),
 }
@@ -177,6 +182,10 @@ EXPORT_FORMATS = {"i420": 0, "argb": 1}
 # mobi_batch_export_device: (fmt, layout) -> MOBI_EXPORT_*; torch dtype name -> MOBI_DTYPE_*
 DEVICE_EXPORT_FORMATS = {("i420", None): 0, ("argb", None): 1, ("rgb", "nchw"): 2, ("rgb", "nhwc"): 3}
 DEVICE_EXPORT_DTYPES = {"uint8": 0, "float16": 1, "float32": 2}
+# mobi_batch_export_motion: fmt -> (MOBI_MOTION_*, channels, the block size it has or None for a choice, torch dtype names: the first is the
+# default); torch dtype name -> MOBI_DTYPE_*
+MOTION_FORMATS = {"cells": (0, 3, 2, ("int16",)), "mb": (1, 5, 16, ("int32",)), "flow": (2, 2, None, ("float32", "float16"))}
+MOTION_DTYPES = {"float16": 1, "float32": 2, "int16": 3, "int32": 4}
 
 
 class _HostBlock:
@@ -668,6 +677,78 @@ class MobiclipBatch:
         else:
             rc = self._lib.mobi_batch_export_device(self._h, code, DEVICE_EXPORT_DTYPES[dname], sb, int(ring_idx), F, clips.start, N,
                                                     out.data_ptr(), out.numel() * out.element_size(), stream.cuda_stream)
+        if rc != 0:
+            raise MobiclipError(error_string(rc))
+        return out
+
+    def set_motion(self, on):
+        """Keep the motion field and macroblock data of every frame decoded from now on (mobi_batch_set_motion): a motion ring of six slots
+        per clip beside the picture ring, written by one more kernel per frame step; set_motion(False) frees it.  Only with nothing in
+        flight (no submitted step, no group, no export that may still run).  A batch that never calls this pays nothing."""
+        e = self._lib.mobi_batch_set_motion(self._h, 1 if on else 0)
+        if e != 0:
+            raise MobiclipError(error_string(e))
+
+    def motion_launches(self):
+        """launches of the motion kernel so far (0 for a batch that never switched motion on)"""
+        return int(self._lib.mobi_batch_motion_launches(self._h))
+
+    def motion_bytes(self):
+        """device memory the motion ring holds (0: motion is off)"""
+        return int(self._lib.mobi_batch_motion_bytes(self._h))
+
+    def export_motion(self, fmt="cells", ring_idx=0, n_frames=1, clips=None, block=None, dtype=None, scale=1.0, out=None, stream=None):
+        """The motion the stream carries, of many clips and frames, into a torch tensor [n_frames, n_clips, C, h, w] on the batch's GPU
+        (mobi_batch_export_motion; set_motion(True) first), enqueued on `stream` without a host wait, as export_tensor's pictures are.
+        Frame j = ring index ring_idx - j (oldest first), clips = a range / slice of step 1 (None: all).
+
+        fmt="cells": int16, C = 3: dx, dy (half samples, from the block to its source) and ref (0 = intra, 1..5 = frames back) of every
+                     2x2 cell; h, w = H/2, W/2.
+        fmt="mb":    int32, C = 5: type (0 inter, 1 intra), quantiser field, cbp6, coded levels, sum of their magnitudes; h, w = H/16, W/16.
+        fmt="flow":  torch.float32 (default) or torch.float16, C = 2: x, y; block = 2, 4, 8 or 16 (default 16), h, w = H/block, W/block:
+                     the mean over the block's cells of the displacement per frame back, in pixels, times `scale`, exact up to one
+                     rounding (include/mobiclip_hip.h has the arithmetic).
+        The vectors are canonical: -2 * Stride <= dx < 2 * Stride (mobiclip_hip.h).  out: a contiguous, 16-byte aligned tensor of that
+        shape and dtype on the batch's device.  Every argument is checked before the library is called (ValueError)."""
+        import torch
+        if fmt not in MOTION_FORMATS:
+            raise ValueError(f"fmt must be one of {sorted(MOTION_FORMATS)}, not {fmt!r}")
+        code, channels, fixed_block, dnames = MOTION_FORMATS[fmt]
+        if block is None:
+            block = fixed_block or 16
+        if isinstance(block, bool) or not isinstance(block, (int, np.integer)) or (block != fixed_block if fixed_block else block not in (2, 4, 8, 16)):
+            raise ValueError(f"fmt={fmt!r}: block must be {fixed_block if fixed_block else '2, 4, 8 or 16'}, not {block!r}")
+        block = int(block)
+        if dtype is None:
+            dtype = getattr(torch, dnames[0])
+        if not isinstance(dtype, torch.dtype) or str(dtype).split(".")[-1] not in dnames:
+            raise ValueError(f"fmt={fmt!r}: dtype must be {' or '.join('torch.' + d for d in dnames)}, not {dtype!r}")
+        try:
+            scale = float(scale)
+        except (TypeError, ValueError):
+            raise ValueError(f"scale must be a float, not {scale!r}") from None
+        if not np.isfinite(np.float32(scale)):
+            raise ValueError(f"scale must be finite in float32, not {scale!r}")
+        if fmt != "flow" and scale != 1.0:
+            raise ValueError("scale applies to fmt='flow' only")
+        _check_frames(ring_idx, n_frames)
+        clips = self._clip_range(clips)
+        F, N = int(n_frames), len(clips)
+        shape = (F, N, channels, self.Height // block, self.Width // block)
+        dev = torch.device("cuda", self.device)
+        if stream is not None and (not isinstance(stream, torch.cuda.Stream) or stream.device != dev):
+            raise ValueError(f"stream must be a torch.cuda.Stream of {dev}, not {stream!r}")
+        if out is not None and (not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != dtype or tuple(out.shape) != shape
+                                or not out.is_contiguous() or out.data_ptr() % 16):
+            raise ValueError(f"out must be a contiguous, 16-byte aligned {dtype} tensor of shape {shape} on {dev}")
+        _check_one_hip_runtime()
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        if out is None:
+            with torch.cuda.stream(stream):
+                out = torch.empty(shape, dtype=dtype, device=dev)
+        rc = self._lib.mobi_batch_export_motion(self._h, code, MOTION_DTYPES[str(dtype).split(".")[-1]], block, scale, int(ring_idx), F, clips.start, N,
+                                                out.data_ptr(), out.numel() * out.element_size(), stream.cuda_stream)
         if rc != 0:
             raise MobiclipError(error_string(rc))
         return out
