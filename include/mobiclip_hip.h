@@ -376,6 +376,12 @@ int mobi_batch_export_device_boxes(mobi_batch *b, int format, int dtype, const f
  *             -2 Stride <= dx < 2 Stride, however the macroblock was partitioned.  Stride >= Width: every vector that moves by less than a
  *             picture width is exported as the stream codes it.
  *   A clip whose frame was refused or idle: the content of its slot is unspecified, as its picture's is.
+ *   RESET:    mobi_batch_reset_clips moves no motion word, as it moves no pixel, and the motion ring turns with the picture ring for every
+ *             clip alike.  Whether a ring index has motion at all is a property of the batch (frames stepped since motion was switched
+ *             on), not of the clip: after a reset, ring index r of the clip holds the new stream's motion for r < min(6,
+ *             mobi_batch_clip_frames) and beyond that still the words of the OLD stream's frames, exactly as they were exported before
+ *             the reset -- the same rule as for its pictures.  A step or group in flight when the reset is called writes the old stream's
+ *             motion.  Neighbouring clips are not touched.
  * mobi_batch_export_motion follows mobi_batch_export_device in every respect -- picture order and dst + (j * n_clips + (c - clip0)) *
  * picture_bytes, STREAM, SNAPSHOT (a later step that writes a motion slot waits for the kernels reading it), LIFETIME, and its refusals --
  * and refuses with MOBI_E_ARG when motion is not enabled or format / dtype / block / scale are outside the list below, and with

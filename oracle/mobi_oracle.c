@@ -196,6 +196,69 @@ void mobi_oracle_coverage(uint64_t *out, int reset) {
   if (reset) memset(g_cov, 0, sizeof(g_cov));
 }
 
+/* ---- motion trace (tests/test_motion_oracle.py): what THIS decoder does with motion and residual, written down where it does it:
+ * mc_leaf's own arguments for every 2x2 luma cell, read_dct's levels for every macroblock.  Thread-local and test-side only, like the
+ * counters above: armed for one mobi_oracle_decode, it changes no result.  Layout in mobi_oracle.h. ---- */
+static __thread struct {
+  int armed, on, state; /* state: 0 no trace, 1 valid, -1 the frame threw */
+  int cw, ch, mbw, mbh;  /* cells and macroblocks per row / column */
+  int mb, intra, area;   /* the macroblock being decoded, and the 8x8 area (luma 0-3, U 4, V 5) of an intra macroblock */
+  int16_t *cells;        /* [3][ch][cw]     both buffers belong to the thread: replaced by its next armed decode, never freed at its  */
+  int32_t *mbs;          /* [5][mbh][mbw]   exit (a few KB per thread that ever armed a trace; the tests arm from one thread)         */
+} g_mt;
+#define MT_MB(v) (g_mt.mbs[(size_t)(v) * g_mt.mbw * g_mt.mbh + g_mt.mb])
+static void mt_begin(const D *d) {
+  g_mt.on = 0;
+  g_mt.state = 0;
+  if (!g_mt.armed) return;
+  g_mt.armed = 0;
+  g_mt.cw = (int)d->Width / 2; g_mt.ch = (int)d->Height / 2;
+  g_mt.mbw = (int)d->Width / 16; g_mt.mbh = (int)d->Height / 16;
+  free(g_mt.cells);
+  free(g_mt.mbs);
+  g_mt.cells = (int16_t *)calloc((size_t)3 * g_mt.cw * g_mt.ch + 1, sizeof(int16_t));
+  g_mt.mbs = (int32_t *)calloc((size_t)5 * g_mt.mbw * g_mt.mbh + 1, sizeof(int32_t));
+  g_mt.on = g_mt.cells && g_mt.mbs;
+  g_mt.state = -1; /* until the frame has been decoded to its end */
+}
+/* macroblock at luma offset Offset starts: inter until an intra decode says otherwise */
+static void mt_mb(const D *d, int Offset, int intra) {
+  if (!g_mt.on) return;
+  g_mt.mb = (Offset / d->Stride / 16) * g_mt.mbw + (Offset % d->Stride) / 16;
+  if (g_mt.mb < 0 || g_mt.mb >= g_mt.mbw * g_mt.mbh) { g_mt.on = 0; return; }
+  g_mt.intra = intra;
+  g_mt.area = 0;
+  MT_MB(0) = intra;
+  MT_MB(1) = (int32_t)d->Quantizer;
+}
+static void mt_leaf(const D *d, uint32_t srcFrame, uint32_t w, uint32_t h, int dx, int dy, int Offset) {
+  if (!g_mt.on) return;
+  const int x0 = (Offset % d->Stride) / 2, y0 = Offset / d->Stride / 2;
+  const size_t plane = (size_t)g_mt.cw * g_mt.ch;
+  for (int y = y0; y < y0 + (int)h / 2; y++)
+    for (int x = x0; x < x0 + (int)w / 2; x++) {
+      if (x < 0 || x >= g_mt.cw || y < 0 || y >= g_mt.ch) continue;
+      int16_t *c = g_mt.cells + (size_t)y * g_mt.cw + x;
+      c[0] = (int16_t)dx;
+      c[plane] = (int16_t)dy;
+      c[2 * plane] = (int16_t)(srcFrame / 4);
+    }
+}
+static void mt_level(int value) {
+  if (!g_mt.on) return;
+  MT_MB(3) += 1;
+  MT_MB(4) += value < 0 ? -value : value;
+  if (g_mt.intra) MT_MB(2) |= 1 << g_mt.area;
+}
+#define MT_AREA(a) (g_mt.area = (a))
+void mobi_oracle_motion_trace_arm(void) { g_mt.armed = 1; }
+int mobi_oracle_motion_trace(int16_t *cells, int32_t *mbs) {
+  if (g_mt.state == 0) return 0;
+  if (cells) memcpy(cells, g_mt.cells, (size_t)3 * g_mt.cw * g_mt.ch * sizeof(int16_t));
+  if (mbs) memcpy(mbs, g_mt.mbs, (size_t)5 * g_mt.mbw * g_mt.mbh * sizeof(int32_t));
+  return g_mt.state;
+}
+
 /* loc_1147B0 / loc_114A64 / loc_114CAC / loc_114ED4 (MD.cs:409,592,692,795): one MC leaf, width w */
 static void mc_leaf(D *d, int io, uint32_t srcFrame, uint32_t w, uint32_t h, int dx, int dy, int Offset) {
   *IN(d, io) = (uint32_t)dx;
@@ -203,6 +266,7 @@ static void mc_leaf(D *d, int io, uint32_t srcFrame, uint32_t w, uint32_t h, int
   uint32_t f = srcFrame / 4;
   if (f >= 1 && f <= 5) COV(MOBI_COV_REF + f - 1);
   COV(MOBI_COV_PHASE + ((dx & 1) | ((dy & 1) << 1)));
+  mt_leaf(d, srcFrame, w, h, dx, dy, Offset);
   copy_block(d, d->Y[f], dx, dy, w, h, d->Y[0], Offset);
   copy_block(d, d->UV[f], dx >> 1, dy >> 1, w >> 1, h >> 1, d->UV[0], Offset / 2);
   copy_block(d, d->UV[f], dx >> 1, dy >> 1, w >> 1, h >> 1, d->UV[0], Offset / 2 + d->Stride / 2);
@@ -237,6 +301,7 @@ static void pblock(D *d, int wi, int hi, int io, int Offset) {
   int nb = mobi_part_bits[ver][s][code];
   TAKE(d, nb);
   if (code < 10) COV(MOBI_COV_PART + (ver * 16 + s) * 10 + code);
+  if (s == 0) mt_mb(d, Offset, code == 6 || code == 7);
   switch (code) {
     case 0:
       mc_leaf(d, io, 4, w, h, (int)d->Internal[219], (int)d->Internal[220], Offset);
@@ -348,6 +413,7 @@ static void read_dct(D *d, uint32_t *pr12) {
       skip = (int)(e & 0x3F);
       e >>= 6;
     }
+    mt_level(value);
     r12 = (uint32_t)(r12 + (uint32_t)skip);
     r8 = *IN(d, (long)r12);
     r12++;
@@ -578,6 +644,7 @@ static void p_residual(D *d, int Offset) {
   uint32_t ue = read_ue(d);
   if (ue >= sizeof(mobi_cbp_inter)) THROW(d, ORA_E_INDEX);
   uint32_t m = mobi_cbp_inter[ue];
+  if (g_mt.on) MT_MB(2) = (int32_t)m;
   const int S = d->Stride;
   if (m & 1) resid8_or_4x4(d, d->Y[0], Offset);
   Offset += 8;
@@ -1001,8 +1068,10 @@ static void intra_chroma(D *d, uint32_t cbp, int Offset) {
     p = read_se(d);
     plane_pred(d, d->UV[0], Offset / 2 + S / 2, 8, p);
   }
+  MT_AREA(4);
   if (((cbp >> 4) & 1) == 1) intra_full_coded(d, d->UV[0], Offset / 2, m);
   else predict_intra(d, m, d->UV[0], Offset / 2);
+  MT_AREA(5);
   if (((cbp >> 5) & 1) == 1) intra_full_coded(d, d->UV[0], Offset / 2 + S / 2, m);
   else predict_intra(d, m, d->UV[0], Offset / 2 + S / 2);
 }
@@ -1022,6 +1091,7 @@ static void dec_intra_full(D *d, int Offset) {
   static const int bx[4] = {0, 8, 0, 8}, by[4] = {0, 0, 8, 8};
   for (int k = 0; k < 4; k++) {
     int o = Offset + by[k] * S + bx[k];
+    MT_AREA(k);
     if ((cbp >> k) & 1) intra_full_coded(d, d->Y[0], o, m);
     else predict_intra(d, m, d->Y[0], o);
   }
@@ -1036,6 +1106,7 @@ static void dec_intra_sub(D *d, int Offset) {
   static const int bx[4] = {0, 8, 0, 8}, by[4] = {0, 0, 8, 8}, ci[4] = {9, 0xB, 0x19, 0x1B};
   for (int k = 0; k < 4; k++) {
     int o = Offset + by[k] * S + bx[k];
+    MT_AREA(k);
     if (((cbp >> k) & 1) == 0) intra_sub_uncoded(d, ci[k], d->Y[0], o);
     else intra_sub_coded(d, ci[k], d->Y[0], o);
   }
@@ -1133,6 +1204,7 @@ static void decode_vxs2(D *d) {
         d->r3 += d->r3;
         d->nbr--;
         if (d->nbr < 0) fill_bits(d);
+        mt_mb(d, r11, 1);
         if (sub) dec_intra_sub(d, r11);
         else dec_intra_full(d, r11);
         r11 += 0x10;
@@ -1169,11 +1241,14 @@ int mobi_oracle_decode(mobi_oracle *d, const uint8_t *data, size_t len, int32_t 
   d->Data = data;
   d->DataLen = (long)len;
   d->Offset = *offset;
+  mt_begin(d);
   int rc = setjmp(d->jb);
   if (rc == 0) {
     if (d->Version == MOBI_VER_MODSDS || d->Version == MOBI_VER_MOFLEX3DS) decode_vxs2(d);
     else rc = ORA_E_VERSION;
   }
+  if (g_mt.state != 0) g_mt.state = (rc == 0 && g_mt.on) ? 1 : -1;
+  g_mt.on = 0;
   *offset = d->Offset;
   return rc;
 }

@@ -82,6 +82,22 @@ void mobi_oracle_motion_search(const mobi_oracle *d, const uint8_t *src, uint32_
 enum { MOBI_COV_PART = 0, MOBI_COV_INTRA = 320, MOBI_COV_PLANE = 340, MOBI_COV_ESCAPE = 343, MOBI_COV_VLCTAB = 346, MOBI_COV_REF = 348,
        MOBI_COV_PHASE = 353, MOBI_COV_IDCT = 357, MOBI_COV_WORDS = 363 };
 void mobi_oracle_coverage(uint64_t *out, int reset);
+/* Motion trace (tests/test_motion_oracle.py): the motion and residual of one frame as this decoder itself applies them, for the tests of
+ * the library's motion export.  Thread-local and test-side only, like the counters: it changes no result.
+ * mobi_oracle_motion_trace_arm() arms the trace for the next mobi_oracle_decode of the calling thread (one frame; the trace of an earlier
+ * frame is dropped).  mobi_oracle_motion_trace copies it out: returns 1 = valid, -1 = the traced frame threw (what was written up to there
+ * is copied, and means nothing), 0 = no frame has been traced (nothing is copied).  Either pointer may be NULL.
+ *   cells  int16 [3][Height/2][Width/2] = dx, dy, ref of every 2x2 luma cell: written where a leaf is motion compensated (loc_1147B0 and
+ *          its twins, MD.cs:409,592,692,795) from that call's own (srcFrame, w, h, dx, dy, Offset): every cell of the w x h leaf at Offset
+ *          gets (dx, dy, srcFrame / 4), the RAW vector as CopyBlock receives it.  Cells of intra macroblocks, and every cell of an I-frame,
+ *          stay (0, 0, 0).
+ *   mbs    int32 [5][Height/16][Width/16] = type (0 inter, 1 intra: DecIntraFullBlockPMode / DecIntraSubBlockPMode decoded it); Quantizer
+ *          when the macroblock is decoded; the coded-area pattern, six bits (luma 0-3, U 4, V 5): an inter macroblock's pattern as
+ *          loc_1161A0 looks it up (MD.cs:1818), for an intra macroblock the areas in which ReadDCTMatrix ran at all (an area signalled as coded whose
+ *          4x4 pattern is empty has no bit); the number of levels ReadDCTMatrix produced for the macroblock; the sum of their |value|
+ *          (the level as read, before dequantisation). */
+void mobi_oracle_motion_trace_arm(void);
+int mobi_oracle_motion_trace(int16_t *cells, int32_t *mbs);
 /* testing hooks: direct access to the Internal[392] word array (MD.cs:28) */
 uint32_t *mobi_oracle_internal(mobi_oracle *d);
 

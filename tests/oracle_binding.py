@@ -41,6 +41,9 @@ def lib():
         L.mobi_oracle_copyblock.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int, C.c_int, C.c_int]
         L.mobi_oracle_predict.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
         L.mobi_oracle_plane.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]
+        L.mobi_oracle_motion_trace_arm.argtypes = []
+        L.mobi_oracle_motion_trace_arm.restype = None
+        L.mobi_oracle_motion_trace.argtypes = [C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -64,6 +67,17 @@ class OracleDecoder:
         self.Offset = off.value
         self.last_error = rc
         return None if rc != 0 else (self.y(0), self.uv(0))
+
+    def DecodeFrameTraced(self):
+        """DecodeFrame() with the motion trace armed (oracle/mobi_oracle.h) -> (planes or None, cells int16 [3, H/2, W/2], mbs int32
+        [5, H/16, W/16]); cells and mbs are None when the frame threw.  Arming and decoding happen on the calling thread."""
+        self.L.mobi_oracle_motion_trace_arm()
+        planes = self.DecodeFrame()
+        cells = np.empty((3, self.Height // 2, self.Width // 2), np.int16)
+        mbs = np.empty((5, self.Height // 16, self.Width // 16), np.int32)
+        state = self.L.mobi_oracle_motion_trace(cells.ctypes.data, mbs.ctypes.data)
+        assert state == (1 if self.last_error == 0 else -1), (state, self.last_error)
+        return (planes, cells, mbs) if state == 1 else (planes, None, None)
 
     def y(self, idx):
         p = self.L.mobi_oracle_y(self.h, idx)

@@ -2,6 +2,8 @@
 
 What the kernels must give is said on the CPU: the scripted clips' own vectors, and tests/tools/libmobi_motionhost.so (csrc/mobi_motion.h's
 host build) over the host parser's command list -- tests/test_motion_field.py, which has checked the one against the other.
+(That tool shares the header with the kernel.  The comparison with a side that does not -- the oracle's motion trace -- and the life-cycle
+paths with motion on are tests/test_motion_oracle.py and tests/test_motion_trace_gpu.py.)
 """
 import functools
 
