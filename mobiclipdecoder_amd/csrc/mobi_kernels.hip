@@ -1222,6 +1222,8 @@ MOBI_OCT_KERNEL(mobi_recon_inter8_prof, 4, 1, 16) // (in-kernel cycle records, M
 // area (4x4 blocks, one sample per lane), 6..24 steps, two descriptor words per step, built once by the lane that holds the block's
 // record and read back by all 16.  The wave runs as many steps as its longest macroblock has (95 % of the areas are unsplit in the
 // generator's mix); the wave-level branches inside a step ask "does any of the four need a plane / a DC / an 8x8 / a 4x4 now".
+// Seven waves in ten of the headline batch carry no split area at all (the host sorts every level by that): they take a second, straight-line
+// instance of the schedule and of the step loop -- six steps, area a at place a, no 4x4 half (`plain` below; profiles/intra_unsplit_path.txt).
 namespace {
 // LDS of one macroblock, 1888 bytes, two lives:
 //   while the residuals are made    [0, 1536) coefficients, int32 [6][64]               [1536, 1856) dequant scales
@@ -1246,6 +1248,9 @@ enum { SD_O = 0,           // [10:0]  byte offset of the block's top-left sample
        SD_KTAP = 1 << 23, SD_KDC = 1 << 24, SD_KPLANE = 1 << 25, // predictor kind; none of them: what is there stays (plane passes, mode 9)
        SD_TA = 1 << 26, SD_LA = 1 << 27,                         // DC: row above / column to the left available (MD.cs:1923-1924)
        SD_P4 = 1 << 30 };  // the plane is a 4x4 one
+__host__ __device__ constexpr int iq_area_tile(int a) { // SD_O of the 8x8 block of area a: luma areas 0..3 in raster order, U, V
+  return (a < 4 ? ((a >> 1) * 8 + 1) * TP + 4 + (a & 1) * 8 : (a == 4 ? IQ_TCU : IQ_TCV) + TP + 4);
+}
 // word 1: [8:0] index of the step's first residual (+ lane's), [13:9] 1 + the plane parameter's index among the macroblock's wide parameters
 //         (mobi_cmd.h: a parameter that does not fit 16 bits; 0: it does), [31:16] plane parameter
 
@@ -1500,8 +1505,56 @@ __device__ __forceinline__ void recon_intra_quad(const MobiReconArgs &A, uint32_
 
   // ---- the schedule: one step per unsplit area, four per split one, in decode order.  Lane 4a + s of the row owns the candidate
   // (area a, block s); its place in the list follows from how many areas before a are split. ----
-  int n_iter;
-  {
+  // SPLITS = std::false_type: no area of the macroblock is split (s == 0, rown == r0): what a split area needs folds away
+  auto build = [=](auto SPLITS, int a, int s, uint32_t rown, uint32_t r0) -> uint2 {
+    const bool split = decltype(SPLITS)::value && mobi_rec_split(r0), pre = mobi_rec_pre_plane(r0);
+    const uint32_t rs = split ? rown : r0;
+    const int mode = mobi_rec_mode(rs);
+    const bool coded = mobi_rec_coded(rs), luma = a < 4;
+    const int by = (luma ? (a >> 1) * 8 : 0) + (split ? (s >> 1) * 4 : 0), bx = (luma ? (a & 1) * 8 : 0) + (split ? (s & 1) * 4 : 0);
+    const int o_blk = (luma ? 0 : a == 4 ? IQ_TCU : IQ_TCV) + (by + 1) * TP + 4 + bx;
+    const bool k_dc = mode == 3, k_tap = mode < 2 || (mode >= 4 && mode <= 8);
+    const bool plane_blk = mode == 2, plane_pre = pre && s == 0;
+    const uint32_t param = plane_blk ? rs >> MOBI_REC_PARAM_S : r0 >> MOBI_REC_PARAM_S; // (an expression: a reader function here changes the kernel's code)
+    const int mi = !k_tap ? 0 : mode < 2 ? mode : mode - 2;
+    const int tapbase = split ? MOBI_TAP_4X4 + mi * 16 : mi * 64;
+    const int boff = (luma ? off : (off >> 1) + (a - 4) * (S >> 1)) + by * S + bx;
+    const bool vfix = !luma && (boff & (S - 1)) >= (S >> 1);                                              // MD.cs:1886
+    const bool la = ((boff - (vfix ? (S >> 1) : 0)) & (S - 1)) != 0, ta = boff >= S;                      // :1923-1924
+    const int ri = a * 64 + (split ? (s >> 1) * 32 + (s & 1) * 4 : 0);
+    const uint32_t widx = ((plane_blk ? rs : plane_pre ? r0 : 0u) & MOBI_REC_WIDE) ? (uint32_t)(a * 4 + (split ? s : 0) + 1) : 0u;
+    uint32_t d0 = (uint32_t)o_blk | ((uint32_t)tapbase << SD_TAP);
+    if (split) d0 |= SD_IS4;
+    if (coded) d0 |= SD_CODED;
+    if (k_tap) d0 |= SD_KTAP;
+    if (k_dc) d0 |= SD_KDC;
+    if (plane_blk || plane_pre) d0 |= SD_KPLANE;
+    if (ta) d0 |= SD_TA;
+    if (la) d0 |= SD_LA;
+    if (plane_blk && split) d0 |= SD_P4;
+    return uint2{d0, (uint32_t)ri | (widx << 9) | (param << 16)};
+  };
+  auto put_step = [&](int t, uint2 d) {
+    *(uint32_t *)(Gb + step_word(2 * t)) = d.x;
+    *(uint32_t *)(Gb + step_word(2 * t + 1)) = d.y;
+  };
+  // One question for the wave: does any of its macroblocks have a split area (the first record of an area says so; padding rows hold
+  // zeros)?  Seven macroblocks in ten have none, and the host sorts a level by that (LevelPlan): a wave without one runs exactly six steps,
+  // all on 8x8 blocks, area a at place a -- its schedule below and its steps further down are the general ones with the 4x4 half folded away.
+  const bool plain = __builtin_amdgcn_ballot_w64((mobi_rec_split(recA) || mobi_rec_split(recB)) && (l & 3) == 0) == 0;
+  int n_iter = 6;
+  if (plain) {
+    // lane 4a of the row holds the record of area a < 4; lanes 1 and 5 take those of areas 4 and 5 from their left neighbours: one evaluation
+    const bool own = (l & 3) == 0;
+    const int a = (l >> 2) + (own ? 0 : 4);
+    uint32_t rB = recB;
+#if defined(__HIP_DEVICE_COMPILE__)
+    rB = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)recB, 0x111, 0xF, 0xF, true); // row_shr:1 (by every lane: a lane switched off is read as 0)
+#endif
+    const uint32_t r = own ? recA : rB;
+    const uint2 d = build(std::false_type{}, a, 0, r, r);
+    if (own || l == 1 || l == 5) put_step(a, d);
+  } else {
     const uint64_t balA = __builtin_amdgcn_ballot_w64(mobi_rec_split(recA) && (l & 3) == 0);          // areas 0..3: lanes 0, 4, 8, 12 of the row
     const uint64_t balB = __builtin_amdgcn_ballot_w64(mobi_rec_split(recB) && (l & 3) == 0 && l < 8); // areas 4, 5: lanes 0, 4
     const uint32_t mA = (uint32_t)(balA >> (lane & 48)) & 0x1111u, mB = (uint32_t)(balB >> (lane & 48)) & 0x11u;
@@ -1510,46 +1563,17 @@ __device__ __forceinline__ void recon_intra_quad(const MobiReconArgs &A, uint32_
     n_iter = max(max(__builtin_amdgcn_readlane(nst, 0), __builtin_amdgcn_readlane(nst, 16)), max(__builtin_amdgcn_readlane(nst, 32), __builtin_amdgcn_readlane(nst, 48)));
     // rows with fewer steps than the longest of the four idle through the rest: a descriptor that does nothing
     const uint2 idle = uint2{(uint32_t)(TP + 4), 0u};
-    auto put_step = [&](int t, uint2 d) {
-      *(uint32_t *)(Gb + step_word(2 * t)) = d.x;
-      *(uint32_t *)(Gb + step_word(2 * t + 1)) = d.y;
-    };
     put_step(l, idle);
     if (l < 8) put_step(16 + l, idle);
     wave_sync();
-    auto build = [=](int t, uint32_t rown, uint32_t r0, int &pos) -> uint2 {
+    auto place = [=](int t, uint32_t r0) { // of candidate t = 4 * area + block in the list, -1: blocks 1..3 of an unsplit area
       const int a = t >> 2, s = t & 3;
-      const bool split = mobi_rec_split(r0), pre = mobi_rec_pre_plane(r0);
-      pos = (s == 0 || split) ? a + 3 * __builtin_popcount(splits & ((1u << a) - 1u)) + s : -1;
-      const uint32_t rs = split ? rown : r0;
-      const int mode = mobi_rec_mode(rs);
-      const bool coded = mobi_rec_coded(rs), luma = a < 4;
-      const int by = (luma ? (a >> 1) * 8 : 0) + (split ? (s >> 1) * 4 : 0), bx = (luma ? (a & 1) * 8 : 0) + (split ? (s & 1) * 4 : 0);
-      const int o_blk = (luma ? 0 : a == 4 ? IQ_TCU : IQ_TCV) + (by + 1) * TP + 4 + bx;
-      const bool k_dc = mode == 3, k_tap = mode < 2 || (mode >= 4 && mode <= 8);
-      const bool plane_blk = mode == 2, plane_pre = pre && s == 0;
-      const uint32_t param = plane_blk ? rs >> MOBI_REC_PARAM_S : r0 >> MOBI_REC_PARAM_S; // (an expression: a reader function here changes the kernel's code)
-      const int mi = !k_tap ? 0 : mode < 2 ? mode : mode - 2;
-      const int tapbase = split ? MOBI_TAP_4X4 + mi * 16 : mi * 64;
-      const int boff = (luma ? off : (off >> 1) + (a - 4) * (S >> 1)) + by * S + bx;
-      const bool vfix = !luma && (boff & (S - 1)) >= (S >> 1);                                              // MD.cs:1886
-      const bool la = ((boff - (vfix ? (S >> 1) : 0)) & (S - 1)) != 0, ta = boff >= S;                      // :1923-1924
-      const int ri = a * 64 + (split ? (s >> 1) * 32 + (s & 1) * 4 : 0);
-      const uint32_t widx = ((plane_blk ? rs : plane_pre ? r0 : 0u) & MOBI_REC_WIDE) ? (uint32_t)(a * 4 + (split ? s : 0) + 1) : 0u;
-      uint32_t d0 = (uint32_t)o_blk | ((uint32_t)tapbase << SD_TAP);
-      if (split) d0 |= SD_IS4;
-      if (coded) d0 |= SD_CODED;
-      if (k_tap) d0 |= SD_KTAP;
-      if (k_dc) d0 |= SD_KDC;
-      if (plane_blk || plane_pre) d0 |= SD_KPLANE;
-      if (ta) d0 |= SD_TA;
-      if (la) d0 |= SD_LA;
-      if (plane_blk && split) d0 |= SD_P4;
-      return uint2{d0, (uint32_t)ri | (widx << 9) | (param << 16)};
+      return (s == 0 || mobi_rec_split(r0)) ? a + 3 * __builtin_popcount(splits & ((1u << a) - 1u)) + s : -1;
     };
-    int posA, posB;
-    const uint2 dA = build(l, recA, quad_first(recA), posA);
-    const uint2 dB = build(16 + (l & 7), recB, quad_first(recB), posB);
+    const uint32_t fA = quad_first(recA), fB = quad_first(recB);
+    const int tB = 16 + (l & 7), posA = place(l, fA), posB = place(tB, fB);
+    const uint2 dA = build(std::true_type{}, l >> 2, l & 3, recA, fA);
+    const uint2 dB = build(std::true_type{}, tB >> 2, tB & 3, recB, fB);
     if (posA >= 0) put_step(posA, dA);
     if (l < 8 && posB >= 0) put_step(posB, dB);
   }
@@ -1662,17 +1686,22 @@ __device__ __forceinline__ void recon_intra_quad(const MobiReconArgs &A, uint32_
   s16x2 flo = {0, 0}, fhi = {0, 0}; // range of prediction + residual over the 8x8 steps (clamp table domain [-64, 319], MobiConst.cs:587)
   // The tap table entries of a directional block do not depend on pixels: they are asked for one step ahead (two register sets taken in
   // turn: r03 rotated three sets through eleven 64-bit moves per step).
-  auto load_step = [&](int t, uint2 &d, uint4 &ea, uint4 &eb) {
+  // AREA (do_step as well): -1, any step of the general list; a >= 0, step a of a wave without split areas: the 8x8 block of area a, whose
+  // place in the list, tile offset and first residual are constants
+  auto load_step = [&](auto AREA, int t, uint2 &d, uint4 &ea, uint4 &eb) {
+    constexpr bool any = decltype(AREA)::value < 0;
     d = uint2{*(const uint32_t *)(Gb + step_word(2 * t)), *(const uint32_t *)(Gb + step_word(2 * t + 1))};
-    const uint2 *tp = taps + (((d.x >> SD_TAP) & 0x3FF) + ((d.x & SD_IS4) ? l : 4 * l));
+    const uint2 *tp = taps + (((d.x >> SD_TAP) & 0x3FF) + (any && (d.x & SD_IS4) ? l : 4 * l));
     ea = *(const uint4_a4 *)tp;
     eb = *(const uint4_a4 *)(tp + 2);
   };
-  auto do_step = [&](const uint2 d, const uint4 ea, const uint4 eb) {
-    const int o = (int)(d.x & 0x7FF);
-    const bool is4 = (d.x & SD_IS4) != 0;
+  auto do_step = [&](auto AREA, const uint2 d, const uint4 ea, const uint4 eb) {
+    constexpr int area = decltype(AREA)::value;
+    constexpr bool any = area < 0;
+    const int o = any ? (int)(d.x & 0x7FF) : iq_area_tile(any ? 0 : area), ri = any ? (int)(d.y & 0x1FF) : 64 * area;
+    const bool is4 = any && (d.x & SD_IS4) != 0;
     if (__builtin_amdgcn_ballot_w64((d.x & SD_KPLANE) != 0) != 0) { // plane with delta, 8x8 (MD.cs:3168-3251) or 4x4 (:3253-3327): a lane makes a word of four samples
-      const bool p4 = (d.x & SD_P4) != 0;
+      const bool p4 = any && (d.x & SD_P4) != 0;
       if ((d.x & SD_KPLANE) && l < (p4 ? 4 : 16)) {
         const int yy = p4 ? l : l >> 1, x0 = p4 ? 0 : (l & 1) * 4;
         const uint32_t widx = (d.y >> 9) & 31u;
@@ -1704,7 +1733,7 @@ __device__ __forceinline__ void recon_intra_quad(const MobiReconArgs &A, uint32_
           word = (uint32_t)dcv * 0x01010101u;
         }
         if (d.x & SD_CODED) { // two samples per instruction, as in the inter kernel (idct_pass2_q)
-          const uint2 rr = *(const uint2 *)(res16 + (d.y & 0x1FF) + ro8);
+          const uint2 rr = *(const uint2 *)(res16 + ri + ro8);
           union { s16x2 v; uint32_t u; } p01, p23, r01, r23;
           p01.u = __builtin_amdgcn_perm(0u, word, 0x0c010c00u);
           p23.u = __builtin_amdgcn_perm(0u, word, 0x0c030c02u);
@@ -1718,13 +1747,13 @@ __device__ __forceinline__ void recon_intra_quad(const MobiReconArgs &A, uint32_
         *(uint32_t *)px = word;
       }
     }
-    if (__builtin_amdgcn_ballot_w64(w4) != 0) {
+    if (any && __builtin_amdgcn_ballot_w64(w4) != 0) {
       if (w4) {
         uint8_t *px = tile + o + po4;
         int p = *px;
         if (d.x & SD_KTAP) p = (int)tap4(tile_lds + (uint32_t)o, ea.x, ea.y);
         else if (d.x & SD_KDC) p = dcv;
-        if (d.x & SD_CODED) p = mobi_add_clamp(p, (int)res16[(d.y & 0x1FF) + ro4], &fault);
+        if (d.x & SD_CODED) p = mobi_add_clamp(p, (int)res16[ri + ro4], &fault);
         *px = (uint8_t)p;
       }
     }
@@ -1734,14 +1763,34 @@ __device__ __forceinline__ void recon_intra_quad(const MobiReconArgs &A, uint32_
   MOBI_ISTOP(6);
   uint2 dA, dB = uint2{0, 0};
   uint4 eaA, ebA, eaB = uint4{0, 0, 0, 0}, ebB = uint4{0, 0, 0, 0};
-  load_step(0, dA, eaA, ebA);
+  if (plain) { // six steps in a row, on the same two register sets
+    if (n_iter) {
+#define MOBI_AREA(a) std::integral_constant<int, a>{}
+      load_step(MOBI_AREA(0), 0, dA, eaA, ebA);
+      load_step(MOBI_AREA(1), 1, dB, eaB, ebB);
+      do_step(MOBI_AREA(0), dA, eaA, ebA);
+      load_step(MOBI_AREA(2), 2, dA, eaA, ebA);
+      do_step(MOBI_AREA(1), dB, eaB, ebB);
+      load_step(MOBI_AREA(3), 3, dB, eaB, ebB);
+      do_step(MOBI_AREA(2), dA, eaA, ebA);
+      load_step(MOBI_AREA(4), 4, dA, eaA, ebA);
+      do_step(MOBI_AREA(3), dB, eaB, ebB);
+      load_step(MOBI_AREA(5), 5, dB, eaB, ebB);
+      do_step(MOBI_AREA(4), dA, eaA, ebA);
+      do_step(MOBI_AREA(5), dB, eaB, ebB);
+#undef MOBI_AREA
+    }
+  } else {
+    const std::integral_constant<int, -1> any;
+    load_step(any, 0, dA, eaA, ebA);
 #pragma unroll 1
-  for (int t = 0; t < n_iter; t += 2) {
-    if (t + 1 < n_iter) load_step(t + 1, dB, eaB, ebB);
-    do_step(dA, eaA, ebA);
-    if (t + 1 >= n_iter) break;
-    if (t + 2 < n_iter) load_step(t + 2, dA, eaA, ebA);
-    do_step(dB, eaB, ebB);
+    for (int t = 0; t < n_iter; t += 2) {
+      if (t + 1 < n_iter) load_step(any, t + 1, dB, eaB, ebB);
+      do_step(any, dA, eaA, ebA);
+      if (t + 1 >= n_iter) break;
+      if (t + 2 < n_iter) load_step(any, t + 2, dA, eaA, ebA);
+      do_step(any, dB, eaB, ebB);
+    }
   }
   if (flo.x < -64 || flo.y < -64 || fhi.x > 319 || fhi.y > 319) fault = 1;
   MOBI_ISTOP(7);
