@@ -248,6 +248,13 @@ int mobi_batch_gop_begin(mobi_batch *b, int n_frames, const uint8_t *const *data
 int mobi_batch_gop_finish(mobi_batch *b, int32_t *offsets_out, int *rc);
 int mobi_batch_gop_in_flight(const mobi_batch *b); /* groups begun and not yet finished: 0, 1 or 2 */
 int mobi_batch_gop_frames_pending(const mobi_batch *b); /* frames of the oldest such group that no finish has reported yet (0: none begun) */
+/* Every frame of the oldest group that no mobi_batch_gop_finish has reported yet, in one call: offsets_out and rc have
+ * mobi_batch_gop_frames_pending(b) * n_clips entries, and the results equal those of mobi_batch_gop_finish called until nothing is
+ * pending.  One host wait at the end instead of one per six frames -- the six-frame parts exist so that the caller can read the ring
+ * between them; a caller that reads it through a clip sink (below), or wants only the group's last six frames, which the ring holds
+ * afterwards, needs none.  The parse of the group begun behind goes out as behind a last part.  Allowed with or without a sink, and
+ * after some parts of the group have been finished the ordinary way. */
+int mobi_batch_gop_finish_all(mobi_batch *b, int32_t *offsets_out, int *rc);
 /* Wall-clock milliseconds the last mobi_batch_decode call spent inside the library (parse or upload, launches, sync). */
 float mobi_batch_last_decode_ms(const mobi_batch *b);
 int mobi_batch_get_planes(mobi_batch *b, int clip, int ring_idx, uint8_t *y_out, uint8_t *uv_out);
@@ -405,6 +412,57 @@ long mobi_batch_motion_launches(const mobi_batch *b); /* launches of mobi_motion
 size_t mobi_batch_motion_bytes(const mobi_batch *b);  /* device memory the motion ring holds (0: motion is off) */
 int mobi_batch_export_motion(mobi_batch *b, int format, int dtype, int block, float scale, int ring_idx, int n_frames, int clip0, int n_clips,
                              void *dst, size_t dst_bytes, void *stream);
+/* ---- the clip sink: frame steps write chosen frames into one (N, T, ...) tensor ------------------------------------------------------
+ * The exports above reach the six pictures of the ring, frame-major.  A video model wants T frames of every clip, every s-th frame, from a
+ * start that differs per clip, as (N, T, 3, H, W), (N, 3, T, H, W) or (N, T, H, W, 3).  An armed sink rides along with the batch's frame
+ * steps: behind the reconstruction of a step, on the batch's own stream, one more kernel (mobi_sink) writes the pictures that step
+ * contributes straight to their place in the tensor.
+ *   STEPS:     step numbers count the frame steps the batch runs after arming: step 0 is the next one.  Every path counts: decode,
+ *              submit / wait, each frame of a group, replay.
+ *   SELECTION: clip c contributes picture t at step start[c] + t * stride, t = 0 .. n_frames - 1.
+ *   VALUES:    picture (c, t) holds exactly what mobi_batch_export_device_boxes(..., ring_idx 0, n_frames 1, ...) would write for clip c if
+ *              it were called right after that step, with the same box, size, dtype and scale_bias (boxes NULL: the whole picture, no
+ *              flip).  A clip whose frame was refused or idle gets whatever its slot holds, as that export would give.  The sink follows
+ *              batch steps, not streams: mobi_batch_reset_clips does not touch it.
+ *   ADDRESSES: in ELEMENTS of the dtype.  Planar: element (c, t, ch, y, x) is at dst + (c * clip_stride + t * frame_stride + ch * chan_stride
+ *              + y * out_w + x) * esize; packed: (c * clip_stride + t * frame_stride + (y * out_w + x) * 3 + ch) * esize, chan_stride 0.
+ *              That covers (N,T,3,H,W), (N,3,T,H,W), (N,T,H,W,3), the exports' frame-major order and strided views of them.
+ *   REFUSED:   MOBI_E_ARG, changing and enqueuing nothing: every geometry refusal of mobi_batch_export_device_boxes (format, dtype /
+ *              scale_bias combination, a box outside the picture, flag bits, out_w not a multiple of 4, D > 2^23); n_frames < 1 or
+ *              stride < 1; a negative start or start + (n_frames - 1) * stride beyond int32; dst not 16-byte aligned; a stride that is not
+ *              a multiple of 4 elements; pictures that overlap or leave [dst, dst + dst_bytes) -- the rule: order the (extent, stride)
+ *              pairs of clips, frames and (planar) channels by stride; each stride must be at least the span of everything with a smaller
+ *              stride, and the whole span must fit --; dst not device memory of the batch's device; arming, replacing or disarming while
+ *              a submitted step or a group is outstanding; a poisoned batch.
+ *   LIFETIME:  boxes and start are copied before the call returns.  dst stays valid until mobi_batch_sink_pending is 0 and the call that
+ *              reports the last contributing frame has returned, or until the sink is disarmed (mobi_batch_set_sink(b, NULL), which
+ *              waits for the batch's stream).  With its last picture written the sink disarms itself: later steps write nothing and
+ *              launch nothing.
+ *   ORDER:     when the call that reports a frame returns (decode, wait, gop_finish, gop_finish_all; mobi_batch_sync after replay) that
+ *              frame's sink pictures are complete.  A clip repaired in mobi_batch_wait has its pictures of the repaired steps written
+ *              again: the same words, or the repaired frame's.
+ * A batch that never arms a sink runs the code it ran before: no allocation, no launch (mobi_batch_sink_launches stays 0). */
+typedef struct mobi_sink {
+  int format;               /* MOBI_EXPORT_RGB_PLANAR or MOBI_EXPORT_RGB_PACKED */
+  int dtype;                /* MOBI_DTYPE_U8 / _F16 / _F32; scale_bias as mobi_batch_export_device (NULL for U8) */
+  const float *scale_bias;
+  const int32_t *boxes;     /* host, n_clips x {x, y, w, h, flags} as mobi_batch_export_device_boxes; NULL: the whole picture, no flip */
+  int out_w, out_h;
+  int n_frames;             /* T >= 1: pictures every clip contributes */
+  int stride;               /* s >= 1: every s-th step */
+  const int32_t *start;     /* host, n_clips, each >= 0: the step of the clip's first picture; NULL: all 0 */
+  int64_t clip_stride, frame_stride, chan_stride;   /* in ELEMENTS */
+  void *dst; size_t dst_bytes;                      /* device memory of the batch's device */
+} mobi_sink;
+int mobi_batch_set_sink(mobi_batch *b, const mobi_sink *spec); /* NULL: disarm */
+int mobi_batch_sink_pending(const mobi_batch *b);   /* (clip, t) pictures the armed sink has not written yet; 0: none armed or complete */
+long mobi_batch_sink_launches(const mobi_batch *b); /* launches of mobi_sink so far */
+/* host only, no GPU: every refusal above that needs no batch state and no look at dst's memory */
+int mobi_sink_check(const mobi_sink *spec, int n_clips, uint32_t width, uint32_t height);
+/* host only: the clips selected in `step` (ascending, into clips_out) and the element offset of their picture's first element (into
+ * elem_off_out); either may be NULL.  Returns the count, or MOBI_E_ARG for a spec mobi_sink_check could not read (spec NULL, n_clips < 1,
+ * n_frames < 1, stride < 1) */
+int mobi_sink_plan(const mobi_sink *spec, int n_clips, int64_t step, int32_t *clips_out, int64_t *elem_off_out);
 /* Encoder-side analysis: Analyzer.InterPredict2x2 (Analyzer.cs:608-681) for every 2x2 luma block of
  * every macroblock of every clip, as SolveInterPredictionPuzzle calls it (:683-693): three-step search (6, 3, 1 pels) in up
  * to five past frames = ring slots 0..4 of this batch (the encoder's PastFramesY, MobiEncoder.cs:138-144).

@@ -40,7 +40,7 @@ ABI_CALLER = os.path.join(ROOT, "tests", "tools", "abi_caller")  # plain-C calle
 
 
 # the sources of libmobiclip_hip.so: *.cpp are host objects (g++), *.hip kernel objects (hipcc --offload-arch=gfx950); linked in this order
-HIP_SOURCES = ("mobi_batch.cpp", "mobi_step_host.cpp", "mobi_step_device.cpp", "mobi_step_groups.cpp", "mobi_replay.cpp", "mobi_pictures.cpp", "mobi_parse.cpp", "mobi_demux.cpp", "mobi_moflex.cpp", "mobi_export.cpp", "mobi_txcode.cpp", "mobi_audio_plan.cpp", "mobi_audio.cpp", "mobi_kernels.hip", "mobi_rgb.hip", "mobi_dparse.hip", "mobi_lsparse.hip", "mobi_gop.hip", "mobi_analysis.hip", "mobi_export.hip", "mobi_txcode.hip", "mobi_export_rgb.hip", "mobi_export_scale.hip", "mobi_export_resample.hip", "mobi_reset.hip", "mobi_idle.hip", "mobi_audio.hip", "mobi_sx.hip", "mobi_motion.hip")
+HIP_SOURCES = ("mobi_batch.cpp", "mobi_step_host.cpp", "mobi_step_device.cpp", "mobi_step_groups.cpp", "mobi_replay.cpp", "mobi_pictures.cpp", "mobi_parse.cpp", "mobi_demux.cpp", "mobi_moflex.cpp", "mobi_export.cpp", "mobi_txcode.cpp", "mobi_audio_plan.cpp", "mobi_audio.cpp", "mobi_kernels.hip", "mobi_rgb.hip", "mobi_dparse.hip", "mobi_lsparse.hip", "mobi_gop.hip", "mobi_analysis.hip", "mobi_export.hip", "mobi_txcode.hip", "mobi_export_rgb.hip", "mobi_export_scale.hip", "mobi_export_resample.hip", "mobi_reset.hip", "mobi_idle.hip", "mobi_audio.hip", "mobi_sx.hip", "mobi_motion.hip", "mobi_sink.cpp", "mobi_sink.hip")
 
 
 def hip_objects(profiling=False):

@@ -1,7 +1,7 @@
 // mobi_batch.h -- internal to the C-ABI layer of libmobiclip_hip.so (include/mobiclip_hip.h), never installed: the buffer and handle holders,
 // the host parse pool, the launch plan, struct mobi_batch and the one copy of every idiom a frame step is made of -- among them what a
 // device-parsed hand-over (a step, an asynchronous step, a group) owns and reports: DpSet, HostShare, and the staged image of mobi_handover.h.
-// The entry points are in mobi_batch.cpp, mobi_step_host.cpp, mobi_step_device.cpp, mobi_step_groups.cpp, mobi_replay.cpp and mobi_pictures.cpp.  There is no CPU
+// The entry points are in mobi_batch.cpp, mobi_step_host.cpp, mobi_step_device.cpp, mobi_step_groups.cpp, mobi_replay.cpp, mobi_pictures.cpp and mobi_sink.cpp.  There is no CPU
 // reconstruction path: every entry point that produces pixels goes through mobi_launch_inter / mobi_launch_intra.
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -456,13 +456,41 @@ struct mobi_batch {
     return MOBI_OK;
   }
 
+  // the clip sink (mobi_batch_set_sink; mobi_sink.h, mobi_sink.cpp): armed, it rides along with the frame steps.  A batch that never arms
+  // one has sink.on == false: no allocation, and sink_step below returns at its first test.
+  struct Sink {
+    bool on = false;                   // armed, or complete with a step that may still be repaired in flight (begin_step retires it)
+    int planar = 0, esize = 0;
+    MobiRgbAffine sb{};
+    MobiResampleCall call{};           // out size, the largest tiling and LDS of the clips, the records in device memory
+    MobiSinkSched sch{};               // stride, T, the three strides (step: filled per launch)
+    uint8_t *dst = nullptr;
+    std::vector<uint32_t> start;       // [clip], the host's copy of the records' `start`
+    DevArr<MobiResampleClip> d_recs;   // [clip], uploaded once at arming
+    int64_t now = -1;                  // the step begun last (-1: none since arming)
+    int64_t counted = -1;              // steps up to this one have been taken off `pending` (a repair launches an earlier step again)
+    int64_t last = 0;                  // the last step in which any clip contributes
+    int64_t pending = 0;               // (clip, t) pictures not launched yet
+  };
+  Sink sink;
+  long sink_launches = 0;              // launches of mobi_sink so far (mobi_batch_sink_launches)
+  int sink_launch(const MobiReconArgs &a); // mobi_sink.cpp
+  // The hook of every place that launches reconstruction into a ring slot, directly behind the step's LAST reconstruction launch (the intra
+  // one) on the batch's stream: the pictures this step contributes go to the tensor.  a = the step's own arguments; a partial launch (a
+  // repair, recon_clips) carries its first clip in `planes`, its clip count in n_clips and the ring slot of the EARLIER step it rewrites,
+  // from which the step's number follows.  No guard: the sink reads the slot behind its writers and in front of the next, in stream order.
+  // Idempotent: a step launched twice writes the same words twice.
+  int sink_step(const MobiReconArgs &a) { return sink.on ? sink_launch(a) : MOBI_OK; }
+
   // The ring-slot guard, called by every step that writes a ring slot, right after the ring has turned and before anything of the step is
   // enqueued: the slot the step writes (ring_base) may still be read by the pack of an export; the batch's stream then waits for it.  With no
   // export outstanding (or none ever) it does nothing.
   int guard_slot() { return exporter ? mobi_exporter_guard(exporter, ring_base, stream) : MOBI_OK; }
   // a frame step begins: the ring turns -- Y[i] = Y[i-1]; Y[0] = new (MD.cs:102-108), even if the parse threw --, the step gets its tag, its slot is guarded
   void next_tag() { step_tag = step_tag + 1 ? step_tag + 1 : 1; }
-  int begin_step() { ring_base = (ring_base + 1) % 6; next_tag(); argb_all_valid = false; frames_started++; return guard_slot(); }
+  // (an armed sink counts the step; a complete one goes once no submitted step, which mobi_batch_wait may still repair, is in flight)
+  void sink_begin_step() { if (sink.pending == 0 && async_count == 0) sink.on = false; else sink.now++; }
+  int begin_step() { ring_base = (ring_base + 1) % 6; next_tag(); argb_all_valid = false; frames_started++; if (sink.on) sink_begin_step(); return guard_slot(); }
   // the fault words of the step(s) enqueued, read back into dst[n] and cleared for the next, in stream order
   int read_faults(int *dst) {
     HIP_TRY(hipMemcpyAsync(dst, d_fault, sizeof(int) * n, hipMemcpyDeviceToHost, stream));
@@ -519,7 +547,8 @@ struct mobi_batch {
       if (ktiming) { ep.a = get_event(); ep.b = get_event(); (void)hipEventRecord(ep.a, stream); }
       if (mobi_launch_step(&a, items_dev, (int)plan.n_items, stream) != 0) return MOBI_E_DEVICE;
       if (ktiming) { (void)hipEventRecord(ep.b, stream); evs.push_back(ep); }
-      return motion_step(a);
+      if (int e = motion_step(a)) return e;
+      return sink_step(a);
     }
     if (plan.any_inter) {
       EvPair ep{nullptr, nullptr, 0};
@@ -534,7 +563,7 @@ struct mobi_batch {
       if (mobi_launch_intra(&a, items_dev, (int)plan.n_items, stream) != 0) return MOBI_E_DEVICE;
       if (ktiming >= 2) { (void)hipEventRecord(ep.b, stream); evs.push_back(ep); }
     }
-    return MOBI_OK;
+    return sink_step(a);
   }
   void drain_events() {
     for (auto &e : evs) {

@@ -87,7 +87,8 @@ struct MobiResampleClip {
   uint32_t chunk_rows, chunk_cols; // source rows (even) and columns (a multiple of 4) converted at a time
   uint32_t half;                  // D / 2
   MobiScaleDiv div;               // by D = dx * dy
-  uint32_t pad[2];
+  uint32_t start;                 // the clip sink's schedule (mobi_sink.h): the step of the clip's first picture; the exports leave it 0
+  uint32_t pad;
 };
 constexpr uint32_t kMobiResampleLanes = 256u;
 constexpr uint32_t kMobiResampleStripMax = 64u;      // output columns of one strip at most
@@ -134,7 +135,7 @@ MOBI_TILE_FN MobiResampleClip mobi_resample_plan(uint32_t x, uint32_t y, uint32_
   const uint64_t D = mobi_resample_den(w, h, ow, oh);
   k.half = (uint32_t)(D / 2u);
   k.div = mobi_scale_div_make((uint32_t)D);
-  k.pad[0] = k.pad[1] = 0u;
+  k.start = k.pad = 0u;
   return k;
 }
 MOBI_TILE_FN uint32_t mobi_resample_blocks(const MobiResampleClip *k) { return k->n_bands * k->n_strips; }

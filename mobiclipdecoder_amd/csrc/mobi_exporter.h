@@ -12,6 +12,7 @@
 
 #include "mobi_export_resample.h"
 #include "mobi_export_scale.h"
+#include "mobi_sink.h"
 
 // the ring of one batch as the export reads it (MobiReconArgs' layout: [clip][slot 0..5][tiled Y | tiled UV])
 struct MobiExportGeom {
@@ -47,6 +48,12 @@ struct MobiResampleCall {
 };
 extern "C" int mobi_launch_export_resample(const MobiExportGeom *g, int version, int planar, int esize, const MobiResampleCall *call, int n_frames,
                                            int n_clips, int clip0, int slot0, const MobiRgbAffine *sb, uint8_t *out_dev, hipStream_t s);
+
+// mobi_sink.hip: the pictures the step in ring slot `slot` contributes to a clip tensor (mobi_sink.h), of clips [clip0, clip0 + n_clips) of
+// the batch.  call->clips_dev = the records of ALL the batch's clips (record c is clip c's, with its `start`), call->blocks and
+// call->lds_bytes the largest of them
+extern "C" int mobi_launch_sink(const MobiExportGeom *g, int version, int planar, int esize, const MobiResampleCall *call, int slot, int clip0, int n_clips,
+                                const MobiSinkSched *sch, const MobiRgbAffine *sb, uint8_t *out_dev, hipStream_t s);
 
 #if !defined(__HIPCC__) || !defined(__HIP_DEVICE_COMPILE__)
 struct MobiExporter;

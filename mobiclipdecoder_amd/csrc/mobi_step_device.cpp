@@ -367,6 +367,7 @@ int decode_device_parse(mobi_batch *b, const uint8_t *const *data, const size_t 
   if (int e = b->motion_step(a)) return e;
   if (K && mobi_launch_intra_cl(&a, (const uint32_t *)B.items.p, &d_res[0].n_intra, (int)(sizeof(MobiDevResult) / 4), (int)K, 0, b->stream) != 0)
     return MOBI_E_DEVICE;
+  if (int e = b->sink_step(a)) return e;
   if (int e = b->read_faults(b->h_fault.data())) return e;
   if (!host_clips.empty())
     if (int e = dp_return(b, host_clips, rc, b->ps_cur, B, b->stream)) return e; // (ps_cur: what the next step's parse reads)
@@ -531,6 +532,7 @@ int mobi_batch_submit(mobi_batch *b, const uint8_t *const *data, const size_t *l
   // the parse has not run yet, so nobody knows how many intra macroblocks the longest list will have: MOBI_ASYNC_INTRA_SLOTS slots are launched
   // (a P-frame's lists are shorter), and a second launch (mobi_recon_intra_walk, one workgroup per four clips) goes through the rest of theirs (an I-frame: every macroblock)
   if (mobi_launch_intra_cl(&a, (const uint32_t *)B.items.p, &d_res[0].n_intra, (int)(sizeof(MobiDevResult) / 4), std::min(n_mbs, MOBI_ASYNC_INTRA_SLOTS), 1, b->stream) != 0) return MOBI_E_DEVICE;
+  if (int e = b->sink_step(a)) return e;
   if (int e = b->read_faults(B.faults())) return e;
   HIP_TRY(hipEventRecord(S.ev_done, b->stream));
   poison.armed = false;

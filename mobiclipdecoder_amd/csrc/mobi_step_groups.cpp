@@ -255,7 +255,8 @@ static int gop_sort(mobi_batch *b, mobi_batch::GopSlot &S) {
   }
   return MOBI_OK;
 }
-// 4. the reconstruction steps k0 .. k1 - 1 of this part -- at most six: the ring holds six pictures -- from consecutive command lists
+// 4. the reconstruction steps k0 .. k1 - 1 of this part, from consecutive command lists: any number of them.  (It is the caller of
+// mobi_batch_gop_finish that is limited to six, the pictures the ring holds for it to read; mobi_batch_gop_finish_all runs all the rest.)
 static int gop_recon_part(mobi_batch *b, mobi_batch::GopSlot &S, int k0, int k1) {
   const int n = b->n, K = S.H.K;
   auto &host_from = S.H.host_from, &hslot = S.hslot, &hrc = S.H.rc;
@@ -283,6 +284,7 @@ static int gop_recon_part(mobi_batch *b, mobi_batch::GopSlot &S, int k0, int k1)
       if (S.sorted_items[k] && mobi_launch_intra(&a, (const uint32_t *)S.d_sorted.p + S.sorted_off[k] * 4, (int)S.sorted_items[k], b->stream) != 0) return MOBI_E_DEVICE;
     } else if (Kint && mobi_launch_intra_cl(&a, (const uint32_t *)rows.items, &rows.res->n_intra, (int)(sizeof(MobiDevResult) / 4), (int)Kint, 0, b->stream) != 0)
       return MOBI_E_DEVICE;
+    if (int e = b->sink_step(a)) return e;
   }
   b->pay_clip_words = (uint32_t)S.B.cap_words;
   HIP_TRY(hipMemcpyAsync(S.B.h_fault.p + (size_t)k0 * n * sizeof(int), S.d_fault.p + (size_t)k0 * n * sizeof(int), (size_t)(k1 - k0) * n * sizeof(int), hipMemcpyDeviceToHost, b->stream));
@@ -324,7 +326,8 @@ static int gop_parse_next(mobi_batch *b, mobi_batch::GopSlot &S, bool last) {
   }
   return MOBI_OK;
 }
-int mobi_batch_gop_finish(mobi_batch *b, int32_t *offsets_out, int *rc) {
+// the oldest group's next part (six frames at most), or with `all` every frame it still has, as ONE part: one wait
+static int gop_finish_part(mobi_batch *b, int32_t *offsets_out, int *rc, bool all) {
   if (!b || !rc) return MOBI_E_ARG;
   HIP_TRY(hipSetDevice(b->device));
   if (b->poisoned) return MOBI_E_DEVICE;
@@ -346,7 +349,7 @@ int mobi_batch_gop_finish(mobi_batch *b, int32_t *offsets_out, int *rc) {
     S.resolved = true;
     S.done = 0;
   }
-  const int k0 = S.done, k1 = std::min(K, k0 + 6);
+  const int k0 = S.done, k1 = all ? K : std::min(K, k0 + 6);
   const bool last = k1 == K;
   if (int e = gop_recon_part(b, S, k0, k1)) return e;
   b->phase_ms[2] = ms_since(q0);
@@ -371,6 +374,8 @@ int mobi_batch_gop_finish(mobi_batch *b, int32_t *offsets_out, int *rc) {
   }
   return MOBI_OK;
 }
+int mobi_batch_gop_finish(mobi_batch *b, int32_t *offsets_out, int *rc) { return gop_finish_part(b, offsets_out, rc, false); }
+int mobi_batch_gop_finish_all(mobi_batch *b, int32_t *offsets_out, int *rc) { return gop_finish_part(b, offsets_out, rc, true); }
 // frames of the OLDEST group begun that mobi_batch_gop_finish has not reported yet (0: no group is begun); the next finish reports min(6, that)
 int mobi_batch_gop_frames_pending(const mobi_batch *b) {
   if (!b || b->gop_count == 0) return 0;

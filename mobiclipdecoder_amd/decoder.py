@@ -113,6 +113,12 @@ _SIGS = {
     "mobi_batch_motion_bytes": (C.c_size_t, [C.c_void_p]),
     "mobi_batch_export_motion": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                            C.c_size_t, C.c_void_p]),
+    "mobi_batch_set_sink": (C.c_int, [C.c_void_p, C.c_void_p]),  # (a mobi_sink by reference: C.byref(SinkSpec), or None)
+    "mobi_batch_sink_pending": (C.c_int, [C.c_void_p]),
+    "mobi_batch_sink_launches": (C.c_long, [C.c_void_p]),
+    "mobi_sink_check": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32]),
+    "mobi_sink_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "mobi_batch_gop_finish_all": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "mobi_error_string": (C.c_char_p, [C.c_int]),
     "mobi_build_info": (C.c_char_p, []),
 }
@@ -186,6 +192,18 @@ DEVICE_EXPORT_DTYPES = {"uint8": 0, "float16": 1, "float32": 2}
 # default); torch dtype name -> MOBI_DTYPE_*
 MOTION_FORMATS = {"cells": (0, 3, 2, ("int16",)), "mb": (1, 5, 16, ("int32",)), "flow": (2, 2, None, ("float32", "float16"))}
 MOTION_DTYPES = {"float16": 1, "float32": 2, "int16": 3, "int32": 4}
+
+
+class SinkSpec(C.Structure):
+    """struct mobi_sink of include/mobiclip_hip.h (mobi_batch_set_sink, mobi_sink_check, mobi_sink_plan)"""
+    _fields_ = [("format", C.c_int), ("dtype", C.c_int), ("scale_bias", C.POINTER(C.c_float)), ("boxes", C.POINTER(C.c_int32)),
+                ("out_w", C.c_int), ("out_h", C.c_int), ("n_frames", C.c_int), ("stride", C.c_int), ("start", C.POINTER(C.c_int32)),
+                ("clip_stride", C.c_int64), ("frame_stride", C.c_int64), ("chan_stride", C.c_int64), ("dst", C.c_void_p),
+                ("dst_bytes", C.c_size_t)]
+
+
+# MobiclipBatch.set_sink: layout -> (planar?, the tensor's dimensions as letters: n clips, t frames, c channels, h, w)
+SINK_LAYOUTS = {"ntchw": (True, "ntchw"), "ncthw": (True, "ncthw"), "nthwc": (False, "nthwc"), "tnchw": (True, "tnchw"), "tnhwc": (False, "tnhwc")}
 
 
 class _HostBlock:
@@ -752,6 +770,122 @@ class MobiclipBatch:
         if rc != 0:
             raise MobiclipError(error_string(rc))
         return out
+
+    # -- the clip sink: frame steps write chosen frames into one (N, T, ...) tensor (mobiclip_hip.h, mobi_batch_set_sink) ----------
+    def set_sink(self, size=None, n_frames=None, stride=1, start=None, boxes=None, flip=None, layout="ntchw", dtype=None, scale=None, bias=None,
+                 out=None):
+        """Arm a clip sink and return its tensor: from the next frame step on -- decode, submit / wait, every frame of a group, replay -- clip
+        c's picture t is written at step start[c] + t * stride (t = 0 .. n_frames - 1; steps count from 0 at arming) straight into the tensor,
+        by one more kernel behind the step's reconstruction on the batch's stream.  When the call that reports a frame returns, the frame's
+        pictures are there; sink_pending() == 0 says all of them are, and the sink has disarmed itself.
+
+        size=(out_h, out_w), boxes=(n, 4) ints (x, y, w, h; None: the whole picture), flip=n bools or None: export_tensor's, a box per clip,
+        with the same values (the definition is include/mobiclip_hip.h's).  start: n ints >= 0 (None: all 0).
+        layout: "ntchw" (N, T, 3, H, W), "ncthw" (N, 3, T, H, W), "nthwc" (N, T, H, W, 3), "tnchw" (T, N, 3, H, W), "tnhwc" (T, N, H, W, 3).
+        dtype, scale, bias: export_tensor's.  out: a tensor of the layout's shape and the dtype on the batch's device whose innermost H, W
+        (H, W, 3) are contiguous; the other strides are taken as they are (multiples of 4 elements, no overlap), so a view into a larger buffer
+        works; default: a new contiguous tensor.  The batch keeps a reference to the tensor while the sink is armed.
+        set_sink(None) disarms.  Arming, replacing and disarming need nothing in flight (no submitted step, no group)."""
+        if size is None and n_frames is None and out is None:
+            e = self._lib.mobi_batch_set_sink(self._h, None)
+            if e != 0:
+                raise MobiclipError(error_string(e))
+            self._sink_out = None
+            return None
+        import torch
+        if layout not in SINK_LAYOUTS:
+            raise ValueError(f"layout must be one of {sorted(SINK_LAYOUTS)}, not {layout!r}")
+        planar, dims = SINK_LAYOUTS[layout]
+        if dtype is None:
+            dtype = torch.uint8
+        if not isinstance(dtype, torch.dtype) or str(dtype).split(".")[-1] not in DEVICE_EXPORT_DTYPES:
+            raise ValueError(f"dtype must be torch.uint8, torch.float16 or torch.float32, not {dtype!r}")
+        dname = str(dtype).split(".")[-1]
+        sb = None
+        if scale is not None or bias is not None:
+            if dtype == torch.uint8:
+                raise ValueError("scale and bias apply to a float dtype only")
+            vals = []
+            for name, v, dflt in (("scale", scale, 1.0), ("bias", bias, 0.0)):
+                v = [dflt] * 3 if v is None else v
+                try:
+                    v = [float(x) for x in v]
+                except (TypeError, ValueError):
+                    raise ValueError(f"{name} must be three floats, not {v!r}") from None
+                if len(v) != 3 or not all(np.isfinite(v)):
+                    raise ValueError(f"{name} must be three finite floats, not {v!r}")
+                vals += v
+            sb = (C.c_float * 6)(*np.asarray(vals, np.float32).tolist())
+        N = self.n
+        (T,) = _ints("n_frames", (n_frames,), 1)
+        (s,) = _ints("stride", (stride,), 1)
+        if T < 1 or s < 1:
+            raise ValueError(f"n_frames and stride must be at least 1, not {T} and {s}")
+        if boxes is None:
+            if flip is not None:
+                raise ValueError("flip applies to boxes only")
+            boxes = np.tile(np.array([0, 0, self.Width, self.Height], np.int64), (N, 1))
+        box_rows, ow, oh = self._box_geometry("rgb", N, None, size, boxes, flip)
+        if start is None:
+            st = np.zeros(N, np.int64)
+        else:
+            try:
+                st = np.asarray(start)
+            except (TypeError, ValueError):
+                raise ValueError(f"start must be {N} non-negative ints") from None
+            if st.dtype == np.bool_ or not np.issubdtype(st.dtype, np.integer) or st.shape != (N,):
+                raise ValueError(f"start must be {N} non-negative ints, not {st.dtype} {st.shape}")
+            st = st.astype(np.int64)
+        if (st < 0).any() or int(st.max()) + (T - 1) * s > 2**31 - 1:
+            raise ValueError(f"start must be non-negative, and start + (n_frames - 1) * stride at most 2**31 - 1")
+        st = np.ascontiguousarray(st, dtype=np.int32)
+        extent = {"n": N, "t": T, "c": 3, "h": oh, "w": ow}
+        shape = tuple(extent[d] for d in dims)
+        dev = torch.device("cuda", self.device)
+        if out is not None:
+            if not isinstance(out, torch.Tensor) or out.dtype != dtype or tuple(out.shape) != shape:
+                raise ValueError(f"out must be a {dtype} tensor of shape {shape} (layout {layout!r})")
+            sd = dict(zip(dims, out.stride()))
+            inner = (sd["h"], sd["w"]) == (ow, 1) if planar else (sd["h"], sd["w"], sd["c"]) == (3 * ow, 3, 1)
+            if not inner:
+                raise ValueError(f"out: the innermost {'H, W' if planar else 'H, W, 3'} of layout {layout!r} must be contiguous, strides are {tuple(out.stride())}")
+            if out.device != dev or out.data_ptr() % 16:
+                raise ValueError(f"out must be a 16-byte aligned tensor on {dev}")
+        _check_one_hip_runtime()
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=dev)
+        sd = dict(zip(dims, out.stride()))
+        # the bytes from out's first element to the end of the memory it may address: its storage's, which a view does not own alone
+        avail = out.untyped_storage().nbytes() - out.storage_offset() * out.element_size()
+        spec = SinkSpec(DEVICE_EXPORT_FORMATS[("rgb", "nchw" if planar else "nhwc")], DEVICE_EXPORT_DTYPES[dname], sb,
+                        box_rows.ctypes.data_as(C.POINTER(C.c_int32)), ow, oh, T, s, st.ctypes.data_as(C.POINTER(C.c_int32)), sd["n"], sd["t"],
+                        sd["c"] if planar else 0, out.data_ptr(), avail)
+        torch.cuda.current_stream(dev).synchronize()  # (whatever was filling `out` is done before the batch's stream writes it)
+        e = self._lib.mobi_batch_set_sink(self._h, C.byref(spec))
+        if e != 0:
+            raise MobiclipError(error_string(e))
+        self._sink_out = out
+        return out
+
+    def sink_pending(self):
+        """(clip, t) pictures the armed sink has not written yet; 0: no sink armed, or complete"""
+        return int(self._lib.mobi_batch_sink_pending(self._h))
+
+    def sink_launches(self):
+        """launches of the sink kernel so far (0 for a batch that never armed one)"""
+        return int(self._lib.mobi_batch_sink_launches(self._h))
+
+    def gop_finish_all(self):
+        """gop_finish() for every frame of the oldest group that is still pending, in one call with one wait: -> (rc, offsets) as gop_finish(),
+        gop_frames_pending() rows each.  The ring holds the group's last six frames afterwards; the earlier ones reach the caller through a
+        sink (set_sink)."""
+        K = self._lib.mobi_batch_gop_frames_pending(self._h)
+        offs = (C.c_int32 * max(1, K * self.n))()
+        rcs = (C.c_int * max(1, K * self.n))()
+        e = self._lib.mobi_batch_gop_finish_all(self._h, offs, rcs)
+        if e != 0:
+            raise MobiclipError(error_string(e))
+        return [list(rcs[k * self.n:(k + 1) * self.n]) for k in range(K)], [list(offs[k * self.n:(k + 1) * self.n]) for k in range(K)]
 
     def _box_geometry(self, fmt, N, crop, size, boxes, flip):
         """export_tensor's boxes / flip / size, checked -> the (N, 5) int32 rows (x, y, w, h, flip) of the library call, out_w, out_h"""
