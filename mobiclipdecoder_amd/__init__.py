@@ -18,4 +18,5 @@ from .decoder import (  # noqa: F401
     transform_code,
 )
 from .audio import MobiclipAudio  # noqa: F401
+from .encode import MobiclipIntraEncoder  # noqa: F401
 from .streamgen import GenParams, generate_clip, default_params  # noqa: F401

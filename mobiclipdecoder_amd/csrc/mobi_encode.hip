@@ -1,0 +1,390 @@
+// mobi_encode.hip -- the intra encoder on gfx950 (include/mobiclip_encode.h; the rules are mobi_encode.h's, DESIGN.md "Intra encoder").
+//
+// Stage 1, decide and reconstruct.  One wave = one macroblock.  Its 64 lanes are eight groups of eight: groups 0..2 try the luma modes
+// 0, 1, 3 side by side, groups 3..5 the chroma modes, groups 6 and 7 ride along.  A group runs its trial's blocks in sequence (four luma
+// blocks; U, then V), one lane = one row of the block, the arithmetic and its lane mapping those of mobi_txcode.hip.  Every trial keeps
+// its own reconstruction in an LDS patch whose border row and column come from the picture's reconstruction, so a block predicts from
+// the earlier blocks of the same trial.  The two winners' patches and levels go to memory; lane 0 adds the macroblock to the statistics.
+// Macroblock (x, y) needs (x - 1, y) and (x, y - 1): anti-diagonals are independent, and the order between them is kept ONLY by kernel
+// boundaries: mobi_enc_decide_diag is launched once per diagonal over all pictures.  The other shape -- mobi_enc_decide_loop, one
+// workgroup per picture whose waves share a diagonal's macroblocks with __syncthreads() between diagonals -- was measured against it:
+// slower at 8 and 512 pictures, level at 4096; it lives on in the profiling twin for that comparison.  No wave ever waits on memory.
+//
+// Stage 2, write bits.  mobi_enc_scan: one workgroup per picture, exclusive scan of the macroblocks' bit lengths behind the 9 header bits,
+// the stream's length, whether it fits its slot.  mobi_enc_write: one lane per macroblock spells its bit string at its own offset into the
+// zeroed slot: whole 32-bit words by plain stores, its first and last (shared with the neighbours) by atomic OR.
+#include <hip/hip_runtime.h>
+
+#include "mobi_encode.h"
+
+namespace {
+
+constexpr int WAVES = 4; // per workgroup, both stage-1 shapes
+
+struct WaveLds {
+  uint8_t patch[6][18][20]; // luma: [1 + y][1 + x] of the 16x16, row 0 / column 0 = the border; chroma: U rows 0..8, V rows 9..17
+  int tile[8][8][9];        // transposes (pitch 9: a column read of eight lanes hits eight banks)
+  int16_t nat[8][64];       // a block's levels in natural order
+  int16_t lev[6][4][64];    // every trial's levels in scan order
+};
+
+// the lanes of one wave exchange data through LDS: LDS operations of a wave complete in order, the fences keep the compiler from moving them
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+__device__ __forceinline__ uint32_t sum8(uint32_t v) {
+#pragma unroll
+  for (int m = 1; m < 8; m <<= 1) v += (uint32_t)__shfl_xor((int)v, m, 8);
+  return v;
+}
+__device__ __forceinline__ uint32_t or8(uint32_t v) {
+#pragma unroll
+  for (int m = 1; m < 8; m <<= 1) v |= (uint32_t)__shfl_xor((int)v, m, 8);
+  return v;
+}
+__device__ __forceinline__ int64_t shfl64(int64_t v, int src) {
+  const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, src), hi = (uint32_t)__shfl((int)(uint32_t)((uint64_t)v >> 32), src);
+  return (int64_t)((uint64_t)hi << 32 | lo);
+}
+__device__ __forceinline__ int ue_bits(uint32_t code) {
+  return 2 * (31 - __builtin_clz(code + 1u)) + 1;
+}
+
+__device__ __forceinline__ void encode_mb(const MobiEncArgs &A, int pic, int mbx, int mby, WaveLds &L, const uint8_t *lut) {
+  const MobiEncConst *K = A.k;
+  const int lane = threadIdx.x & 63, g = lane >> 3, r = lane & 7;
+  const bool chroma = g >= 3 && g < 6;
+  const int gp = g < 6 ? g : 0;                   // the patch a group works in (6 and 7 shadow group 0 and keep nothing)
+  const int mode = mobi_enc_mode(g % 3);
+  const int W = A.W, q = A.q[pic];
+  const size_t ysz = (size_t)W * A.H, frame = ysz + ysz / 2;
+  const uint8_t *src = A.src + (size_t)pic * A.src_pitch;
+  uint8_t *rec = A.rec + (size_t)pic * frame;
+  const int64_t lam = mobi_enc_lambda(q);
+  const int32_t *Qrow = K->q8[q] + r * 8;
+  const float *RQrow = K->rq8[q] + r * 8;
+  int zi[8];
+#pragma unroll
+  for (int j = 0; j < 8; j++) zi[j] = K->zz8[r * 8 + j];
+
+  // the luma border: 16 samples above, 16 to the left (read only where they exist)
+  if (!chroma) {
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+      const int i = r + 8 * h;
+      L.patch[gp][0][1 + i] = mby > 0 ? rec[(size_t)(mby * 16 - 1) * W + mbx * 16 + i] : 0;
+      L.patch[gp][1 + i][0] = mbx > 0 ? rec[(size_t)(mby * 16 + i) * W + mbx * 16 - 1] : 0;
+    }
+  }
+  int64_t J = 0;
+  uint32_t coded_m = 0, bits_t = 0, sad_t = 0, clamp_t = 0, range_t = 0;
+#pragma unroll 1
+  for (int it = 0; it < 4; it++) {
+    const bool live = g < 6 && (!chroma || it < 2);
+    const int cp = it < 2 ? it : 1; // the chroma plane of this round
+    const int pitch = chroma ? W / 2 : W;
+    const size_t plane = chroma ? ysz + (size_t)cp * (ysz / 4) : 0;
+    const int x0 = chroma ? mbx * 8 : mbx * 16 + (it & 1) * 8, y0 = chroma ? mby * 8 : mby * 16 + (it >> 1) * 8;
+    const int oy = chroma ? 1 + 9 * cp : 1 + 8 * (it >> 1), ox = chroma ? 1 : 1 + 8 * (it & 1);
+    if (chroma && it < 2) { // this plane's border
+      L.patch[gp][oy - 1][1 + r] = y0 > 0 ? rec[plane + (size_t)(y0 - 1) * pitch + x0 + r] : 0;
+      L.patch[gp][oy + r][0] = x0 > 0 ? rec[plane + (size_t)(y0 + r) * pitch + x0 - 1] : 0;
+    }
+    wave_sync();
+    int s[8], p[8], x[8], o[8], d[8];
+    {
+      const uint2 v = *(const uint2 *)(src + plane + (size_t)(y0 + r) * pitch + x0);
+#pragma unroll
+      for (int k = 0; k < 4; k++) { s[k] = (v.x >> (8 * k)) & 0xFF; s[k + 4] = (v.y >> (8 * k)) & 0xFF; }
+    }
+    // the decoder's predictor on the trial's own reconstruction
+    auto nb = [&](int dy, int dx) -> int { return L.patch[gp][oy + dy][ox + dx]; };
+    if (mode == 3) {
+      const int dc = mobi_pred_px(3, 8, 0, 0, y0 != 0, x0 != 0, nb);
+#pragma unroll
+      for (int k = 0; k < 8; k++) p[k] = dc;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 8; k++) p[k] = mobi_pred_px(mode, 8, r, k, 1, 1, nb);
+    }
+    // forward transform, quantise, first inverse pass (mobi_txcode.hip's steps)
+#pragma unroll
+    for (int k = 0; k < 8; k++) x[k] = (s[k] - p[k]) * 64;
+    mobi_dct8_pass(x, o);
+#pragma unroll
+    for (int k = 0; k < 8; k++) L.tile[g][r][k] = o[k];
+    wave_sync();
+#pragma unroll
+    for (int j = 0; j < 8; j++) x[j] = L.tile[g][j][r];
+    mobi_dct8_pass(x, d);
+    wave_sync(); // the column reads are done before the tile is written again
+    uint32_t big = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      const int Q = Qrow[k], lev = mobi_tc_quant(d[k], Q, RQrow[k]);
+      L.nat[g][r * 8 + k] = (int16_t)lev;
+      big |= (uint32_t)(lev > MOBI_ENC_MAX_LEVEL || lev < -MOBI_ENC_MAX_LEVEL);
+      x[k] = lev * Q;
+    }
+    if (r == 0) x[0] += 0x20;
+    mobi_idct8_pass(x, o);
+#pragma unroll
+    for (int k = 0; k < 8; k++) L.tile[g][k][r] = o[k];
+    wave_sync();
+    // levels in scan order, run / last from the block's nonzero mask, bit cost from the table
+    int lv[8];
+    uint32_t nzl = 0;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      lv[j] = L.nat[g][zi[j]];
+      nzl |= (uint32_t)(lv[j] != 0) << j;
+    }
+    const uint32_t lo = or8(r < 4 ? nzl << (8 * r) : 0u), hi = or8(r >= 4 ? nzl << (8 * (r - 4)) : 0u);
+    const uint64_t mask = (uint64_t)hi << 32 | lo;
+    uint32_t bits = 0;
+    if (mask) {
+      const int last = 63 - __builtin_clzll(mask);
+#pragma unroll
+      for (int j = 0; j < 8; j++) {
+        const int k = r * 8 + j;
+        const uint64_t below = mask & ((1ull << k) - 1ull);
+        const int prev = below ? 63 - __builtin_clzll(below) : -1;
+        const int v = lv[j] < 0 ? -lv[j] : lv[j];
+        const int c = v < MOBI_TC_LUT_V ? (int)lut[mobi_tc_lut_index(v, k - prev - 1, k == last)] : MOBI_TC_ESCAPE_BITS;
+        bits += lv[j] ? (uint32_t)c : 0u;
+      }
+    }
+    // second inverse pass = pixel row r, the clamp table, both SADs
+#pragma unroll
+    for (int j = 0; j < 8; j++) x[j] = L.tile[g][r][j];
+    mobi_idct8_pass(x, o);
+    uint32_t sad = 0, sadp = 0, bad = 0;
+    int px[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      const int t = 0x40 + p[k] + (o[k] >> 6);
+      bad += (uint32_t)t >= 384u;
+      px[k] = t < 0x40 ? 0 : t > 0x40 + 255 ? 255 : t - 0x40;
+      sad += (uint32_t)__builtin_abs(s[k] - px[k]);
+      sadp += (uint32_t)__builtin_abs(s[k] - p[k]);
+    }
+    // sad <= 64 * 255 < 2^14, bits <= 64 * 28 < 2^11, faults <= 64 < 2^7; the prediction's sad with the level-range flag above it
+    const uint32_t sum = sum8(sad | bits << 14 | bad << 25), sum2 = sum8(sadp | big << 14);
+    const MobiEncBlock b = mobi_enc_block_result(mask != 0, (sum >> 25) != 0, (sum2 >> 14) != 0, (int)((sum >> 14) & 0x7FF), (int)(sum & 0x3FFF),
+                                                 (int)(sum2 & 0x3FFF));
+    if (live) {
+      J += mobi_enc_cost(lam, b);
+      coded_m |= (uint32_t)b.coded << it;
+      bits_t += (uint32_t)b.bits;
+      sad_t += (uint32_t)b.sad;
+      clamp_t += b.clamp;
+      range_t += b.range;
+#pragma unroll
+      for (int k = 0; k < 8; k++) L.patch[g][oy + r][ox + k] = (uint8_t)(b.coded ? px[k] : p[k]);
+#pragma unroll
+      for (int j = 0; j < 8; j++) L.lev[g][it][r * 8 + j] = (int16_t)(b.coded ? lv[j] : 0);
+    }
+  }
+  wave_sync();
+
+  // ---- the argmin of each half: candidates in mode order, a tie keeps the smaller mode ----
+  int gl = -1, gc = -1;
+  int64_t Jl = 0, Jc = 0;
+#pragma unroll
+  for (int c = 0; c < MOBI_ENC_NMODES; c++) {
+    const int64_t a = shfl64(J, c * 8), b = shfl64(J, (3 + c) * 8);
+    if (!mobi_enc_mode_allowed(mobi_enc_mode(c), mbx, mby)) continue;
+    if (gl < 0 || a < Jl) { gl = c; Jl = a; }
+    if (gc < 0 || b < Jc) { gc = 3 + c; Jc = b; }
+  }
+  // the winners' reconstruction: 64 words of luma, 32 of chroma
+  {
+    const int row = lane >> 2, cw = lane & 3;
+    const uint8_t *s4 = &L.patch[gl][1 + row][1 + 4 * cw];
+    *(uint32_t *)(rec + (size_t)(mby * 16 + row) * W + mbx * 16 + 4 * cw) = (uint32_t)s4[0] | (uint32_t)s4[1] << 8 | (uint32_t)s4[2] << 16 | (uint32_t)s4[3] << 24;
+    if (lane < 32) {
+      const int cp = lane >> 4, crow = (lane & 15) >> 1, ccw = lane & 1;
+      const uint8_t *c4 = &L.patch[gc][1 + 9 * cp + crow][1 + 4 * ccw];
+      *(uint32_t *)(rec + ysz + (size_t)cp * (ysz / 4) + (size_t)(mby * 8 + crow) * (W / 2) + mbx * 8 + 4 * ccw) =
+          (uint32_t)c4[0] | (uint32_t)c4[1] << 8 | (uint32_t)c4[2] << 16 | (uint32_t)c4[3] << 24;
+    }
+  }
+  MobiEncMb *mb = A.mbs + (size_t)pic * ((size_t)A.mbw * A.mbh) + (size_t)mby * A.mbw + mbx;
+#pragma unroll
+  for (int i = 0; i < 3; i++) { // 6 x 64 levels = 192 words
+    const int w = lane + 64 * i, a = w >> 5, idx = w & 31;
+    ((uint32_t *)mb->lev[a])[idx] = ((const uint32_t *)L.lev[a < 4 ? gl : gc][a < 4 ? a : a - 4])[idx];
+  }
+  const uint32_t cl = (uint32_t)__shfl((int)coded_m, gl * 8), cc = (uint32_t)__shfl((int)coded_m, gc * 8);
+  const uint32_t bl = (uint32_t)__shfl((int)bits_t, gl * 8), bc = (uint32_t)__shfl((int)bits_t, gc * 8);
+  const uint32_t sl = (uint32_t)__shfl((int)sad_t, gl * 8), sc = (uint32_t)__shfl((int)sad_t, gc * 8);
+  const uint32_t kl = (uint32_t)__shfl((int)clamp_t, gl * 8), kc = (uint32_t)__shfl((int)clamp_t, gc * 8);
+  const uint32_t rl = (uint32_t)__shfl((int)range_t, gl * 8), rc = (uint32_t)__shfl((int)range_t, gc * 8);
+  if (lane == 0) {
+    const uint32_t cbp = cl | cc << 4;
+    mb->bits = 1u + (uint32_t)ue_bits(K->inv_cbp[cbp]) + 6u + bl + bc;
+    mb->luma_mode = (uint8_t)mobi_enc_mode(gl);
+    mb->chroma_mode = (uint8_t)mobi_enc_mode(gc - 3);
+    mb->cbp = (uint8_t)cbp;
+    mb->pad = 0;
+    if (A.stats) {
+      mobi_enc_stats *st = A.stats + pic;
+      atomicAdd((unsigned long long *)&st->sad, (unsigned long long)(sl + sc));
+      atomicAdd(&st->luma_modes[mobi_enc_mode(gl)], 1u);
+      atomicAdd(&st->chroma_modes[mobi_enc_mode(gc - 3)], 1u);
+      if (__popc(cbp)) atomicAdd(&st->coded_blocks, (uint32_t)__popc(cbp));
+      if (kl + kc) atomicAdd(&st->fallback_clamp, kl + kc);
+      if (rl + rc) atomicAdd(&st->fallback_level, rl + rc);
+    }
+  }
+  wave_sync(); // the patches and levels are read before the wave's next macroblock writes them
+}
+
+__device__ __forceinline__ const uint8_t *stage_lut(const MobiEncArgs &A, uint32_t *lut32) {
+  for (int i = threadIdx.x; i < MOBI_TC_LUT_BYTES / 4; i += WAVES * 64) lut32[i] = ((const uint32_t *)A.k->lut)[i];
+  __syncthreads();
+  return (const uint8_t *)lut32;
+}
+// macroblocks of diagonal d: x from max(0, d - mbh + 1) to min(d, mbw - 1), y = d - x
+__device__ __forceinline__ void diag_range(const MobiEncArgs &A, int d, int &x_lo, int &count) {
+  x_lo = d - A.mbh + 1 > 0 ? d - A.mbh + 1 : 0;
+  const int x_hi = d < A.mbw - 1 ? d : A.mbw - 1;
+  count = x_hi - x_lo + 1;
+}
+
+} // namespace
+
+#if defined(MOBI_PROFILING)
+// the shape that was measured against the kept one and did not win ("Intra encoder"): in the profiling twin only, for tools/exp_encode.py
+extern "C" __global__ __launch_bounds__(WAVES * 64) void mobi_enc_decide_loop(MobiEncArgs A) {
+  __shared__ uint32_t lut32[MOBI_TC_LUT_BYTES / 4];
+  __shared__ WaveLds lds[WAVES];
+  const uint8_t *lut = stage_lut(A, lut32);
+  const int wave = threadIdx.x >> 6, pic = blockIdx.x;
+  for (int d = 0; d < A.mbw + A.mbh - 1; d++) {
+    int x_lo, count;
+    diag_range(A, d, x_lo, count);
+    for (int i = wave; i < count; i += WAVES) encode_mb(A, pic, x_lo + i, d - (x_lo + i), lds[wave], lut);
+    __syncthreads(); // this diagonal's reconstruction is written before the next one reads it (every wave arrives, whatever it encoded)
+  }
+}
+#endif
+
+extern "C" __global__ __launch_bounds__(WAVES * 64) void mobi_enc_decide_diag(MobiEncArgs A, int d) {
+  __shared__ uint32_t lut32[MOBI_TC_LUT_BYTES / 4];
+  __shared__ WaveLds lds[WAVES];
+  const uint8_t *lut = stage_lut(A, lut32);
+  const int wave = threadIdx.x >> 6, pic = blockIdx.y;
+  int x_lo, count;
+  diag_range(A, d, x_lo, count);
+  const int i = blockIdx.x * WAVES + wave;
+  if (i < count) encode_mb(A, pic, x_lo + i, d - (x_lo + i), lds[wave], lut);
+}
+
+// ---- stage 2 ----
+extern "C" __global__ __launch_bounds__(256) void mobi_enc_scan(MobiEncArgs A) {
+  __shared__ uint32_t sh[256];
+  const int pic = blockIdx.x, nmb = A.mbw * A.mbh, t = threadIdx.x;
+  const MobiEncMb *mbs = A.mbs + (size_t)pic * nmb;
+  uint32_t *off = A.mb_off + (size_t)pic * nmb;
+  uint32_t carry = MOBI_ENC_HEADER_BITS;
+  for (int base = 0; base < nmb; base += 256) {
+    const int i = base + t;
+    const uint32_t v = i < nmb ? mbs[i].bits : 0u;
+    sh[t] = v;
+    __syncthreads();
+    for (int s = 1; s < 256; s <<= 1) {
+      const uint32_t a = t >= s ? sh[t - s] : 0u;
+      __syncthreads();
+      sh[t] += a;
+      __syncthreads();
+    }
+    if (i < nmb) off[i] = carry + sh[t] - v;
+    carry += sh[255];
+    __syncthreads();
+  }
+  if (t == 0) {
+    const uint64_t bytes = mobi_enc_stream_bytes(carry - MOBI_ENC_HEADER_BITS);
+    A.bytes_out[pic] = (int32_t)bytes;
+    A.fits[pic] = bytes <= A.slot_bytes;
+    if (A.stats) A.stats[pic].bits = carry;
+  }
+}
+
+namespace {
+// MSB-first bits into 16-bit little-endian words, a 32-bit word (two of them) at a time
+struct SlotSink {
+  uint32_t *slot;
+  uint32_t pos, cur;
+  bool first;
+  __device__ void flush() {
+    const uint32_t w = cur >> 16 | cur << 16;
+    uint32_t *at = slot + ((pos - 1) >> 5);
+    if (first) atomicOr(at, w); else *at = w;
+    first = false;
+    cur = 0;
+  }
+  __device__ void operator()(uint32_t v, int n) {
+    const int b = (int)(pos & 31);
+    if (b + n <= 32) {
+      cur |= v << (32 - b - n);
+      pos += n;
+      if ((pos & 31) == 0) flush();
+    } else {
+      const int rest = b + n - 32;
+      cur |= v >> rest;
+      pos += n - rest;
+      flush();
+      cur = v << (32 - rest);
+      pos += rest;
+    }
+  }
+  __device__ void finish() {
+    if (pos & 31) {
+      pos = (pos + 31) & ~31u; // flush() addresses the word before pos
+      first = true;            // the last word is shared with the next macroblock
+      flush();
+    }
+  }
+};
+} // namespace
+
+extern "C" __global__ __launch_bounds__(64) void mobi_enc_write(MobiEncArgs A) {
+  const int pic = blockIdx.y, nmb = A.mbw * A.mbh, i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= nmb || !A.fits[pic]) return;
+  const MobiEncMb *mb = A.mbs + (size_t)pic * nmb + i;
+  SlotSink s;
+  s.slot = (uint32_t *)(A.streams + (size_t)pic * A.slot_bytes);
+  s.cur = 0;
+  s.first = true;
+  if (i == 0) {
+    s.pos = 0;
+    s(mobi_enc_header(A.yuv_format, A.q[pic]), MOBI_ENC_HEADER_BITS);
+  } else {
+    s.pos = A.mb_off[(size_t)pic * nmb + i];
+  }
+  mobi_enc_write_mb(A.k, mb, [&](uint32_t v, int n) { s(v, n); }, (uint32_t *)nullptr);
+  s.finish();
+}
+
+// stages: bit 0 = decide, bit 1 = write (the product always runs both); loop_shape: the profiling twin's other stage-1 shape
+extern "C" int mobi_launch_encode(const MobiEncArgs *a, int stages, int loop_shape, hipStream_t s) {
+  const int nmb = a->mbw * a->mbh;
+  if (stages & 1) {
+#if defined(MOBI_PROFILING)
+    if (loop_shape) hipLaunchKernelGGL(mobi_enc_decide_loop, dim3(a->n), dim3(WAVES * 64), 0, s, *a);
+    else
+#endif
+      for (int d = 0; d < a->mbw + a->mbh - 1; d++) {
+        const int lo = d - a->mbh + 1 > 0 ? d - a->mbh + 1 : 0, hi = d < a->mbw - 1 ? d : a->mbw - 1;
+        hipLaunchKernelGGL(mobi_enc_decide_diag, dim3((hi - lo + 1 + WAVES - 1) / WAVES, a->n), dim3(WAVES * 64), 0, s, *a, d);
+      }
+  }
+  if (stages & 2) {
+    hipLaunchKernelGGL(mobi_enc_scan, dim3(a->n), dim3(256), 0, s, *a);
+    hipLaunchKernelGGL(mobi_enc_write, dim3((nmb + 63) / 64, a->n), dim3(64), 0, s, *a);
+  }
+  return (int)hipGetLastError();
+}
