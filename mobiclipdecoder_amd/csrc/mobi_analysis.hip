@@ -10,7 +10,7 @@
 
 #include "mobi_kernels.h"
 #include "mobi_tile.h"
-#include "mobi_txcode.h"
+#include "mobi_txcode_lanes.h"
 
 namespace {
 enum { WIN_ROWS = 36, WIN_DW = 10, REACH = 10 }; // 6 + 3 + 1 pels either way around a 16 x 16 macroblock; 40 bytes per row from column BX - 12
@@ -96,52 +96,31 @@ extern "C" int mobi_launch_motion_search(const MobiReconArgs *a, const uint8_t *
 // Pure integer: x64, a fixed integer matrix per pass, a C# integer division (truncating) -- rows, then columns, results of the second
 // pass stored transposed, as the reference does.  One lane = one row (then one column) of a block: 8 lanes per 8x8 block, 4 per 4x4;
 // the transpose between the passes goes through LDS.  512 B (128 B) of traffic per block: HBM-bound.
-// The quantiser, the bit cost and the reconstruction behind it are mobi_txcode.hip (mobi_transform_code); both kernels use the passes of
-// mobi_txcode.h.
+// The step is mobi_txcode_lanes.h's forward step, the one mobi_txcode.hip (mobi_transform_code: the quantiser, the bit cost and the
+// reconstruction behind it) and the intra encoder run.
 
-extern "C" __global__ __launch_bounds__(256) void mobi_fwd_dct8(const int32_t *in, int32_t *out, uint32_t n_blocks) {
-  __shared__ int tile[32][8][9]; // 32 blocks per workgroup; pitch 9: the column reads of eight lanes hit eight banks
-  const uint32_t blk = blockIdx.x * 32u + (threadIdx.x >> 3);
-  const int lb = threadIdx.x >> 3, r = threadIdx.x & 7;
+template <int N> __device__ __forceinline__ void fwd_dct(const int32_t *in, int32_t *out, uint32_t n_blocks) {
+  constexpr int BPW = 256 / N; // blocks per workgroup
+  __shared__ int tile[BPW][N][N + 1]; // pitch N + 1: the column reads of N lanes hit N banks
+  const int lb = threadIdx.x / N, r = threadIdx.x % N;
+  const uint32_t blk = blockIdx.x * (uint32_t)BPW + (uint32_t)lb;
   const bool on = blk < n_blocks;
-  int x[8], o[8];
-  if (on) {
-    const int4 a = *(const int4 *)(in + (size_t)blk * 64 + r * 8), b = *(const int4 *)(in + (size_t)blk * 64 + r * 8 + 4);
-    x[0] = a.x * 64; x[1] = a.y * 64; x[2] = a.z * 64; x[3] = a.w * 64; x[4] = b.x * 64; x[5] = b.y * 64; x[6] = b.z * 64; x[7] = b.w * 64;
-    mobi_dct8_pass(x, o);
+  const size_t row = (size_t)blk * (N * N) + r * N;
+  // lanes past n_blocks transform zeros and store nothing: the step contains the barrier, every lane runs it
+  int x[N], o[N];
 #pragma unroll
-    for (int k = 0; k < 8; k++) tile[lb][r][k] = o[k];
+  for (int k = 0; k < N; k += 4) {
+    const int4 a = on ? *(const int4 *)(in + row + k) : int4{0, 0, 0, 0};
+    x[k] = a.x; x[k + 1] = a.y; x[k + 2] = a.z; x[k + 3] = a.w;
   }
-  __syncthreads();
+  mobi_lanes_forward<N>(x, r, tile[lb], MobiSyncWorkgroup(), o);
   if (on) {
 #pragma unroll
-    for (int j = 0; j < 8; j++) x[j] = tile[lb][j][r]; // column r
-    mobi_dct8_pass(x, o);
-    *(int4 *)(out + (size_t)blk * 64 + r * 8) = int4{o[0], o[1], o[2], o[3]};
-    *(int4 *)(out + (size_t)blk * 64 + r * 8 + 4) = int4{o[4], o[5], o[6], o[7]};
+    for (int k = 0; k < N; k += 4) *(int4 *)(out + row + k) = int4{o[k], o[k + 1], o[k + 2], o[k + 3]};
   }
 }
-extern "C" __global__ __launch_bounds__(256) void mobi_fwd_dct4(const int32_t *in, int32_t *out, uint32_t n_blocks) {
-  __shared__ int tile[64][4][5];
-  const uint32_t blk = blockIdx.x * 64u + (threadIdx.x >> 2);
-  const int lb = threadIdx.x >> 2, r = threadIdx.x & 3;
-  const bool on = blk < n_blocks;
-  int x[4], o[4];
-  if (on) {
-    const int4 a = *(const int4 *)(in + (size_t)blk * 16 + r * 4);
-    x[0] = a.x * 64; x[1] = a.y * 64; x[2] = a.z * 64; x[3] = a.w * 64;
-    mobi_dct4_pass(x, o);
-#pragma unroll
-    for (int k = 0; k < 4; k++) tile[lb][r][k] = o[k];
-  }
-  __syncthreads();
-  if (on) {
-#pragma unroll
-    for (int j = 0; j < 4; j++) x[j] = tile[lb][j][r];
-    mobi_dct4_pass(x, o);
-    *(int4 *)(out + (size_t)blk * 16 + r * 4) = int4{o[0], o[1], o[2], o[3]};
-  }
-}
+extern "C" __global__ __launch_bounds__(256) void mobi_fwd_dct8(const int32_t *in, int32_t *out, uint32_t n_blocks) { fwd_dct<8>(in, out, n_blocks); }
+extern "C" __global__ __launch_bounds__(256) void mobi_fwd_dct4(const int32_t *in, int32_t *out, uint32_t n_blocks) { fwd_dct<4>(in, out, n_blocks); }
 extern "C" int mobi_launch_fwd_dct(int n, const int32_t *in_dev, int32_t *out_dev, uint32_t n_blocks, hipStream_t s) {
   if (n_blocks == 0) return 0;
   if (n == 8) hipLaunchKernelGGL(mobi_fwd_dct8, dim3((n_blocks + 31) / 32), dim3(256), 0, s, in_dev, out_dev, n_blocks);

@@ -5,7 +5,7 @@
 //   block rule      coded iff some level is nonzero; sent uncoded (reconstruction = prediction, 0 bits) when the reconstruction would
 //                   leave the clamp table or some |level| > 2047
 //   one block       mobi_enc_block: the arithmetic of mobi_transform_code at n = 8 (mobi_txcode.h), scalar: the host model's; the kernel
-//                   runs the same functions of mobi_txcode.h eight lanes to a block and shares mobi_enc_block_result's rule
+//                   runs the same functions eight lanes to a block (mobi_txcode_lanes.h) and shares mobi_enc_block_result's rule
 //   one macroblock  mobi_enc_macroblock: three luma and three chroma trials on the decoder's own predictors (mobi_recon_math.h)
 //   bit writer      mobi_enc_symbol (one (last, run, level) in the order mobi_tc_cost prices the forms), mobi_enc_write_mb (a macroblock's
 //                   bit string into any sink: MobiEncHostSink here, the kernel's word-at-a-time sink in mobi_encode.hip; both put bits
@@ -22,7 +22,7 @@
 enum { MOBI_ENC_QMIN = 12, MOBI_ENC_QMAX = 52,
        MOBI_ENC_HEADER_BITS = 9,        // 1 (intra), yuv_format, 0 (VLC table 0), quantiser in 6
        MOBI_ENC_TAIL_BITS = 16,         // zero bits behind the last macroblock, then zeros to a 16-bit boundary
-       MOBI_ENC_MAX_LEVEL = 2047,       // the raw escape holds 12 bits, two's complement
+       MOBI_ENC_MAX_LEVEL = MOBI_TC_MAX_LEVEL, // the raw escape holds 12 bits, two's complement
        MOBI_ENC_NMODES = 3,
        MOBI_ENC_FORM_OWN = 0, MOBI_ENC_FORM_RUN = 1, MOBI_ENC_FORM_LEVEL = 2, MOBI_ENC_FORM_RAW = 3 };
 
@@ -55,16 +55,37 @@ MOBI_TC_FN MobiEncBlock mobi_enc_block_result(bool nz, bool clamp, bool range, i
 }
 MOBI_TC_FN int64_t mobi_enc_cost(int64_t lam, const MobiEncBlock &b) { return ((int64_t)b.sad << 8) + lam * b.bits; }
 
-// per-device constants, built on the host once per encoder (mobi_enc_build_const)
-struct MobiEncConst {
-  int32_t q8[MOBI_TC_NQ][64];
-  float rq8[MOBI_TC_NQ][64];
-  uint8_t zz8[64];
-  uint8_t lut[MOBI_TC_LUT_BYTES];
+// per-device constants, built on the host once per encoder (mobi_enc_build_const): the transform coding's (mobi_tc_build_const: Q rows,
+// reciprocals, scan orders, the cost table) as the base, so that the block coder takes the same pointer, and the bit writer's behind them
+struct MobiEncConst : MobiTcConst {
   uint32_t code[2 * 64 * 32]; // [(last * 64 + run) * 32 + v]: length << 16 | the code word with a positive sign; 0 = the pair has none
   uint8_t esc[256];           // mobi_vx2table0_b
   uint8_t inv_cbp[64];        // the ue() number whose mobi_cbp_intra entry is cbp6
 };
+
+// ---- small rules the host model and the kernels or their launcher share ----
+// the length of ue(code): z zeros, a one, z more bits of code + 1 (BitWriter.WriteVarIntUnsigned)
+MOBI_TC_FN int mobi_enc_ue_bits(uint32_t code) { return 2 * (31 - __builtin_clz(code + 1u)) + 1; }
+// a macroblock's bits in front of its blocks: 0 (the full-block syntax), ue(cbp), two 3-bit modes
+MOBI_TC_FN uint32_t mobi_enc_mb_header_bits(const MobiEncConst *K, uint32_t cbp) { return 1u + (uint32_t)mobi_enc_ue_bits(K->inv_cbp[cbp]) + 6u; }
+// macroblocks of anti-diagonal d: x from max(0, d - mbh + 1) to min(d, mbw - 1), y = d - x
+MOBI_TC_FN void mobi_enc_diag_range(int mbw, int mbh, int d, int *x_lo, int *count) {
+  *x_lo = d - mbh + 1 > 0 ? d - mbh + 1 : 0;
+  const int x_hi = d < mbw - 1 ? d : mbw - 1;
+  *count = x_hi - *x_lo + 1;
+}
+// where block k of a macroblock's luma (k = 0..3) or chroma (k = 0: U, 1: V) lies: plane 0..2 of the I420 picture, its pitch, the corner
+struct MobiEncBlockAt {
+  int plane, pitch, x0, y0;
+};
+MOBI_TC_FN MobiEncBlockAt mobi_enc_block_at(bool chroma, int k, int mbx, int mby, int W) {
+  MobiEncBlockAt a;
+  a.plane = chroma ? 1 + k : 0;
+  a.pitch = chroma ? W / 2 : W;
+  a.x0 = chroma ? mbx * 8 : mbx * 16 + (k & 1) * 8;
+  a.y0 = chroma ? mby * 8 : mby * 16 + (k >> 1) * 8;
+  return a;
+}
 
 // one macroblock as stage 1 leaves it for the bit writer
 struct MobiEncMb {
@@ -119,12 +140,7 @@ MOBI_TC_FN uint32_t mobi_enc_symbol(const MobiEncConst *K, int level, int run, i
 template <class Put>
 MOBI_TC_FN void mobi_enc_write_mb(const MobiEncConst *K, const MobiEncMb *m, Put put, uint32_t *forms) {
   put(0u, 1); // the full-block syntax
-  { // ue(): z zeros, a one, z more bits (BitWriter.WriteVarIntUnsigned)
-    const uint32_t v = K->inv_cbp[m->cbp] + 1u;
-    int z = 0;
-    while ((v >> (z + 1)) != 0) z++;
-    put(v, 2 * z + 1);
-  }
+  put(K->inv_cbp[m->cbp] + 1u, mobi_enc_ue_bits(K->inv_cbp[m->cbp])); // ue(): the leading zeros are the pattern's own
   for (int k = 0; k < 6; k++) {
     if (k == 0) put(m->luma_mode, 3);
     if (k == 4) put(m->chroma_mode, 3);
@@ -183,7 +199,7 @@ MOBI_TC_FN MobiEncBlock mobi_enc_block(const MobiEncConst *K, int q, const int *
       x[k] = l * Q;
     }
     if (r == 0) x[0] += 0x20;
-    mobi_idct8_pass(x, o);
+    mobi_bfly8(x, o);
     for (int k = 0; k < 8; k++) t[k * 8 + r] = o[k];
   }
   int vlc = 0, prev = -1, lastpos = -1;
@@ -199,19 +215,18 @@ MOBI_TC_FN MobiEncBlock mobi_enc_block(const MobiEncConst *K, int q, const int *
     prev = p;
   }
   int sad_rec = 0, sad_pred = 0;
-  bool clamp = false;
+  int clamp = 0;
   for (int r = 0; r < 8; r++) {
     for (int j = 0; j < 8; j++) x[j] = t[r * 8 + j];
-    mobi_idct8_pass(x, o);
+    mobi_bfly8(x, o);
     for (int k = 0; k < 8; k++) {
-      const int s = src[r * 8 + k], p = pred[r * 8 + k], c = 0x40 + p + (o[k] >> 6);
-      clamp |= (uint32_t)c >= 384u;
-      rec[r * 8 + k] = c < 0x40 ? 0 : c > 0x40 + 255 ? 255 : c - 0x40;
+      const int s = src[r * 8 + k], p = pred[r * 8 + k];
+      rec[r * 8 + k] = mobi_add_clamp(p, o[k] >> 6, &clamp);
       sad_rec += s > rec[r * 8 + k] ? s - rec[r * 8 + k] : rec[r * 8 + k] - s;
       sad_pred += s > p ? s - p : p - s;
     }
   }
-  const MobiEncBlock b = mobi_enc_block_result(lastpos >= 0, clamp, range, vlc, sad_rec, sad_pred);
+  const MobiEncBlock b = mobi_enc_block_result(lastpos >= 0, clamp != 0, range, vlc, sad_rec, sad_pred);
   if (!b.coded)
     for (int i = 0; i < 64; i++) { rec[i] = pred[i]; lev[i] = 0; }
   return b;
@@ -245,8 +260,8 @@ static inline void mobi_enc_macroblock(const MobiEncConst *K, int q, int W, int 
       MobiEncBlock tres[4];
       int64_t J = 0;
       for (int k = 0; k < nb; k++) {
-        const int plane = chroma ? 1 + k : 0, pitch = chroma ? W / 2 : W;
-        const int x0 = chroma ? mbx * 8 : mbx * 16 + (k & 1) * 8, y0 = chroma ? mby * 8 : mby * 16 + (k >> 1) * 8;
+        const MobiEncBlockAt at = mobi_enc_block_at(chroma, k, mbx, mby, W);
+        const int plane = at.plane, pitch = at.pitch, x0 = at.x0, y0 = at.y0;
         // neighbours: earlier blocks of this trial first, the picture's reconstruction elsewhere
         auto nbr = [&](int dy, int dx) -> int {
           const int y = y0 + dy, x = x0 + dx;
@@ -276,10 +291,10 @@ static inline void mobi_enc_macroblock(const MobiEncConst *K, int q, int W, int 
     }
     (chroma ? out->chroma_mode : out->luma_mode) = (uint8_t)best;
     for (int k = 0; k < nb; k++) {
-      const int a = chroma ? 4 + k : k, plane = chroma ? 1 + k : 0, pitch = chroma ? W / 2 : W;
-      const int x0 = chroma ? mbx * 8 : mbx * 16 + (k & 1) * 8, y0 = chroma ? mby * 8 : mby * 16 + (k >> 1) * 8;
+      const int a = chroma ? 4 + k : k;
+      const MobiEncBlockAt at = mobi_enc_block_at(chroma, k, mbx, mby, W);
       for (int y = 0; y < 8; y++)
-        for (int x = 0; x < 8; x++) rec[plane][(size_t)(y0 + y) * pitch + x0 + x] = (uint8_t)brec[k][y * 8 + x];
+        for (int x = 0; x < 8; x++) rec[at.plane][(size_t)(at.y0 + y) * at.pitch + at.x0 + x] = (uint8_t)brec[k][y * 8 + x];
       memcpy(out->lev[a], blev[k], sizeof blev[k]);
       out->cbp |= (uint8_t)(bres[k].coded << a);
       out->bits += (uint32_t)bres[k].bits;
@@ -289,22 +304,13 @@ static inline void mobi_enc_macroblock(const MobiEncConst *K, int q, int W, int 
       st->range += bres[k].range;
     }
   }
-  // 0, ue(cbp), two 3-bit modes
-  const uint32_t v = K->inv_cbp[out->cbp] + 1u;
-  int z = 0;
-  while ((v >> (z + 1)) != 0) z++;
-  out->bits += 1 + (2 * z + 1) + 6;
+  out->bits += mobi_enc_mb_header_bits(K, out->cbp);
 }
 
 // the constants from the decoder's tables
 static inline void mobi_enc_build_const(MobiEncConst *K) {
   memset(K, 0, sizeof *K);
-  for (int q = 0; q < MOBI_TC_NQ; q++) {
-    mobi_tc_qtable(q, 8, K->q8[q]);
-    for (int i = 0; i < 64; i++) K->rq8[q][i] = 1.0f / (float)K->q8[q][i];
-  }
-  memcpy(K->zz8, mobi_zz8, sizeof K->zz8);
-  mobi_tc_build_lut(K->lut);
+  mobi_tc_build_const(K);
   int16_t ref[32 * 64 * 2];
   mobi_tc_build_ref(ref);
   // the code word of table index j (the reader's 12-bit window) with length nb, sign included: the window's top nb bits, where the first j

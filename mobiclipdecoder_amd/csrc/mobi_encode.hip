@@ -2,7 +2,7 @@
 //
 // Stage 1, decide and reconstruct.  One wave = one macroblock.  Its 64 lanes are eight groups of eight: groups 0..2 try the luma modes
 // 0, 1, 3 side by side, groups 3..5 the chroma modes, groups 6 and 7 ride along.  A group runs its trial's blocks in sequence (four luma
-// blocks; U, then V), one lane = one row of the block, the arithmetic and its lane mapping those of mobi_txcode.hip.  Every trial keeps
+// blocks; U, then V), one lane = one row of the block: the block coder of mobi_txcode_lanes.h at wave scope.  Every trial keeps
 // its own reconstruction in an LDS patch whose border row and column come from the picture's reconstruction, so a block predicts from
 // the earlier blocks of the same trial.  The two winners' patches and levels go to memory; lane 0 adds the macroblock to the statistics.
 // Macroblock (x, y) needs (x - 1, y) and (x, y - 1): anti-diagonals are independent, and the order between them is kept ONLY by kernel
@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mobi_encode.h"
+#include "mobi_txcode_lanes.h"
 
 namespace {
 
@@ -28,32 +29,14 @@ struct WaveLds {
   int16_t lev[6][4][64];    // every trial's levels in scan order
 };
 
-// the lanes of one wave exchange data through LDS: LDS operations of a wave complete in order, the fences keep the compiler from moving them
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ uint32_t sum8(uint32_t v) {
-#pragma unroll
-  for (int m = 1; m < 8; m <<= 1) v += (uint32_t)__shfl_xor((int)v, m, 8);
-  return v;
-}
-__device__ __forceinline__ uint32_t or8(uint32_t v) {
-#pragma unroll
-  for (int m = 1; m < 8; m <<= 1) v |= (uint32_t)__shfl_xor((int)v, m, 8);
-  return v;
-}
 __device__ __forceinline__ int64_t shfl64(int64_t v, int src) {
   const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, src), hi = (uint32_t)__shfl((int)(uint32_t)((uint64_t)v >> 32), src);
   return (int64_t)((uint64_t)hi << 32 | lo);
 }
-__device__ __forceinline__ int ue_bits(uint32_t code) {
-  return 2 * (31 - __builtin_clz(code + 1u)) + 1;
-}
 
 __device__ __forceinline__ void encode_mb(const MobiEncArgs &A, int pic, int mbx, int mby, WaveLds &L, const uint8_t *lut) {
   const MobiEncConst *K = A.k;
+  const MobiSyncWave wave_sync; // a wave owns its WaveLds: no workgroup barrier inside a macroblock
   const int lane = threadIdx.x & 63, g = lane >> 3, r = lane & 7;
   const bool chroma = g >= 3 && g < 6;
   const int gp = g < 6 ? g : 0;                   // the patch a group works in (6 and 7 shadow group 0 and keep nothing)
@@ -63,11 +46,8 @@ __device__ __forceinline__ void encode_mb(const MobiEncArgs &A, int pic, int mbx
   const uint8_t *src = A.src + (size_t)pic * A.src_pitch;
   uint8_t *rec = A.rec + (size_t)pic * frame;
   const int64_t lam = mobi_enc_lambda(q);
-  const int32_t *Qrow = K->q8[q] + r * 8;
-  const float *RQrow = K->rq8[q] + r * 8;
   int zi[8];
-#pragma unroll
-  for (int j = 0; j < 8; j++) zi[j] = K->zz8[r * 8 + j];
+  mobi_lanes_scan<8>(K, r, zi);
 
   // the luma border: 16 samples above, 16 to the left (read only where they exist)
   if (!chroma) {
@@ -84,21 +64,17 @@ __device__ __forceinline__ void encode_mb(const MobiEncArgs &A, int pic, int mbx
   for (int it = 0; it < 4; it++) {
     const bool live = g < 6 && (!chroma || it < 2);
     const int cp = it < 2 ? it : 1; // the chroma plane of this round
-    const int pitch = chroma ? W / 2 : W;
-    const size_t plane = chroma ? ysz + (size_t)cp * (ysz / 4) : 0;
-    const int x0 = chroma ? mbx * 8 : mbx * 16 + (it & 1) * 8, y0 = chroma ? mby * 8 : mby * 16 + (it >> 1) * 8;
+    const MobiEncBlockAt at = mobi_enc_block_at(chroma, chroma ? cp : it, mbx, mby, W);
+    const int pitch = at.pitch, x0 = at.x0, y0 = at.y0;
+    const size_t plane = at.plane ? ysz + (size_t)(at.plane - 1) * (ysz / 4) : 0;
     const int oy = chroma ? 1 + 9 * cp : 1 + 8 * (it >> 1), ox = chroma ? 1 : 1 + 8 * (it & 1);
     if (chroma && it < 2) { // this plane's border
       L.patch[gp][oy - 1][1 + r] = y0 > 0 ? rec[plane + (size_t)(y0 - 1) * pitch + x0 + r] : 0;
       L.patch[gp][oy + r][0] = x0 > 0 ? rec[plane + (size_t)(y0 + r) * pitch + x0 - 1] : 0;
     }
     wave_sync();
-    int s[8], p[8], x[8], o[8], d[8];
-    {
-      const uint2 v = *(const uint2 *)(src + plane + (size_t)(y0 + r) * pitch + x0);
-#pragma unroll
-      for (int k = 0; k < 4; k++) { s[k] = (v.x >> (8 * k)) & 0xFF; s[k + 4] = (v.y >> (8 * k)) & 0xFF; }
-    }
+    int s[8], p[8], x[8], d[8];
+    Row<8>::unpack(*(const uint2 *)(src + plane + (size_t)(y0 + r) * pitch + x0), s);
     // the decoder's predictor on the trial's own reconstruction
     auto nb = [&](int dy, int dx) -> int { return L.patch[gp][oy + dy][ox + dx]; };
     if (mode == 3) {
@@ -109,71 +85,15 @@ __device__ __forceinline__ void encode_mb(const MobiEncArgs &A, int pic, int mbx
 #pragma unroll
       for (int k = 0; k < 8; k++) p[k] = mobi_pred_px(mode, 8, r, k, 1, 1, nb);
     }
-    // forward transform, quantise, first inverse pass (mobi_txcode.hip's steps)
+    // the block coder's steps (mobi_txcode_lanes.h) at wave scope; every group runs them, the idle ones too: the shuffles stay convergent
 #pragma unroll
-    for (int k = 0; k < 8; k++) x[k] = (s[k] - p[k]) * 64;
-    mobi_dct8_pass(x, o);
-#pragma unroll
-    for (int k = 0; k < 8; k++) L.tile[g][r][k] = o[k];
-    wave_sync();
-#pragma unroll
-    for (int j = 0; j < 8; j++) x[j] = L.tile[g][j][r];
-    mobi_dct8_pass(x, d);
-    wave_sync(); // the column reads are done before the tile is written again
-    uint32_t big = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-      const int Q = Qrow[k], lev = mobi_tc_quant(d[k], Q, RQrow[k]);
-      L.nat[g][r * 8 + k] = (int16_t)lev;
-      big |= (uint32_t)(lev > MOBI_ENC_MAX_LEVEL || lev < -MOBI_ENC_MAX_LEVEL);
-      x[k] = lev * Q;
-    }
-    if (r == 0) x[0] += 0x20;
-    mobi_idct8_pass(x, o);
-#pragma unroll
-    for (int k = 0; k < 8; k++) L.tile[g][k][r] = o[k];
-    wave_sync();
-    // levels in scan order, run / last from the block's nonzero mask, bit cost from the table
-    int lv[8];
-    uint32_t nzl = 0;
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-      lv[j] = L.nat[g][zi[j]];
-      nzl |= (uint32_t)(lv[j] != 0) << j;
-    }
-    const uint32_t lo = or8(r < 4 ? nzl << (8 * r) : 0u), hi = or8(r >= 4 ? nzl << (8 * (r - 4)) : 0u);
-    const uint64_t mask = (uint64_t)hi << 32 | lo;
-    uint32_t bits = 0;
-    if (mask) {
-      const int last = 63 - __builtin_clzll(mask);
-#pragma unroll
-      for (int j = 0; j < 8; j++) {
-        const int k = r * 8 + j;
-        const uint64_t below = mask & ((1ull << k) - 1ull);
-        const int prev = below ? 63 - __builtin_clzll(below) : -1;
-        const int v = lv[j] < 0 ? -lv[j] : lv[j];
-        const int c = v < MOBI_TC_LUT_V ? (int)lut[mobi_tc_lut_index(v, k - prev - 1, k == last)] : MOBI_TC_ESCAPE_BITS;
-        bits += lv[j] ? (uint32_t)c : 0u;
-      }
-    }
-    // second inverse pass = pixel row r, the clamp table, both SADs
-#pragma unroll
-    for (int j = 0; j < 8; j++) x[j] = L.tile[g][r][j];
-    mobi_idct8_pass(x, o);
-    uint32_t sad = 0, sadp = 0, bad = 0;
-    int px[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-      const int t = 0x40 + p[k] + (o[k] >> 6);
-      bad += (uint32_t)t >= 384u;
-      px[k] = t < 0x40 ? 0 : t > 0x40 + 255 ? 255 : t - 0x40;
-      sad += (uint32_t)__builtin_abs(s[k] - px[k]);
-      sadp += (uint32_t)__builtin_abs(s[k] - p[k]);
-    }
-    // sad <= 64 * 255 < 2^14, bits <= 64 * 28 < 2^11, faults <= 64 < 2^7; the prediction's sad with the level-range flag above it
-    const uint32_t sum = sum8(sad | bits << 14 | bad << 25), sum2 = sum8(sadp | big << 14);
-    const MobiEncBlock b = mobi_enc_block_result(mask != 0, (sum >> 25) != 0, (sum2 >> 14) != 0, (int)((sum >> 14) & 0x7FF), (int)(sum & 0x3FFF),
-                                                 (int)(sum2 & 0x3FFF));
+    for (int k = 0; k < 8; k++) x[k] = s[k] - p[k];
+    mobi_lanes_forward<8>(x, r, L.tile[g], wave_sync, d);
+    MobiLaneCoded<8> c;
+    mobi_lanes_code<8>(K, lut, q, r, zi, s, p, d, L.tile[g], L.nat[g], wave_sync, c);
+    // the prediction's sad with the level-range flag above it
+    const uint32_t sum2 = mobi_lanes_sum<8>(c.sad_pred | c.range << 14);
+    const MobiEncBlock b = mobi_enc_block_result(c.mask != 0, c.clamp(), (sum2 >> 14) != 0, (int)c.bits(), (int)c.sad(), (int)(sum2 & 0x3FFF));
     if (live) {
       J += mobi_enc_cost(lam, b);
       coded_m |= (uint32_t)b.coded << it;
@@ -182,9 +102,9 @@ __device__ __forceinline__ void encode_mb(const MobiEncArgs &A, int pic, int mbx
       clamp_t += b.clamp;
       range_t += b.range;
 #pragma unroll
-      for (int k = 0; k < 8; k++) L.patch[g][oy + r][ox + k] = (uint8_t)(b.coded ? px[k] : p[k]);
+      for (int k = 0; k < 8; k++) L.patch[g][oy + r][ox + k] = (uint8_t)(b.coded ? c.px[k] : p[k]);
 #pragma unroll
-      for (int j = 0; j < 8; j++) L.lev[g][it][r * 8 + j] = (int16_t)(b.coded ? lv[j] : 0);
+      for (int j = 0; j < 8; j++) L.lev[g][it][r * 8 + j] = (int16_t)(b.coded ? c.lv[j] : 0);
     }
   }
   wave_sync();
@@ -224,7 +144,7 @@ __device__ __forceinline__ void encode_mb(const MobiEncArgs &A, int pic, int mbx
   const uint32_t rl = (uint32_t)__shfl((int)range_t, gl * 8), rc = (uint32_t)__shfl((int)range_t, gc * 8);
   if (lane == 0) {
     const uint32_t cbp = cl | cc << 4;
-    mb->bits = 1u + (uint32_t)ue_bits(K->inv_cbp[cbp]) + 6u + bl + bc;
+    mb->bits = mobi_enc_mb_header_bits(K, cbp) + bl + bc;
     mb->luma_mode = (uint8_t)mobi_enc_mode(gl);
     mb->chroma_mode = (uint8_t)mobi_enc_mode(gc - 3);
     mb->cbp = (uint8_t)cbp;
@@ -242,16 +162,11 @@ __device__ __forceinline__ void encode_mb(const MobiEncArgs &A, int pic, int mbx
   wave_sync(); // the patches and levels are read before the wave's next macroblock writes them
 }
 
-__device__ __forceinline__ const uint8_t *stage_lut(const MobiEncArgs &A, uint32_t *lut32) {
-  for (int i = threadIdx.x; i < MOBI_TC_LUT_BYTES / 4; i += WAVES * 64) lut32[i] = ((const uint32_t *)A.k->lut)[i];
+// the cost table in LDS, staged by the whole workgroup
+__device__ __forceinline__ const uint8_t *stage_lut(const MobiEncArgs &A, uint32_t (&lut32)[MOBI_TC_LUT_BYTES / 4]) {
+  const uint8_t *lut = mobi_lanes_stage_lut<WAVES * 64>(A.k, lut32);
   __syncthreads();
-  return (const uint8_t *)lut32;
-}
-// macroblocks of diagonal d: x from max(0, d - mbh + 1) to min(d, mbw - 1), y = d - x
-__device__ __forceinline__ void diag_range(const MobiEncArgs &A, int d, int &x_lo, int &count) {
-  x_lo = d - A.mbh + 1 > 0 ? d - A.mbh + 1 : 0;
-  const int x_hi = d < A.mbw - 1 ? d : A.mbw - 1;
-  count = x_hi - x_lo + 1;
+  return lut;
 }
 
 } // namespace
@@ -265,7 +180,7 @@ extern "C" __global__ __launch_bounds__(WAVES * 64) void mobi_enc_decide_loop(Mo
   const int wave = threadIdx.x >> 6, pic = blockIdx.x;
   for (int d = 0; d < A.mbw + A.mbh - 1; d++) {
     int x_lo, count;
-    diag_range(A, d, x_lo, count);
+    mobi_enc_diag_range(A.mbw, A.mbh, d, &x_lo, &count);
     for (int i = wave; i < count; i += WAVES) encode_mb(A, pic, x_lo + i, d - (x_lo + i), lds[wave], lut);
     __syncthreads(); // this diagonal's reconstruction is written before the next one reads it (every wave arrives, whatever it encoded)
   }
@@ -278,7 +193,7 @@ extern "C" __global__ __launch_bounds__(WAVES * 64) void mobi_enc_decide_diag(Mo
   const uint8_t *lut = stage_lut(A, lut32);
   const int wave = threadIdx.x >> 6, pic = blockIdx.y;
   int x_lo, count;
-  diag_range(A, d, x_lo, count);
+  mobi_enc_diag_range(A.mbw, A.mbh, d, &x_lo, &count);
   const int i = blockIdx.x * WAVES + wave;
   if (i < count) encode_mb(A, pic, x_lo + i, d - (x_lo + i), lds[wave], lut);
 }
@@ -378,8 +293,9 @@ extern "C" int mobi_launch_encode(const MobiEncArgs *a, int stages, int loop_sha
     else
 #endif
       for (int d = 0; d < a->mbw + a->mbh - 1; d++) {
-        const int lo = d - a->mbh + 1 > 0 ? d - a->mbh + 1 : 0, hi = d < a->mbw - 1 ? d : a->mbw - 1;
-        hipLaunchKernelGGL(mobi_enc_decide_diag, dim3((hi - lo + 1 + WAVES - 1) / WAVES, a->n), dim3(WAVES * 64), 0, s, *a, d);
+        int x_lo, count;
+        mobi_enc_diag_range(a->mbw, a->mbh, d, &x_lo, &count);
+        hipLaunchKernelGGL(mobi_enc_decide_diag, dim3((count + WAVES - 1) / WAVES, a->n), dim3(WAVES * 64), 0, s, *a, d);
       }
   }
   if (stages & 2) {

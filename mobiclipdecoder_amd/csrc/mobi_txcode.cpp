@@ -21,15 +21,7 @@ MobiTcConst *device_const(int device) {
   std::lock_guard<std::mutex> l(g_const_mutex);
   if ((size_t)device < g_const.size() && g_const[device]) return g_const[device];
   MobiTcConst h;
-  for (int q = 0; q < MOBI_TC_NQ; q++) {
-    mobi_tc_qtable(q, 8, h.q8[q]);
-    mobi_tc_qtable(q, 4, h.q4[q]);
-    for (int i = 0; i < 64; i++) h.rq8[q][i] = 1.0f / (float)h.q8[q][i];
-    for (int i = 0; i < 16; i++) h.rq4[q][i] = 1.0f / (float)h.q4[q][i];
-  }
-  memcpy(h.zz8, mobi_zz8, sizeof h.zz8);
-  memcpy(h.zz4, mobi_zz4, sizeof h.zz4);
-  mobi_tc_build_lut(h.lut);
+  mobi_tc_build_const(&h);
   MobiTcConst *d = nullptr;
   if (hipMalloc((void **)&d, sizeof h) != hipSuccess) return nullptr;
   if (hipMemcpy(d, &h, sizeof h, hipMemcpyHostToDevice) != hipSuccess) {

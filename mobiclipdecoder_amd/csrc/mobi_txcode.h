@@ -3,7 +3,7 @@
 //
 //   forward transforms   MobiEncoder.DCT64 / DCT16 (Encoder/MobiEncoder.cs:962-1010, 1146-1178): one pass over a row or a column
 //                        (mobi_forward_dct and mobi_transform_code share them)
-//   inverse transforms   MobiEncoder.IDCT64 / IDCT16 (:1012-1144, 1180-1240): the 8- and 4-point integer butterflies, in int32
+//   inverse transforms   MobiEncoder.IDCT64 / IDCT16 (:1012-1144, 1180-1240): the decoder's butterflies and clamp (mobi_recon_math.h)
 //   quantise             (int)Math.Round(dct / QTable) (Encoder/MacroBlock.cs:591-595, 612-616): round half to even of an exact
 //                        integer quotient (why that is what the reference computes: DESIGN.md, "Transform coding")
 //   bit cost             CalculateNrBitsDCT(EncodeDct, 0) (MobiEncoder.cs:767-858) of one coefficient, and the [2][64][44] table of it
@@ -12,6 +12,8 @@
 #ifndef MOBI_TXCODE_H
 #define MOBI_TXCODE_H
 #include <stdint.h>
+
+#include "mobi_recon_math.h"
 
 #if defined(__HIPCC__)
 #define MOBI_TC_FN static __host__ __device__ __forceinline__
@@ -22,7 +24,8 @@
 enum { MOBI_TC_NQ = 54,                 // quantisers 0..53
        MOBI_TC_LUT_V = 44,              // |level| >= 44 always costs 28 bits: max mobi_vx2table0_b[0..127] = 12, so v - B <= 31 needs v <= 43
        MOBI_TC_LUT_BYTES = 2 * 64 * MOBI_TC_LUT_V,
-       MOBI_TC_ESCAPE_BITS = 28 };      // the fallback of :847-853: 7 + 1 + 1 + 1 + 6 + 12
+       MOBI_TC_ESCAPE_BITS = 28,        // the fallback of :847-853: 7 + 1 + 1 + 1 + 6 + 12
+       MOBI_TC_MAX_LEVEL = 2047 };      // what those 12 bits hold, two's complement
 
 // ---- forward transforms: x = samples 0..7 (0..3) of one row or column, already x64 in the first pass ----
 MOBI_TC_FN void mobi_dct8_pass(const int (&x)[8], int (&o)[8]) {
@@ -44,27 +47,10 @@ MOBI_TC_FN void mobi_dct4_pass(const int (&x)[4], int (&o)[4]) {
   o[3] = (-t + 2 * s - 2 * r + q) / 5;
 }
 
-// ---- inverse transforms, one 1-D pass.  The reference runs it over the rows of the coefficients (the DC row with + 0x20, :1024),
-// stores the results transposed, runs it again over the rows of that and adds (result >> 6) to the prediction (:1119-1126).
-// Even half from x0, x2, x4, x6, odd half from x1, x3, x5, x7 (shifts are arithmetic), then o[k] / o[7 - k] = even +/- odd. ----
-MOBI_TC_FN void mobi_idct8_pass(const int (&x)[8], int (&o)[8]) {
-  const int s04 = x[0] + x[4], d04 = x[0] - x[4];
-  const int h26 = x[2] + (x[6] >> 1), l26 = (x[2] >> 1) - x[6];
-  const int e0 = s04 + h26, e1 = d04 + l26, e2 = d04 - l26, e3 = s04 - h26;
-  const int a = x[1] + x[7] - x[3] - (x[3] >> 1);
-  const int b = x[5] - x[1] + x[7] + (x[5] >> 1);
-  const int c = x[5] - x[3] - x[7] - (x[7] >> 1);
-  const int d = x[1] + x[3] + x[5] + (x[1] >> 1);
-  const int f0 = d - (c >> 2), f1 = (a >> 2) - b, f2 = a + (b >> 2), f3 = c + (d >> 2);
-  o[0] = e0 + f0; o[7] = e0 - f0;
-  o[1] = e1 + f1; o[6] = e1 - f1;
-  o[2] = e2 + f2; o[5] = e2 - f2;
-  o[3] = e3 + f3; o[4] = e3 - f3;
-}
-MOBI_TC_FN void mobi_idct4_pass(const int (&x)[4], int (&o)[4]) {
-  const int s02 = x[0] + x[2], d02 = x[0] - x[2], h = x[1] + (x[3] >> 1), l = (x[1] >> 1) - x[3];
-  o[0] = s02 + h; o[1] = d02 + l; o[2] = d02 - l; o[3] = s02 - h;
-}
+// ---- inverse transforms, one 1-D pass: mobi_bfly8 / mobi_bfly4 of mobi_recon_math.h.  MobiEncoder.IDCT64 / IDCT16 are the decoder's
+// butterflies term for term (one was written from the reference's encoder, the other from its decoder).  The reference runs the pass
+// over the rows of the coefficients (the DC row with + 0x20, :1024), stores the results transposed, runs it again over the rows of that
+// and adds (result >> 6) to the prediction (:1119-1126) through the clamp table: mobi_add_clamp. ----
 
 // ---- quantise: round_half_even(d / Q), Q an integer in [4, 7424].  rq is any float within a few ulps of 1 / Q (the host table holds
 // 1.0f / Q): |d| * rq is then within 2^-10 of |d| / Q for |d| < 2^15, so its truncation is floor(|d| / Q) or one off, and the remainder
@@ -122,6 +108,8 @@ struct MobiTcArgs {
 };
 
 #if !defined(__HIP_DEVICE_COMPILE__)
+#include <string.h>
+
 #include "mobi_tables.h"
 
 // VxTable0_A_Ref[v][skip][last] (MobiConst.cs, 32 x 64 x 2): the first j whose code word in mobi_vx2table0_a says value v, skip, last
@@ -145,6 +133,18 @@ static inline void mobi_tc_build_lut(uint8_t *lut) {
 static inline void mobi_tc_qtable(int q, int n, int32_t *Q) {
   const int sh = mobi_qdiv6[q] + (n == 4 ? 8 : 6), m = mobi_qmod6[q];
   for (int k = 0; k < n * n; k++) Q[n == 4 ? mobi_zz4[k] : mobi_zz8[k]] = (n == 4 ? mobi_dq4[m * 16 + k] : mobi_dq8[m * 64 + k]) << sh >> 8;
+}
+// the constants from the decoder's tables
+static inline void mobi_tc_build_const(MobiTcConst *K) {
+  for (int q = 0; q < MOBI_TC_NQ; q++) {
+    mobi_tc_qtable(q, 8, K->q8[q]);
+    mobi_tc_qtable(q, 4, K->q4[q]);
+    for (int i = 0; i < 64; i++) K->rq8[q][i] = 1.0f / (float)K->q8[q][i];
+    for (int i = 0; i < 16; i++) K->rq4[q][i] = 1.0f / (float)K->q4[q][i];
+  }
+  memcpy(K->zz8, mobi_zz8, sizeof K->zz8);
+  memcpy(K->zz4, mobi_zz4, sizeof K->zz4);
+  mobi_tc_build_lut(K->lut);
 }
 #endif
 #endif
