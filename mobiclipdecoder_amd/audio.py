@@ -6,7 +6,8 @@ import ctypes as C
 
 import numpy as np
 
-from .decoder import MobiclipError, _as_u8, _check_one_hip_runtime, default_device, error_string, load_library
+from .binding import Handle, as_u8, bind
+from .decoder import MobiclipError, check_out, check_rc, check_stream, default_device, dtype_name, error_string, load_library, stream_and_out, tensor_bytes
 
 MOBI_E_INDEX = -1  # include/mobiclip_hip.h: where the reference would throw
 MOBI_E_UNSUPPORTED = -6
@@ -47,18 +48,10 @@ _SX_SIGS = {
 }
 SX_PACKET_SAMPLES = 128
 SX_CODEBOOK_BYTES = 0xC34  # MOBI_MODS_CODEBOOK_BYTES
-_BOUND = False
 
 
 def _lib():
-    global _BOUND
-    lib = load_library()
-    if not _BOUND:
-        for name, (res, args) in list(_SIGS.items()) + list(_SX_SIGS.items()):
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
-        _BOUND = True
-    return lib
+    return bind(load_library(), _SIGS, _SX_SIGS)
 
 
 def _codec(codec, framing):
@@ -98,7 +91,7 @@ def plan(framing, codec, n_channels, data, offset=0, n_packets=0, cursor=0, fres
     """mobi_audio_plan: the blocks one frame of one stream yields, by the reference's framing rules.  Needs no device.
     -> (rc, blocks as a list of (offset, channel, header, header_offset), samples per channel as an int32 array, the cursor afterwards)."""
     fr, name, nc = _framing_codec_channels(framing, codec, n_channels)
-    buf = _as_u8(data)
+    buf = as_u8(data)
     lib = _lib()
     fresh_a = None if fresh is None else np.ascontiguousarray(np.asarray(fresh, np.uint8))
     if fresh_a is not None and fresh_a.shape != (nc,):
@@ -119,7 +112,7 @@ def sx_plan(n_channels, data, offset=0, n_packets=0, cursor=0):
     """mobi_sx_plan: the Sx packets one Mods frame of one stream yields.  Needs no device.
     -> (rc, packets as a list of (offset, channel), samples per channel as an int32 array, the cursor afterwards)."""
     nc = _framing_codec_channels("mods", "sx", n_channels)[2]
-    buf = _as_u8(data)
+    buf = as_u8(data)
     lib = _lib()
     ptr = buf.ctypes.data if buf.size else None
     cur, n, ns = C.c_int(int(cursor)), C.c_size_t(), np.zeros(nc, np.int32)
@@ -144,7 +137,7 @@ def _codebook_rows(codebooks, n_rows, n_channels, what):
     for r in rows:
         for b in r:
             try:
-                a = _as_u8(b)
+                a = as_u8(b)
             except (TypeError, ValueError):
                 raise ValueError("a codebook must be a byte buffer") from None
             if a.size != SX_CODEBOOK_BYTES:
@@ -153,11 +146,12 @@ def _codebook_rows(codebooks, n_rows, n_channels, what):
     return flat
 
 
-class MobiclipAudio:
+class MobiclipAudio(Handle):
     """n_streams decoders of n_channels channels each, decoded side by side on one GPU: one lane per (stream, channel), the decoder states
     in device memory.  codec: "fastaudio", "ima", "pcm16", or the container's number (Moflex codec_id / Mods audio_codec); framing:
     "moflex" (frames of MoLiveDemux with chunk_id 2) or "mods" (ModsDemuxer.ReadFrame packets).  "sx" (Mods audio_codec 1) needs
     codebooks: n_streams sequences of n_channels buffers of 0xC34 bytes (per stream: ModsDemuxer.AudioCodebooks)."""
+    _destroy = "mobi_audio_destroy"
 
     def __init__(self, n_streams, n_channels, codec, framing, device=None, codebooks=None):
         self.framing = framing
@@ -202,13 +196,9 @@ class MobiclipAudio:
                 raise ValueError("new codebooks set the cursor to 0: keep_cursor does not go with codebooks")
             books = _codebook_rows(codebooks, len(idx), self.n_channels, "len(streams)")
             ptrs = (C.c_void_p * max(1, len(books)))(*[b.ctypes.data for b in books])
-            rc = self._lib.mobi_sx_reset(self._h, arr, len(idx), ptrs)
-            if rc != 0:
-                raise MobiclipError(error_string(rc))
+            check_rc(self._lib.mobi_sx_reset(self._h, arr, len(idx), ptrs))
             return
-        rc = self._lib.mobi_audio_reset(self._h, arr, len(idx), int(bool(keep_cursor)))
-        if rc != 0:
-            raise MobiclipError(error_string(rc))
+        check_rc(self._lib.mobi_audio_reset(self._h, arr, len(idx), int(bool(keep_cursor))))
 
     def decode(self, frames, offsets=None, n_packets=None, dtype=None, layout="planar", out=None, max_samples=None, stream=None):
         """One frame per stream -> (tensor, n_samples, rc).
@@ -227,8 +217,7 @@ class MobiclipAudio:
         S, nc = self.n_streams, self.n_channels
         if dtype is None:
             dtype = torch.int16
-        if not isinstance(dtype, torch.dtype) or str(dtype).split(".")[-1] not in DTYPES:
-            raise ValueError(f"dtype must be torch.int16 or torch.float32, not {dtype!r}")
+        dname = dtype_name(dtype, DTYPES, f"dtype must be torch.int16 or torch.float32, not {dtype!r}")
         if layout not in LAYOUTS:
             raise ValueError(f"layout must be 'planar' or 'interleaved', not {layout!r}")
         try:
@@ -238,7 +227,7 @@ class MobiclipAudio:
         if len(frames) != S:
             raise ValueError(f"frames must hold {S} buffers, not {len(frames)}")
         try:
-            bufs = [_as_u8(f) for f in frames]
+            bufs = [as_u8(f) for f in frames]
         except (TypeError, ValueError):
             raise ValueError("frames must be byte buffers or None") from None
         mods = self.framing == "mods"
@@ -254,8 +243,7 @@ class MobiclipAudio:
             if len(offs) != S or len(pk) != S or any(v < 0 for v in offs) or any(v < 0 or v >= 1 << 32 for v in pk):
                 raise ValueError(f"offsets and n_packets must hold {S} non-negative ints each")
         dev = torch.device("cuda", self.device)
-        if stream is not None and (not isinstance(stream, torch.cuda.Stream) or stream.device != dev):
-            raise ValueError(f"stream must be a torch.cuda.Stream of {dev}, not {stream!r}")
+        check_stream(stream, dev)
         if max_samples is not None and (isinstance(max_samples, bool) or not isinstance(max_samples, (int, np.integer))
                                         or not 0 < int(max_samples) < 1 << 31):
             raise ValueError(f"max_samples must be a positive int below 2**31, not {max_samples!r}")
@@ -270,23 +258,15 @@ class MobiclipAudio:
             max_samples = max(1, self._longest_row(bufs, pk))
         max_samples = int(max_samples)
         shape = (S, nc, max_samples) if layout == "planar" else (S, max_samples, nc)
-        if out is not None and (out.device != dev or out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous()):
-            raise ValueError(f"out must be a contiguous {dtype} tensor of shape {shape} on {dev}")
-        _check_one_hip_runtime()
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        if out is None:
-            with torch.cuda.stream(stream):
-                out = torch.empty(shape, dtype=dtype, device=dev)
+        check_out(out, dev, dtype, shape, aligned=False)
+        stream, out = stream_and_out(stream, out, dev, dtype, shape)
         ptrs = (C.c_void_p * S)(*[b.ctypes.data if b.size else None for b in bufs])
         lens = (C.c_size_t * S)(*[b.size for b in bufs])
         n_samples, rc = np.zeros((S, nc), np.int32), np.zeros(S, np.int32)
-        ret = self._lib.mobi_audio_decode(self._h, stream.cuda_stream, ptrs, lens, (C.c_size_t * S)(*offs) if mods else None,
-                                          (C.c_uint32 * S)(*pk) if mods else None, DTYPES[str(dtype).split(".")[-1]], LAYOUTS[layout],
-                                          out.data_ptr(), out.numel() * out.element_size(), max_samples,
-                                          n_samples.ctypes.data_as(C.POINTER(C.c_int32)), rc.ctypes.data_as(C.POINTER(C.c_int)))
-        if ret != 0:
-            raise MobiclipError(error_string(ret))
+        check_rc(self._lib.mobi_audio_decode(self._h, stream.cuda_stream, ptrs, lens, (C.c_size_t * S)(*offs) if mods else None,
+                                             (C.c_uint32 * S)(*pk) if mods else None, DTYPES[dname], LAYOUTS[layout],
+                                             out.data_ptr(), tensor_bytes(out), max_samples,
+                                             n_samples.ctypes.data_as(C.POINTER(C.c_int32)), rc.ctypes.data_as(C.POINTER(C.c_int))))
         return out, n_samples, rc
 
     def _longest_row(self, bufs, n_packets):
@@ -302,14 +282,3 @@ class MobiclipAudio:
                                                     0, C.byref(n), ns.ctypes.data_as(C.POINTER(C.c_int32))) == 0:
                 longest = max(longest, int(ns.max()))
         return longest
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.mobi_audio_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

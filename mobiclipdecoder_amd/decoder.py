@@ -19,6 +19,8 @@ import weakref
 
 import numpy as np
 
+from .binding import Handle, as_u8, bind, byte_arrays
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 
@@ -128,12 +130,7 @@ LIB_PATH = os.environ.get("MOBI_LIB") or os.path.join(_HERE, "libmobiclip_hip.so
 
 def bind_library(path):
     """dlopen one build of the library and bind every entry point of include/mobiclip_hip.h"""
-    lib = C.CDLL(path)
-    for name, (res, args) in _SIGS.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    return lib
+    return bind(C.CDLL(path), _SIGS)
 
 
 def load_library():
@@ -158,16 +155,12 @@ def error_string(rc):
     return load_library().mobi_error_string(rc).decode()
 
 
-_NO_DATA = np.zeros(0, np.uint8)
-
-
-def _as_u8(data):
-    if data is None:  # an idle slot (MobiclipBatch.set_idle): a NULL pointer for the library
-        return _NO_DATA
-    a = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data
-    if a.dtype != np.uint8:
-        a = a.view(np.uint8)
-    return np.ascontiguousarray(a)
+def check_rc(rc, counts=False, null_ok=False):
+    """The rc of a library call, handed back; MobiclipError with the library's text for it when it is not 0 -- when it is negative, for an
+    entry that returns a count (counts) -- and not the MOBI_E_NULLREF of a ring slot never filled, where that is an answer (null_ok)."""
+    if (rc < 0 if counts else rc != 0) and not (null_ok and rc == -2):
+        raise MobiclipError(error_string(rc))
+    return rc
 
 
 class _PlaneRing:
@@ -248,20 +241,17 @@ class ExportHandle:
     def done(self):
         if not self._batch._h:
             return True  # (mobi_batch_destroy waited for it)
-        r = self._batch._lib.mobi_batch_export_query(self._batch._h, self.ticket)
-        if r < 0:
-            raise MobiclipError(error_string(r))
-        return r == 1
+        return check_rc(self._batch._lib.mobi_batch_export_query(self._batch._h, self.ticket), counts=True) == 1
 
     def wait(self):
         if self._batch._h:
-            r = self._batch._lib.mobi_batch_export_wait(self._batch._h, self.ticket)
-            if r != 0:
-                raise MobiclipError(error_string(r))
+            check_rc(self._batch._lib.mobi_batch_export_wait(self._batch._h, self.ticket))
         return self.out
 
 
-class MobiclipDecoder:
+class MobiclipDecoder(Handle):
+    _destroy = "mobi_destroy"
+
     def __init__(self, Width, Height, Version, device=None):
         self._lib = load_library()
         self.Width, self.Height, self.Version = int(Width), int(Height), MobiclipVersion(Version)
@@ -296,7 +286,7 @@ class MobiclipDecoder:
         if self.Data is None:
             self.last_error = -2
             return None
-        buf = _as_u8(self.Data)
+        buf = as_u8(self.Data)
         off = C.c_int32(int(self.Offset))
         rc = self._lib.mobi_decode(self._h, buf.ctypes.data, buf.size, C.byref(off))
         self.Offset = off.value
@@ -311,33 +301,15 @@ class MobiclipDecoder:
         uv = np.empty(S * H // 2, np.uint8) if which == 1 else None
         rc = self._lib.mobi_get_planes(self._h, idx, y.ctypes.data if y is not None else None,
                                        uv.ctypes.data if uv is not None else None)
-        if rc == -2:
+        if check_rc(rc, null_ok=True):
             return None  # null slot, like the reference's unfilled ring entries
-        if rc != 0:
-            raise MobiclipError(error_string(rc))
         return (y.reshape(H, S) if which == 0 else uv.reshape(H // 2, S))
 
     def Bitmap(self):
         """The Bitmap DecodeFrame() returns in the reference (MD.cs:260-323), for the frame just decoded:
         (Height, Width) uint32 array of 0xAARRGGBB; None before the first frame."""
         out = np.empty((self.Height, self.Width), np.uint32)
-        rc = self._lib.mobi_get_argb(self._h, out.ctypes.data)
-        if rc == -2:  # MOBI_E_NULLREF
-            return None
-        if rc != 0:
-            raise MobiclipError(error_string(rc))
-        return out
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.mobi_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return None if check_rc(self._lib.mobi_get_argb(self._h, out.ctypes.data), null_ok=True) else out
 
 
 def _check_frames(ring_idx, n_frames):
@@ -355,6 +327,74 @@ def _ints(name, v, n):
     return [int(i) for i in v]
 
 
+# -- the arguments an entry point takes from torch, each checked in one place: the entry points differ in which checks they make, in their
+# order and in some wording (`refusal`), not in the checks themselves --------------------------------------------------------------------
+def dtype_name(dtype, allowed, refusal):
+    """the name of a torch.dtype ("float16" for torch.float16) when `allowed` holds it, ValueError(refusal) for anything else"""
+    import torch
+    name = str(dtype).split(".")[-1] if isinstance(dtype, torch.dtype) else None
+    if name not in allowed:
+        raise ValueError(refusal)
+    return name
+
+
+def scale_bias(scale, bias, applies, refusal):
+    """scale and bias of an RGB export (three floats each; None: 1 and 0) as the library's float[6], None when both are None;
+    ValueError(refusal) when one is given where they do not apply"""
+    if scale is None and bias is None:
+        return None
+    if not applies:
+        raise ValueError(refusal)
+    vals = []
+    for name, v, dflt in (("scale", scale, 1.0), ("bias", bias, 0.0)):
+        v = [dflt] * 3 if v is None else v
+        try:
+            v = [float(x) for x in v]
+        except (TypeError, ValueError):
+            raise ValueError(f"{name} must be three floats, not {v!r}") from None
+        if len(v) != 3 or not all(np.isfinite(v)):
+            raise ValueError(f"{name} must be three finite floats, not {v!r}")
+        vals += v
+    return (C.c_float * 6)(*np.asarray(vals, np.float32).tolist())
+
+
+def check_stream(stream, dev):
+    import torch
+    if stream is not None and (not isinstance(stream, torch.cuda.Stream) or stream.device != dev):
+        raise ValueError(f"stream must be a torch.cuda.Stream of {dev}, not {stream!r}")
+
+
+def check_out(out, dev, dtype, shape, aligned=True):
+    """out, where it is given: a contiguous tensor of this dtype and shape on dev, 16-byte aligned where the kernel stores vectors"""
+    import torch
+    if out is not None and (not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != dtype or tuple(out.shape) != shape
+                            or not out.is_contiguous() or (aligned and out.data_ptr() % 16)):
+        raise ValueError(f"out must be a contiguous{', 16-byte aligned' if aligned else ''} {dtype} tensor of shape {shape} on {dev}")
+
+
+def stream_and_out(stream, out, dev, dtype, shape):
+    """behind the last argument check: one HIP runtime in the process; no stream = the device's current one; no out = a new tensor,
+    allocated on the stream (torch's allocator then knows which stream uses it) -> (stream, out)"""
+    import torch
+    _check_one_hip_runtime()
+    if stream is None:
+        stream = torch.cuda.current_stream(dev)
+    if out is None:
+        with torch.cuda.stream(stream):
+            out = torch.empty(shape, dtype=dtype, device=dev)
+    return stream, out
+
+
+def tensor_bytes(t):
+    """the bytes of a contiguous tensor: the room the library is told it may write"""
+    return t.numel() * t.element_size()
+
+
+def _rows(flat, K, n):
+    """a C array [k * n + c] as K lists of n"""
+    return [list(flat[k * n:(k + 1) * n]) for k in range(K)]
+
+
 def unpack_motion_search(words):
     """Packed results of mobi_batch_motion_search / the oracle -> dict(dx, dy, frame, score)."""
     w = np.asarray(words, dtype=np.uint32)
@@ -362,10 +402,11 @@ def unpack_motion_search(words):
             "frame": ((w >> 16) & 7).astype(np.int32), "score": (w >> 20).astype(np.int32), "packed": w}
 
 
-class MobiclipBatch:
+class MobiclipBatch(Handle):
     """N independent decoder instances of equal geometry decoded in lock step on one GPU
     (decoder instances share nothing: MD.cs:15-39).  Also the pre-parsed replay path used for
     throughput measurement."""
+    _destroy = "mobi_batch_destroy"
 
     def __init__(self, n_clips, Width, Height, Version, device=None, device_parse=None):
         """device_parse: True = decode() parses the bitstreams on the GPU (one wavefront per clip, mobi_dparse.hip),
@@ -385,33 +426,23 @@ class MobiclipBatch:
                 mode = device_parse  # the library's own numbering: 0 host, 1 device, 2 hybrid, 3 device with the lock-step parser in front
             else:
                 mode = 2 if device_parse == "hybrid" else 3 if device_parse == "lockstep" else int(bool(device_parse))
-            rc = self._lib.mobi_batch_set_parse_mode(self._h, mode)
-            if rc != 0:
-                raise MobiclipError(error_string(rc))
+            check_rc(self._lib.mobi_batch_set_parse_mode(self._h, mode))
 
     def decode(self, datas, offsets):
         """One DecodeFrame() per clip.  datas: list of byte buffers; offsets: list of ints.
         Returns (rc list, new offsets list)."""
-        bufs = [_as_u8(d) for d in datas]
-        ptrs = (C.c_void_p * self.n)(*[None if b is _NO_DATA else b.ctypes.data for b in bufs])
-        lens = (C.c_size_t * self.n)(*[b.size for b in bufs])
+        bufs, ptrs, lens = byte_arrays(datas, self.n)
         offs = (C.c_int32 * self.n)(*[int(o) for o in offsets])
         rcs = (C.c_int * self.n)()
-        e = self._lib.mobi_batch_decode(self._h, ptrs, lens, offs, rcs)
-        if e != 0:
-            raise MobiclipError(error_string(e))
+        check_rc(self._lib.mobi_batch_decode(self._h, ptrs, lens, offs, rcs))
         return list(rcs), list(offs)
 
     def submit(self, datas, offsets):
         """Asynchronous decode(): enqueue one frame step (device parse only, at most two in flight); the buffers may be reused at
         once.  Results come from wait(), oldest step first."""
-        bufs = [_as_u8(d) for d in datas]
-        ptrs = (C.c_void_p * self.n)(*[None if b is _NO_DATA else b.ctypes.data for b in bufs])
-        lens = (C.c_size_t * self.n)(*[b.size for b in bufs])
+        bufs, ptrs, lens = byte_arrays(datas, self.n)
         offs = (C.c_int32 * self.n)(*[int(o) for o in offsets])
-        e = self._lib.mobi_batch_submit(self._h, ptrs, lens, offs)
-        if e != 0:
-            raise MobiclipError(error_string(e))
+        check_rc(self._lib.mobi_batch_submit(self._h, ptrs, lens, offs))
 
     # -- frame-parallel groups: K consecutive frames of every clip per call (mobiclip_hip.h, mobi_batch_decode_gop) -------------
     def _gop_arrays(self, frames, offsets):
@@ -422,9 +453,7 @@ class MobiclipBatch:
                 raise ValueError(f"frames[{k}] has {len(fr)} entries, the batch has {self.n} clips")
         if offsets is not None and (len(offsets) != K or any(len(row) != self.n for row in offsets)):
             raise ValueError(f"offsets must have the shape of frames: {K} rows of {self.n}")
-        bufs = [_as_u8(d) for fr in frames for d in fr]
-        ptrs = (C.c_void_p * (K * self.n))(*[None if b is _NO_DATA else b.ctypes.data for b in bufs])
-        lens = (C.c_size_t * (K * self.n))(*[b.size for b in bufs])
+        bufs, ptrs, lens = byte_arrays([d for fr in frames for d in fr], K * self.n)
         flat = [0] * (K * self.n) if offsets is None else [int(o) for row in offsets for o in row]
         offs = (C.c_int32 * (K * self.n))(*flat)
         return K, bufs, ptrs, lens, offs
@@ -434,38 +463,32 @@ class MobiclipBatch:
         K lists of n: exactly what K decode() calls return."""
         K, bufs, ptrs, lens, offs = self._gop_arrays(frames, offsets)
         rcs = (C.c_int * (K * self.n))()
-        e = self._lib.mobi_batch_decode_gop(self._h, K, ptrs, lens, offs, rcs)
-        if e != 0:
-            raise MobiclipError(error_string(e))
-        return [list(rcs[k * self.n:(k + 1) * self.n]) for k in range(K)], [list(offs[k * self.n:(k + 1) * self.n]) for k in range(K)]
+        check_rc(self._lib.mobi_batch_decode_gop(self._h, K, ptrs, lens, offs, rcs))
+        return _rows(rcs, K, self.n), _rows(offs, K, self.n)
 
     def gop_begin(self, frames, offsets=None):
         """first half of decode_gop(): gather, upload (and parse, when no group is in front); at most two groups begun and not finished"""
         K, bufs, ptrs, lens, offs = self._gop_arrays(frames, offsets)
-        e = self._lib.mobi_batch_gop_begin(self._h, K, ptrs, lens, offs)
-        if e != 0:
-            raise MobiclipError(error_string(e))
+        check_rc(self._lib.mobi_batch_gop_begin(self._h, K, ptrs, lens, offs))
+
+    def _gop_finish(self, entry, K):
+        """(rc, offsets) of K frames of the oldest group begun, from mobi_batch_gop_finish or mobi_batch_gop_finish_all"""
+        offs = (C.c_int32 * max(1, K * self.n))()
+        rcs = (C.c_int * max(1, K * self.n))()
+        check_rc(entry(self._h, offs, rcs))
+        return _rows(rcs, K, self.n), _rows(offs, K, self.n)
 
     def gop_finish(self):
         """second half, for the OLDEST group begun: hand-overs, the reconstruction steps; -> (rc, offsets) as decode_gop().  A group of more
         than six frames (gop_begin takes up to 128) is handed out six at a time: call again while gop_frames_pending() > 0."""
-        K = min(6, self._lib.mobi_batch_gop_frames_pending(self._h))
-        offs = (C.c_int32 * (K * self.n))()
-        rcs = (C.c_int * (K * self.n))()
-        e = self._lib.mobi_batch_gop_finish(self._h, offs, rcs)
-        if e != 0:
-            raise MobiclipError(error_string(e))
-        return [list(rcs[k * self.n:(k + 1) * self.n]) for k in range(K)], [list(offs[k * self.n:(k + 1) * self.n]) for k in range(K)]
+        return self._gop_finish(self._lib.mobi_batch_gop_finish, min(6, self._lib.mobi_batch_gop_frames_pending(self._h)))
 
     def gop_frames_pending(self):
         return self._lib.mobi_batch_gop_frames_pending(self._h)
 
     def compare_clips(self, modulus):
         """clips whose newest frame differs from that of clip (index mod modulus), compared on the device (batches made of copies)"""
-        e = self._lib.mobi_batch_compare_clips(self._h, int(modulus), None)
-        if e < 0:
-            raise MobiclipError(error_string(e))
-        return e
+        return check_rc(self._lib.mobi_batch_compare_clips(self._h, int(modulus), None), counts=True)
 
     def host_clips(self):
         """clips the host parser parses at present: all of them in host mode, else the hybrid share plus every clip that has had a frame
@@ -493,9 +516,7 @@ class MobiclipBatch:
             if idx.size and (idx.min() < 0 or idx.max() >= self.n):
                 raise ValueError(f"clip index outside [0, {self.n})")
         idx = np.ascontiguousarray(idx, dtype=np.int32)
-        e = self._lib.mobi_batch_reset_clips(self._h, idx.ctypes.data_as(C.POINTER(C.c_int32)), int(idx.size))
-        if e != 0:
-            raise MobiclipError(error_string(e))
+        check_rc(self._lib.mobi_batch_reset_clips(self._h, idx.ctypes.data_as(C.POINTER(C.c_int32)), int(idx.size)))
 
     def set_idle(self, mask):
         """Mark frame slots of the NEXT step or group handed over as idle: "this clip has no frame here, its stream has ended".  mask:
@@ -513,16 +534,13 @@ class MobiclipBatch:
                 raise ValueError(f"an idle mask is [K][{self.n}] or [{self.n}], 1 <= K <= 128, not {np.asarray(mask).shape}")
             m = np.ascontiguousarray(m != 0, dtype=np.uint8)
             e = self._lib.mobi_batch_set_idle(self._h, m.ctypes.data, int(m.shape[0]))
-        if e != 0:
-            raise MobiclipError(error_string(e))
+        check_rc(e)
 
     def clip_idle(self):
         """int32[n]: idle slots handed over per clip since its last live frame or reset (steps and groups in flight included).  Ring
         index r of clip c holds a picture of its current stream iff clip_idle()[c] <= r < min(6, clip_idle()[c] + clip_frames()[c])."""
         out = np.zeros(self.n, np.int32)
-        e = self._lib.mobi_batch_clip_idle(self._h, out.ctypes.data_as(C.POINTER(C.c_int32)))
-        if e != 0:
-            raise MobiclipError(error_string(e))
+        check_rc(self._lib.mobi_batch_clip_idle(self._h, out.ctypes.data_as(C.POINTER(C.c_int32))))
         return out
 
     def idle_launches(self):
@@ -534,43 +552,32 @@ class MobiclipBatch:
         frame of a finished group part count; idle slots do not); without idle slots ring index r of clip c holds the current stream's
         picture iff r < min(6, that) -- clip_idle() has the general rule."""
         out = np.zeros(self.n, np.int32)
-        e = self._lib.mobi_batch_clip_frames(self._h, out.ctypes.data_as(C.POINTER(C.c_int32)))
-        if e != 0:
-            raise MobiclipError(error_string(e))
+        check_rc(self._lib.mobi_batch_clip_frames(self._h, out.ctypes.data_as(C.POINTER(C.c_int32))))
         return out
 
     def wait(self):
         """(rc list, new offsets list) of the oldest submitted step, when its reconstruction is done."""
         offs = (C.c_int32 * self.n)()
         rcs = (C.c_int * self.n)()
-        e = self._lib.mobi_batch_wait(self._h, offs, rcs)
-        if e != 0:
-            raise MobiclipError(error_string(e))
+        check_rc(self._lib.mobi_batch_wait(self._h, offs, rcs))
         return list(rcs), list(offs)
 
     def planes(self, clip, idx=0):
         S, H = self.Stride, self.Height
         y = np.empty(S * H, np.uint8)
         uv = np.empty(S * H // 2, np.uint8)
-        rc = self._lib.mobi_batch_get_planes(self._h, clip, idx, y.ctypes.data, uv.ctypes.data)
-        if rc == -2:
+        if check_rc(self._lib.mobi_batch_get_planes(self._h, clip, idx, y.ctypes.data, uv.ctypes.data), null_ok=True):
             return None
-        if rc != 0:
-            raise MobiclipError(error_string(rc))
         return y.reshape(H, S), uv.reshape(H // 2, S)
 
     def convert_argb(self):
         """Bitmaps of every clip's current frame into a device-resident buffer (asynchronous)."""
-        rc = self._lib.mobi_batch_convert_argb(self._h)
-        if rc != 0:
-            raise MobiclipError(error_string(rc))
+        check_rc(self._lib.mobi_batch_convert_argb(self._h))
 
     def bitmap(self, clip, idx=0):
         """the Bitmap of the frame at ring index idx (0 = the newest)"""
         out = np.empty((self.Height, self.Width), np.uint32)
-        rc = self._lib.mobi_batch_get_argb_at(self._h, clip, idx, out.ctypes.data) if idx else self._lib.mobi_batch_get_argb(self._h, clip, out.ctypes.data)
-        if rc != 0:
-            raise MobiclipError(error_string(rc))
+        check_rc(self._lib.mobi_batch_get_argb_at(self._h, clip, idx, out.ctypes.data) if idx else self._lib.mobi_batch_get_argb(self._h, clip, out.ctypes.data))
         return out
 
     def _clip_range(self, clips):
@@ -600,10 +607,8 @@ class MobiclipBatch:
               or not out.flags.writeable):
             raise ValueError(f"out must be a writeable C-contiguous {np.dtype(dtype).name} array of shape {shape}")
         ticket = C.c_uint64(0)
-        rc = self._lib.mobi_batch_export(self._h, EXPORT_FORMATS[fmt], int(ring_idx), int(n_frames), clips.start, len(clips), out.ctypes.data,
-                                         out.nbytes, C.byref(ticket))
-        if rc != 0:
-            raise MobiclipError(error_string(rc))
+        check_rc(self._lib.mobi_batch_export(self._h, EXPORT_FORMATS[fmt], int(ring_idx), int(n_frames), clips.start, len(clips), out.ctypes.data,
+                                             out.nbytes, C.byref(ticket)))
         h = ExportHandle(self, ticket.value, out)
         return h.wait() if wait else h
 
@@ -637,26 +642,10 @@ class MobiclipBatch:
             raise ValueError(f"layout must be 'nchw' or 'nhwc', not {layout!r}")
         if dtype is None:
             dtype = torch.uint8
-        if not isinstance(dtype, torch.dtype) or str(dtype).split(".")[-1] not in DEVICE_EXPORT_DTYPES:
-            raise ValueError(f"dtype must be torch.uint8, torch.float16 or torch.float32, not {dtype!r}")
-        dname = str(dtype).split(".")[-1]
+        dcode = DEVICE_EXPORT_DTYPES[dtype_name(dtype, DEVICE_EXPORT_DTYPES, f"dtype must be torch.uint8, torch.float16 or torch.float32, not {dtype!r}")]
         if fmt != "rgb" and dtype != torch.uint8:
             raise ValueError(f"fmt={fmt!r} has bytes only: dtype must be torch.uint8")
-        sb = None
-        if scale is not None or bias is not None:
-            if fmt != "rgb" or dtype == torch.uint8:
-                raise ValueError("scale and bias apply to fmt='rgb' with a float dtype only")
-            vals = []
-            for name, v, dflt in (("scale", scale, 1.0), ("bias", bias, 0.0)):
-                v = [dflt] * 3 if v is None else v
-                try:
-                    v = [float(x) for x in v]
-                except (TypeError, ValueError):
-                    raise ValueError(f"{name} must be three floats, not {v!r}") from None
-                if len(v) != 3 or not all(np.isfinite(v)):
-                    raise ValueError(f"{name} must be three finite floats, not {v!r}")
-                vals += v
-            sb = (C.c_float * 6)(*np.asarray(vals, np.float32).tolist())
+        sb = scale_bias(scale, bias, fmt == "rgb" and dtype != torch.uint8, "scale and bias apply to fmt='rgb' with a float dtype only")
         _check_frames(ring_idx, n_frames)
         clips = self._clip_range(clips)
         F, N, W, H = int(n_frames), len(clips), self.Width, self.Height
@@ -673,39 +662,25 @@ class MobiclipBatch:
         else:
             shape, tdtype = ((F, N, 3, H, W) if layout == "nchw" else (F, N, H, W, 3)), dtype
         dev = torch.device("cuda", self.device)
-        if stream is not None and (not isinstance(stream, torch.cuda.Stream) or stream.device != dev):
-            raise ValueError(f"stream must be a torch.cuda.Stream of {dev}, not {stream!r}")
-        if out is not None and (not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != tdtype or tuple(out.shape) != shape
-                                or not out.is_contiguous() or out.data_ptr() % 16):
-            raise ValueError(f"out must be a contiguous, 16-byte aligned {tdtype} tensor of shape {shape} on {dev}")
-        _check_one_hip_runtime()
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        if out is None:
-            with torch.cuda.stream(stream):
-                out = torch.empty(shape, dtype=tdtype, device=dev)
+        check_stream(stream, dev)
+        check_out(out, dev, tdtype, shape)
+        stream, out = stream_and_out(stream, out, dev, tdtype, shape)
         code = DEVICE_EXPORT_FORMATS[(fmt, layout if fmt == "rgb" else None)]
+        frames_dst = (int(ring_idx), F, clips.start, N, out.data_ptr(), tensor_bytes(out), stream.cuda_stream)
         if box_rows is not None:
-            rc = self._lib.mobi_batch_export_device_boxes(self._h, code, DEVICE_EXPORT_DTYPES[dname], sb, box_rows.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                          W, H, int(ring_idx), F, clips.start, N, out.data_ptr(),
-                                                          out.numel() * out.element_size(), stream.cuda_stream)
+            rc = self._lib.mobi_batch_export_device_boxes(self._h, code, dcode, sb, box_rows.ctypes.data_as(C.POINTER(C.c_int32)), W, H, *frames_dst)
         elif crop_size is not None:
-            rc = self._lib.mobi_batch_export_device_scaled(self._h, code, DEVICE_EXPORT_DTYPES[dname], sb, *crop_size, int(ring_idx), F,
-                                                           clips.start, N, out.data_ptr(), out.numel() * out.element_size(), stream.cuda_stream)
+            rc = self._lib.mobi_batch_export_device_scaled(self._h, code, dcode, sb, *crop_size, *frames_dst)
         else:
-            rc = self._lib.mobi_batch_export_device(self._h, code, DEVICE_EXPORT_DTYPES[dname], sb, int(ring_idx), F, clips.start, N,
-                                                    out.data_ptr(), out.numel() * out.element_size(), stream.cuda_stream)
-        if rc != 0:
-            raise MobiclipError(error_string(rc))
+            rc = self._lib.mobi_batch_export_device(self._h, code, dcode, sb, *frames_dst)
+        check_rc(rc)
         return out
 
     def set_motion(self, on):
         """Keep the motion field and macroblock data of every frame decoded from now on (mobi_batch_set_motion): a motion ring of six slots
         per clip beside the picture ring, written by one more kernel per frame step; set_motion(False) frees it.  Only with nothing in
         flight (no submitted step, no group, no export that may still run).  A batch that never calls this pays nothing."""
-        e = self._lib.mobi_batch_set_motion(self._h, 1 if on else 0)
-        if e != 0:
-            raise MobiclipError(error_string(e))
+        check_rc(self._lib.mobi_batch_set_motion(self._h, 1 if on else 0))
 
     def motion_launches(self):
         """launches of the motion kernel so far (0 for a batch that never switched motion on)"""
@@ -739,8 +714,7 @@ class MobiclipBatch:
         block = int(block)
         if dtype is None:
             dtype = getattr(torch, dnames[0])
-        if not isinstance(dtype, torch.dtype) or str(dtype).split(".")[-1] not in dnames:
-            raise ValueError(f"fmt={fmt!r}: dtype must be {' or '.join('torch.' + d for d in dnames)}, not {dtype!r}")
+        dname = dtype_name(dtype, dnames, f"fmt={fmt!r}: dtype must be {' or '.join('torch.' + d for d in dnames)}, not {dtype!r}")
         try:
             scale = float(scale)
         except (TypeError, ValueError):
@@ -754,21 +728,11 @@ class MobiclipBatch:
         F, N = int(n_frames), len(clips)
         shape = (F, N, channels, self.Height // block, self.Width // block)
         dev = torch.device("cuda", self.device)
-        if stream is not None and (not isinstance(stream, torch.cuda.Stream) or stream.device != dev):
-            raise ValueError(f"stream must be a torch.cuda.Stream of {dev}, not {stream!r}")
-        if out is not None and (not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != dtype or tuple(out.shape) != shape
-                                or not out.is_contiguous() or out.data_ptr() % 16):
-            raise ValueError(f"out must be a contiguous, 16-byte aligned {dtype} tensor of shape {shape} on {dev}")
-        _check_one_hip_runtime()
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        if out is None:
-            with torch.cuda.stream(stream):
-                out = torch.empty(shape, dtype=dtype, device=dev)
-        rc = self._lib.mobi_batch_export_motion(self._h, code, MOTION_DTYPES[str(dtype).split(".")[-1]], block, scale, int(ring_idx), F, clips.start, N,
-                                                out.data_ptr(), out.numel() * out.element_size(), stream.cuda_stream)
-        if rc != 0:
-            raise MobiclipError(error_string(rc))
+        check_stream(stream, dev)
+        check_out(out, dev, dtype, shape)
+        stream, out = stream_and_out(stream, out, dev, dtype, shape)
+        check_rc(self._lib.mobi_batch_export_motion(self._h, code, MOTION_DTYPES[dname], block, scale, int(ring_idx), F, clips.start, N,
+                                                    out.data_ptr(), tensor_bytes(out), stream.cuda_stream))
         return out
 
     # -- the clip sink: frame steps write chosen frames into one (N, T, ...) tensor (mobiclip_hip.h, mobi_batch_set_sink) ----------
@@ -787,9 +751,7 @@ class MobiclipBatch:
         works; default: a new contiguous tensor.  The batch keeps a reference to the tensor while the sink is armed.
         set_sink(None) disarms.  Arming, replacing and disarming need nothing in flight (no submitted step, no group)."""
         if size is None and n_frames is None and out is None:
-            e = self._lib.mobi_batch_set_sink(self._h, None)
-            if e != 0:
-                raise MobiclipError(error_string(e))
+            check_rc(self._lib.mobi_batch_set_sink(self._h, None))
             self._sink_out = None
             return None
         import torch
@@ -798,24 +760,8 @@ class MobiclipBatch:
         planar, dims = SINK_LAYOUTS[layout]
         if dtype is None:
             dtype = torch.uint8
-        if not isinstance(dtype, torch.dtype) or str(dtype).split(".")[-1] not in DEVICE_EXPORT_DTYPES:
-            raise ValueError(f"dtype must be torch.uint8, torch.float16 or torch.float32, not {dtype!r}")
-        dname = str(dtype).split(".")[-1]
-        sb = None
-        if scale is not None or bias is not None:
-            if dtype == torch.uint8:
-                raise ValueError("scale and bias apply to a float dtype only")
-            vals = []
-            for name, v, dflt in (("scale", scale, 1.0), ("bias", bias, 0.0)):
-                v = [dflt] * 3 if v is None else v
-                try:
-                    v = [float(x) for x in v]
-                except (TypeError, ValueError):
-                    raise ValueError(f"{name} must be three floats, not {v!r}") from None
-                if len(v) != 3 or not all(np.isfinite(v)):
-                    raise ValueError(f"{name} must be three finite floats, not {v!r}")
-                vals += v
-            sb = (C.c_float * 6)(*np.asarray(vals, np.float32).tolist())
+        dname = dtype_name(dtype, DEVICE_EXPORT_DTYPES, f"dtype must be torch.uint8, torch.float16 or torch.float32, not {dtype!r}")
+        sb = scale_bias(scale, bias, dtype != torch.uint8, "scale and bias apply to a float dtype only")
         N = self.n
         (T,) = _ints("n_frames", (n_frames,), 1)
         (s,) = _ints("stride", (stride,), 1)
@@ -861,9 +807,7 @@ class MobiclipBatch:
                         box_rows.ctypes.data_as(C.POINTER(C.c_int32)), ow, oh, T, s, st.ctypes.data_as(C.POINTER(C.c_int32)), sd["n"], sd["t"],
                         sd["c"] if planar else 0, out.data_ptr(), avail)
         torch.cuda.current_stream(dev).synchronize()  # (whatever was filling `out` is done before the batch's stream writes it)
-        e = self._lib.mobi_batch_set_sink(self._h, C.byref(spec))
-        if e != 0:
-            raise MobiclipError(error_string(e))
+        check_rc(self._lib.mobi_batch_set_sink(self._h, C.byref(spec)))
         self._sink_out = out
         return out
 
@@ -879,13 +823,7 @@ class MobiclipBatch:
         """gop_finish() for every frame of the oldest group that is still pending, in one call with one wait: -> (rc, offsets) as gop_finish(),
         gop_frames_pending() rows each.  The ring holds the group's last six frames afterwards; the earlier ones reach the caller through a
         sink (set_sink)."""
-        K = self._lib.mobi_batch_gop_frames_pending(self._h)
-        offs = (C.c_int32 * max(1, K * self.n))()
-        rcs = (C.c_int * max(1, K * self.n))()
-        e = self._lib.mobi_batch_gop_finish_all(self._h, offs, rcs)
-        if e != 0:
-            raise MobiclipError(error_string(e))
-        return [list(rcs[k * self.n:(k + 1) * self.n]) for k in range(K)], [list(offs[k * self.n:(k + 1) * self.n]) for k in range(K)]
+        return self._gop_finish(self._lib.mobi_batch_gop_finish_all, self._lib.mobi_batch_gop_frames_pending(self._h))
 
     def _box_geometry(self, fmt, N, crop, size, boxes, flip):
         """export_tensor's boxes / flip / size, checked -> the (N, 5) int32 rows (x, y, w, h, flip) of the library call, out_w, out_h"""
@@ -957,9 +895,7 @@ class MobiclipBatch:
         assert len(pics) == self.n and all(p.shape == (self.Height, self.Width) for p in pics)
         ptrs = (C.c_void_p * self.n)(*[p.ctypes.data for p in pics])
         out = np.empty((self.n, self.Height // 16, self.Width // 16, 8, 8), np.uint32)
-        rc = self._lib.mobi_batch_motion_search(self._h, ptrs, out.ctypes.data)
-        if rc != 0:
-            raise MobiclipError(error_string(rc))
+        check_rc(self._lib.mobi_batch_motion_search(self._h, ptrs, out.ctypes.data))
         return unpack_motion_search(out)
 
     def last_decode_ms(self):
@@ -968,29 +904,23 @@ class MobiclipBatch:
 
     # -- replay ---------------------------------------------------------------------------------
     def preload(self, clip, data, frame_off):
-        buf = _as_u8(data)
+        buf = as_u8(data)
         fo = np.ascontiguousarray(frame_off, dtype=np.uint32)
         n_frames = fo.size - 1
         rcs = (C.c_int * n_frames)()
         rc = self._lib.mobi_batch_preload(self._h, clip, buf.ctypes.data, buf.size, fo.ctypes.data, n_frames, rcs)
         if rc == MOBI_E_ARG:  # bad clip index / frame offsets: nothing was staged (a stream error comes back per frame instead)
-            raise MobiclipError(error_string(rc))
+            check_rc(rc)
         return list(rcs)
 
     def preload_clone(self, clip, src):
-        rc = self._lib.mobi_batch_preload_clone(self._h, clip, src)
-        if rc != 0:
-            raise MobiclipError(error_string(rc))
+        check_rc(self._lib.mobi_batch_preload_clone(self._h, clip, src))
 
     def commit(self):
-        rc = self._lib.mobi_batch_commit(self._h)
-        if rc != 0:
-            raise MobiclipError(error_string(rc))
+        check_rc(self._lib.mobi_batch_commit(self._h))
 
     def replay(self, frame_idx):
-        rc = self._lib.mobi_batch_replay(self._h, frame_idx)
-        if rc != 0:
-            raise MobiclipError(error_string(rc))
+        check_rc(self._lib.mobi_batch_replay(self._h, frame_idx))
 
     def sync(self):
         return self._lib.mobi_batch_sync(self._h)
@@ -1001,9 +931,7 @@ class MobiclipBatch:
     def intra_stats(self, frame_idx):
         """(intra macroblocks, command-list bytes that belong to them) of one frame step, all clips."""
         n, by = C.c_uint64(), C.c_uint64()
-        rc = self._lib.mobi_batch_intra_stats(self._h, frame_idx, C.byref(n), C.byref(by))
-        if rc != 0:
-            raise MobiclipError(error_string(rc))
+        check_rc(self._lib.mobi_batch_intra_stats(self._h, frame_idx, C.byref(n), C.byref(by)))
         return int(n.value), int(by.value)
 
     def time_begin(self):
@@ -1011,9 +939,7 @@ class MobiclipBatch:
 
     def time_end(self):
         ms = C.c_float()
-        rc = self._lib.mobi_batch_time_end(self._h, C.byref(ms))
-        if rc != 0:
-            raise MobiclipError(error_string(rc))
+        check_rc(self._lib.mobi_batch_time_end(self._h, C.byref(ms)))
         return ms.value
 
     def set_kernel_timing(self, level):
@@ -1025,17 +951,6 @@ class MobiclipBatch:
         self._lib.mobi_batch_kernel_ms(self._h, C.byref(a), C.byref(b), C.byref(na), C.byref(nb))
         return {"inter_ms": a.value, "intra_ms": b.value, "inter_launches": na.value, "intra_launches": nb.value}
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.mobi_batch_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def forward_dct(blocks, device=None):
     """MobiEncoder.DCT64 / DCT16 (Encoder/MobiEncoder.cs:962, 1146) on the GPU: blocks = int32 array (n_blocks, 64) or (n_blocks, 16)
@@ -1044,9 +959,7 @@ def forward_dct(blocks, device=None):
     if a.ndim != 2 or a.shape[1] not in (64, 16):
         raise ValueError("blocks must be (n, 64) or (n, 16)")
     out = np.empty_like(a)
-    rc = load_library().mobi_forward_dct(default_device() if device is None else device, 8 if a.shape[1] == 64 else 4, a.ctypes.data, out.ctypes.data, a.shape[0])
-    if rc != 0:
-        raise MobiclipError(error_string(rc))
+    check_rc(load_library().mobi_forward_dct(default_device() if device is None else device, 8 if a.shape[1] == 64 else 4, a.ctypes.data, out.ctypes.data, a.shape[0]))
     return out
 
 
@@ -1054,9 +967,7 @@ def quant_tables(q):
     """MobiEncoder.SetupQuantizationTables (Encoder/MobiEncoder.cs:930-960) for quantiser q in [0, 53]: (QTable4x4 float32[16],
     QTable8x8 float32[64]) in natural DCT order, as the reference's float[] holds them.  Needs no device."""
     q4, q8 = np.empty(16, np.float32), np.empty(64, np.float32)
-    rc = load_library().mobi_encoder_qtables(int(q), q4.ctypes.data, q8.ctypes.data)
-    if rc != 0:
-        raise MobiclipError(error_string(rc))
+    check_rc(load_library().mobi_encoder_qtables(int(q), q4.ctypes.data, q8.ctypes.data))
     return q4, q8
 
 
@@ -1136,6 +1047,5 @@ def transform_code(src, pred, quantizers, levels=True, recon=True, sad=True, dev
         ptr = {k: v.ctypes.data for k, v in out.items()}
         rc = lib.mobi_transform_code(default_device() if device is None else device, n, qarr, nq, src.ctypes.data, pred.ctypes.data, nb,
                                      ptr.get("levels"), ptr.get("recon"), ptr["bits"], ptr.get("sad"), ptr["flags"])
-    if rc != 0:
-        raise MobiclipError(error_string(rc))
+    check_rc(rc)
     return out

@@ -4,6 +4,7 @@ import ctypes as C
 
 import numpy as np
 
+from .binding import Handle, bind
 from .decoder import load_library
 
 
@@ -48,22 +49,15 @@ _SIGS = {
     "mobi_moc5_open": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(_Moc5Info)]),
     "mobi_moc5_next_block": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]),
 }
-_BOUND = False
 
 
 def _lib():
-    global _BOUND
-    lib = load_library()
-    if not _BOUND:
-        for name, (res, args) in _SIGS.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
-        _BOUND = True
-    return lib
+    return bind(load_library(), _SIGS)
 
 
-class ModsDemuxer:
+class ModsDemuxer(Handle):
     """new ModsDemuxer(stream): Header, KeyFrames, ReadFrame(), JumpToKeyFrame() (ModsDemuxer.cs:16-117)."""
+    _destroy = "mobi_mods_close"
 
     def __init__(self, data):
         self._buf = np.ascontiguousarray(np.frombuffer(data, np.uint8) if not isinstance(data, np.ndarray) else data)
@@ -98,17 +92,6 @@ class ModsDemuxer:
         start = p.value - self._buf.ctypes.data
         return self._buf[start:start + size.value], na.value, bool(key.value)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.mobi_mods_close(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def moc5_info(data):
     buf = np.ascontiguousarray(np.frombuffer(data, np.uint8) if not isinstance(data, np.ndarray) else data)
@@ -133,9 +116,10 @@ def moc5_blocks(data):
         yield dec.value, bs.value
 
 
-class MoLiveDemux:
+class MoLiveDemux(Handle):
     """MoLiveDemux over a file held in memory (MoLiveDemux.cs): ReadPacket() with the reference's return codes, completed
     frames via frames() / next_frame() instead of the OnCompleteFrameReceived event."""
+    _destroy = "mobi_moflex_close"
 
     def __init__(self, data):
         self._buf = np.ascontiguousarray(np.frombuffer(data, np.uint8) if not isinstance(data, np.ndarray) else data)
@@ -167,14 +151,3 @@ class MoLiveDemux:
     def frames(self):
         while (fr := self.next_frame()) is not None:
             yield fr
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.mobi_moflex_close(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -5,7 +5,8 @@ import ctypes as C
 
 import numpy as np
 
-from .decoder import MobiclipError, _check_one_hip_runtime, default_device, error_string, load_library
+from .binding import Handle, bind
+from .decoder import MobiclipError, _check_one_hip_runtime, check_rc, default_device, load_library
 
 # mobi_enc_stats, one per picture
 STATS_DTYPE = np.dtype([("bits", "<u8"), ("sad", "<u8"), ("luma_modes", "<u4", 4), ("chroma_modes", "<u4", 4), ("coded_blocks", "<u4"),
@@ -21,18 +22,10 @@ _SIGS = {
     "mobi_enc_intra_async": (C.c_int, [C.c_void_p, _P, C.c_int, _P, C.c_size_t, _P, C.c_int, _P, C.c_size_t, _P, _P, _P]),
     "mobi_enc_intra": (C.c_int, [C.c_void_p, C.c_int, _P, C.c_size_t, _P, C.c_int, _P, C.c_size_t, _P, _P, _P]),
 }
-_BOUND = False
 
 
 def _lib():
-    global _BOUND
-    lib = load_library()
-    if not _BOUND:
-        for name, (res, args) in _SIGS.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
-        _BOUND = True
-    return lib
+    return bind(load_library(), _SIGS)
 
 
 def stream_bound(width, height):
@@ -40,8 +33,9 @@ def stream_bound(width, height):
     return int(_lib().mobi_enc_stream_bound(width, height))
 
 
-class MobiclipIntraEncoder:
+class MobiclipIntraEncoder(Handle):
     """mobi_enc: I-frames of width x height pictures for MobiclipVersion.Moflex3DS or .ModsDS, up to max_pictures per call."""
+    _destroy = "mobi_enc_destroy"
 
     def __init__(self, width, height, version, max_pictures, device=None):
         self._h = None
@@ -50,24 +44,11 @@ class MobiclipIntraEncoder:
         self.device = default_device() if device is None else int(device)
         self.frame_bytes = self.width * self.height * 3 // 2
         q = np.full(1, 12, np.uint8)
-        rc = self._lib.mobi_enc_check(self.max_pictures, self.width, self.height, self.version, 1, (self.frame_bytes + 7) & ~7, q.ctypes.data, 0, 0)
-        if rc != 0:
-            raise MobiclipError(error_string(rc))
+        check_rc(self._lib.mobi_enc_check(self.max_pictures, self.width, self.height, self.version, 1, (self.frame_bytes + 7) & ~7, q.ctypes.data, 0, 0))
         self._h = self._lib.mobi_enc_create(self.max_pictures, self.width, self.height, self.version, self.device)
         if not self._h:
             raise MobiclipError("mobi_enc_create failed: no usable HIP device, or out of device memory")
         self.stream_bound = stream_bound(self.width, self.height)
-
-    def close(self):
-        if self._h:
-            self._lib.mobi_enc_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def encode(self, pictures, quantizer, yuv_format=0, recon=False, stats=False, slot_bytes=None, stream=None):
         """pictures: (N, width * height * 3 / 2) uint8, packed I420 as export_tensor("i420") writes it -- a torch tensor on the encoder's
@@ -101,9 +82,7 @@ class MobiclipIntraEncoder:
                 raise ValueError("pictures must be a uint8 tensor on the encoder's device")
             pictures = pictures.contiguous()
             dev = pictures.device
-            rc = self._lib.mobi_enc_check(self.max_pictures, self.width, self.height, self.version, n, self.frame_bytes, qs.ctypes.data, int(yuv_format), slot)
-            if rc != 0:
-                raise MobiclipError(error_string(rc))
+            check_rc(self._lib.mobi_enc_check(self.max_pictures, self.width, self.height, self.version, n, self.frame_bytes, qs.ctypes.data, int(yuv_format), slot))
             s = torch.cuda.current_stream(dev) if stream is None else stream
             with torch.cuda.stream(s):  # torch's allocator then knows which stream uses the outputs
                 out = torch.empty((n, slot), dtype=torch.uint8, device=dev)
@@ -112,11 +91,9 @@ class MobiclipIntraEncoder:
                     extras["recon"] = torch.empty((n, self.frame_bytes), dtype=torch.uint8, device=dev)
                 if stats:
                     extras["stats"] = torch.empty((n, STATS_DTYPE.itemsize), dtype=torch.uint8, device=dev)
-            rc = self._lib.mobi_enc_intra_async(self._h, s.cuda_stream, n, pictures.data_ptr(), self.frame_bytes, qs.ctypes.data, int(yuv_format),
-                                                out.data_ptr(), slot, sizes.data_ptr(), extras["recon"].data_ptr() if recon else None,
-                                                extras["stats"].data_ptr() if stats else None)
-            if rc != 0:
-                raise MobiclipError(error_string(rc))
+            check_rc(self._lib.mobi_enc_intra_async(self._h, s.cuda_stream, n, pictures.data_ptr(), self.frame_bytes, qs.ctypes.data, int(yuv_format),
+                                                    out.data_ptr(), slot, sizes.data_ptr(), extras["recon"].data_ptr() if recon else None,
+                                                    extras["stats"].data_ptr() if stats else None))
             if slot_bytes is not None:
                 return (out, sizes, extras) if extras else (out, sizes)
             s.synchronize()
@@ -133,10 +110,8 @@ class MobiclipIntraEncoder:
             if stats:
                 extras["stats"] = np.zeros(n, STATS_DTYPE)
             pitch = self.frame_bytes  # a multiple of 8: width and height are multiples of 16
-            rc = self._lib.mobi_enc_intra(self._h, n, pictures.ctypes.data, pitch, qs.ctypes.data, int(yuv_format), out.ctypes.data, slot,
-                                          sizes.ctypes.data, extras["recon"].ctypes.data if recon else None, extras["stats"].ctypes.data if stats else None)
-            if rc != 0:
-                raise MobiclipError(error_string(rc))
+            check_rc(self._lib.mobi_enc_intra(self._h, n, pictures.ctypes.data, pitch, qs.ctypes.data, int(yuv_format), out.ctypes.data, slot,
+                                              sizes.ctypes.data, extras["recon"].ctypes.data if recon else None, extras["stats"].ctypes.data if stats else None))
         streams = [out[i, :sizes[i]].tobytes() if sizes[i] <= slot else b"" for i in range(n)]
         if slot_bytes is not None:
             extras["sizes"] = sizes

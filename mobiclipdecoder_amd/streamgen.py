@@ -8,6 +8,8 @@ import os
 
 import numpy as np
 
+from .binding import bind
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 
@@ -25,22 +27,21 @@ class GenParams(C.Structure):
     ]
 
 
+_SIGS = {
+    "mobi_gen_default_params": (None, [C.POINTER(GenParams), C.c_int, C.c_uint64]),
+    "mobi_gen_clip": (C.c_int64, [C.POINTER(GenParams), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mobi_gen_clip_scripted": (C.c_int64, [C.POINTER(GenParams), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mobi_gen_clip_scripted_mv": (C.c_int64, [C.POINTER(GenParams), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+}
+
+
 def _lib():
     global _LIB
     if _LIB is None:
         path = os.path.join(_HERE, "libmobi_streamgen.so")
         if not os.path.exists(path):
             raise ImportError(f"{path} missing: run `python -m mobiclipdecoder_amd.build` (or __graft_entry__.build())")
-        lib = C.CDLL(path)
-        lib.mobi_gen_default_params.argtypes = [C.POINTER(GenParams), C.c_int, C.c_uint64]
-        lib.mobi_gen_default_params.restype = None
-        lib.mobi_gen_clip.argtypes = [C.POINTER(GenParams), C.c_void_p, C.c_size_t, C.c_void_p]
-        lib.mobi_gen_clip.restype = C.c_int64
-        lib.mobi_gen_clip_scripted.argtypes = [C.POINTER(GenParams), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]
-        lib.mobi_gen_clip_scripted.restype = C.c_int64
-        lib.mobi_gen_clip_scripted_mv.argtypes = [C.POINTER(GenParams), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]
-        lib.mobi_gen_clip_scripted_mv.restype = C.c_int64
-        _LIB = lib
+        _LIB = bind(C.CDLL(path), _SIGS)
     return _LIB
 
 
