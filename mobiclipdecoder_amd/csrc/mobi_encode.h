@@ -136,6 +136,24 @@ MOBI_TC_FN uint32_t mobi_enc_symbol(const MobiEncConst *K, int level, int run, i
   return 15u << 19 | (uint32_t)last << 18 | (uint32_t)run << 12 | ((uint32_t)level & 0xFFF);
 }
 
+// ---- one coded block's bit string: 1 (one 8x8 transform), then its symbols; lev = 64 levels in scan order, some nonzero ----
+template <class Put>
+MOBI_TC_FN void mobi_enc_write_block(const MobiEncConst *K, const int16_t *lev, Put put, uint32_t *forms) {
+  put(1u, 1); // one 8x8 transform
+  int lastpos = 0;
+  for (int p = 0; p < 64; p++)
+    if (lev[p]) lastpos = p;
+  int prev = -1;
+  for (int p = 0; p <= lastpos; p++) {
+    const int lv = lev[p];
+    if (!lv) continue;
+    int n, form;
+    const uint32_t bits = mobi_enc_symbol(K, lv, p - prev - 1, p == lastpos, &n, &form);
+    put(bits, n);
+    if (forms) forms[form]++;
+    prev = p;
+  }
+}
 // ---- a macroblock's bit string: put(pattern, nbits) with nbits <= 28; forms[4] (may be NULL) counts the code forms written ----
 template <class Put>
 MOBI_TC_FN void mobi_enc_write_mb(const MobiEncConst *K, const MobiEncMb *m, Put put, uint32_t *forms) {
@@ -144,21 +162,7 @@ MOBI_TC_FN void mobi_enc_write_mb(const MobiEncConst *K, const MobiEncMb *m, Put
   for (int k = 0; k < 6; k++) {
     if (k == 0) put(m->luma_mode, 3);
     if (k == 4) put(m->chroma_mode, 3);
-    if (!((m->cbp >> k) & 1)) continue;
-    put(1u, 1); // one 8x8 transform
-    int lastpos = 0;
-    for (int p = 0; p < 64; p++)
-      if (m->lev[k][p]) lastpos = p;
-    int prev = -1;
-    for (int p = 0; p <= lastpos; p++) {
-      const int lv = m->lev[k][p];
-      if (!lv) continue;
-      int n, form;
-      const uint32_t bits = mobi_enc_symbol(K, lv, p - prev - 1, p == lastpos, &n, &form);
-      put(bits, n);
-      if (forms) forms[form]++;
-      prev = p;
-    }
+    if ((m->cbp >> k) & 1) mobi_enc_write_block(K, m->lev[k], put, forms);
   }
 }
 
@@ -172,10 +176,11 @@ struct MobiEncHostSink {
   }
 };
 MOBI_TC_FN uint32_t mobi_enc_header(int yuv_format, int q) { return 1u << 8 | (uint32_t)(yuv_format & 1) << 7 | (uint32_t)q; }
-// a stream's bytes from the sum of its macroblocks' bits
-MOBI_TC_FN uint64_t mobi_enc_stream_bytes(uint64_t mb_bits) {
-  return (MOBI_ENC_HEADER_BITS + mb_bits + MOBI_ENC_TAIL_BITS + 15) / 16 * 2;
+// a stream's bytes from its header's bits and the sum of its macroblocks' bits (an I-frame's header is MOBI_ENC_HEADER_BITS long)
+MOBI_TC_FN uint64_t mobi_enc_stream_bytes_h(uint64_t header_bits, uint64_t mb_bits) {
+  return (header_bits + mb_bits + MOBI_ENC_TAIL_BITS + 15) / 16 * 2;
 }
+MOBI_TC_FN uint64_t mobi_enc_stream_bytes(uint64_t mb_bits) { return mobi_enc_stream_bytes_h(MOBI_ENC_HEADER_BITS, mb_bits); }
 
 // ---- one block, scalar: src / pred 8x8 row-major; lev = levels in scan order, rec = the block's reconstruction under the rule ----
 MOBI_TC_FN MobiEncBlock mobi_enc_block(const MobiEncConst *K, int q, const int *src, const int *pred, int16_t *lev, int *rec) {

@@ -10,12 +10,14 @@
 // workgroup per picture whose waves share a diagonal's macroblocks with __syncthreads() between diagonals -- was measured against it:
 // slower at 8 and 512 pictures, level at 4096; it lives on in the profiling twin for that comparison.  No wave ever waits on memory.
 //
-// Stage 2, write bits.  mobi_enc_scan: one workgroup per picture, exclusive scan of the macroblocks' bit lengths behind the 9 header bits,
-// the stream's length, whether it fits its slot.  mobi_enc_write: one lane per macroblock spells its bit string at its own offset into the
-// zeroed slot: whole 32-bit words by plain stores, its first and last (shared with the neighbours) by atomic OR.
+// Stage 2, write bits (mobi_encode_write.h, shared with the inter encoder; the I-frame's speller is here).  mobi_enc_scan: one workgroup per
+// picture, exclusive scan of the macroblocks' bit lengths behind the 9 header bits, the stream's length, whether it fits its slot.
+// mobi_enc_write: one lane per macroblock spells its bit string at its own offset into the zeroed slot: whole 32-bit words by plain
+// stores, its first and last (shared with the neighbours) by atomic OR.
 #include <hip/hip_runtime.h>
 
 #include "mobi_encode.h"
+#include "mobi_encode_write.h"
 #include "mobi_txcode_lanes.h"
 
 namespace {
@@ -198,91 +200,22 @@ extern "C" __global__ __launch_bounds__(WAVES * 64) void mobi_enc_decide_diag(Mo
   if (i < count) encode_mb(A, pic, x_lo + i, d - (x_lo + i), lds[wave], lut);
 }
 
-// ---- stage 2 ----
-extern "C" __global__ __launch_bounds__(256) void mobi_enc_scan(MobiEncArgs A) {
-  __shared__ uint32_t sh[256];
-  const int pic = blockIdx.x, nmb = A.mbw * A.mbh, t = threadIdx.x;
-  const MobiEncMb *mbs = A.mbs + (size_t)pic * nmb;
-  uint32_t *off = A.mb_off + (size_t)pic * nmb;
-  uint32_t carry = MOBI_ENC_HEADER_BITS;
-  for (int base = 0; base < nmb; base += 256) {
-    const int i = base + t;
-    const uint32_t v = i < nmb ? mbs[i].bits : 0u;
-    sh[t] = v;
-    __syncthreads();
-    for (int s = 1; s < 256; s <<= 1) {
-      const uint32_t a = t >= s ? sh[t - s] : 0u;
-      __syncthreads();
-      sh[t] += a;
-      __syncthreads();
-    }
-    if (i < nmb) off[i] = carry + sh[t] - v;
-    carry += sh[255];
-    __syncthreads();
-  }
-  if (t == 0) {
-    const uint64_t bytes = mobi_enc_stream_bytes(carry - MOBI_ENC_HEADER_BITS);
-    A.bytes_out[pic] = (int32_t)bytes;
-    A.fits[pic] = bytes <= A.slot_bytes;
-    if (A.stats) A.stats[pic].bits = carry;
-  }
-}
-
+// ---- stage 2: mobi_encode_write.h's scan and writer with the I-frame's speller ----
 namespace {
-// MSB-first bits into 16-bit little-endian words, a 32-bit word (two of them) at a time
-struct SlotSink {
-  uint32_t *slot;
-  uint32_t pos, cur;
-  bool first;
-  __device__ void flush() {
-    const uint32_t w = cur >> 16 | cur << 16;
-    uint32_t *at = slot + ((pos - 1) >> 5);
-    if (first) atomicOr(at, w); else *at = w;
-    first = false;
-    cur = 0;
+struct IntraSpeller {
+  __device__ static uint32_t header_bits(const MobiEncArgs &, int) { return MOBI_ENC_HEADER_BITS; }
+  template <class Put> __device__ static void header(const MobiEncArgs &A, int pic, Put put) { put(mobi_enc_header(A.yuv_format, A.q[pic]), MOBI_ENC_HEADER_BITS); }
+  template <class Put> __device__ static void macroblock(const MobiEncArgs &A, int pic, int i, Put put) {
+    mobi_enc_write_mb(A.k, A.mbs + (size_t)pic * ((size_t)A.mbw * A.mbh) + i, put, (uint32_t *)nullptr);
   }
-  __device__ void operator()(uint32_t v, int n) {
-    const int b = (int)(pos & 31);
-    if (b + n <= 32) {
-      cur |= v << (32 - b - n);
-      pos += n;
-      if ((pos & 31) == 0) flush();
-    } else {
-      const int rest = b + n - 32;
-      cur |= v >> rest;
-      pos += n - rest;
-      flush();
-      cur = v << (32 - rest);
-      pos += rest;
-    }
-  }
-  __device__ void finish() {
-    if (pos & 31) {
-      pos = (pos + 31) & ~31u; // flush() addresses the word before pos
-      first = true;            // the last word is shared with the next macroblock
-      flush();
-    }
+  __device__ static void total(const MobiEncArgs &A, int pic, uint32_t bits) {
+    if (A.stats) A.stats[pic].bits = bits;
   }
 };
 } // namespace
 
-extern "C" __global__ __launch_bounds__(64) void mobi_enc_write(MobiEncArgs A) {
-  const int pic = blockIdx.y, nmb = A.mbw * A.mbh, i = blockIdx.x * 64 + threadIdx.x;
-  if (i >= nmb || !A.fits[pic]) return;
-  const MobiEncMb *mb = A.mbs + (size_t)pic * nmb + i;
-  SlotSink s;
-  s.slot = (uint32_t *)(A.streams + (size_t)pic * A.slot_bytes);
-  s.cur = 0;
-  s.first = true;
-  if (i == 0) {
-    s.pos = 0;
-    s(mobi_enc_header(A.yuv_format, A.q[pic]), MOBI_ENC_HEADER_BITS);
-  } else {
-    s.pos = A.mb_off[(size_t)pic * nmb + i];
-  }
-  mobi_enc_write_mb(A.k, mb, [&](uint32_t v, int n) { s(v, n); }, (uint32_t *)nullptr);
-  s.finish();
-}
+extern "C" __global__ __launch_bounds__(256) void mobi_enc_scan(MobiEncArgs A) { mobi_enc_scan_body<IntraSpeller>(A); }
+extern "C" __global__ __launch_bounds__(64) void mobi_enc_write(MobiEncArgs A) { mobi_enc_write_body<IntraSpeller>(A); }
 
 // stages: bit 0 = decide, bit 1 = write (the product always runs both); loop_shape: the profiling twin's other stage-1 shape
 extern "C" int mobi_launch_encode(const MobiEncArgs *a, int stages, int loop_shape, hipStream_t s) {

@@ -1,0 +1,177 @@
+"""The inter encoder (include/mobiclip_encode_inter.h): a batch of I420 pictures, each with the reconstruction of the frame before it, to
+Mobiclip P-frames, one stream per picture, on the GPU; and encode_clips, which chains it behind the intra encoder over whole clips.
+Every stream decodes -- in the reference decoder and in MobiclipBatch, behind the frame that was its reference -- to exactly the
+reconstruction the encoder reports; decisions and bits are only ever produced by the HIP kernels (mobi_encode_inter.hip).  DESIGN.md,
+"Inter encoder", has the rules."""
+import ctypes as C
+
+import numpy as np
+
+from .binding import Handle, bind
+from .decoder import MobiclipError, _check_one_hip_runtime, check_rc, default_device, load_library
+from .encode import MobiclipIntraEncoder
+
+# mobi_enc_inter_stats, one per picture
+STATS_DTYPE = np.dtype([("bits", "<u8"), ("sad", "<u8"), ("mv_bits", "<u8"), ("coded_blocks", "<u4"), ("fallback_clamp", "<u4"),
+                        ("fallback_level", "<u4"), ("code0", "<u4"), ("nonzero_mv", "<u4"), ("halfpel_mv", "<u4"), ("reserved", "<u4", 4)])
+
+_P = C.c_void_p
+# names must match include/mobiclip_encode_inter.h (tests/test_encode_inter_model.py checks header, library and this table)
+_SIGS = {
+    "mobi_enc_inter_create": (C.c_void_p, [C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_int]),
+    "mobi_enc_inter_destroy": (None, [C.c_void_p]),
+    "mobi_enc_inter_stream_bound": (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    "mobi_enc_inter_check": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_size_t, C.c_size_t, _P, _P, C.c_size_t]),
+    "mobi_enc_inter_async": (C.c_int, [C.c_void_p, _P, C.c_int, _P, C.c_size_t, _P, C.c_size_t, _P, _P, _P, C.c_size_t, _P, _P, _P]),
+    "mobi_enc_inter": (C.c_int, [C.c_void_p, C.c_int, _P, C.c_size_t, _P, C.c_size_t, _P, _P, _P, C.c_size_t, _P, _P, _P]),
+}
+
+
+def _lib():
+    return bind(load_library(), _SIGS)
+
+
+def stream_bound(width, height):
+    """mobi_enc_inter_stream_bound: no P-frame of a width x height picture is longer (bytes, a multiple of 4); 0 for refused dimensions"""
+    return int(_lib().mobi_enc_inter_stream_bound(width, height))
+
+
+def _quantizers(q, n, what):
+    qs = np.full(n, int(q), np.int64) if np.isscalar(q) else np.asarray([int(v) for v in q], np.int64)
+    if qs.shape != (n,) or n < 1 or qs.min() < 0 or qs.max() > 255:
+        raise ValueError(f"one {what}, or one per picture")
+    return qs.astype(np.uint8)
+
+
+class MobiclipInterEncoder(Handle):
+    """mobi_enc_inter_ctx: P-frames of width x height pictures for MobiclipVersion.Moflex3DS or .ModsDS, up to max_pictures per call."""
+    _destroy = "mobi_enc_inter_destroy"
+
+    def __init__(self, width, height, version, max_pictures, device=None):
+        self._h = None
+        self._lib = _lib()
+        self.width, self.height, self.version, self.max_pictures = int(width), int(height), int(version), int(max_pictures)
+        self.device = default_device() if device is None else int(device)
+        self.frame_bytes = self.width * self.height * 3 // 2
+        q = np.full(1, 12, np.uint8)
+        pitch = (self.frame_bytes + 7) & ~7
+        check_rc(self._lib.mobi_enc_inter_check(self.max_pictures, self.width, self.height, self.version, 1, pitch, pitch, q.ctypes.data, q.ctypes.data, 0))
+        self._h = self._lib.mobi_enc_inter_create(self.max_pictures, self.width, self.height, self.version, self.device)
+        if not self._h:
+            raise MobiclipError("mobi_enc_inter_create failed: no usable HIP device, or out of device memory")
+        self.stream_bound = stream_bound(self.width, self.height)
+
+    def encode(self, pictures, references, prev_quantizer, quantizer, recon=False, stats=False, slot_bytes=None, stream=None):
+        """pictures, references: (N, width * height * 3 / 2) uint8 each, packed I420 -- torch tensors on the encoder's device (encoded
+        where they lie, on `stream` or torch's current one) or numpy arrays (the synchronous host entry point).  references[i] is the
+        reconstruction of the frame before pictures[i], as an encoder reported it (`recon`).  prev_quantizer, quantizer: that frame's and
+        this one's, ints in [12, 52] or one per picture.  slot_bytes: the room of one stream (a multiple of 4; default: the bound).
+
+        Returns what MobiclipIntraEncoder.encode returns: a list of N bytes objects; for a torch input with slot_bytes given
+        (streams, sizes), enqueued and not waited for; with recon and / or stats a dict as the last element ("recon" (N, frame) uint8,
+        "stats" (N,) STATS_DTYPE, for the unsynchronised torch form an (N, 64) uint8 tensor)."""
+        if not self._h:
+            raise MobiclipError("encoder is closed")
+        is_torch = type(pictures).__module__.startswith("torch")
+        if is_torch != type(references).__module__.startswith("torch"):
+            raise ValueError("pictures and references must both be torch tensors or both numpy arrays")
+        if not is_torch:
+            pictures, references = np.ascontiguousarray(pictures), np.ascontiguousarray(references)
+            if pictures.dtype != np.uint8 or references.dtype != np.uint8:
+                raise ValueError("pictures and references must be uint8")
+        if pictures.ndim != 2 or int(pictures.shape[1]) != self.frame_bytes or tuple(references.shape) != tuple(pictures.shape):
+            raise ValueError(f"pictures and references must be (N, {self.frame_bytes})")
+        n = int(pictures.shape[0])
+        pq, qs = _quantizers(prev_quantizer, n, "prev_quantizer"), _quantizers(quantizer, n, "quantizer")
+        slot = self.stream_bound if slot_bytes is None else int(slot_bytes)
+        extras = {}
+        if is_torch:
+            import torch
+            _check_one_hip_runtime()
+            for t in (pictures, references):
+                if t.dtype != torch.uint8 or not t.is_cuda or (t.device.index or 0) != self.device:
+                    raise ValueError("pictures and references must be uint8 tensors on the encoder's device")
+            pictures, references = pictures.contiguous(), references.contiguous()
+            dev = pictures.device
+            check_rc(self._lib.mobi_enc_inter_check(self.max_pictures, self.width, self.height, self.version, n, self.frame_bytes, self.frame_bytes,
+                                                    pq.ctypes.data, qs.ctypes.data, slot))
+            s = torch.cuda.current_stream(dev) if stream is None else stream
+            with torch.cuda.stream(s):  # torch's allocator then knows which stream uses the outputs
+                out = torch.empty((n, slot), dtype=torch.uint8, device=dev)
+                sizes = torch.empty((n,), dtype=torch.int32, device=dev)
+                if recon:
+                    extras["recon"] = torch.empty((n, self.frame_bytes), dtype=torch.uint8, device=dev)
+                if stats:
+                    extras["stats"] = torch.empty((n, STATS_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+            check_rc(self._lib.mobi_enc_inter_async(self._h, s.cuda_stream, n, pictures.data_ptr(), self.frame_bytes, references.data_ptr(), self.frame_bytes,
+                                                    pq.ctypes.data, qs.ctypes.data, out.data_ptr(), slot, sizes.data_ptr(),
+                                                    extras["recon"].data_ptr() if recon else None, extras["stats"].data_ptr() if stats else None))
+            if slot_bytes is not None:
+                return (out, sizes, extras) if extras else (out, sizes)
+            s.synchronize()
+            out, sizes = out.cpu().numpy(), sizes.cpu().numpy()
+            if recon:
+                extras["recon"] = extras["recon"].cpu().numpy()
+            if stats:
+                extras["stats"] = extras["stats"].cpu().numpy().view(STATS_DTYPE).reshape(n)
+        else:
+            out = np.zeros((n, slot), np.uint8)
+            sizes = np.zeros(n, np.int32)
+            if recon:
+                extras["recon"] = np.zeros((n, self.frame_bytes), np.uint8)
+            if stats:
+                extras["stats"] = np.zeros(n, STATS_DTYPE)
+            pitch = self.frame_bytes  # a multiple of 8: width and height are multiples of 16
+            check_rc(self._lib.mobi_enc_inter(self._h, n, pictures.ctypes.data, pitch, references.ctypes.data, pitch, pq.ctypes.data, qs.ctypes.data,
+                                              out.ctypes.data, slot, sizes.ctypes.data, extras["recon"].ctypes.data if recon else None,
+                                              extras["stats"].ctypes.data if stats else None))
+        streams = [out[i, :sizes[i]].tobytes() if sizes[i] <= slot else b"" for i in range(n)]
+        if slot_bytes is not None:
+            extras["sizes"] = sizes
+            extras["slots"] = out
+        return (streams, extras) if extras else streams
+
+
+def encode_clips(frames, quantizer, gop, version, width, height, recon=False):
+    """frames: an (N, T, width * height * 3 / 2) uint8 torch tensor on a GPU, packed I420 (what a clip sink or export_tensor("i420")
+    writes).  Frame 0 and every gop-th frame of every clip go through the intra encoder, the rest through the inter encoder; the
+    reconstructions stay on the device and become the next frame's reference.  quantizer: an int in [12, 52] or T of them, one per frame.
+
+    Returns, per clip, the list of its T frame streams (bytes); with recon=True also the (N, T, frame) uint8 tensor of reconstructions:
+    what a decoder fed the streams of clip i in order holds after each."""
+    import torch
+    if not type(frames).__module__.startswith("torch") or frames.ndim != 3 or frames.dtype != torch.uint8 or not frames.is_cuda:
+        raise ValueError("frames must be an (N, T, frame_bytes) uint8 tensor on a GPU")
+    n, t_n = int(frames.shape[0]), int(frames.shape[1])
+    if int(gop) < 1 or n < 1 or t_n < 1:
+        raise ValueError("gop, clips and frames must be at least 1")
+    qs = [int(quantizer)] * t_n if np.isscalar(quantizer) else [int(q) for q in quantizer]
+    if len(qs) != t_n:
+        raise ValueError("one quantizer, or one per frame")
+    device = frames.device.index or 0
+    intra = MobiclipIntraEncoder(width, height, version, n, device=device)
+    inter = MobiclipInterEncoder(width, height, version, n, device=device) if t_n > 1 and int(gop) > 1 else None
+    slot = max(intra.stream_bound, inter.stream_bound if inter else 0)
+    held, rec_all, ref = [], [], None
+    try:
+        for t in range(t_n):
+            pics = frames[:, t].contiguous()
+            if t % int(gop) == 0:
+                out, sizes, ex = intra.encode(pics, qs[t], recon=True, slot_bytes=slot)
+            else:
+                out, sizes, ex = inter.encode(pics, ref, qs[t - 1], qs[t], recon=True, slot_bytes=slot)
+            ref = ex["recon"]
+            held.append((out, sizes))
+            if recon:
+                rec_all.append(ref)
+        torch.cuda.current_stream(frames.device).synchronize()
+    finally:
+        intra.close()
+        if inter:
+            inter.close()
+    clips = [[] for _ in range(n)]
+    for out, sizes in held:
+        out, sizes = out.cpu().numpy(), sizes.cpu().numpy()
+        for i in range(n):
+            clips[i].append(out[i, :sizes[i]].tobytes())
+    return (clips, torch.stack(rec_all, 1)) if recon else clips
