@@ -12,6 +12,7 @@
   tests/tools/libmobi_motionhost.so  "command list -> motion" (csrc/mobi_motion.h) on the CPU = TEST TOOL (g++)
   tests/tools/libmobi_encode_host.so  the intra encoder (csrc/mobi_encode.h) on the CPU: the host model = TEST TOOL (g++)
   tests/tools/libmobi_encode_inter_host.so  the inter encoder (csrc/mobi_encode_inter.h) on the CPU: the host model = TEST TOOL (g++)
+      (both by build_enc_host, over tests/tools/enc_host_pool.h; the encoders' shared host side, csrc/mobi_encode_ctx.h, is part of the product)
   tests/tools/abi_caller            plain-C caller of the product's C ABI = TEST TOOL (gcc)
 
 hipcc cross-compiles gfx950 without a GPU.  The built .so files are git-ignored but travel to the
@@ -181,20 +182,24 @@ def build_motionhost(force=False):
     return LIB_MOTIONHOST
 
 
+def build_enc_host(inter, force=False):
+    """the host model of the intra (inter=False) or the inter encoder: tests/tools/mobi_encode[_inter]_host.cpp over the headers beside
+    it (tests/tools/enc_host_pool.h; whichever are there: the sources under tests/ say what they include, this list only what to watch)"""
+    lib, name = (LIB_ENCINTERHOST, "mobi_encode_inter") if inter else (LIB_ENCHOST, "mobi_encode")
+    src = os.path.join(ROOT, "tests", "tools", name + "_host.cpp")
+    hdrs = [os.path.join(CSRC, h) for h in ("mobi_encode_inter.h", "mobi_encode.h", "mobi_txcode.h", "mobi_recon_math.h", "mobi_tables.h")[0 if inter else 1:]]
+    hdrs += [os.path.join(ROOT, "include", h) for h in ("mobiclip_encode_inter.h", "mobiclip_encode.h")[0 if inter else 1:]] + _hdrs(os.path.join(ROOT, "tests", "tools"))
+    if force or _newer(lib, [src] + hdrs):
+        _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-variable", "-fwrapv", "-pthread", "-I" + CSRC, src, "-o", lib])
+    return lib
+
+
 def build_enchost(force=False):
-    src = os.path.join(ROOT, "tests", "tools", "mobi_encode_host.cpp")
-    hdrs = [os.path.join(CSRC, h) for h in ("mobi_encode.h", "mobi_txcode.h", "mobi_recon_math.h", "mobi_tables.h")] + [os.path.join(ROOT, "include", "mobiclip_encode.h")]
-    if force or _newer(LIB_ENCHOST, [src] + hdrs):
-        _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-variable", "-fwrapv", "-pthread", "-I" + CSRC, src, "-o", LIB_ENCHOST])
-    return LIB_ENCHOST
+    return build_enc_host(False, force)
 
 
 def build_encinterhost(force=False):
-    src = os.path.join(ROOT, "tests", "tools", "mobi_encode_inter_host.cpp")
-    hdrs = [os.path.join(CSRC, h) for h in ("mobi_encode_inter.h", "mobi_encode.h", "mobi_txcode.h", "mobi_recon_math.h", "mobi_tables.h")] + [os.path.join(ROOT, "include", "mobiclip_encode_inter.h"), os.path.join(ROOT, "include", "mobiclip_encode.h")]
-    if force or _newer(LIB_ENCINTERHOST, [src] + hdrs):
-        _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-variable", "-fwrapv", "-pthread", "-I" + CSRC, src, "-o", LIB_ENCINTERHOST])
-    return LIB_ENCINTERHOST
+    return build_enc_host(True, force)
 
 
 def build_caller(force=False):

@@ -1,37 +1,13 @@
-// mobi_encode.cpp -- the C entry points of the intra encoder (include/mobiclip_encode.h): the encoder object with everything stage 1 and
-// stage 2 (mobi_encode.hip) need, allocated once; the refusals; the host-pointer twin.
-#include <hip/hip_runtime_api.h>
-
-#include <cstdlib>
-#include <cstring>
-
-#include "../../include/mobiclip_hip.h"
-#include "mobi_encode.h"
+// mobi_encode.cpp -- the C entry points of the intra encoder (include/mobiclip_encode.h): the refusals, and the launch of stage 1 and stage 2
+// (mobi_encode.hip).  The encoder object, the prologue of the call and the host-pointer twin are mobi_encode_ctx.h's.
+#include "mobi_encode_ctx.h"
 
 extern "C" int mobi_launch_encode(const MobiEncArgs *a, int stages, int loop_shape, hipStream_t s);
 
-struct mobi_enc {
-  int max_pictures, version, device;
-  uint32_t width, height;
-  size_t frame, nmb;
-  // one device allocation, carved: constants, macroblock records, bit offsets, fit flags, quantisers, the reconstruction
-  uint8_t *mem;
-  MobiEncConst *k;
-  MobiEncMb *mbs;
-  uint32_t *mb_off, *fits;
-  uint8_t *q, *rec;
-  // the host-pointer call's device copies, made at its first use and kept: pictures in, reconstruction, lengths, statistics; the slots
-  // grow with the largest slot_bytes seen
-  uint8_t *st_in, *st_rec, *st_streams;
-  int32_t *st_bytes;
-  mobi_enc_stats *st_stats;
-  size_t st_stream_bytes;
-  hipStream_t st_stream;
-};
+struct mobi_enc : MobiEncCtx {};
 
 namespace {
 int g_stages = 3, g_loop_shape = 0; // what the launch runs; only the profiling twin's hook below changes them (tools/exp_encode.py)
-size_t up(size_t b) { return (b + 255) & ~(size_t)255; }
 } // namespace
 
 #if defined(MOBI_PROFILING)
@@ -53,78 +29,27 @@ mobi_enc *mobi_enc_create(int max_pictures, uint32_t width, uint32_t height, int
   if (device < 0 || max_pictures < 1 ||
       mobi_enc_check_args(max_pictures, width, height, version, 1, (size_t)width * height * 3 / 2, &q, 0, 0) != MOBI_OK)
     return nullptr;
-  if (hipSetDevice(device) != hipSuccess) return nullptr;
-  mobi_enc *e = (mobi_enc *)calloc(1, sizeof *e);
-  if (!e) return nullptr;
-  e->max_pictures = max_pictures;
-  e->version = version;
-  e->device = device;
-  e->width = width;
-  e->height = height;
-  e->frame = (size_t)width * height * 3 / 2;
-  e->nmb = (size_t)(width / 16) * (height / 16);
-  const size_t N = (size_t)max_pictures;
-  const size_t o_mbs = up(sizeof(MobiEncConst)), o_off = o_mbs + up(N * e->nmb * sizeof(MobiEncMb)), o_fits = o_off + up(N * e->nmb * 4),
-               o_q = o_fits + up(N * 4), o_rec = o_q + up(N), total = o_rec + up(N * e->frame);
-  MobiEncConst *h = new MobiEncConst;
-  mobi_enc_build_const(h);
-  const bool ok = hipMalloc((void **)&e->mem, total) == hipSuccess && hipMemcpy(e->mem, h, sizeof *h, hipMemcpyHostToDevice) == hipSuccess;
-  delete h;
-  if (!ok) {
-    mobi_enc_destroy(e);
-    return nullptr;
-  }
-  e->k = (MobiEncConst *)e->mem;
-  e->mbs = (MobiEncMb *)(e->mem + o_mbs);
-  e->mb_off = (uint32_t *)(e->mem + o_off);
-  e->fits = (uint32_t *)(e->mem + o_fits);
-  e->q = e->mem + o_q;
-  e->rec = e->mem + o_rec;
-  return e;
+  mobi_enc *e = mobi_enc_ctx_new<mobi_enc>(max_pictures, width, height, version, device);
+  return e && mobi_enc_ctx_carve(e, mobi_enc_build_const, 1, {}) ? e : nullptr;
 }
 
-void mobi_enc_destroy(mobi_enc *e) {
-  if (!e) return;
-  if (e->st_stream) (void)hipStreamDestroy(e->st_stream);
-  for (void *p : {(void *)e->mem, (void *)e->st_in, (void *)e->st_rec, (void *)e->st_streams, (void *)e->st_bytes, (void *)e->st_stats})
-    if (p) (void)hipFree(p);
-  free(e);
-}
+void mobi_enc_destroy(mobi_enc *e) { mobi_enc_ctx_destroy(e); }
 
 int mobi_enc_intra_async(mobi_enc *e, void *stream, int n, const uint8_t *i420, size_t picture_pitch, const uint8_t *quantizers, int yuv_format,
                          uint8_t *streams, size_t slot_bytes, int32_t *bytes_out, uint8_t *recon_i420, mobi_enc_stats *stats) {
   if (!e) return MOBI_E_ARG;
-  const int rc = mobi_enc_check_args(e->max_pictures, e->width, e->height, e->version, n, picture_pitch, quantizers, yuv_format, slot_bytes);
+  int rc = mobi_enc_check_args(e->max_pictures, e->width, e->height, e->version, n, picture_pitch, quantizers, yuv_format, slot_bytes);
   if (rc != MOBI_OK) return rc;
   // the kernels read pictures 8 bytes and write reconstruction and slots 4 bytes at a time
   if (!i420 || !streams || !bytes_out || (uintptr_t)i420 % 8 || (uintptr_t)streams % 4 || (uintptr_t)recon_i420 % 4 || (uintptr_t)bytes_out % 4 ||
       (uintptr_t)stats % 8)
     return MOBI_E_ARG;
-  if (hipSetDevice(e->device) != hipSuccess) return MOBI_E_DEVICE;
   hipStream_t s = (hipStream_t)stream;
-  // (pageable source: the copy has left `quantizers` when the call returns)
-  if (hipMemcpyAsync(e->q, quantizers, (size_t)n, hipMemcpyHostToDevice, s) != hipSuccess) return MOBI_E_DEVICE;
-  if (slot_bytes && hipMemsetAsync(streams, 0, (size_t)n * slot_bytes, s) != hipSuccess) return MOBI_E_DEVICE;
-  if (stats && hipMemsetAsync(stats, 0, (size_t)n * sizeof *stats, s) != hipSuccess) return MOBI_E_DEVICE;
   MobiEncArgs a;
   memset(&a, 0, sizeof a);
-  a.src = i420;
-  a.src_pitch = picture_pitch;
-  a.rec = recon_i420 ? recon_i420 : e->rec;
-  a.mbs = e->mbs;
-  a.mb_off = e->mb_off;
-  a.fits = e->fits;
-  a.q = e->q;
-  a.k = e->k;
+  rc = mobi_enc_ctx_begin(e, s, n, i420, picture_pitch, {quantizers}, streams, slot_bytes, bytes_out, recon_i420, stats, &a);
+  if (rc != MOBI_OK) return rc;
   a.stats = stats;
-  a.streams = streams;
-  a.slot_bytes = slot_bytes;
-  a.bytes_out = bytes_out;
-  a.W = (int32_t)e->width;
-  a.H = (int32_t)e->height;
-  a.mbw = (int32_t)(e->width / 16);
-  a.mbh = (int32_t)(e->height / 16);
-  a.n = n;
   a.yuv_format = yuv_format;
   return mobi_launch_encode(&a, g_stages, g_loop_shape, s) == 0 ? MOBI_OK : MOBI_E_DEVICE;
 }
@@ -132,34 +57,11 @@ int mobi_enc_intra_async(mobi_enc *e, void *stream, int n, const uint8_t *i420, 
 int mobi_enc_intra(mobi_enc *e, int n, const uint8_t *i420, size_t picture_pitch, const uint8_t *quantizers, int yuv_format, uint8_t *streams,
                    size_t slot_bytes, int32_t *bytes_out, uint8_t *recon_i420, mobi_enc_stats *stats) {
   if (!e) return MOBI_E_ARG;
-  int rc = mobi_enc_check_args(e->max_pictures, e->width, e->height, e->version, n, picture_pitch, quantizers, yuv_format, slot_bytes);
+  const int rc = mobi_enc_check_args(e->max_pictures, e->width, e->height, e->version, n, picture_pitch, quantizers, yuv_format, slot_bytes);
   if (rc != MOBI_OK) return rc;
   if (!i420 || !streams || !bytes_out) return MOBI_E_ARG;
-  if (hipSetDevice(e->device) != hipSuccess) return MOBI_E_DEVICE;
-  const size_t N = (size_t)e->max_pictures;
-  if (!e->st_in) {
-    if (hipMalloc((void **)&e->st_in, N * e->frame) != hipSuccess || hipMalloc((void **)&e->st_rec, N * e->frame) != hipSuccess ||
-        hipMalloc((void **)&e->st_bytes, N * 4) != hipSuccess || hipMalloc((void **)&e->st_stats, N * sizeof(mobi_enc_stats)) != hipSuccess ||
-        hipStreamCreateWithFlags(&e->st_stream, hipStreamNonBlocking) != hipSuccess)
-      return MOBI_E_DEVICE;
-  }
-  if (N * slot_bytes > e->st_stream_bytes) {
-    if (e->st_streams) (void)hipFree(e->st_streams);
-    e->st_streams = nullptr;
-    e->st_stream_bytes = 0;
-    if (hipMalloc((void **)&e->st_streams, N * slot_bytes) != hipSuccess) return MOBI_E_DEVICE;
-    e->st_stream_bytes = N * slot_bytes;
-  }
-  uint8_t *d_streams = e->st_streams ? e->st_streams : e->st_in; // slot_bytes == 0: nothing is written there
-  hipStream_t s = e->st_stream;
-  if (hipMemcpy2DAsync(e->st_in, e->frame, i420, picture_pitch, e->frame, (size_t)n, hipMemcpyHostToDevice, s) != hipSuccess) return MOBI_E_DEVICE;
-  rc = mobi_enc_intra_async(e, s, n, e->st_in, e->frame, quantizers, yuv_format, d_streams, slot_bytes, e->st_bytes, e->st_rec, e->st_stats);
-  if (rc == MOBI_OK &&
-      ((slot_bytes && hipMemcpyAsync(streams, d_streams, (size_t)n * slot_bytes, hipMemcpyDeviceToHost, s) != hipSuccess) ||
-       hipMemcpyAsync(bytes_out, e->st_bytes, (size_t)n * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
-       (recon_i420 && hipMemcpyAsync(recon_i420, e->st_rec, (size_t)n * e->frame, hipMemcpyDeviceToHost, s) != hipSuccess) ||
-       (stats && hipMemcpyAsync(stats, e->st_stats, (size_t)n * sizeof *stats, hipMemcpyDeviceToHost, s) != hipSuccess)))
-    rc = MOBI_E_DEVICE;
-  if (hipStreamSynchronize(s) != hipSuccess) rc = MOBI_E_DEVICE;
-  return rc;
+  return mobi_enc_ctx_host(e, n, i420, picture_pitch, streams, slot_bytes, bytes_out, recon_i420, stats, [&](hipStream_t s, uint8_t *d_streams) {
+    return mobi_enc_intra_async(e, s, n, e->st_in, e->frame, quantizers, yuv_format, d_streams, slot_bytes, (int32_t *)e->st_bytes, e->st_rec,
+                                (mobi_enc_stats *)e->st_stats);
+  });
 }

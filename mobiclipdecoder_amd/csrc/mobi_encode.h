@@ -9,7 +9,8 @@
 //   one macroblock  mobi_enc_macroblock: three luma and three chroma trials on the decoder's own predictors (mobi_recon_math.h)
 //   bit writer      mobi_enc_symbol (one (last, run, level) in the order mobi_tc_cost prices the forms), mobi_enc_write_mb (a macroblock's
 //                   bit string into any sink: MobiEncHostSink here, the kernel's word-at-a-time sink in mobi_encode.hip; both put bits
-//                   MSB-first into 16-bit little-endian words), mobi_enc_picture (a whole picture on the CPU)
+//                   MSB-first into 16-bit little-endian words), mobi_enc_picture (a whole picture on the CPU), mobi_enc_finish_picture
+//                   (how a picture ends there, for this encoder and for mobi_encode_inter.h's: length, statistics, slot, sink)
 #ifndef MOBI_ENCODE_H
 #define MOBI_ENCODE_H
 #include <stdint.h>
@@ -357,8 +358,25 @@ static inline int mobi_enc_check_args(int max_pictures, uint32_t width, uint32_t
   return 0;
 }
 
-// ---- one picture on the CPU: the whole encoder in raster order.  rec (W * H * 3 / 2) and mbs (macroblocks) are required; slot is
-// zeroed and filled as the device does; forms[4] may be NULL.  Returns whether the bits written are the bits priced. ----
+// ---- how a picture on the CPU ends, for either encoder (st: mobi_enc_stats or mobi_enc_inter_stats), once its macroblocks are priced:
+// the length from the header's and the macroblocks' bits, the statistics handed out, the slot zeroed as the device does and, if the
+// stream fits, filled by write(put): header, then macroblocks.  Returns whether the bits written are the bits priced. ----
+template <class Stats, class Write>
+static inline bool mobi_enc_finish_picture(uint64_t header_bits, uint64_t mb_bits, Stats &st, Stats *stats, uint8_t *slot, size_t slot_bytes,
+                                           int32_t *bytes_out, Write write) {
+  st.bits = header_bits + mb_bits;
+  const uint64_t bytes = mobi_enc_stream_bytes_h(header_bits, mb_bits);
+  *bytes_out = (int32_t)bytes;
+  if (stats) *stats = st;
+  memset(slot, 0, slot_bytes);
+  if (bytes > slot_bytes) return true;
+  MobiEncHostSink sink{slot, 0};
+  write([&](uint32_t v, int n) { sink(v, n); });
+  return sink.pos == header_bits + mb_bits;
+}
+
+// ---- one picture on the CPU: the whole encoder in raster order.  rec (W * H * 3 / 2) and mbs (macroblocks) are required; forms[4] may
+// be NULL.  Returns what mobi_enc_finish_picture returns. ----
 static inline bool mobi_enc_picture(const MobiEncConst *K, int W, int H, int q, int yuv_format, const uint8_t *i420, uint8_t *slot, size_t slot_bytes,
                                     int32_t *bytes_out, uint8_t *rec, mobi_enc_stats *stats, MobiEncMb *mbs, uint32_t *forms) {
   const size_t ysz = (size_t)W * H;
@@ -381,16 +399,10 @@ static inline bool mobi_enc_picture(const MobiEncConst *K, int W, int H, int q, 
       st.fallback_clamp += ms.clamp;
       st.fallback_level += ms.range;
     }
-  st.bits = MOBI_ENC_HEADER_BITS + mb_bits;
-  const uint64_t bytes = mobi_enc_stream_bytes(mb_bits);
-  *bytes_out = (int32_t)bytes;
-  if (stats) *stats = st;
-  memset(slot, 0, slot_bytes);
-  if (bytes > slot_bytes) return true;
-  MobiEncHostSink sink{slot, 0};
-  sink(mobi_enc_header(yuv_format, q), MOBI_ENC_HEADER_BITS);
-  for (int i = 0; i < mbw * mbh; i++) mobi_enc_write_mb(K, mbs + i, [&](uint32_t v, int n) { sink(v, n); }, forms);
-  return sink.pos == MOBI_ENC_HEADER_BITS + mb_bits;
+  return mobi_enc_finish_picture(MOBI_ENC_HEADER_BITS, mb_bits, st, stats, slot, slot_bytes, bytes_out, [&](auto put) {
+    put(mobi_enc_header(yuv_format, q), MOBI_ENC_HEADER_BITS);
+    for (int i = 0; i < mbw * mbh; i++) mobi_enc_write_mb(K, mbs + i, put, forms);
+  });
 }
 #endif
 #endif

@@ -262,18 +262,10 @@ static inline bool mobi_encp_picture(const MobiEncInterConst *K, int ver, int W,
       st.nonzero_mv += mv[i] != 0;
       st.halfpel_mv += ((mobi_encp_dx(mv[i]) | mobi_encp_dy(mv[i])) & 1) != 0;
     }
-  const uint64_t hdr = (uint64_t)mobi_encp_header_bits(q, prev_q);
-  st.bits = hdr + mb_bits;
-  const uint64_t bytes = mobi_enc_stream_bytes_h(hdr, mb_bits);
-  *bytes_out = (int32_t)bytes;
-  if (stats) *stats = st;
-  memset(slot, 0, slot_bytes);
-  if (bytes > slot_bytes) return true;
-  MobiEncHostSink sink{slot, 0};
-  auto put = [&](uint32_t v, int n) { sink(v, n); };
-  mobi_encp_write_header(put, q, prev_q);
-  for (int i = 0; i < mbw * mbh; i++) mobi_encp_write_mb(K, ver, mbs + i, mv[i], mvp[i], put, forms);
-  return sink.pos == hdr + mb_bits;
+  return mobi_enc_finish_picture((uint64_t)mobi_encp_header_bits(q, prev_q), mb_bits, st, stats, slot, slot_bytes, bytes_out, [&](auto put) {
+    mobi_encp_write_header(put, q, prev_q);
+    for (int i = 0; i < mbw * mbh; i++) mobi_encp_write_mb(K, ver, mbs + i, mv[i], mvp[i], put, forms);
+  });
 }
 #endif
 #endif

@@ -1,6 +1,7 @@
 """The intra encoder (include/mobiclip_encode.h): a batch of I420 pictures to Mobiclip I-frames, one stream per picture, on the GPU.
 Every stream decodes -- in the reference decoder and in MobiclipBatch -- to exactly the reconstruction the encoder reports; decisions and
-bits are only ever produced by the HIP kernels (mobi_encode.hip).  DESIGN.md, "Intra encoder", has the rules."""
+bits are only ever produced by the HIP kernels (mobi_encode.hip).  DESIGN.md, "Intra encoder", has the rules.
+_Encoder here is the one Python side of both encoders: this module's MobiclipIntraEncoder and encode_inter.py's MobiclipInterEncoder."""
 import ctypes as C
 
 import numpy as np
@@ -33,22 +34,106 @@ def stream_bound(width, height):
     return int(_lib().mobi_enc_stream_bound(width, height))
 
 
-class MobiclipIntraEncoder(Handle):
-    """mobi_enc: I-frames of width x height pictures for MobiclipVersion.Moflex3DS or .ModsDS, up to max_pictures per call."""
-    _destroy = "mobi_enc_destroy"
+def _quantizers(q, n, what):
+    qs = np.full(n, int(q), np.int64) if np.isscalar(q) else np.asarray([int(v) for v in q], np.int64)
+    if qs.shape != (n,) or n < 1 or qs.min() < 0 or qs.max() > 255:
+        raise ValueError(f"one {what}, or one per picture")
+    return qs.astype(np.uint8)
+
+
+class _Encoder(Handle):
+    """What MobiclipIntraEncoder and MobiclipInterEncoder (encode_inter.py) share: creation and the one body of encode().  A subclass
+    names its entry points (_prefix + _create / _check / _stream_bound, _call + _async and _call for host pointers) and their table
+    (_sigs), its picture arrays as messages call them (_what), its statistics record (_stats) and the C arguments that stand between the
+    quantisers and the slots when a call has none of its own to give (_no_extra).  The check and both calls take a pitch and a quantiser
+    array per picture array."""
+    _sigs = _prefix = _call = _what = _stats = _no_extra = None
 
     def __init__(self, width, height, version, max_pictures, device=None):
         self._h = None
-        self._lib = _lib()
+        self._lib = bind(load_library(), self._sigs)
         self.width, self.height, self.version, self.max_pictures = int(width), int(height), int(version), int(max_pictures)
         self.device = default_device() if device is None else int(device)
         self.frame_bytes = self.width * self.height * 3 // 2
-        q = np.full(1, 12, np.uint8)
-        check_rc(self._lib.mobi_enc_check(self.max_pictures, self.width, self.height, self.version, 1, (self.frame_bytes + 7) & ~7, q.ctypes.data, 0, 0))
-        self._h = self._lib.mobi_enc_create(self.max_pictures, self.width, self.height, self.version, self.device)
+        self._check(1, (self.frame_bytes + 7) & ~7, [np.full(1, 12, np.uint8)] * len(self._what), self._no_extra, 0)
+        self._h = getattr(self._lib, self._prefix + "_create")(self.max_pictures, self.width, self.height, self.version, self.device)
         if not self._h:
-            raise MobiclipError("mobi_enc_create failed: no usable HIP device, or out of device memory")
-        self.stream_bound = stream_bound(self.width, self.height)
+            raise MobiclipError(self._prefix + "_create failed: no usable HIP device, or out of device memory")
+        self.stream_bound = int(getattr(self._lib, self._prefix + "_stream_bound")(self.width, self.height))
+
+    def _check(self, n, pitch, qs, extra, slot):
+        check_rc(getattr(self._lib, self._prefix + "_check")(self.max_pictures, self.width, self.height, self.version, n, *[pitch] * len(qs),
+                                                             *[q.ctypes.data for q in qs], *extra, slot))
+
+    def _encode(self, inputs, quantizers, extra, recon, stats, slot_bytes, stream):
+        """inputs: the picture arrays; quantizers: per array (its quantiser or quantisers, their name in a message); extra: as _no_extra"""
+        if not self._h:
+            raise MobiclipError("encoder is closed")
+        what = " and ".join(self._what)
+        is_torch = type(inputs[0]).__module__.startswith("torch")
+        if any(type(a).__module__.startswith("torch") != is_torch for a in inputs[1:]):
+            raise ValueError(f"{what} must both be torch tensors or both numpy arrays")
+        if not is_torch:
+            inputs = [np.ascontiguousarray(a) for a in inputs]
+            if any(a.dtype != np.uint8 for a in inputs):
+                raise ValueError(f"{what} must be uint8")
+        F = self.frame_bytes  # as a pitch a multiple of 8: width and height are multiples of 16
+        if inputs[0].ndim != 2 or int(inputs[0].shape[1]) != F or any(tuple(a.shape) != tuple(inputs[0].shape) for a in inputs[1:]):
+            raise ValueError(f"{what} must be (N, {F})")
+        n = int(inputs[0].shape[0])
+        qs = [_quantizers(q, n, name) for q, name in quantizers]
+        slot = self.stream_bound if slot_bytes is None else int(slot_bytes)
+        extras = {}
+        if is_torch:
+            import torch
+            _check_one_hip_runtime()
+            for t in inputs:
+                if t.dtype != torch.uint8 or not t.is_cuda or (t.device.index or 0) != self.device:
+                    raise ValueError(f"{what} must be {'a uint8 tensor' if len(inputs) == 1 else 'uint8 tensors'} on the encoder's device")
+            inputs = [t.contiguous() for t in inputs]
+            dev = inputs[0].device
+            extra = [int(x) for x in extra]
+            self._check(n, F, qs, extra, slot)
+            s = torch.cuda.current_stream(dev) if stream is None else stream
+            with torch.cuda.stream(s):  # torch's allocator then knows which stream uses the outputs
+                out = torch.empty((n, slot), dtype=torch.uint8, device=dev)
+                sizes = torch.empty((n,), dtype=torch.int32, device=dev)
+                if recon:
+                    extras["recon"] = torch.empty((n, F), dtype=torch.uint8, device=dev)
+                if stats:
+                    extras["stats"] = torch.empty((n, self._stats.itemsize), dtype=torch.uint8, device=dev)
+            fn, head, ptr = getattr(self._lib, self._call + "_async"), (self._h, s.cuda_stream, n), lambda t: t.data_ptr()
+        else:
+            out = np.zeros((n, slot), np.uint8)
+            sizes = np.zeros(n, np.int32)
+            if recon:
+                extras["recon"] = np.zeros((n, F), np.uint8)
+            if stats:
+                extras["stats"] = np.zeros(n, self._stats)
+            extra = [int(x) for x in extra]
+            fn, head, ptr = getattr(self._lib, self._call), (self._h, n), lambda a: a.ctypes.data
+        check_rc(fn(*head, *[x for a in inputs for x in (ptr(a), F)], *[q.ctypes.data for q in qs], *extra, ptr(out), slot, ptr(sizes),
+                    ptr(extras["recon"]) if recon else None, ptr(extras["stats"]) if stats else None))
+        if is_torch:
+            if slot_bytes is not None:
+                return (out, sizes, extras) if extras else (out, sizes)
+            s.synchronize()
+            out, sizes = out.cpu().numpy(), sizes.cpu().numpy()
+            if recon:
+                extras["recon"] = extras["recon"].cpu().numpy()
+            if stats:
+                extras["stats"] = extras["stats"].cpu().numpy().view(self._stats).reshape(n)
+        streams = [out[i, :sizes[i]].tobytes() if sizes[i] <= slot else b"" for i in range(n)]
+        if slot_bytes is not None:
+            extras["sizes"] = sizes
+            extras["slots"] = out
+        return (streams, extras) if extras else streams
+
+
+class MobiclipIntraEncoder(_Encoder):
+    """mobi_enc: I-frames of width x height pictures for MobiclipVersion.Moflex3DS or .ModsDS, up to max_pictures per call."""
+    _destroy = "mobi_enc_destroy"
+    _sigs, _prefix, _call, _what, _stats, _no_extra = _SIGS, "mobi_enc", "mobi_enc_intra", ("pictures",), STATS_DTYPE, (0,)
 
     def encode(self, pictures, quantizer, yuv_format=0, recon=False, stats=False, slot_bytes=None, stream=None):
         """pictures: (N, width * height * 3 / 2) uint8, packed I420 as export_tensor("i420") writes it -- a torch tensor on the encoder's
@@ -59,61 +144,4 @@ class MobiclipIntraEncoder(Handle):
         (N,) int32 tensor, enqueued and not waited for; a stream longer than slot_bytes leaves its slot zero and its true size in sizes.
         With recon and / or stats a dict follows as the last element: "recon" (N, frame) uint8, "stats" (N,) STATS_DTYPE (for the
         unsynchronised torch form an (N, 64) uint8 tensor: .cpu().numpy().view(STATS_DTYPE))."""
-        if not self._h:
-            raise MobiclipError("encoder is closed")
-        is_torch = type(pictures).__module__.startswith("torch")
-        if not is_torch:
-            pictures = np.ascontiguousarray(pictures)
-            if pictures.dtype != np.uint8:
-                raise ValueError("pictures must be uint8")
-        if pictures.ndim != 2 or int(pictures.shape[1]) != self.frame_bytes:
-            raise ValueError(f"pictures must be (N, {self.frame_bytes})")
-        n = int(pictures.shape[0])
-        qs = np.full(n, int(quantizer), np.int64) if np.isscalar(quantizer) else np.asarray([int(q) for q in quantizer], np.int64)
-        if qs.shape != (n,) or n < 1 or qs.min() < 0 or qs.max() > 255:
-            raise ValueError("one quantizer, or one per picture")
-        qs = qs.astype(np.uint8)
-        slot = self.stream_bound if slot_bytes is None else int(slot_bytes)
-        extras = {}
-        if is_torch:
-            import torch
-            _check_one_hip_runtime()
-            if pictures.dtype != torch.uint8 or not pictures.is_cuda or (pictures.device.index or 0) != self.device:
-                raise ValueError("pictures must be a uint8 tensor on the encoder's device")
-            pictures = pictures.contiguous()
-            dev = pictures.device
-            check_rc(self._lib.mobi_enc_check(self.max_pictures, self.width, self.height, self.version, n, self.frame_bytes, qs.ctypes.data, int(yuv_format), slot))
-            s = torch.cuda.current_stream(dev) if stream is None else stream
-            with torch.cuda.stream(s):  # torch's allocator then knows which stream uses the outputs
-                out = torch.empty((n, slot), dtype=torch.uint8, device=dev)
-                sizes = torch.empty((n,), dtype=torch.int32, device=dev)
-                if recon:
-                    extras["recon"] = torch.empty((n, self.frame_bytes), dtype=torch.uint8, device=dev)
-                if stats:
-                    extras["stats"] = torch.empty((n, STATS_DTYPE.itemsize), dtype=torch.uint8, device=dev)
-            check_rc(self._lib.mobi_enc_intra_async(self._h, s.cuda_stream, n, pictures.data_ptr(), self.frame_bytes, qs.ctypes.data, int(yuv_format),
-                                                    out.data_ptr(), slot, sizes.data_ptr(), extras["recon"].data_ptr() if recon else None,
-                                                    extras["stats"].data_ptr() if stats else None))
-            if slot_bytes is not None:
-                return (out, sizes, extras) if extras else (out, sizes)
-            s.synchronize()
-            out, sizes = out.cpu().numpy(), sizes.cpu().numpy()
-            if recon:
-                extras["recon"] = extras["recon"].cpu().numpy()
-            if stats:
-                extras["stats"] = extras["stats"].cpu().numpy().view(STATS_DTYPE).reshape(n)
-        else:
-            out = np.zeros((n, slot), np.uint8)
-            sizes = np.zeros(n, np.int32)
-            if recon:
-                extras["recon"] = np.zeros((n, self.frame_bytes), np.uint8)
-            if stats:
-                extras["stats"] = np.zeros(n, STATS_DTYPE)
-            pitch = self.frame_bytes  # a multiple of 8: width and height are multiples of 16
-            check_rc(self._lib.mobi_enc_intra(self._h, n, pictures.ctypes.data, pitch, qs.ctypes.data, int(yuv_format), out.ctypes.data, slot,
-                                              sizes.ctypes.data, extras["recon"].ctypes.data if recon else None, extras["stats"].ctypes.data if stats else None))
-        streams = [out[i, :sizes[i]].tobytes() if sizes[i] <= slot else b"" for i in range(n)]
-        if slot_bytes is not None:
-            extras["sizes"] = sizes
-            extras["slots"] = out
-        return (streams, extras) if extras else streams
+        return self._encode([pictures], [(quantizer, "quantizer")], (yuv_format,), recon, stats, slot_bytes, stream)

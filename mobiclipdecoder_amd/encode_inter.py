@@ -7,9 +7,9 @@ import ctypes as C
 
 import numpy as np
 
-from .binding import Handle, bind
-from .decoder import MobiclipError, _check_one_hip_runtime, check_rc, default_device, load_library
-from .encode import MobiclipIntraEncoder
+from .binding import bind
+from .decoder import load_library
+from .encode import MobiclipIntraEncoder, _Encoder
 
 # mobi_enc_inter_stats, one per picture
 STATS_DTYPE = np.dtype([("bits", "<u8"), ("sad", "<u8"), ("mv_bits", "<u8"), ("coded_blocks", "<u4"), ("fallback_clamp", "<u4"),
@@ -36,30 +36,10 @@ def stream_bound(width, height):
     return int(_lib().mobi_enc_inter_stream_bound(width, height))
 
 
-def _quantizers(q, n, what):
-    qs = np.full(n, int(q), np.int64) if np.isscalar(q) else np.asarray([int(v) for v in q], np.int64)
-    if qs.shape != (n,) or n < 1 or qs.min() < 0 or qs.max() > 255:
-        raise ValueError(f"one {what}, or one per picture")
-    return qs.astype(np.uint8)
-
-
-class MobiclipInterEncoder(Handle):
+class MobiclipInterEncoder(_Encoder):
     """mobi_enc_inter_ctx: P-frames of width x height pictures for MobiclipVersion.Moflex3DS or .ModsDS, up to max_pictures per call."""
     _destroy = "mobi_enc_inter_destroy"
-
-    def __init__(self, width, height, version, max_pictures, device=None):
-        self._h = None
-        self._lib = _lib()
-        self.width, self.height, self.version, self.max_pictures = int(width), int(height), int(version), int(max_pictures)
-        self.device = default_device() if device is None else int(device)
-        self.frame_bytes = self.width * self.height * 3 // 2
-        q = np.full(1, 12, np.uint8)
-        pitch = (self.frame_bytes + 7) & ~7
-        check_rc(self._lib.mobi_enc_inter_check(self.max_pictures, self.width, self.height, self.version, 1, pitch, pitch, q.ctypes.data, q.ctypes.data, 0))
-        self._h = self._lib.mobi_enc_inter_create(self.max_pictures, self.width, self.height, self.version, self.device)
-        if not self._h:
-            raise MobiclipError("mobi_enc_inter_create failed: no usable HIP device, or out of device memory")
-        self.stream_bound = stream_bound(self.width, self.height)
+    _sigs, _prefix, _call, _what, _stats, _no_extra = _SIGS, "mobi_enc_inter", "mobi_enc_inter", ("pictures", "references"), STATS_DTYPE, ()
 
     def encode(self, pictures, references, prev_quantizer, quantizer, recon=False, stats=False, slot_bytes=None, stream=None):
         """pictures, references: (N, width * height * 3 / 2) uint8 each, packed I420 -- torch tensors on the encoder's device (encoded
@@ -70,66 +50,7 @@ class MobiclipInterEncoder(Handle):
         Returns what MobiclipIntraEncoder.encode returns: a list of N bytes objects; for a torch input with slot_bytes given
         (streams, sizes), enqueued and not waited for; with recon and / or stats a dict as the last element ("recon" (N, frame) uint8,
         "stats" (N,) STATS_DTYPE, for the unsynchronised torch form an (N, 64) uint8 tensor)."""
-        if not self._h:
-            raise MobiclipError("encoder is closed")
-        is_torch = type(pictures).__module__.startswith("torch")
-        if is_torch != type(references).__module__.startswith("torch"):
-            raise ValueError("pictures and references must both be torch tensors or both numpy arrays")
-        if not is_torch:
-            pictures, references = np.ascontiguousarray(pictures), np.ascontiguousarray(references)
-            if pictures.dtype != np.uint8 or references.dtype != np.uint8:
-                raise ValueError("pictures and references must be uint8")
-        if pictures.ndim != 2 or int(pictures.shape[1]) != self.frame_bytes or tuple(references.shape) != tuple(pictures.shape):
-            raise ValueError(f"pictures and references must be (N, {self.frame_bytes})")
-        n = int(pictures.shape[0])
-        pq, qs = _quantizers(prev_quantizer, n, "prev_quantizer"), _quantizers(quantizer, n, "quantizer")
-        slot = self.stream_bound if slot_bytes is None else int(slot_bytes)
-        extras = {}
-        if is_torch:
-            import torch
-            _check_one_hip_runtime()
-            for t in (pictures, references):
-                if t.dtype != torch.uint8 or not t.is_cuda or (t.device.index or 0) != self.device:
-                    raise ValueError("pictures and references must be uint8 tensors on the encoder's device")
-            pictures, references = pictures.contiguous(), references.contiguous()
-            dev = pictures.device
-            check_rc(self._lib.mobi_enc_inter_check(self.max_pictures, self.width, self.height, self.version, n, self.frame_bytes, self.frame_bytes,
-                                                    pq.ctypes.data, qs.ctypes.data, slot))
-            s = torch.cuda.current_stream(dev) if stream is None else stream
-            with torch.cuda.stream(s):  # torch's allocator then knows which stream uses the outputs
-                out = torch.empty((n, slot), dtype=torch.uint8, device=dev)
-                sizes = torch.empty((n,), dtype=torch.int32, device=dev)
-                if recon:
-                    extras["recon"] = torch.empty((n, self.frame_bytes), dtype=torch.uint8, device=dev)
-                if stats:
-                    extras["stats"] = torch.empty((n, STATS_DTYPE.itemsize), dtype=torch.uint8, device=dev)
-            check_rc(self._lib.mobi_enc_inter_async(self._h, s.cuda_stream, n, pictures.data_ptr(), self.frame_bytes, references.data_ptr(), self.frame_bytes,
-                                                    pq.ctypes.data, qs.ctypes.data, out.data_ptr(), slot, sizes.data_ptr(),
-                                                    extras["recon"].data_ptr() if recon else None, extras["stats"].data_ptr() if stats else None))
-            if slot_bytes is not None:
-                return (out, sizes, extras) if extras else (out, sizes)
-            s.synchronize()
-            out, sizes = out.cpu().numpy(), sizes.cpu().numpy()
-            if recon:
-                extras["recon"] = extras["recon"].cpu().numpy()
-            if stats:
-                extras["stats"] = extras["stats"].cpu().numpy().view(STATS_DTYPE).reshape(n)
-        else:
-            out = np.zeros((n, slot), np.uint8)
-            sizes = np.zeros(n, np.int32)
-            if recon:
-                extras["recon"] = np.zeros((n, self.frame_bytes), np.uint8)
-            if stats:
-                extras["stats"] = np.zeros(n, STATS_DTYPE)
-            pitch = self.frame_bytes  # a multiple of 8: width and height are multiples of 16
-            check_rc(self._lib.mobi_enc_inter(self._h, n, pictures.ctypes.data, pitch, references.ctypes.data, pitch, pq.ctypes.data, qs.ctypes.data,
-                                              out.ctypes.data, slot, sizes.ctypes.data, extras["recon"].ctypes.data if recon else None,
-                                              extras["stats"].ctypes.data if stats else None))
-        streams = [out[i, :sizes[i]].tobytes() if sizes[i] <= slot else b"" for i in range(n)]
-        if slot_bytes is not None:
-            extras["sizes"] = sizes
-            extras["slots"] = out
-        return (streams, extras) if extras else streams
+        return self._encode([pictures, references], [(prev_quantizer, "prev_quantizer"), (quantizer, "quantizer")], (), recon, stats, slot_bytes, stream)
 
 
 def encode_clips(frames, quantizer, gop, version, width, height, recon=False):

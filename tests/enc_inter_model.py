@@ -48,19 +48,13 @@ def unpack_mv(mv):
 
 
 def host_encode(W, H, version, pictures, refs, prev_q, q, slot_bytes=None, threads=1, pitch=None, ref_pitch=None):
-    """the host model over a batch -> dict(streams, bytes, recon, stats, mbs, mv, mvp (N, macroblocks) packed, forms)"""
+    """the host model over a batch -> the intra model's dict (enc_model.host_outputs) with mv, mvp (N, macroblocks) packed before forms"""
     L = host()
     pictures, refs = np.ascontiguousarray(pictures, np.uint8), np.ascontiguousarray(refs, np.uint8)
-    n, frame, nmb = pictures.shape[0], W * H * 3 // 2, (W // 16) * (H // 16)
     pq, q = np.ascontiguousarray(prev_q, np.uint8), np.ascontiguousarray(q, np.uint8)
-    slot = L.encp_host_bound(W, H) if slot_bytes is None else slot_bytes
-    out = {"streams": np.full((n, slot), 0xAA, np.uint8), "bytes": np.zeros(n, np.int32), "recon": np.zeros((n, frame), np.uint8),
-           "stats": np.zeros(n, STATS_DTYPE), "mbs": np.zeros((n, nmb), E.MB_DTYPE), "mv": np.zeros((n, nmb), np.uint32),
-           "mvp": np.zeros((n, nmb), np.uint32), "forms": np.zeros(4, np.uint32)}
-    rc = L.encp_host_inter(W, H, version, n, pictures.ctypes.data, pictures.shape[1] if pitch is None else pitch, refs.ctypes.data,
-                           refs.shape[1] if ref_pitch is None else ref_pitch, pq.ctypes.data, q.ctypes.data, out["streams"].ctypes.data, slot,
-                           out["bytes"].ctypes.data, out["recon"].ctypes.data, out["stats"].ctypes.data, out["mbs"].ctypes.data, out["mv"].ctypes.data,
-                           out["mvp"].ctypes.data, out["forms"].ctypes.data, threads)
+    out, args = E.host_outputs(W, H, pictures.shape[0], L.encp_host_bound(W, H) if slot_bytes is None else slot_bytes, STATS_DTYPE, mv=np.uint32, mvp=np.uint32)
+    rc = L.encp_host_inter(W, H, version, pictures.shape[0], pictures.ctypes.data, pictures.shape[1] if pitch is None else pitch, refs.ctypes.data,
+                           refs.shape[1] if ref_pitch is None else ref_pitch, pq.ctypes.data, q.ctypes.data, *args, threads)
     assert rc == 0, rc
     return out
 

@@ -61,18 +61,25 @@ def txref(tmpdir):
     return _REF
 
 
+def host_outputs(W, H, n, slot, stats_dtype, **more):
+    """what either host model fills -> (dict(streams (N, slot) uint8, bytes (N,), recon (N, frame), stats (N,), mbs (N, macroblocks), one
+    (N, macroblocks) array of dtype per name in `more`, forms (4,)), the arguments of the model's entry point from `streams` to `forms`)"""
+    nmb = (W // 16) * (H // 16)
+    out = {"streams": np.full((n, slot), 0xAA, np.uint8), "bytes": np.zeros(n, np.int32), "recon": np.zeros((n, W * H * 3 // 2), np.uint8),
+           "stats": np.zeros(n, stats_dtype), "mbs": np.zeros((n, nmb), MB_DTYPE), **{k: np.zeros((n, nmb), dt) for k, dt in more.items()},
+           "forms": np.zeros(4, np.uint32)}
+    ptrs = [a.ctypes.data for a in out.values()]  # in the entry points' order; the slot's size follows the slots
+    return out, ptrs[:1] + [slot] + ptrs[1:]
+
+
 def host_encode(W, H, version, pictures, quantizers, yuv_format=0, slot_bytes=None, threads=1, pitch=None):
-    """the host model over a batch -> dict(streams (N, slot) uint8, bytes (N,), recon (N, frame), stats (N,), mbs (N, macroblocks), forms (4,))"""
+    """the host model over a batch -> host_outputs' dict"""
     L = host()
     pictures = np.ascontiguousarray(pictures, np.uint8)
-    n, frame = pictures.shape[0], W * H * 3 // 2
     q = np.ascontiguousarray(quantizers, np.uint8)
-    slot = L.enc_host_bound(W, H) if slot_bytes is None else slot_bytes
-    out = {"streams": np.full((n, slot), 0xAA, np.uint8), "bytes": np.zeros(n, np.int32), "recon": np.zeros((n, frame), np.uint8),
-           "stats": np.zeros(n, STATS_DTYPE), "mbs": np.zeros((n, (W // 16) * (H // 16)), MB_DTYPE), "forms": np.zeros(4, np.uint32)}
-    rc = L.enc_host_intra(W, H, version, n, pictures.ctypes.data, pictures.shape[1] if pitch is None else pitch, q.ctypes.data, yuv_format,
-                          out["streams"].ctypes.data, slot, out["bytes"].ctypes.data, out["recon"].ctypes.data, out["stats"].ctypes.data,
-                          out["mbs"].ctypes.data, out["forms"].ctypes.data, threads)
+    out, args = host_outputs(W, H, pictures.shape[0], L.enc_host_bound(W, H) if slot_bytes is None else slot_bytes, STATS_DTYPE)
+    rc = L.enc_host_intra(W, H, version, pictures.shape[0], pictures.ctypes.data, pictures.shape[1] if pitch is None else pitch, q.ctypes.data, yuv_format,
+                          *args, threads)
     assert rc == 0, rc
     return out
 

@@ -1,10 +1,8 @@
 // mobi_encode_host.cpp -- TEST TOOL: the intra encoder on the CPU, from the product's own header (csrc/mobi_encode.h): the host model that
 // the kernels (csrc/mobi_encode.hip) are compared against byte for byte, and the thing the oracle judges without a GPU.
-// Built by mobiclipdecoder_amd/build.py (build_enchost) and, with sanitizers, into tests/tools/enc_host_main.cpp's program.
-#include <atomic>
-#include <thread>
-#include <vector>
-
+// The constants-once idiom and the picture pool are enc_host_pool.h's.
+// Built by mobiclipdecoder_amd/build.py (build_enc_host) and, with sanitizers, into tests/tools/enc_host_main.cpp's program.
+#include "enc_host_pool.h"
 #include "mobi_encode.h"
 
 extern "C" {
@@ -24,43 +22,21 @@ int enc_host_intra(uint32_t width, uint32_t height, int version, int n, const ui
   const int rc = mobi_enc_check_args(n, width, height, version, n, picture_pitch, quantizers, yuv_format, slot_bytes);
   if (rc) return rc;
   if (!i420 || !streams || !bytes_out || threads < 1) return -7;
-  static const MobiEncConst *K = [] {
-    MobiEncConst *k = new MobiEncConst;
-    mobi_enc_build_const(k);
-    return k;
-  }();
+  const MobiEncConst *K = enc_host_const(mobi_enc_build_const);
   const size_t frame = (size_t)width * height * 3 / 2, nmb = (size_t)(width / 16) * (height / 16);
-  std::atomic<int> next{0}, bad{0};
-  std::vector<std::vector<uint32_t>> tforms(threads, std::vector<uint32_t>(4, 0));
-  auto work = [&](int t) {
-    std::vector<uint8_t> rec(frame);
-    std::vector<MobiEncMb> mb(nmb);
-    for (int i; (i = next.fetch_add(1)) < n;) {
-      uint8_t *r = recon_i420 ? recon_i420 + (size_t)i * frame : rec.data();
-      MobiEncMb *m = mbs ? mbs + (size_t)i * nmb : mb.data();
-      if (!mobi_enc_picture(K, (int)width, (int)height, quantizers[i], yuv_format, i420 + (size_t)i * picture_pitch, streams + (size_t)i * slot_bytes,
-                            slot_bytes, bytes_out + i, r, stats ? stats + i : nullptr, m, tforms[t].data()))
-        bad++;
-    }
-  };
-  if (threads == 1) {
-    work(0);
-  } else {
-    std::vector<std::thread> pool;
-    for (int t = 0; t < threads; t++) pool.emplace_back(work, t);
-    for (auto &th : pool) th.join();
-  }
-  if (forms)
-    for (int t = 0; t < threads; t++)
-      for (int f = 0; f < 4; f++) forms[f] += tforms[t][f];
-  return bad ? 1 : 0;
+  return enc_host_pool(n, threads, forms, [&](int i, uint32_t *tforms) {
+    std::vector<uint8_t> rec(recon_i420 ? 0 : frame);
+    std::vector<MobiEncMb> mb(mbs ? 0 : nmb);
+    return mobi_enc_picture(K, (int)width, (int)height, quantizers[i], yuv_format, i420 + (size_t)i * picture_pitch, streams + (size_t)i * slot_bytes,
+                            slot_bytes, bytes_out + i, recon_i420 ? recon_i420 + (size_t)i * frame : rec.data(), stats ? stats + i : nullptr,
+                            mbs ? mbs + (size_t)i * nmb : mb.data(), tforms);
+  });
 }
 
 // every (|level|, run, last) the writer can meet: the length mobi_enc_symbol writes against the price mobi_tc_cost states.
 // Returns the number of disagreements; patterns [44 * 64 * 2] and lengths receive what was written for a positive level (may be NULL).
 int enc_host_symbol_walk(uint32_t *patterns, int32_t *lengths, int32_t *form_out) {
-  MobiEncConst *K = new MobiEncConst;
-  mobi_enc_build_const(K);
+  const MobiEncConst *K = enc_host_const(mobi_enc_build_const);
   int16_t ref[32 * 64 * 2];
   mobi_tc_build_ref(ref);
   int wrong = 0;
@@ -80,28 +56,24 @@ int enc_host_symbol_walk(uint32_t *patterns, int32_t *lengths, int32_t *form_out
           if (form_out) form_out[at] = form;
         }
       }
-  delete K;
   return wrong;
 }
 
 // one block through the block rule at ANY table quantiser (the encoder itself refuses q < 12, where alone a level can leave the raw
 // escape's 12 bits): src / pred 64 bytes; lev [64] scan order, rec [64]; out = {sad, bits, coded, clamp fallback, level-range fallback}
 void enc_host_block(int q, const uint8_t *src, const uint8_t *pred, int16_t *lev, uint8_t *rec, int32_t *out) {
-  MobiEncConst *K = new MobiEncConst;
-  mobi_enc_build_const(K);
+  const MobiEncConst *K = enc_host_const(mobi_enc_build_const);
   int s[64], p[64], r[64];
   for (int i = 0; i < 64; i++) { s[i] = src[i]; p[i] = pred[i]; }
   const MobiEncBlock b = mobi_enc_block(K, q, s, p, lev, r);
   for (int i = 0; i < 64; i++) rec[i] = (uint8_t)r[i];
   out[0] = b.sad; out[1] = b.bits; out[2] = b.coded; out[3] = b.clamp; out[4] = b.range;
-  delete K;
 }
 
 // the bit writer alone over given macroblock records (their bits fields are filled in): the stream into slot (slot_bytes, zeroed first);
 // returns its length in bytes, or 0 if it does not fit
 size_t enc_host_write(uint32_t width, uint32_t height, int q, int yuv_format, MobiEncMb *mbs, uint8_t *slot, size_t slot_bytes) {
-  MobiEncConst *K = new MobiEncConst;
-  mobi_enc_build_const(K);
+  const MobiEncConst *K = enc_host_const(mobi_enc_build_const);
   const size_t nmb = (size_t)(width / 16) * (height / 16);
   uint64_t total = 0;
   for (size_t i = 0; i < nmb; i++) {
@@ -117,7 +89,6 @@ size_t enc_host_write(uint32_t width, uint32_t height, int q, int yuv_format, Mo
     sink(mobi_enc_header(yuv_format, q), MOBI_ENC_HEADER_BITS);
     for (size_t i = 0; i < nmb; i++) mobi_enc_write_mb(K, mbs + i, [&](uint32_t v, int nb) { sink(v, nb); }, (uint32_t *)nullptr);
   }
-  delete K;
   return bytes <= slot_bytes ? (size_t)bytes : 0;
 }
 }

@@ -1,11 +1,9 @@
 // mobi_encode_inter_host.cpp -- TEST TOOL: the inter encoder on the CPU, from the product's own header (csrc/mobi_encode_inter.h): the host
 // model that the kernels (csrc/mobi_encode_inter.hip) are compared against byte for byte, and the thing the oracle judges without a GPU.
 // A scalar loop of its own: search, prediction and block coding share the kernels' rule functions, not their lane code.
-// Built by mobiclipdecoder_amd/build.py (build_encinterhost) and, with sanitizers, into tests/tools/enc_inter_host_main.cpp's program.
-#include <atomic>
-#include <thread>
-#include <vector>
-
+// The constants-once idiom and the picture pool are enc_host_pool.h's.
+// Built by mobiclipdecoder_amd/build.py (build_enc_host) and, with sanitizers, into tests/tools/enc_inter_host_main.cpp's program.
+#include "enc_host_pool.h"
 #include "mobi_encode_inter.h"
 
 extern "C" {
@@ -28,36 +26,16 @@ int encp_host_inter(uint32_t width, uint32_t height, int version, int n, const u
   const int rc = mobi_encp_check_args(n, width, height, version, n, picture_pitch, ref_pitch, prev_quantizers, quantizers, slot_bytes);
   if (rc) return rc;
   if (!i420 || !ref_i420 || !streams || !bytes_out || threads < 1) return -7;
-  static const MobiEncInterConst *K = [] {
-    MobiEncInterConst *k = new MobiEncInterConst;
-    mobi_encp_build_const(k);
-    return k;
-  }();
+  const MobiEncInterConst *K = enc_host_const(mobi_encp_build_const);
   const size_t frame = (size_t)width * height * 3 / 2, nmb = (size_t)(width / 16) * (height / 16);
-  std::atomic<int> next{0}, bad{0};
-  std::vector<std::vector<uint32_t>> tforms(threads, std::vector<uint32_t>(4, 0));
-  auto work = [&](int t) {
-    std::vector<uint8_t> rec(frame);
-    std::vector<MobiEncMb> mb(nmb);
-    std::vector<uint32_t> v(nmb), vp(nmb);
-    for (int i; (i = next.fetch_add(1)) < n;) {
-      if (!mobi_encp_picture(K, mobi_encp_ver(version), (int)width, (int)height, prev_quantizers[i], quantizers[i], i420 + (size_t)i * picture_pitch,
+  return enc_host_pool(n, threads, forms, [&](int i, uint32_t *tforms) {
+    std::vector<uint8_t> rec(recon_i420 ? 0 : frame);
+    std::vector<MobiEncMb> mb(mbs ? 0 : nmb);
+    std::vector<uint32_t> v(mv ? 0 : nmb), vp(mvp ? 0 : nmb);
+    return mobi_encp_picture(K, mobi_encp_ver(version), (int)width, (int)height, prev_quantizers[i], quantizers[i], i420 + (size_t)i * picture_pitch,
                              ref_i420 + (size_t)i * ref_pitch, streams + (size_t)i * slot_bytes, slot_bytes, bytes_out + i,
                              recon_i420 ? recon_i420 + (size_t)i * frame : rec.data(), stats ? stats + i : nullptr, mbs ? mbs + (size_t)i * nmb : mb.data(),
-                             mv ? mv + (size_t)i * nmb : v.data(), mvp ? mvp + (size_t)i * nmb : vp.data(), tforms[t].data()))
-        bad++;
-    }
-  };
-  if (threads == 1) {
-    work(0);
-  } else {
-    std::vector<std::thread> pool;
-    for (int t = 0; t < threads; t++) pool.emplace_back(work, t);
-    for (auto &th : pool) th.join();
-  }
-  if (forms)
-    for (int t = 0; t < threads; t++)
-      for (int f = 0; f < 4; f++) forms[f] += tforms[t][f];
-  return bad ? 1 : 0;
+                             mv ? mv + (size_t)i * nmb : v.data(), mvp ? mvp + (size_t)i * nmb : vp.data(), tforms);
+  });
 }
 }
