@@ -7,6 +7,8 @@
  * argmin of an integer cost ("Inter encoder").  It is NOT MobiEncoder.EncodeInter bit for bit.  MOBI_VERSION_MOFLEX3DS and
  * MOBI_VERSION_MODSDS; one reference (the previous frame), every macroblock one 16x16 leaf with a vector of at most 17 half-pels either
  * way whose three windows lie inside the picture, 8x8 transforms, VLC table 0.  Error codes: mobiclip_hip.h.
+ * mobiclip_encode_parts.h adds an opt-in mode of the same encoder object in which a macroblock may be split down to 8x8 leaves; what is
+ * said here holds for mode 0, the state after create.
  */
 #ifndef MOBICLIP_ENCODE_INTER_H
 #define MOBICLIP_ENCODE_INTER_H

@@ -1,12 +1,17 @@
-// mobi_encode_inter.cpp -- the C entry points of the inter encoder (include/mobiclip_encode_inter.h): the refusals, and the launch of the
-// three stages (mobi_encode_inter.hip).  The encoder object, the prologue of the call and the host-pointer twin are mobi_encode_ctx.h's;
+// mobi_encode_inter.cpp -- the C entry points of the inter encoder (include/mobiclip_encode_inter.h) and of its partition mode
+// (include/mobiclip_encode_parts.h): the refusals, and the launch of the three stages (mobi_encode_inter.hip; in mode 1
+// mobi_encode_parts.hip).  The encoder object, the prologue of the call and the host-pointer twin are mobi_encode_ctx.h's;
 // this encoder adds the vectors and their predictors, the previous frames' quantiser row and the staged references.
 #include "mobi_encode_ctx.h"
+#include "mobi_encode_parts.h"
 
 extern "C" int mobi_launch_encode_inter(const MobiEncInterArgs *a, int stages, hipStream_t s);
+extern "C" int mobi_launch_encode_parts(const MobiEncPartsArgs *a, int stages, hipStream_t s);
 
 struct mobi_enc_inter_ctx : MobiEncCtx {
   uint32_t *mv, *mvp; // carved with the rest
+  uint32_t *mv4;      // ... and the quadrants' vectors of mode 1
+  int partitions;     // the mode: 0 after create
   uint8_t *st_ref;    // the host-pointer call's copy of the references
 };
 
@@ -19,6 +24,14 @@ extern "C" __attribute__((visibility("default"))) void mobi_debug_encp_select(in
 #endif
 
 size_t mobi_enc_inter_stream_bound(uint32_t width, uint32_t height) { return mobi_encp_bound(width, height); }
+size_t mobi_enc_inter_stream_bound_partitions(uint32_t width, uint32_t height, int mode) { return mobi_encq_bound(width, height, mode); }
+
+int mobi_enc_inter_set_partitions(mobi_enc_inter_ctx *e, int mode) {
+  if (!e || (mode != 0 && mode != 1)) return MOBI_E_ARG;
+  e->partitions = mode;
+  return MOBI_OK;
+}
+int mobi_enc_inter_get_partitions(const mobi_enc_inter_ctx *e) { return e ? e->partitions : MOBI_E_ARG; }
 
 int mobi_enc_inter_check(int max_pictures, uint32_t width, uint32_t height, int version, int n, size_t picture_pitch, size_t ref_pitch,
                          const uint8_t *prev_quantizers, const uint8_t *quantizers, size_t slot_bytes) {
@@ -32,7 +45,8 @@ mobi_enc_inter_ctx *mobi_enc_inter_create(int max_pictures, uint32_t width, uint
   mobi_enc_inter_ctx *e = mobi_enc_ctx_new<mobi_enc_inter_ctx>(max_pictures, width, height, version, device);
   if (!e) return nullptr;
   const size_t cells = (size_t)max_pictures * e->nmb * 4;
-  return mobi_enc_ctx_carve(e, mobi_encp_build_const, 2, {{&e->mv, cells}, {&e->mvp, cells}}) ? e : nullptr; // quantiser rows: previous, current
+  // the constants of mode 1 begin with those of mode 0; quantiser rows: previous, current
+  return mobi_enc_ctx_carve(e, mobi_encq_build_const, 2, {{&e->mv, cells}, {&e->mvp, cells}, {&e->mv4, 4 * cells}}) ? e : nullptr;
 }
 
 void mobi_enc_inter_destroy(mobi_enc_inter_ctx *e) {
@@ -51,7 +65,7 @@ int mobi_enc_inter_async(mobi_enc_inter_ctx *e, void *stream, int n, const uint8
       (uintptr_t)bytes_out % 4 || (uintptr_t)stats % 8)
     return MOBI_E_ARG;
   hipStream_t s = (hipStream_t)stream;
-  MobiEncInterArgs a;
+  MobiEncPartsArgs a;
   memset((void *)&a, 0, sizeof a);
   rc = mobi_enc_ctx_begin(e, s, n, i420, picture_pitch, {prev_quantizers, quantizers}, streams, slot_bytes, bytes_out, recon_i420, stats, &a);
   if (rc != MOBI_OK) return rc;
@@ -63,7 +77,9 @@ int mobi_enc_inter_async(mobi_enc_inter_ctx *e, void *stream, int n, const uint8
   a.kp = (const MobiEncInterConst *)e->mem;
   a.pstats = stats;
   a.ver = mobi_encp_ver(e->version);
-  return mobi_launch_encode_inter(&a, g_stages, s) == 0 ? MOBI_OK : MOBI_E_DEVICE;
+  a.mv4 = e->mv4;
+  a.kq = (const MobiEncPartsConst *)e->mem;
+  return (e->partitions ? mobi_launch_encode_parts(&a, g_stages, s) : mobi_launch_encode_inter(&a, g_stages, s)) == 0 ? MOBI_OK : MOBI_E_DEVICE;
 }
 
 int mobi_enc_inter(mobi_enc_inter_ctx *e, int n, const uint8_t *i420, size_t picture_pitch, const uint8_t *ref_i420, size_t ref_pitch,

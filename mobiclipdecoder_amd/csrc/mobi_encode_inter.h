@@ -90,6 +90,13 @@ MOBI_TC_FN void mobi_encp_write_header(Put put, int q, int prev_q) {
   put(0u, 1); // a P-frame
   mobi_encp_put_se(put, q - prev_q);
 }
+// what follows a macroblock's partition tree (here and in mobi_encode_parts.h): ue(cbp), the coded blocks
+template <class Put>
+MOBI_TC_FN void mobi_encp_write_residual(const MobiEncInterConst *K, const MobiEncMb *m, Put put, uint32_t *forms) {
+  put(K->inv_cbp_p[m->cbp] + 1u, mobi_enc_ue_bits(K->inv_cbp_p[m->cbp]));
+  for (int k = 0; k < 6; k++)
+    if ((m->cbp >> k) & 1) mobi_enc_write_block(K, m->lev[k], put, forms);
+}
 template <class Put>
 MOBI_TC_FN void mobi_encp_write_mb(const MobiEncInterConst *K, int ver, const MobiEncMb *m, uint32_t v, uint32_t pred, Put put, uint32_t *forms) {
   const int code = v != pred;
@@ -98,9 +105,7 @@ MOBI_TC_FN void mobi_encp_write_mb(const MobiEncInterConst *K, int ver, const Mo
     mobi_encp_put_se(put, mobi_encp_dx(v) - mobi_encp_dx(pred));
     mobi_encp_put_se(put, mobi_encp_dy(v) - mobi_encp_dy(pred));
   }
-  put(K->inv_cbp_p[m->cbp] + 1u, mobi_enc_ue_bits(K->inv_cbp_p[m->cbp]));
-  for (int k = 0; k < 6; k++)
-    if ((m->cbp >> k) & 1) mobi_enc_write_block(K, m->lev[k], put, forms);
+  mobi_encp_write_residual(K, m, put, forms);
 }
 
 // one call's launch arguments (device pointers): the intra call's, with its stats NULL and yuv_format unused, and the inter call's own

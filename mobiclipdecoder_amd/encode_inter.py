@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from .binding import bind
-from .decoder import load_library
+from .decoder import MobiclipError, check_rc, load_library
 from .encode import MobiclipIntraEncoder, _Encoder
 
 # mobi_enc_inter_stats, one per picture
@@ -27,19 +27,46 @@ _SIGS = {
 }
 
 
+# the partition mode; names must match include/mobiclip_encode_parts.h (tests/test_encode_parts_model.py checks header, library and this table)
+_PARTS_SIGS = {
+    "mobi_enc_inter_set_partitions": (C.c_int, [C.c_void_p, C.c_int]),
+    "mobi_enc_inter_get_partitions": (C.c_int, [C.c_void_p]),
+    "mobi_enc_inter_stream_bound_partitions": (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_int]),
+}
+# mobi_enc_inter_stats.reserved in the partition mode (MOBI_ENC_PARTS_STAT_*): macroblocks sent split, leaves sent
+STAT_SPLIT, STAT_LEAVES = 0, 1
+
+
 def _lib():
-    return bind(load_library(), _SIGS)
+    return bind(bind(load_library(), _SIGS), _PARTS_SIGS)
 
 
-def stream_bound(width, height):
-    """mobi_enc_inter_stream_bound: no P-frame of a width x height picture is longer (bytes, a multiple of 4); 0 for refused dimensions"""
-    return int(_lib().mobi_enc_inter_stream_bound(width, height))
+def stream_bound(width, height, partitions=False):
+    """mobi_enc_inter_stream_bound[_partitions]: no P-frame of a width x height picture is longer (bytes, a multiple of 4); 0 for refused
+    dimensions"""
+    return int(_lib().mobi_enc_inter_stream_bound_partitions(width, height, int(bool(partitions))))
 
 
 class MobiclipInterEncoder(_Encoder):
-    """mobi_enc_inter_ctx: P-frames of width x height pictures for MobiclipVersion.Moflex3DS or .ModsDS, up to max_pictures per call."""
+    """mobi_enc_inter_ctx: P-frames of width x height pictures for MobiclipVersion.Moflex3DS or .ModsDS, up to max_pictures per call.
+    partitions=True: macroblocks may be split into 16x8, 8x16 and 8x8 leaves with a vector each (include/mobiclip_encode_parts.h)."""
     _destroy = "mobi_enc_inter_destroy"
     _sigs, _prefix, _call, _what, _stats, _no_extra = _SIGS, "mobi_enc_inter", "mobi_enc_inter", ("pictures", "references"), STATS_DTYPE, ()
+
+    def __init__(self, width, height, version, max_pictures, device=None, partitions=False):
+        super().__init__(width, height, version, max_pictures, device)
+        bind(self._lib, _PARTS_SIGS)
+        self.partitions = False
+        if partitions:
+            self.set_partitions(True)
+
+    def set_partitions(self, on):
+        """mobi_enc_inter_set_partitions: holds for the calls of encode() after it; stream_bound follows the mode"""
+        if not self._h:
+            raise MobiclipError("encoder is closed")
+        check_rc(self._lib.mobi_enc_inter_set_partitions(self._h, int(bool(on))))
+        self.partitions = bool(self._lib.mobi_enc_inter_get_partitions(self._h))
+        self.stream_bound = int(self._lib.mobi_enc_inter_stream_bound_partitions(self.width, self.height, int(self.partitions)))
 
     def encode(self, pictures, references, prev_quantizer, quantizer, recon=False, stats=False, slot_bytes=None, stream=None):
         """pictures, references: (N, width * height * 3 / 2) uint8 each, packed I420 -- torch tensors on the encoder's device (encoded
@@ -53,10 +80,11 @@ class MobiclipInterEncoder(_Encoder):
         return self._encode([pictures, references], [(prev_quantizer, "prev_quantizer"), (quantizer, "quantizer")], (), recon, stats, slot_bytes, stream)
 
 
-def encode_clips(frames, quantizer, gop, version, width, height, recon=False):
+def encode_clips(frames, quantizer, gop, version, width, height, recon=False, partitions=False):
     """frames: an (N, T, width * height * 3 / 2) uint8 torch tensor on a GPU, packed I420 (what a clip sink or export_tensor("i420")
     writes).  Frame 0 and every gop-th frame of every clip go through the intra encoder, the rest through the inter encoder; the
     reconstructions stay on the device and become the next frame's reference.  quantizer: an int in [12, 52] or T of them, one per frame.
+    partitions: the inter encoder's mode (MobiclipInterEncoder).
 
     Returns, per clip, the list of its T frame streams (bytes); with recon=True also the (N, T, frame) uint8 tensor of reconstructions:
     what a decoder fed the streams of clip i in order holds after each."""
@@ -71,7 +99,7 @@ def encode_clips(frames, quantizer, gop, version, width, height, recon=False):
         raise ValueError("one quantizer, or one per frame")
     device = frames.device.index or 0
     intra = MobiclipIntraEncoder(width, height, version, n, device=device)
-    inter = MobiclipInterEncoder(width, height, version, n, device=device) if t_n > 1 and int(gop) > 1 else None
+    inter = MobiclipInterEncoder(width, height, version, n, device=device, partitions=partitions) if t_n > 1 and int(gop) > 1 else None
     slot = max(intra.stream_bound, inter.stream_bound if inter else 0)
     held, rec_all, ref = [], [], None
     try:

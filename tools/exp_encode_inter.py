@@ -7,14 +7,19 @@ current stream, warm-up, HIP-event timing over `--iters` calls); prints ONE JSON
                            noise on top; the reference is the intra encoder's reconstruction of the frame before at the same quantiser
                noisy       the same with strong noise on every frame: the search finds little, the residual is large
              CONTENT MATTERS: vectors, bits and coded blocks follow the pictures and the quantiser, and no real media exists in this
+               two_motion  the translated mix with every picture cut into 32x32 tiles in checkerboard order, the tiles' corners at
+                           8 mod 16, the two colours moved by different vectors: every other macroblock straddles two motions
              repository -- read the rates as those of these mixes, not of a film.
   per mix, N in (512, 4096) and q in (26, 40):  search, code and write (scan + bits) each timed alone by HIP events, the whole call,
              pictures/s, bytes per picture, macroblocks by vector kind; beside it the INTRA encoder's whole call on the same pictures
   host       the first `--host-pictures` pairs through the host model (tests/tools/mobi_encode_inter_host.cpp) on 16 threads of the
              same machine; its streams must equal the GPU's (equals_gpu)
+  --partitions  every configuration twice, side by side: mode 0 (keys as without the switch) and mode 1 (keys + "_parts": partitions
+             down to 8x8, include/mobiclip_encode_parts.h), with the share of split macroblocks, the leaves per picture and the search's
+             time as a multiple of mode 0's; the host model is then tests/tools/mobi_encode_parts_host.cpp
 The stage switch is a hook of the profiling twin (libmobiclip_hip_prof.so, mobi_debug_encp_select), which this tool loads.
 For `rocprofv3 --kernel-trace --stats` or `--pmc` runs (--no-host --counts 512 --quantizers 26) the kernels are mobi_encp_search /
-mobi_encp_code / mobi_encp_scan / mobi_encp_write.
+mobi_encp_code / mobi_encp_scan / mobi_encp_write (mode 1: mobi_encq_*).
 """
 import argparse
 import ctypes as C
@@ -46,7 +51,7 @@ def pairs(mix, rng):
         return a
     tex = texture(H + 2 * M2, W + 2 * M2, 32, 224, 3)
     ctex = [texture(H // 2 + M2, W // 2 + M2, 64, 192, 2) for _ in range(2)]
-    amp = 3 if mix == "translated" else 10
+    amp = 10 if mix == "noisy" else 3
 
     def cut(a, x2, y2, w, h, m0):  # the picture at half-pel offset (x2, y2): whole part a shift, an odd part the mean of two neighbours
         x, y = m0 + (x2 >> 1), m0 + (y2 >> 1)
@@ -59,6 +64,12 @@ def pairs(mix, rng):
         return np.clip(p + rng.integers(-amp, amp + 1, p.shape), 0, 255).astype(np.uint8)
     prev = np.stack([picture(0, 0) for _ in MOVES])
     cur = np.stack([picture(dx, dy) for dx, dy in MOVES])
+    if mix == "two_motion":  # the odd tiles from the picture moved by another vector
+        yy, xx = np.mgrid[0:H, 0:W]
+        odd = (((xx + 8) // 32 + (yy + 8) // 32) & 1).astype(bool)
+        mask = np.concatenate([odd.ravel(), odd[::2, ::2].ravel(), odd[::2, ::2].ravel()])
+        other = np.stack([picture(*MOVES[(i + 5) % len(MOVES)]) for i in range(len(MOVES))])
+        cur[:, mask] = other[:, mask]
     return prev, cur
 
 
@@ -80,6 +91,7 @@ def main():
     ap.add_argument("--counts", type=int, nargs="+", default=[512, 4096])
     ap.add_argument("--quantizers", type=int, nargs="+", default=[26, 40])
     ap.add_argument("--mixes", nargs="+", default=["translated", "noisy"])
+    ap.add_argument("--partitions", action="store_true")
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--host-threads", type=int, default=16)
@@ -127,33 +139,49 @@ def main():
                 t_intra = timed(lambda: intra(n), s, a.iters, a.warmup)
                 isz = float(sizes[:n].float().mean().item())
                 assert int(sizes[:n].max().item()) <= slot
-                select(7)
-                whole = timed(lambda: call(n), s, a.iters, a.warmup)
-                sz = sizes[:n].cpu().numpy()
-                st = stats[:n].cpu().numpy().view(encode_inter.STATS_DTYPE).reshape(-1)
-                assert sz.max() <= slot
-                t = {}
-                for name, bit in (("search", 1), ("code", 2), ("write", 4)):
-                    select(bit)
-                    t[name] = timed(lambda: call(n), s, a.iters, 1)
-                select(7)
-                res[k] = {"whole_ms": whole, "search_ms": t["search"], "code_ms": t["code"], "write_ms": t["write"], "pictures_per_s": n / whole * 1e3,
-                          "gpixels_per_s": n * W * H / whole / 1e6, "bytes_per_picture": float(sz.mean()), "coded_blocks_per_picture": float(st["coded_blocks"].mean()),
-                          "code0_per_picture": float(st["code0"].mean()), "nonzero_mv_per_picture": float(st["nonzero_mv"].mean()),
-                          "halfpel_mv_per_picture": float(st["halfpel_mv"].mean()), "intra_whole_ms": t_intra, "intra_pictures_per_s": n / t_intra * 1e3,
-                          "intra_bytes_per_picture": isz}
-            if not a.no_host:
+                for mode in (0, 1) if a.partitions else (0,):
+                    enc.set_partitions(bool(mode))
+                    select(7)
+                    whole = timed(lambda: call(n), s, a.iters, a.warmup)
+                    sz = sizes[:n].cpu().numpy()
+                    st = stats[:n].cpu().numpy().view(encode_inter.STATS_DTYPE).reshape(-1)
+                    assert sz.max() <= slot
+                    t = {}
+                    for name, bit in (("search", 1), ("code", 2), ("write", 4)):
+                        select(bit)
+                        t[name] = timed(lambda: call(n), s, a.iters, 1)
+                    select(7)
+                    r = {"whole_ms": whole, "search_ms": t["search"], "code_ms": t["code"], "write_ms": t["write"], "pictures_per_s": n / whole * 1e3,
+                         "gpixels_per_s": n * W * H / whole / 1e6, "bytes_per_picture": float(sz.mean()), "coded_blocks_per_picture": float(st["coded_blocks"].mean()),
+                         "code0_per_picture": float(st["code0"].mean()), "nonzero_mv_per_picture": float(st["nonzero_mv"].mean()),
+                         "halfpel_mv_per_picture": float(st["halfpel_mv"].mean()), "sad_per_picture": float(st["sad"].mean()), "intra_whole_ms": t_intra,
+                         "intra_pictures_per_s": n / t_intra * 1e3, "intra_bytes_per_picture": isz}
+                    if mode:
+                        r.update(split_share=float(st["reserved"][:, encode_inter.STAT_SPLIT].mean()) / ((W // 16) * (H // 16)),
+                                 leaves_per_picture=float(st["reserved"][:, encode_inter.STAT_LEAVES].mean()), search_vs_mode0=t["search"] / res[k]["search_ms"])
+                    res[k + "_parts" if mode else k] = r
+                    print("done", k, "mode", mode, file=sys.stderr, flush=True)
+            for mode in (0, 1) if a.partitions else (0,):
+                if a.no_host:
+                    break
                 from tests import enc_inter_model as M
+                from tests import enc_parts_model as Q
                 hn = a.host_pictures
                 hp, hr = src[:hn].cpu().numpy(), ref[:hn].cpu().numpy()
                 t0 = time.perf_counter()
-                r = M.host_encode(W, H, VERSION, hp, hr, qs[:hn], qs[:hn], slot_bytes=slot, threads=a.host_threads)
+                if a.partitions:
+                    r = Q.host_encode(W, H, VERSION, mode, hp, hr, qs[:hn], qs[:hn], slot_bytes=slot, threads=a.host_threads)
+                else:
+                    r = M.host_encode(W, H, VERSION, hp, hr, qs[:hn], qs[:hn], slot_bytes=slot, threads=a.host_threads)
                 dt = time.perf_counter() - t0
+                enc.set_partitions(bool(mode))
+                print("host done", mix, q, "mode", mode, round(dt, 1), "s", file=sys.stderr, flush=True)
                 call(hn)
                 s.synchronize()
-                res[f"{mix}_host_n{hn}_q{q}"] = {"threads": a.host_threads, "ms": dt * 1e3, "pictures_per_s": hn / dt,
-                                                 "equals_gpu": bool(np.array_equal(r["streams"], out[:hn].cpu().numpy()) and
-                                                                    np.array_equal(r["bytes"], sizes[:hn].cpu().numpy()))}
+                res[f"{mix}_host_n{hn}_q{q}" + ("_parts" if mode else "")] = {"threads": a.host_threads, "ms": dt * 1e3, "pictures_per_s": hn / dt,
+                                                                              "equals_gpu": bool(np.array_equal(r["streams"], out[:hn].cpu().numpy()) and
+                                                                                                 np.array_equal(r["bytes"], sizes[:hn].cpu().numpy()))}
+            enc.set_partitions(False)
     enc.close()
     ienc.close()
     line = json.dumps(json.loads(json.dumps(res), parse_float=lambda x: round(float(x), 4)))
