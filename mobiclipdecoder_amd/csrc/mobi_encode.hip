@@ -217,7 +217,8 @@ struct IntraSpeller {
 extern "C" __global__ __launch_bounds__(256) void mobi_enc_scan(MobiEncArgs A) { mobi_enc_scan_body<IntraSpeller>(A); }
 extern "C" __global__ __launch_bounds__(64) void mobi_enc_write(MobiEncArgs A) { mobi_enc_write_body<IntraSpeller>(A); }
 
-// stages: bit 0 = decide, bit 1 = write (the product always runs both); loop_shape: the profiling twin's other stage-1 shape
+// stages: bit 0 = decide, bit 1 = scan, bit 2 = write (a frame runs all three; a trial of the rate rule, mobi_encode_rate.h, stops behind the
+// scan and touches no slot); loop_shape: the profiling twin's other stage-1 shape
 extern "C" int mobi_launch_encode(const MobiEncArgs *a, int stages, int loop_shape, hipStream_t s) {
   const int nmb = a->mbw * a->mbh;
   if (stages & 1) {
@@ -231,9 +232,7 @@ extern "C" int mobi_launch_encode(const MobiEncArgs *a, int stages, int loop_sha
         hipLaunchKernelGGL(mobi_enc_decide_diag, dim3((count + WAVES - 1) / WAVES, a->n), dim3(WAVES * 64), 0, s, *a, d);
       }
   }
-  if (stages & 2) {
-    hipLaunchKernelGGL(mobi_enc_scan, dim3(a->n), dim3(256), 0, s, *a);
-    hipLaunchKernelGGL(mobi_enc_write, dim3((nmb + 63) / 64, a->n), dim3(64), 0, s, *a);
-  }
+  if (stages & 2) hipLaunchKernelGGL(mobi_enc_scan, dim3(a->n), dim3(256), 0, s, *a);
+  if (stages & 4) hipLaunchKernelGGL(mobi_enc_write, dim3((nmb + 63) / 64, a->n), dim3(64), 0, s, *a);
   return (int)hipGetLastError();
 }

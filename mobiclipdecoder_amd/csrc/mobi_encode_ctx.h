@@ -1,7 +1,8 @@
 // mobi_encode_ctx.h -- HOST ONLY: what the entry points of the two encoders (mobi_encode.cpp, mobi_encode_inter.cpp) share, once: the
 // common part of the encoder object, the carve of its one device allocation, destroy, the prologue of an _async call (device, quantiser
 // rows, zeroed outputs, the MobiEncArgs base) and the host-pointer twin (staging made at first use, kept and grown; the copies back).
-// The refusals and the alignment rules stay with each entry point: they differ.
+// The refusals and the alignment rules stay with each entry point: they differ.  mobi_enc_ctx_rate is the loop of the two _target_async
+// calls (include/mobiclip_encode_rate.h): the rate rule's kernels around the encoder's own launches.
 #ifndef MOBI_ENCODE_CTX_H
 #define MOBI_ENCODE_CTX_H
 #include <hip/hip_runtime_api.h>
@@ -12,7 +13,10 @@
 #include <vector>
 
 #include "../../include/mobiclip_hip.h"
-#include "mobi_encode_inter.h"
+#include "mobi_encode_rate.h"
+
+extern "C" int mobi_launch_rate_begin(const MobiEncRateArgs *a, int rounds, hipStream_t s);
+extern "C" int mobi_launch_rate_step(const MobiEncRateArgs *a, int last, hipStream_t s);
 
 enum { MOBI_ENC_STATS_BYTES = 64 }; // either encoder's statistics record: zeroed and staged as bytes
 static_assert(sizeof(mobi_enc_stats) == MOBI_ENC_STATS_BYTES && sizeof(mobi_enc_inter_stats) == MOBI_ENC_STATS_BYTES, "a statistics record is 64 bytes");
@@ -27,6 +31,8 @@ struct MobiEncCtx {
   MobiEncMb *mbs;
   uint32_t *mb_off, *fits;
   uint8_t *q, *rec;
+  // the rate rule's state between its rounds, an allocation of its own made at create: a row of lo, a row of hi
+  uint8_t *rate;
   // the host-pointer call's device copies, made at its first use and kept: pictures in, reconstruction, lengths, statistics; the slots
   // grow with the largest slot_bytes seen
   uint8_t *st_in, *st_rec, *st_streams, *st_bytes, *st_stats;
@@ -37,7 +43,7 @@ struct MobiEncCtx {
 inline void mobi_enc_ctx_destroy(MobiEncCtx *e) {
   if (!e) return;
   if (e->st_stream) (void)hipStreamDestroy(e->st_stream);
-  for (void *p : {(void *)e->mem, (void *)e->st_in, (void *)e->st_rec, (void *)e->st_streams, (void *)e->st_bytes, (void *)e->st_stats})
+  for (void *p : {(void *)e->mem, (void *)e->rate, (void *)e->st_in, (void *)e->st_rec, (void *)e->st_streams, (void *)e->st_bytes, (void *)e->st_stats})
     if (p) (void)hipFree(p);
   free(e);
 }
@@ -75,7 +81,8 @@ bool mobi_enc_ctx_carve(MobiEncCtx *e, void (*build)(Const *), int q_rows, std::
   for (const MobiEncPart &p : parts) total += up(p.bytes);
   Const *h = new Const;
   build(h);
-  const bool ok = hipMalloc((void **)&e->mem, total) == hipSuccess && hipMemcpy(e->mem, h, sizeof *h, hipMemcpyHostToDevice) == hipSuccess;
+  const bool ok = hipMalloc((void **)&e->mem, total) == hipSuccess && hipMemcpy(e->mem, h, sizeof *h, hipMemcpyHostToDevice) == hipSuccess &&
+                  hipMalloc((void **)&e->rate, 2 * N) == hipSuccess;
   delete h;
   if (!ok) {
     mobi_enc_ctx_destroy(e);
@@ -119,6 +126,34 @@ inline int mobi_enc_ctx_begin(const MobiEncCtx *e, hipStream_t s, int n, const u
   a->mbh = (int32_t)(e->height / 16);
   a->n = n;
   return MOBI_OK;
+}
+
+// The loop of a _target_async call behind mobi_enc_ctx_begin (called with no quantiser rows: they are made here, on the device).
+// launch(stages) enqueues the encoder's stage kernels and answers 0; `trial` is its stages up to and including the scan -- no slot is
+// written or zeroed --, `whole` the frame's.  prev_in / prev_row: the inter encoder's previous quantisers, the caller's and the
+// encoder's row (NULL for I-frames); q_row: the row the stage kernels read.  Everything is enqueued on s; the host reads no device value.
+template <class Launch>
+int mobi_enc_ctx_rate(const MobiEncCtx *e, hipStream_t s, int n, const int32_t *target_bytes, int qmin, int qmax, const uint8_t *prev_in, uint8_t *prev_row,
+                      uint8_t *q_row, uint8_t *quantizers_out, const int32_t *bytes_out, void *stats, int trial, int whole, Launch launch) {
+  MobiEncRateArgs r;
+  memset(&r, 0, sizeof r);
+  r.target = target_bytes;
+  r.prev_in = prev_in;
+  r.prev_q = prev_row;
+  r.q = q_row;
+  r.lo = e->rate;
+  r.hi = e->rate + (size_t)e->max_pictures;
+  r.q_out = quantizers_out;
+  r.bytes = bytes_out;
+  r.stats = (uint64_t *)stats;
+  r.n = n;
+  r.qmin = qmin;
+  r.qmax = qmax;
+  const int rounds = mobi_enc_rate_rounds_of(qmin, qmax);
+  if (mobi_launch_rate_begin(&r, rounds, s) != 0) return MOBI_E_DEVICE;
+  for (int k = 0; k < rounds; k++)
+    if (launch(trial) != 0 || mobi_launch_rate_step(&r, k == rounds - 1, s) != 0) return MOBI_E_DEVICE;
+  return launch(whole) == 0 ? MOBI_OK : MOBI_E_DEVICE;
 }
 
 // The host-pointer twin of an _async call, its arguments accepted: the pictures up into st_in, `call(stream, slots)` -- the encoder's

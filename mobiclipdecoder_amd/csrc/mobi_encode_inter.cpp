@@ -1,7 +1,7 @@
 // mobi_encode_inter.cpp -- the C entry points of the inter encoder (include/mobiclip_encode_inter.h) and of its partition mode
 // (include/mobiclip_encode_parts.h): the refusals, and the launch of the three stages (mobi_encode_inter.hip; in mode 1
-// mobi_encode_parts.hip).  The encoder object, the prologue of the call and the host-pointer twin are mobi_encode_ctx.h's;
-// this encoder adds the vectors and their predictors, the previous frames' quantiser row and the staged references.
+// mobi_encode_parts.hip), and the inter encoder's call with byte targets (include/mobiclip_encode_rate.h).  The encoder object, the
+// prologue of the call, the loop of the target call and the host-pointer twin are mobi_encode_ctx.h's; this encoder adds the vectors and their predictors, the previous frames' quantiser row and the staged references.
 #include "mobi_encode_ctx.h"
 #include "mobi_encode_parts.h"
 
@@ -16,7 +16,7 @@ struct mobi_enc_inter_ctx : MobiEncCtx {
 };
 
 namespace {
-int g_stages = 7; // what the launch runs; only the profiling twin's hook below changes it (tools/exp_encode_inter.py)
+int g_stages = 15; // what the launch runs; only the profiling twin's hook below changes it (tools/exp_encode_inter.py)
 } // namespace
 
 #if defined(MOBI_PROFILING)
@@ -80,6 +80,40 @@ int mobi_enc_inter_async(mobi_enc_inter_ctx *e, void *stream, int n, const uint8
   a.mv4 = e->mv4;
   a.kq = (const MobiEncPartsConst *)e->mem;
   return (e->partitions ? mobi_launch_encode_parts(&a, g_stages, s) : mobi_launch_encode_inter(&a, g_stages, s)) == 0 ? MOBI_OK : MOBI_E_DEVICE;
+}
+
+int mobi_enc_inter_target_async(mobi_enc_inter_ctx *e, void *stream, int n, const uint8_t *i420, size_t picture_pitch, const uint8_t *ref_i420,
+                                size_t ref_pitch, const uint8_t *prev_quantizers, const int32_t *target_bytes, int qmin, int qmax, uint8_t *streams,
+                                size_t slot_bytes, int32_t *bytes_out, uint8_t *recon_i420, mobi_enc_inter_stats *stats, uint8_t *quantizers_out) {
+  if (!e) return MOBI_E_ARG;
+  const uint8_t q1 = MOBI_ENC_QMIN; // both quantiser rows are made on the device: the check sees one that passes
+  int rc = mobi_encp_check_args(e->max_pictures, e->width, e->height, e->version, 1, picture_pitch, ref_pitch, &q1, &q1, slot_bytes);
+  if (rc != MOBI_OK) return rc;
+  if (n < 1 || n > e->max_pictures || !prev_quantizers || mobi_enc_rate_check_args(target_bytes, qmin, qmax, quantizers_out) != 0) return MOBI_E_ARG;
+  if (!i420 || !ref_i420 || !streams || !bytes_out || (uintptr_t)i420 % 8 || (uintptr_t)ref_i420 % 8 || (uintptr_t)streams % 4 || (uintptr_t)recon_i420 % 8 ||
+      (uintptr_t)bytes_out % 4 || (uintptr_t)stats % 8)
+    return MOBI_E_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  MobiEncPartsArgs a;
+  memset((void *)&a, 0, sizeof a);
+  rc = mobi_enc_ctx_begin(e, s, n, i420, picture_pitch, {}, streams, slot_bytes, bytes_out, recon_i420, stats, &a);
+  if (rc != MOBI_OK) return rc;
+  uint8_t *q_row = e->q + (size_t)e->max_pictures; // rows: previous, current
+  a.q = q_row;
+  a.ref = ref_i420;
+  a.ref_pitch = ref_pitch;
+  a.prev_q = e->q;
+  a.mv = e->mv;
+  a.mvp = e->mvp;
+  a.kp = (const MobiEncInterConst *)e->mem;
+  a.pstats = stats;
+  a.ver = mobi_encp_ver(e->version);
+  a.mv4 = e->mv4;
+  a.kq = (const MobiEncPartsConst *)e->mem;
+  // a trial: search, code and scan; the profiling twin's stage switch holds for the final encode alone
+  return mobi_enc_ctx_rate(e, s, n, target_bytes, qmin, qmax, prev_quantizers, e->q, q_row, quantizers_out, bytes_out, stats, 7, g_stages, [&](int stages) {
+    return e->partitions ? mobi_launch_encode_parts(&a, stages, s) : mobi_launch_encode_inter(&a, stages, s);
+  });
 }
 
 int mobi_enc_inter(mobi_enc_inter_ctx *e, int n, const uint8_t *i420, size_t picture_pitch, const uint8_t *ref_i420, size_t ref_pitch,

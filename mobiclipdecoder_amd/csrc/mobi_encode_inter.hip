@@ -232,14 +232,13 @@ struct InterSpeller {
 extern "C" __global__ __launch_bounds__(256) void mobi_encp_scan(MobiEncInterArgs A) { mobi_enc_scan_body<InterSpeller>(A); }
 extern "C" __global__ __launch_bounds__(64) void mobi_encp_write(MobiEncInterArgs A) { mobi_enc_write_body<InterSpeller>(A); }
 
-// stages: bit 0 = search, bit 1 = code, bit 2 = write (the product always runs all three)
+// stages: bit 0 = search, bit 1 = code, bit 2 = scan, bit 3 = write (a frame runs all four; a trial of the rate rule, mobi_encode_rate.h,
+// stops behind the scan and touches no slot)
 extern "C" int mobi_launch_encode_inter(const MobiEncInterArgs *a, int stages, hipStream_t s) {
   const int nmb = a->mbw * a->mbh;
   if (stages & 1) hipLaunchKernelGGL(mobi_encp_search, dim3(nmb, a->n), dim3(64), 0, s, *a);
   if (stages & 2) hipLaunchKernelGGL(mobi_encp_code, dim3((nmb + WAVES - 1) / WAVES, a->n), dim3(WAVES * 64), 0, s, *a);
-  if (stages & 4) {
-    hipLaunchKernelGGL(mobi_encp_scan, dim3(a->n), dim3(256), 0, s, *a);
-    hipLaunchKernelGGL(mobi_encp_write, dim3((nmb + 63) / 64, a->n), dim3(64), 0, s, *a);
-  }
+  if (stages & 4) hipLaunchKernelGGL(mobi_encp_scan, dim3(a->n), dim3(256), 0, s, *a);
+  if (stages & 8) hipLaunchKernelGGL(mobi_encp_write, dim3((nmb + 63) / 64, a->n), dim3(64), 0, s, *a);
   return (int)hipGetLastError();
 }

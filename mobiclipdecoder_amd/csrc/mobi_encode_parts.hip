@@ -341,9 +341,7 @@ extern "C" int mobi_launch_encode_parts(const MobiEncPartsArgs *a, int stages, h
   const int nmb = a->mbw * a->mbh;
   if (stages & 1) hipLaunchKernelGGL(mobi_encq_search, dim3(nmb, a->n), dim3(64), 0, s, *a);
   if (stages & 2) hipLaunchKernelGGL(mobi_encq_code, dim3((nmb + WAVES - 1) / WAVES, a->n), dim3(WAVES * 64), 0, s, *a);
-  if (stages & 4) {
-    hipLaunchKernelGGL(mobi_encq_scan, dim3(a->n), dim3(256), 0, s, *a);
-    hipLaunchKernelGGL(mobi_encq_write, dim3((nmb + 63) / 64, a->n), dim3(64), 0, s, *a);
-  }
+  if (stages & 4) hipLaunchKernelGGL(mobi_encq_scan, dim3(a->n), dim3(256), 0, s, *a);
+  if (stages & 8) hipLaunchKernelGGL(mobi_encq_write, dim3((nmb + 63) / 64, a->n), dim3(64), 0, s, *a);
   return (int)hipGetLastError();
 }

@@ -145,3 +145,13 @@ class MobiclipIntraEncoder(_Encoder):
         With recon and / or stats a dict follows as the last element: "recon" (N, frame) uint8, "stats" (N,) STATS_DTYPE (for the
         unsynchronised torch form an (N, 64) uint8 tensor: .cpu().numpy().view(STATS_DTYPE))."""
         return self._encode([pictures], [(quantizer, "quantizer")], (yuv_format,), recon, stats, slot_bytes, stream)
+
+    def encode_target(self, pictures, target_bytes, qmin=12, qmax=52, yuv_format=0, recon=False, stats=False, slot_bytes=None, stream=None):
+        """encode() with a byte target per picture in place of the quantiser (include/mobiclip_encode_rate.h): the quantiser is found on the
+        GPU by a bisection of [qmin, qmax] over trial encodes; the stream is no longer than its target, or its quantiser is qmax.
+        pictures: a torch tensor on the encoder's device only.  target_bytes: an int, one per picture, or an (N,) int32 tensor on the device.
+
+        Returns what encode() returns for a tensor, the dict always present and holding "quantizer": the (N,) uint8 chosen quantisers (a
+        device tensor in the unsynchronised form, i.e. with slot_bytes given)."""
+        from .encode_rate import encode_target
+        return encode_target(self, "mobi_enc_intra_target_async", [pictures], None, target_bytes, qmin, qmax, (yuv_format,), recon, stats, slot_bytes, stream)

@@ -79,38 +79,73 @@ class MobiclipInterEncoder(_Encoder):
         "stats" (N,) STATS_DTYPE, for the unsynchronised torch form an (N, 64) uint8 tensor)."""
         return self._encode([pictures, references], [(prev_quantizer, "prev_quantizer"), (quantizer, "quantizer")], (), recon, stats, slot_bytes, stream)
 
+    def encode_target(self, pictures, references, prev_quantizer, target_bytes, qmin=12, qmax=52, recon=False, stats=False, slot_bytes=None, stream=None):
+        """encode() with a byte target per picture in place of the quantiser (include/mobiclip_encode_rate.h), in either partition mode: the
+        quantiser is found on the GPU by a bisection of [qmin, qmax] over trial encodes; the stream is no longer than its target, or its
+        quantiser is qmax.  pictures, references: torch tensors on the encoder's device only.  prev_quantizer: an int, one per picture, or
+        an (N,) uint8 tensor on the device -- the "quantizer" of the call that made the references, not waited for.  target_bytes: an int,
+        one per picture, or an (N,) int32 tensor on the device.
 
-def encode_clips(frames, quantizer, gop, version, width, height, recon=False, partitions=False):
+        Returns what encode() returns for tensors, the dict always present and holding "quantizer": the (N,) uint8 chosen quantisers (a
+        device tensor in the unsynchronised form, i.e. with slot_bytes given)."""
+        from .encode_rate import encode_target
+        return encode_target(self, "mobi_enc_inter_target_async", [pictures, references], prev_quantizer, target_bytes, qmin, qmax, (), recon, stats, slot_bytes, stream)
+
+
+def encode_clips(frames, quantizer, gop, version, width, height, recon=False, partitions=False, target_bytes=None, carry_bytes=0, qmin=12, qmax=52,
+                 quantizers=False):
     """frames: an (N, T, width * height * 3 / 2) uint8 torch tensor on a GPU, packed I420 (what a clip sink or export_tensor("i420")
     writes).  Frame 0 and every gop-th frame of every clip go through the intra encoder, the rest through the inter encoder; the
     reconstructions stay on the device and become the next frame's reference.  quantizer: an int in [12, 52] or T of them, one per frame.
     partitions: the inter encoder's mode (MobiclipInterEncoder).
 
+    Exactly one of quantizer and target_bytes is given (the other is None).  target_bytes: an int or T of them, one per frame index: rate
+    control (encode_target, quantisers from [qmin, qmax]).  Frame t of every clip gets target_t + carry; carry starts at 0 and becomes,
+    after each frame, clamp(target given - bytes produced, 0, carry_bytes): what a frame leaves of its budget the next may spend, up to
+    carry_bytes.  Targets, carry and the chosen quantisers stay on the device; the whole clip still waits once.
+
     Returns, per clip, the list of its T frame streams (bytes); with recon=True also the (N, T, frame) uint8 tensor of reconstructions:
-    what a decoder fed the streams of clip i in order holds after each."""
+    what a decoder fed the streams of clip i in order holds after each; with quantizers=True also the (N, T) uint8 tensor of the frames'
+    quantisers."""
     import torch
     if not type(frames).__module__.startswith("torch") or frames.ndim != 3 or frames.dtype != torch.uint8 or not frames.is_cuda:
         raise ValueError("frames must be an (N, T, frame_bytes) uint8 tensor on a GPU")
     n, t_n = int(frames.shape[0]), int(frames.shape[1])
     if int(gop) < 1 or n < 1 or t_n < 1:
         raise ValueError("gop, clips and frames must be at least 1")
-    qs = [int(quantizer)] * t_n if np.isscalar(quantizer) else [int(q) for q in quantizer]
+    if (quantizer is None) == (target_bytes is None):
+        raise ValueError("exactly one of quantizer and target_bytes")
+    per_frame = quantizer if target_bytes is None else target_bytes
+    qs = [int(per_frame)] * t_n if np.isscalar(per_frame) else [int(q) for q in per_frame]
     if len(qs) != t_n:
-        raise ValueError("one quantizer, or one per frame")
+        raise ValueError(f"one {'quantizer' if target_bytes is None else 'target_bytes'}, or one per frame")
+    if int(carry_bytes) < 0:
+        raise ValueError("carry_bytes must be at least 0")
     device = frames.device.index or 0
     intra = MobiclipIntraEncoder(width, height, version, n, device=device)
     inter = MobiclipInterEncoder(width, height, version, n, device=device, partitions=partitions) if t_n > 1 and int(gop) > 1 else None
     slot = max(intra.stream_bound, inter.stream_bound if inter else 0)
-    held, rec_all, ref = [], [], None
+    held, rec_all, q_all, ref = [], [], [], None
+    carry = q_dev = None
     try:
         for t in range(t_n):
             pics = frames[:, t].contiguous()
-            if t % int(gop) == 0:
+            if target_bytes is not None:
+                given = torch.full((n,), qs[t], dtype=torch.int32, device=frames.device) if carry is None else carry + qs[t]
+                if t % int(gop) == 0:
+                    out, sizes, ex = intra.encode_target(pics, given, qmin, qmax, recon=True, slot_bytes=slot)
+                else:
+                    out, sizes, ex = inter.encode_target(pics, ref, q_dev, given, qmin, qmax, recon=True, slot_bytes=slot)
+                carry = torch.clamp(given - sizes, 0, int(carry_bytes))
+                q_dev = ex["quantizer"]
+            elif t % int(gop) == 0:
                 out, sizes, ex = intra.encode(pics, qs[t], recon=True, slot_bytes=slot)
             else:
                 out, sizes, ex = inter.encode(pics, ref, qs[t - 1], qs[t], recon=True, slot_bytes=slot)
             ref = ex["recon"]
             held.append((out, sizes))
+            if quantizers:
+                q_all.append(q_dev if target_bytes is not None else torch.full((n,), qs[t], dtype=torch.uint8, device=frames.device))
             if recon:
                 rec_all.append(ref)
         torch.cuda.current_stream(frames.device).synchronize()
@@ -123,4 +158,5 @@ def encode_clips(frames, quantizer, gop, version, width, height, recon=False, pa
         out, sizes = out.cpu().numpy(), sizes.cpu().numpy()
         for i in range(n):
             clips[i].append(out[i, :sizes[i]].tobytes())
-    return (clips, torch.stack(rec_all, 1)) if recon else clips
+    res = [clips] + ([torch.stack(rec_all, 1)] if recon else []) + ([torch.stack(q_all, 1)] if quantizers else [])
+    return tuple(res) if len(res) > 1 else clips

@@ -79,7 +79,7 @@ def main():
     ap.add_argument("--out")
     a = ap.parse_args()
     lib = encode._lib()
-    select = lib.mobi_debug_enc_select  # (stages: 1 decide, 2 write, 3 both; shape: 0 launch per diagonal, 1 barrier loop)
+    select = lib.mobi_debug_enc_select  # (stages: 1 decide, 2 scan, 4 write, 7 all; shape: 0 launch per diagonal, 1 barrier loop)
     select.argtypes, select.restype = [C.c_int, C.c_int], None
     dev = torch.device("cuda", torch.cuda.current_device())
     s = torch.cuda.current_stream(dev)
@@ -104,14 +104,14 @@ def main():
     for n in a.counts:
         for q in a.quantizers:
             k = f"n{n}_q{q}"
-            select(3, default_shape)
+            select(7, default_shape)
             whole = timed(lambda: call(n, q), s, a.iters, a.warmup)
             sz = sizes[:n].cpu().numpy()
             st = stats[:n].cpu().numpy().view(encode.STATS_DTYPE).reshape(-1)
             assert sz.max() <= slot
             select(1, default_shape)
             t1 = timed(lambda: call(n, q), s, a.iters, 1)
-            select(2, default_shape)
+            select(6, default_shape)
             t2 = timed(lambda: call(n, q), s, a.iters, 1)
             res[k] = {"whole_ms": whole, "stage1_ms": t1, "stage2_ms": t2, "pictures_per_s": n / whole * 1e3, "gpixels_per_s": n * W * H / whole / 1e6,
                       "bytes_per_picture": float(sz.mean()), "coded_blocks_per_picture": float(st["coded_blocks"].mean()),
@@ -120,14 +120,14 @@ def main():
     for n in (8, 512, max(a.counts)):
         got = {}
         for shape in (0, 1):
-            select(3, shape)
+            select(7, shape)
             call(n, 26)
             s.synchronize()
             got[shape] = (out[:n].cpu().numpy().copy(), sizes[:n].cpu().numpy().copy())
             select(1, shape)
             res[f"{('diag', 'loop')[shape]}_n{n}_stage1_ms"] = timed(lambda: call(n, 26), s, a.iters * (4 if n == 8 else 1), 2)
         res[f"shapes_agree_n{n}"] = bool(np.array_equal(got[0][0], got[1][0]) and np.array_equal(got[0][1], got[1][1]))
-    select(3, default_shape)
+    select(7, default_shape)
     # the host model on the same pictures
     sys.path.insert(0, ROOT)
     from tests import enc_model as E

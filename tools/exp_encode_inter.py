@@ -101,7 +101,7 @@ def main():
     a = ap.parse_args()
     lib = encode_inter._lib()
     ilib = encode._lib()
-    select = lib.mobi_debug_encp_select  # stages: 1 search, 2 code, 4 write, 7 all
+    select = lib.mobi_debug_encp_select  # stages: 1 search, 2 code, 4 scan, 8 write, 15 all
     select.argtypes, select.restype = [C.c_int], None
     dev = torch.device("cuda", torch.cuda.current_device())
     s = torch.cuda.current_stream(dev)
@@ -141,16 +141,16 @@ def main():
                 assert int(sizes[:n].max().item()) <= slot
                 for mode in (0, 1) if a.partitions else (0,):
                     enc.set_partitions(bool(mode))
-                    select(7)
+                    select(15)
                     whole = timed(lambda: call(n), s, a.iters, a.warmup)
                     sz = sizes[:n].cpu().numpy()
                     st = stats[:n].cpu().numpy().view(encode_inter.STATS_DTYPE).reshape(-1)
                     assert sz.max() <= slot
                     t = {}
-                    for name, bit in (("search", 1), ("code", 2), ("write", 4)):
+                    for name, bit in (("search", 1), ("code", 2), ("write", 12)):
                         select(bit)
                         t[name] = timed(lambda: call(n), s, a.iters, 1)
-                    select(7)
+                    select(15)
                     r = {"whole_ms": whole, "search_ms": t["search"], "code_ms": t["code"], "write_ms": t["write"], "pictures_per_s": n / whole * 1e3,
                          "gpixels_per_s": n * W * H / whole / 1e6, "bytes_per_picture": float(sz.mean()), "coded_blocks_per_picture": float(st["coded_blocks"].mean()),
                          "code0_per_picture": float(st["code0"].mean()), "nonzero_mv_per_picture": float(st["nonzero_mv"].mean()),
