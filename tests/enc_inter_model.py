@@ -2,7 +2,8 @@
 
   host model     tests/tools/mobi_encode_inter_host.cpp: the product's csrc/mobi_encode_inter.h run on the CPU (build.build_encinterhost)
   sequences      N clips of an I-frame and three P-frames each, with a quantiser per picture: a textured picture translated by known full-
-                 and half-pel vectors, a noisy sequence, a saturated one (fixed seeds, any multiple-of-16 size)
+                 and half-pel vectors, a noisy sequence, a saturated one (fixed seeds, any multiple-of-16 size); and `still`, a scene
+                 that does not move, for the geometry tests (tests/test_encode_geometry_gpu.py)
   chain          the host model over a set: the I-frames from the intra host model, every P-frame against the reconstruction before it
   parse_p_stream a P-frame of the encoder's subset read back with the ORACLE's tables: header delta, per macroblock partition code, vector
                  difference, cbp, levels, bits
@@ -121,6 +122,30 @@ def sequence_sets(W, H):
 
 
 SETS = ("fullpel", "mixed5", "sat_q52")
+# what the geometry tests run (enc_model.GEOMETRY_SHAPES): the mixed five and the still scene below, which is no member of SETS
+GEOMETRY_SETS = ("mixed5", "still")
+STILL_Q = np.array([[14, 14, 14, 14], [20, 20, 20, 20], [24, 30, 30, 22]], np.uint8)  # two clips at one quantiser, one that changes it (dq != 0)
+_STILL = {}
+
+
+def still(W, H):
+    """-> (frames (3, T, frame), quantizers (3, T)): a scene that does not move.  Frame 0 of the first three clips of 'mixed5'; the source of
+    frame t is the model's own reconstruction of frame t - 1, made by chaining the model, so every P-macroblock has the zero vector and no
+    residual: 2 bits on Moflex3DS, 3 on ModsDS, and 16 or 10 macroblocks in one 32-bit word of the stream.  (Neither the intra model nor
+    an unchanged picture depends on the version or on the partition mode: tests/test_encode_*_model.py, test_geometry_*, assert both.)"""
+    if (W, H) not in _STILL:
+        first = sequence_sets(W, H)["mixed5"][0][:3, 0]
+        frames, rec = [first], E.host_encode(W, H, 2, first, STILL_Q[:, 0])["recon"]
+        for t in range(1, T):
+            frames.append(rec)
+            rec = host_encode(W, H, 2, rec, rec, STILL_Q[:, t - 1], STILL_Q[:, t])["recon"]
+        _STILL[(W, H)] = (np.ascontiguousarray(np.stack(frames, 1)), STILL_Q)
+    return _STILL[(W, H)]
+
+
+def geometry_set(W, H, name):
+    """one of GEOMETRY_SETS as sequence_sets gives its own: (frames (N, T, frame), quantizers (N, T))"""
+    return still(W, H) if name == "still" else sequence_sets(W, H)[name]
 
 
 def chain(W, H, version, frames, qs, **kw):

@@ -24,8 +24,42 @@ STATS_DTYPE = np.dtype([("bits", "<u8"), ("sad", "<u8"), ("luma_modes", "<u4", 4
                         ("fallback_clamp", "<u4"), ("fallback_level", "<u4"), ("reserved", "<u4")])
 VERSIONS = (2, 1)  # MOBI_VERSION_MOFLEX3DS, MOBI_VERSION_MODSDS
 SHAPES = ((16, 16), (48, 32), (256, 192), (272, 208))
+# The shapes of the geometry tests (tests/test_encode_geometry_gpu.py and test_geometry_* of the three model tests), each the smallest that
+# reaches what stands beside it.  The scan of the bit lengths (csrc/mobi_encode_write.h) goes over the macroblocks 256 at a time and the
+# writer 64 at a time; the host models have neither, they sum and write in raster order.
+GEOMETRY_SHAPES = (
+    (256, 256),    # 16 x 16 = 256 macroblocks: one scan round exactly full, the writer's fourth workgroup exactly full
+    (272, 256),    # 17 x 16 = 272: a second scan round with 16 live lanes, a fifth writer workgroup partly filled
+    (1024, 144),   # 64 x 9 = 576: three scan rounds; the widest picture there is (the decoder's stride class 1024); mobi_enc_diag_range
+                   #   gives x_lo > 0 on 63 of its 72 diagonals
+    (16, 4112),    # 1 x 257 = 257: one column, 257 diagonals of one macroblock, a second round with one live lane, vector predictors
+                   #   whose left and top-right neighbours would wrap
+    (32, 80),      # 2 x 5 = 10: taller than wide, the width ends four of the six diagonals (x_hi < d) and x_lo > 0 on the last; cheap
+    (1024, 16),    # 64 x 1 = 64: one row, no neighbour above anywhere, a search window mostly outside the picture
+)
 LAM_BASE = (218, 274, 345)
 _HOST = None
+
+
+def geometry_preconditions(bits, total, where):
+    """What lets the GPU comparison above 256 macroblocks (tests/test_encode_geometry_gpu.py) fail, asserted on a model's output for the five
+    pictures of one call of 'mixed5' (bits: (5, macroblocks) per macroblock, total: (5,) with the header).  For EVERY picture the
+    macroblocks from index 256 on have bits.  For at least four of the five -- printed: which -- their lengths are not all the same, and
+    for at least four macroblock 256 starts inside a 32-bit word, so that the first word of the second scan round is one that two
+    workgroups of the writer share.  Every picture cannot be had for these two from the mixed five: the flat I-frame's last macroblock
+    row is sixteen times the same 8 bits, the first P-frame of saturated noise (q = 52 after 52) is 2 or 3 bits everywhere, and in 7 of
+    the 42 calls one picture's offset is a multiple of 32.  A picture of 1 x 257 has one macroblock behind the first 256, which cannot
+    differ from itself: there macroblocks 255 and 256 must differ."""
+    bits = np.asarray(bits).astype(np.int64)
+    n, nmb = bits.shape
+    assert nmb > 256 and n == 5
+    assert (bits[:, 256:] > 0).all(), where
+    tail = bits[:, 256:] if nmb > 257 else bits[:, 255:]
+    differ = np.array([len(set(t.tolist())) > 1 for t in tail])
+    offset = np.asarray(total).astype(np.int64) - bits.sum(1) + bits[:, :256].sum(1)  # the header and what stands before macroblock 256
+    inside = offset % 32 != 0
+    print(where, "lengths differ:", differ.tolist(), "macroblock 256 inside a word:", inside.tolist())
+    assert differ.sum() >= 4 and inside.sum() >= 4, (where, differ, inside)
 _REF = None
 
 

@@ -10,6 +10,7 @@ the host model the kernels are compared against in tests/test_encode_inter_gpu.p
   4  on the pure full-pel translation every P-frame is shorter than the I-frame of the same picture at the same quantiser
   5  refusals, the stream bound, a slot too small, header / library / binding
   6  the host model as a stand-alone program under -fsanitize=address,undefined
+  7  closed loop and parse-back at enc_model.GEOMETRY_SHAPES, with the still scene, and what the GPU comparison there rests on
 Shapes 16x16 (no neighbour, and no vector but (0, 0) fits the rectangle), 48x32, 272x208 (stride != width); N = 1 and N = 5."""
 import os
 import re
@@ -77,6 +78,56 @@ def test_closed_loop_through_the_oracle(W, H):
                 for t, (dec, used, q) in enumerate(M.oracle_chain(W, H, version, streams)):
                     assert np.array_equal(dec, ch[t]["recon"][c]), (name, version, c, t)
                     assert q == int(qs[c, t]) and used <= len(streams[t]), (name, version, c, t)
+
+
+@pytest.mark.parametrize("version", M.VERSIONS)
+@pytest.mark.parametrize("W,H", E.GEOMETRY_SHAPES)
+def test_geometry_shapes_through_the_oracle(W, H, version):
+    """enc_model.GEOMETRY_SHAPES, the mixed five and the still scene: the oracle decodes I, P, P, P to the reported reconstructions within
+    the streams' bytes; every P-frame reads back to the model's records, its vectors from predictors whose neighbours do NOT wrap round
+    the picture's edge (one column: no left, no top-right neighbour); and the sets meet what the GPU comparison at these shapes rests on"""
+    mbw, nmb = W // 16, (W // 16) * (H // 16)
+    for name in M.GEOMETRY_SETS:
+        frames, qs = M.geometry_set(W, H, name)
+        ch = M.chain(W, H, version, frames, qs)
+        for c in range(frames.shape[0]):
+            streams = []
+            for t in range(M.T):
+                n = int(ch[t]["bytes"][c])
+                assert n % 2 == 0 and n <= ch[t]["streams"].shape[1] and not ch[t]["streams"][c, n:].any()
+                streams.append(ch[t]["streams"][c, :n])
+            for t, (dec, used, q) in enumerate(M.oracle_chain(W, H, version, streams)):
+                assert np.array_equal(dec, ch[t]["recon"][c]), (name, c, t)
+                assert q == int(qs[c, t]) and used <= len(streams[t]), (name, c, t)
+            for t in range(1, M.T):
+                r, where = ch[t], (name, c, t)
+                ps = M.parse_p_stream(streams[t], W, H, version)
+                assert ps["dq"] == int(qs[c, t]) - int(qs[c, t - 1]), where
+                for f in ("lev", "bits", "cbp"):
+                    assert np.array_equal(ps["mbs"][f], r["mbs"][c][f]), (where, f)
+                assert ps["end"] == int(r["stats"]["bits"][c]) == ps["hdr_bits"] + int(r["mbs"]["bits"][c].sum()), where
+                assert 8 * len(streams[t]) == (ps["end"] + 16 + 15) // 16 * 16, where
+                dx, dy = np.zeros(nmb, np.int64), np.zeros(nmb, np.int64)
+                at = lambda a, x, y: int(a[y * mbw + x]) if 0 <= x < mbw and y >= 0 else 0
+                for i in range(nmb):
+                    x, y = i % mbw, i // mbw
+                    dx[i] = M.med3(at(dx, x - 1, y), at(dx, x, y - 1), at(dx, x + 1, y - 1)) + ps["ddx"][i]
+                    dy[i] = M.med3(at(dy, x - 1, y), at(dy, x, y - 1), at(dy, x + 1, y - 1)) + ps["ddy"][i]
+                mdx, mdy = M.unpack_mv(r["mv"][c])
+                assert np.array_equal(dx, mdx) and np.array_equal(dy, mdy), where
+                assert np.array_equal(ps["code"], (r["mv"][c] != r["mvp"][c]).astype(np.int64)), where
+                assert int(r["stats"]["code0"][c]) == int((ps["code"] == 0).sum()) and int(r["stats"]["mv_bits"][c]) == ps["mv_bits"], where
+        for t in range(1, M.T):
+            if name == "still":
+                # nothing moves and nothing is left to code: a partition code 0 (1 bit on Moflex3DS, 2 on ModsDS) and ue(0) per macroblock,
+                # 16 or 10 of them to a 32-bit word, whether or not the header changes the quantiser
+                assert (ch[t]["mbs"]["bits"] == (2 if version == 2 else 3)).all() and (ch[t]["stats"]["code0"] == nmb).all(), t
+                assert np.array_equal(ch[t]["recon"], ch[0]["recon"]) and np.array_equal(frames[:, t], ch[0]["recon"]), t
+            elif nmb > 256:
+                E.geometry_preconditions(ch[t]["mbs"]["bits"], ch[t]["stats"]["bits"], (W, H, version, "inter", t))
+        if name == "still":
+            dq = qs[:, 1:].astype(int) - qs[:, :-1]
+            assert (dq != 0).any(1).sum() == 1 and (dq == 0).all(1).sum() == 2  # one clip's headers change the quantiser, two clips' do not
 
 
 def test_versions_differ_in_code_words_only():

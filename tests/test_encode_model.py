@@ -9,7 +9,8 @@ the kernels are compared against in tests/test_encode_gpu.py).
   3  the picture sets cover what they must (see test_coverage_condition for the one demand that CANNOT be met, and why)
   4  shapes 16x16, 48x32, 256x192 (stride = width), 272x208 (stride != width); N = 1 and N = 5 with a quantiser per picture
   5  refusals and the stream bound
-  6  the host model as a stand-alone program under -fsanitize=address,undefined"""
+  6  the host model as a stand-alone program under -fsanitize=address,undefined
+  7  closed loop and parse-back at enc_model.GEOMETRY_SHAPES, and what the GPU comparison there rests on"""
 import ctypes as C
 import os
 import re
@@ -103,6 +104,38 @@ def test_closed_loop_through_the_oracle(W, H):
                 assert np.array_equal(dec, r["recon"][i]), (name, version, i)
                 assert (q, yf) == (int(qs[i]), yuv)
                 assert used <= n
+
+
+@pytest.mark.parametrize("version", E.VERSIONS)
+@pytest.mark.parametrize("W,H", E.GEOMETRY_SHAPES)
+def test_geometry_shapes_through_the_oracle(W, H, version):
+    """enc_model.GEOMETRY_SHAPES, the mixed five: the oracle decodes every stream to the reported reconstruction within its bytes, the
+    stream reads back to the model's records, and the pictures meet what the GPU comparison at these shapes rests on"""
+    pics, qs = E.picture_sets(W, H)["mixed5"]
+    r = E.host_encode(W, H, version, pics, qs)
+    mbw, nmb = W // 16, (W // 16) * (H // 16)
+    forms = np.zeros(4, np.int64)
+    for i in range(len(qs)):
+        n = int(r["bytes"][i])
+        assert n % 2 == 0 and n <= r["streams"].shape[1] and not r["streams"][i, n:].any()
+        dec, used, q, yf = E.oracle_decode(W, H, version, r["streams"][i, :n])
+        assert np.array_equal(dec, r["recon"][i]), i
+        assert (q, yf) == (int(qs[i]), 0) and used <= n
+        ps = E.parse_stream(r["streams"][i, :n], W, H)
+        for f in ("lev", "bits", "luma_mode", "chroma_mode", "cbp"):
+            assert np.array_equal(ps["mbs"][f], r["mbs"][i][f]), (i, f)
+        assert ps["q"] == int(qs[i]) and ps["end"] == int(r["stats"]["bits"][i]) == 9 + int(r["mbs"]["bits"][i].sum())
+        assert 8 * n == (ps["end"] + 16 + 15) // 16 * 16
+        forms += ps["forms"]
+    assert np.array_equal(forms, r["forms"])
+    if nmb > 256:
+        E.geometry_preconditions(r["mbs"]["bits"], r["stats"]["bits"], (W, H, version, "intra"))
+    if H > W:
+        # below the main diagonal (mby > mbx: the macroblocks a wrong diagonal range would hand an unfinished border) every mode that can
+        # occur is chosen, so a stale border changes bytes.  One column has no left neighbour: mode 1 is not allowed there at all.
+        idx = np.arange(nmb)
+        seen = np.bincount(r["mbs"]["luma_mode"][:, idx // mbw > idx % mbw].ravel(), minlength=4)
+        assert seen[0] > 0 and seen[3] > 0 and seen[2] == 0 and (seen[1] > 0) == (mbw > 1), seen
 
 
 def test_versions_encode_alike():

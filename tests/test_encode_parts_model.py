@@ -11,6 +11,7 @@ tests/tools/mobi_encode_parts_host.cpp, the host model the kernels are compared 
   6   the sets cover what they must (test_coverage_conditions)
   7   on the two-motion set mode 1 is strictly shorter than mode 0 at equal quantisers
   8   the bound; 9 the refusals; 10 the leaf predicate at 16x16 is mobi_encp_vector_ok; 11 the host model under sanitizers
+  12  closed loop and parse-back at enc_model.GEOMETRY_SHAPES, with the still scene, and what the GPU comparison there rests on
 Shapes 16x16 (sub-blocks have candidates the macroblock lacks), 48x32 (every edge), 64x48 (full reach, all three neighbours)."""
 import os
 import re
@@ -135,6 +136,68 @@ def test_streams_parse_back_to_the_models_decisions(W, H, version):
                 assert 8 * n == (ps["end"] + 16 + 15) // 16 * 16, where
                 assert int(st["code0"]) == code0 and int(st["reserved"][Q.STAT_LEAVES]) == leaves, where
                 assert int(st["reserved"][Q.STAT_SPLIT]) == int((trees != 0).sum()) and not st["reserved"][2:].any(), where
+
+
+@pytest.mark.parametrize("version", Q.VERSIONS)
+@pytest.mark.parametrize("W,H", E.GEOMETRY_SHAPES)
+def test_geometry_shapes_through_the_oracle(W, H, version):
+    """enc_model.GEOMETRY_SHAPES in mode 1, the mixed five and the still scene: the oracle decodes I, P, P, P to the reported reconstructions
+    within the streams' bytes; every P-frame reads back to the model's trees, leaves and vectors, the predictors from neighbours that do
+    not wrap round the picture's edge; and the sets meet what the GPU comparison at these shapes rests on"""
+    mbw, nmb = W // 16, (W // 16) * (H // 16)
+    for name in M.GEOMETRY_SETS:
+        frames, qs = M.geometry_set(W, H, name)
+        ch = Q.chain(W, H, version, 1, frames, qs)
+        split = 0
+        for c in range(frames.shape[0]):
+            streams = []
+            for t in range(Q.T):
+                n = int(ch[t]["bytes"][c])
+                assert n % 2 == 0 and n <= ch[t]["streams"].shape[1] and not ch[t]["streams"][c, n:].any()
+                streams.append(ch[t]["streams"][c, :n])
+            for t, (dec, used, q) in enumerate(M.oracle_chain(W, H, version, streams)):
+                assert np.array_equal(dec, ch[t]["recon"][c]), (name, c, t)
+                assert q == int(qs[c, t]) and used <= len(streams[t]), (name, c, t)
+            for t in range(1, Q.T):
+                r, where = ch[t], (name, c, t)
+                ps = Q.parse_p_stream(streams[t], W, H, version)
+                trees, dx4, dy4 = _vectors(r, c)
+                assert ps["dq"] == int(qs[c, t]) - int(qs[c, t - 1]), where
+                assert np.array_equal(ps["mbs"]["luma_mode"], trees), where
+                for f in ("lev", "bits", "cbp"):
+                    assert np.array_equal(ps["mbs"][f], r["mbs"][c][f]), (where, f)
+                assert ps["end"] == int(r["stats"]["bits"][c]) == ps["hdr_bits"] + int(r["mbs"]["bits"][c].sum()), where
+                assert 8 * len(streams[t]) == (ps["end"] + 16 + 15) // 16 * 16, where
+                last = np.zeros((nmb, 2), np.int64)
+                at = lambda k, x, y: int(last[y * mbw + x, k]) if 0 <= x < mbw and y >= 0 else 0
+                pdx, pdy = M.unpack_mv(r["mvp"][c])
+                code0 = 0
+                for i, lv in enumerate(ps["leaves"]):
+                    x, y = i % mbw, i // mbw
+                    px, py = (M.med3(at(k, x - 1, y), at(k, x, y - 1), at(k, x + 1, y - 1)) for k in (0, 1))
+                    assert (px, py) == (int(pdx[i]), int(pdy[i])), (where, i)
+                    assert [f[:4] for f in lv] == [Q.LEAVES[l] for l in Q.tree_leaves(int(trees[i]))], (where, i)
+                    for (lx, ly, w, h, code, ddx, ddy) in lv:
+                        qd = (ly // 8) * 2 + lx // 8
+                        assert (px + ddx, py + ddy) == (int(dx4[i, qd]), int(dy4[i, qd])) and code == int((ddx, ddy) != (0, 0)), (where, i)
+                        last[i] = (px + ddx, py + ddy)
+                        code0 += code == 0
+                assert int(r["stats"]["code0"][c]) == code0 and int(r["stats"]["mv_bits"][c]) == ps["mv_bits"], where
+                assert int(r["stats"]["reserved"][c][Q.STAT_SPLIT]) == int((trees != 0).sum()), where
+                split += int((trees != 0).sum())
+        for t in range(1, Q.T):
+            if name == "still":
+                # nothing moves: no macroblock is split, each is 2 (Moflex3DS) or 3 (ModsDS) bits, and the stream is mode 0's
+                assert (ch[t]["mbs"]["bits"] == (2 if version == 2 else 3)).all() and (ch[t]["stats"]["code0"] == nmb).all(), t
+                assert np.array_equal(ch[t]["recon"], ch[0]["recon"]) and np.array_equal(frames[:, t], ch[0]["recon"]), t
+                m0 = M.host_encode(W, H, version, frames[:, t], ch[t - 1]["recon"], qs[:, t - 1], qs[:, t])
+                assert np.array_equal(m0["bytes"], ch[t]["bytes"]) and np.array_equal(m0["streams"], ch[t]["streams"][:, : m0["streams"].shape[1]]), t
+            elif nmb > 256:
+                E.geometry_preconditions(ch[t]["mbs"]["bits"], ch[t]["stats"]["bits"], (W, H, version, "parts", t))
+        assert (split == 0) == (name == "still"), (name, split)
+        if name == "still":
+            dq = qs[:, 1:].astype(int) - qs[:, :-1]
+            assert (dq != 0).any(1).sum() == 1 and (dq == 0).all(1).sum() == 2
 
 
 @pytest.mark.parametrize("W,H", Q.SHAPES)
