@@ -156,15 +156,21 @@ MOBI_TC_FN void mobi_enc_write_block(const MobiEncConst *K, const int16_t *lev, 
   }
 }
 // ---- a macroblock's bit string: put(pattern, nbits) with nbits <= 28; forms[4] (may be NULL) counts the code forms written ----
+// what follows the bit(s) that say "an intra macroblock in the full-block syntax" (an I-frame's leading 0 below, a P-frame's partition
+// code 6 in mobi_encode_pintra.h): ue(cbp), the modes in front of their blocks, the coded blocks
 template <class Put>
-MOBI_TC_FN void mobi_enc_write_mb(const MobiEncConst *K, const MobiEncMb *m, Put put, uint32_t *forms) {
-  put(0u, 1); // the full-block syntax
+MOBI_TC_FN void mobi_enc_write_mb_body(const MobiEncConst *K, const MobiEncMb *m, Put put, uint32_t *forms) {
   put(K->inv_cbp[m->cbp] + 1u, mobi_enc_ue_bits(K->inv_cbp[m->cbp])); // ue(): the leading zeros are the pattern's own
   for (int k = 0; k < 6; k++) {
     if (k == 0) put(m->luma_mode, 3);
     if (k == 4) put(m->chroma_mode, 3);
     if ((m->cbp >> k) & 1) mobi_enc_write_block(K, m->lev[k], put, forms);
   }
+}
+template <class Put>
+MOBI_TC_FN void mobi_enc_write_mb(const MobiEncConst *K, const MobiEncMb *m, Put put, uint32_t *forms) {
+  put(0u, 1); // the full-block syntax
+  mobi_enc_write_mb_body(K, m, put, forms);
 }
 
 // ---- the sink of the host model: bits MSB-first into 16-bit little-endian words of a zeroed buffer, at bit position pos ----

@@ -68,6 +68,7 @@ struct MobiEncInterConst : MobiEncConst {
   uint8_t inv_cbp_p[64];  // the ue() number whose mobi_cbp_inter entry is cbp6
   uint8_t part_code[2][2]; // [0: Moflex3DS, 1: ModsDS][partition code 0 / 1 at 16x16]: the code word ...
   uint8_t part_nbits[2][2]; // ... and its length
+  uint8_t part6_code[2], part6_nbits[2]; // [version table] partition code 6 at 16x16, an intra macroblock in the full-block syntax (mobi_encode_pintra.h)
 };
 MOBI_TC_FN int mobi_encp_ver(int version) { return version == 2 ? 0 : 1; } // MOBI_VERSION_MOFLEX3DS: table 0
 
@@ -117,6 +118,10 @@ struct MobiEncInterArgs : MobiEncArgs {
   const MobiEncInterConst *kp;
   mobi_enc_inter_stats *pstats; // [n] or NULL
   int32_t ver;
+  // the intra mode's side arrays (mobi_encode_pintra.h), carved in every mode and untouched outside it: [n][mbw * mbh] the inter coding's
+  // cost Jp, and the macroblock's kind with the chosen coding's figures (mobi_encpi_kind)
+  int64_t *jp;
+  uint32_t *kind;
 };
 
 // where the prediction of the 8x8 block k (0..3 luma, 4: U, 5: V) of a macroblock with vector (dx, dy) starts in its reference plane
@@ -175,6 +180,10 @@ static inline void mobi_encp_build_const(MobiEncInterConst *K) {
       for (int i = (1 << peek) - 1; i >= 0; i--)
         if (mobi_part_lut[ver][0][i] == code) K->part_code[ver][code] = (uint8_t)(i >> (peek - nb));
     }
+    const int nb6 = mobi_part_bits[ver][0][6];
+    K->part6_nbits[ver] = (uint8_t)nb6;
+    for (int i = (1 << peek) - 1; i >= 0; i--)
+      if (mobi_part_lut[ver][0][i] == 6) K->part6_code[ver] = (uint8_t)(i >> (peek - nb6));
   }
 }
 

@@ -36,9 +36,17 @@ _PARTS_SIGS = {
 # mobi_enc_inter_stats.reserved in the partition mode (MOBI_ENC_PARTS_STAT_*): macroblocks sent split, leaves sent
 STAT_SPLIT, STAT_LEAVES = 0, 1
 
+# the intra mode; names must match include/mobiclip_encode_pintra.h (tests/test_encode_pintra_model.py checks header, library and this table)
+_PINTRA_SIGS = {
+    "mobi_enc_inter_set_intra": (C.c_int, [C.c_void_p, C.c_int]),
+    "mobi_enc_inter_get_intra": (C.c_int, [C.c_void_p]),
+}
+# mobi_enc_inter_stats.reserved in the intra mode (MOBI_ENC_PINTRA_STAT_INTRA): macroblocks sent intra
+STAT_INTRA = 2
+
 
 def _lib():
-    return bind(bind(load_library(), _SIGS), _PARTS_SIGS)
+    return bind(bind(bind(load_library(), _SIGS), _PARTS_SIGS), _PINTRA_SIGS)
 
 
 def stream_bound(width, height, partitions=False):
@@ -49,16 +57,29 @@ def stream_bound(width, height, partitions=False):
 
 class MobiclipInterEncoder(_Encoder):
     """mobi_enc_inter_ctx: P-frames of width x height pictures for MobiclipVersion.Moflex3DS or .ModsDS, up to max_pictures per call.
-    partitions=True: macroblocks may be split into 16x8, 8x16 and 8x8 leaves with a vector each (include/mobiclip_encode_parts.h)."""
+    partitions=True: macroblocks may be split into 16x8, 8x16 and 8x8 leaves with a vector each (include/mobiclip_encode_parts.h).
+    intra=True: a macroblock is sent intra where that is cheaper (include/mobiclip_encode_pintra.h).  The two modes exclude each other."""
     _destroy = "mobi_enc_inter_destroy"
     _sigs, _prefix, _call, _what, _stats, _no_extra = _SIGS, "mobi_enc_inter", "mobi_enc_inter", ("pictures", "references"), STATS_DTYPE, ()
 
-    def __init__(self, width, height, version, max_pictures, device=None, partitions=False):
+    def __init__(self, width, height, version, max_pictures, device=None, partitions=False, intra=False):
+        self._h = None
+        if partitions and intra:
+            raise ValueError("partitions and intra exclude each other")
         super().__init__(width, height, version, max_pictures, device)
-        bind(self._lib, _PARTS_SIGS)
-        self.partitions = False
+        bind(bind(self._lib, _PARTS_SIGS), _PINTRA_SIGS)
+        self.partitions = self.intra = False
         if partitions:
             self.set_partitions(True)
+        if intra:
+            self.set_intra(True)
+
+    def set_intra(self, on):
+        """mobi_enc_inter_set_intra: holds for the calls of encode() and encode_target() after it; refused (MobiclipError) while partitions are on"""
+        if not self._h:
+            raise MobiclipError("encoder is closed")
+        check_rc(self._lib.mobi_enc_inter_set_intra(self._h, int(bool(on))))
+        self.intra = bool(self._lib.mobi_enc_inter_get_intra(self._h))
 
     def set_partitions(self, on):
         """mobi_enc_inter_set_partitions: holds for the calls of encode() after it; stream_bound follows the mode"""
@@ -93,11 +114,12 @@ class MobiclipInterEncoder(_Encoder):
 
 
 def encode_clips(frames, quantizer, gop, version, width, height, recon=False, partitions=False, target_bytes=None, carry_bytes=0, qmin=12, qmax=52,
-                 quantizers=False):
+                 quantizers=False, intra=False):
     """frames: an (N, T, width * height * 3 / 2) uint8 torch tensor on a GPU, packed I420 (what a clip sink or export_tensor("i420")
     writes).  Frame 0 and every gop-th frame of every clip go through the intra encoder, the rest through the inter encoder; the
     reconstructions stay on the device and become the next frame's reference.  quantizer: an int in [12, 52] or T of them, one per frame.
-    partitions: the inter encoder's mode (MobiclipInterEncoder).
+    partitions, intra: the inter encoder's modes (MobiclipInterEncoder); they exclude each other.  intra=True lets the P-frames behind a scene
+    cut, or content no earlier frame shows, send those macroblocks intra.
 
     Exactly one of quantizer and target_bytes is given (the other is None).  target_bytes: an int or T of them, one per frame index: rate
     control (encode_target, quantisers from [qmin, qmax]).  Frame t of every clip gets target_t + carry; carry starts at 0 and becomes,
@@ -111,6 +133,8 @@ def encode_clips(frames, quantizer, gop, version, width, height, recon=False, pa
     if not type(frames).__module__.startswith("torch") or frames.ndim != 3 or frames.dtype != torch.uint8 or not frames.is_cuda:
         raise ValueError("frames must be an (N, T, frame_bytes) uint8 tensor on a GPU")
     n, t_n = int(frames.shape[0]), int(frames.shape[1])
+    if partitions and intra:
+        raise ValueError("partitions and intra exclude each other")
     if int(gop) < 1 or n < 1 or t_n < 1:
         raise ValueError("gop, clips and frames must be at least 1")
     if (quantizer is None) == (target_bytes is None):
@@ -122,8 +146,9 @@ def encode_clips(frames, quantizer, gop, version, width, height, recon=False, pa
     if int(carry_bytes) < 0:
         raise ValueError("carry_bytes must be at least 0")
     device = frames.device.index or 0
+    intra_mode = bool(intra)  # the name serves the I-frame encoder below
     intra = MobiclipIntraEncoder(width, height, version, n, device=device)
-    inter = MobiclipInterEncoder(width, height, version, n, device=device, partitions=partitions) if t_n > 1 and int(gop) > 1 else None
+    inter = MobiclipInterEncoder(width, height, version, n, device=device, partitions=partitions, intra=intra_mode) if t_n > 1 and int(gop) > 1 else None
     slot = max(intra.stream_bound, inter.stream_bound if inter else 0)
     held, rec_all, q_all, ref = [], [], [], None
     carry = q_dev = None

@@ -17,6 +17,10 @@ current stream, warm-up, HIP-event timing over `--iters` calls); prints ONE JSON
   --partitions  every configuration twice, side by side: mode 0 (keys as without the switch) and mode 1 (keys + "_parts": partitions
              down to 8x8, include/mobiclip_encode_parts.h), with the share of split macroblocks, the leaves per picture and the search's
              time as a multiple of mode 0's; the host model is then tests/tools/mobi_encode_parts_host.cpp
+  --intra    every configuration also in the intra mode (keys + "_pintra": include/mobiclip_encode_pintra.h), with the share of macroblocks
+             sent intra and the two stages the mode adds, decide (one launch per anti-diagonal: mbw + mbh - 1 = 69 here) and finish,
+             timed alone.  The mix `cut` is made for it: the translated pictures against the reconstruction of an UNRELATED texture, so
+             that no macroblock's inter cost is small enough to skip the trials; on `translated` most macroblocks skip them
 The stage switch is a hook of the profiling twin (libmobiclip_hip_prof.so, mobi_debug_encp_select), which this tool loads.
 For `rocprofv3 --kernel-trace --stats` or `--pmc` runs (--no-host --counts 512 --quantizers 26) the kernels are mobi_encp_search /
 mobi_encp_code / mobi_encp_scan / mobi_encp_write (mode 1: mobi_encq_*).
@@ -44,6 +48,8 @@ MOVES = [(0, 0), (2, 0), (0, 2), (-4, 6), (1, 0), (0, 1), (1, 1), (-3, 5), (16, 
 def pairs(mix, rng):
     """16 (previous frame, frame) pairs as (16, frame) uint8 arrays: frame = the previous one moved by MOVES[i] half-pels"""
     M2 = 24
+    if mix == "cut":  # the translated pictures; the frames before them show another texture
+        return pairs("translated", np.random.default_rng(1077))[0], pairs("translated", rng)[1]
     def texture(h, w, lo, hi, blur):  # 8x8 cells of random grey, softened: edges stay, an I-frame of it fits the slots below
         a = rng.integers(lo, hi, (h // 8, w // 8)).repeat(8, 0).repeat(8, 1).astype(np.int64)
         for _ in range(blur):
@@ -92,6 +98,7 @@ def main():
     ap.add_argument("--quantizers", type=int, nargs="+", default=[26, 40])
     ap.add_argument("--mixes", nargs="+", default=["translated", "noisy"])
     ap.add_argument("--partitions", action="store_true")
+    ap.add_argument("--intra", action="store_true")
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--host-threads", type=int, default=16)
@@ -101,7 +108,15 @@ def main():
     a = ap.parse_args()
     lib = encode_inter._lib()
     ilib = encode._lib()
-    select = lib.mobi_debug_encp_select  # stages: 1 search, 2 code, 4 scan, 8 write, 15 all
+    select = lib.mobi_debug_encp_select  # stages: 1 search, 2 code, 4 scan, 8 write, 16 decide, 32 finish (the intra mode's two), 63 all
+    ALL = 63
+    variants = [("", 0, 0)] + ([("_parts", 1, 0)] if a.partitions else []) + ([("_pintra", 0, 1)] if a.intra else [])
+
+    def set_modes(enc, parts, intra):  # never both on: off first
+        enc.set_partitions(False)
+        enc.set_intra(False)
+        enc.set_partitions(bool(parts))
+        enc.set_intra(bool(intra))
     select.argtypes, select.restype = [C.c_int], None
     dev = torch.device("cuda", torch.cuda.current_device())
     s = torch.cuda.current_stream(dev)
@@ -139,18 +154,18 @@ def main():
                 t_intra = timed(lambda: intra(n), s, a.iters, a.warmup)
                 isz = float(sizes[:n].float().mean().item())
                 assert int(sizes[:n].max().item()) <= slot
-                for mode in (0, 1) if a.partitions else (0,):
-                    enc.set_partitions(bool(mode))
-                    select(15)
+                for suffix, mode, pintra in variants:
+                    set_modes(enc, mode, pintra)
+                    select(ALL)
                     whole = timed(lambda: call(n), s, a.iters, a.warmup)
                     sz = sizes[:n].cpu().numpy()
                     st = stats[:n].cpu().numpy().view(encode_inter.STATS_DTYPE).reshape(-1)
                     assert sz.max() <= slot
                     t = {}
-                    for name, bit in (("search", 1), ("code", 2), ("write", 12)):
+                    for name, bit in (("search", 1), ("code", 2), ("write", 12)) + ((("decide", 16), ("finish", 32)) if pintra else ()):
                         select(bit)
                         t[name] = timed(lambda: call(n), s, a.iters, 1)
-                    select(15)
+                    select(ALL)
                     r = {"whole_ms": whole, "search_ms": t["search"], "code_ms": t["code"], "write_ms": t["write"], "pictures_per_s": n / whole * 1e3,
                          "gpixels_per_s": n * W * H / whole / 1e6, "bytes_per_picture": float(sz.mean()), "coded_blocks_per_picture": float(st["coded_blocks"].mean()),
                          "code0_per_picture": float(st["code0"].mean()), "nonzero_mv_per_picture": float(st["nonzero_mv"].mean()),
@@ -159,9 +174,12 @@ def main():
                     if mode:
                         r.update(split_share=float(st["reserved"][:, encode_inter.STAT_SPLIT].mean()) / ((W // 16) * (H // 16)),
                                  leaves_per_picture=float(st["reserved"][:, encode_inter.STAT_LEAVES].mean()), search_vs_mode0=t["search"] / res[k]["search_ms"])
-                    res[k + "_parts" if mode else k] = r
-                    print("done", k, "mode", mode, file=sys.stderr, flush=True)
-            for mode in (0, 1) if a.partitions else (0,):
+                    if pintra:
+                        r.update(decide_ms=t["decide"], finish_ms=t["finish"], decide_launches=W // 16 + H // 16 - 1,
+                                 intra_mb_share=float(st["reserved"][:, encode_inter.STAT_INTRA].mean()) / ((W // 16) * (H // 16)), whole_vs_mode0=whole / res[k]["whole_ms"])
+                    res[k + suffix] = r
+                    print("done", k + suffix, file=sys.stderr, flush=True)
+            for suffix, mode, pintra in variants:
                 if a.no_host:
                     break
                 from tests import enc_inter_model as M
@@ -169,19 +187,22 @@ def main():
                 hn = a.host_pictures
                 hp, hr = src[:hn].cpu().numpy(), ref[:hn].cpu().numpy()
                 t0 = time.perf_counter()
-                if a.partitions:
+                if pintra:
+                    from tests import enc_pintra_model as PI
+                    r = PI.host_encode(W, H, VERSION, 1, hp, hr, qs[:hn], qs[:hn], slot_bytes=slot, threads=a.host_threads)
+                elif a.partitions:
                     r = Q.host_encode(W, H, VERSION, mode, hp, hr, qs[:hn], qs[:hn], slot_bytes=slot, threads=a.host_threads)
                 else:
                     r = M.host_encode(W, H, VERSION, hp, hr, qs[:hn], qs[:hn], slot_bytes=slot, threads=a.host_threads)
                 dt = time.perf_counter() - t0
-                enc.set_partitions(bool(mode))
-                print("host done", mix, q, "mode", mode, round(dt, 1), "s", file=sys.stderr, flush=True)
+                set_modes(enc, mode, pintra)
+                print("host done", mix, q, suffix or "mode 0", round(dt, 1), "s", file=sys.stderr, flush=True)
                 call(hn)
                 s.synchronize()
-                res[f"{mix}_host_n{hn}_q{q}" + ("_parts" if mode else "")] = {"threads": a.host_threads, "ms": dt * 1e3, "pictures_per_s": hn / dt,
+                res[f"{mix}_host_n{hn}_q{q}" + suffix] = {"threads": a.host_threads, "ms": dt * 1e3, "pictures_per_s": hn / dt,
                                                                               "equals_gpu": bool(np.array_equal(r["streams"], out[:hn].cpu().numpy()) and
                                                                                                  np.array_equal(r["bytes"], sizes[:hn].cpu().numpy()))}
-            enc.set_partitions(False)
+            set_modes(enc, 0, 0)
     enc.close()
     ienc.close()
     line = json.dumps(json.loads(json.dumps(res), parse_float=lambda x: round(float(x), 4)))
