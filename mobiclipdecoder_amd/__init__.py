@@ -20,4 +20,5 @@ from .decoder import (  # noqa: F401
 from .audio import MobiclipAudio  # noqa: F401
 from .encode import MobiclipIntraEncoder  # noqa: F401
 from .encode_inter import MobiclipInterEncoder, encode_clips  # noqa: F401
+from .mux import MobiclipMuxer  # noqa: F401
 from .streamgen import GenParams, generate_clip, default_params  # noqa: F401

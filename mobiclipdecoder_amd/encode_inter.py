@@ -114,7 +114,7 @@ class MobiclipInterEncoder(_Encoder):
 
 
 def encode_clips(frames, quantizer, gop, version, width, height, recon=False, partitions=False, target_bytes=None, carry_bytes=0, qmin=12, qmax=52,
-                 quantizers=False, intra=False):
+                 quantizers=False, intra=False, container=None, file_bytes=None, fps=(30, 1, 0x18000000)):
     """frames: an (N, T, width * height * 3 / 2) uint8 torch tensor on a GPU, packed I420 (what a clip sink or export_tensor("i420")
     writes).  Frame 0 and every gop-th frame of every clip go through the intra encoder, the rest through the inter encoder; the
     reconstructions stay on the device and become the next frame's reference.  quantizer: an int in [12, 52] or T of them, one per frame.
@@ -128,7 +128,14 @@ def encode_clips(frames, quantizer, gop, version, width, height, recon=False, pa
 
     Returns, per clip, the list of its T frame streams (bytes); with recon=True also the (N, T, frame) uint8 tensor of reconstructions:
     what a decoder fed the streams of clip i in order holds after each; with quantizers=True also the (N, T) uint8 tensor of the frames'
-    quantisers."""
+    quantisers.
+
+    container: None, or "moflex" / "mods" (mux.py; the version must be the one the container carries: Moflex3DS / ModsDS).  Then each clip
+    comes back as ONE bytes object, its file, in place of the list of frame streams: every frame is appended to the clip's file image on
+    the device behind its encode call (key frames at t % gop == 0), its slots are dropped at once, and the one wait is the muxer's finish,
+    which brings only the files' own bytes to the host.  file_bytes: the room of one file (default: head, tail and index plus T frames of
+    the size of a raw picture; a clip that needs more raises MobiclipError naming file_bytes).  fps: (fps_rate, fps_scale) for the Moflex
+    stream chunk and the raw fps word of the Mods header."""
     import torch
     if not type(frames).__module__.startswith("torch") or frames.ndim != 3 or frames.dtype != torch.uint8 or not frames.is_cuda:
         raise ValueError("frames must be an (N, T, frame_bytes) uint8 tensor on a GPU")
@@ -146,13 +153,27 @@ def encode_clips(frames, quantizer, gop, version, width, height, recon=False, pa
     if int(carry_bytes) < 0:
         raise ValueError("carry_bytes must be at least 0")
     device = frames.device.index or 0
+    if container is not None:
+        from . import mux
+        if container not in mux.CONTAINERS:
+            raise ValueError(f"container must be None or one of {sorted(mux.CONTAINERS)}, not {container!r}")
+        if int(version) != int(mux.CONTAINER_VERSION[container]):
+            raise ValueError(f"a {container} file carries {mux.CONTAINER_VERSION[container].name} streams, not version {int(version)}")
+        if len(fps) != 3:
+            raise ValueError("fps must be (fps_rate, fps_scale, fps_raw)")
     intra_mode = bool(intra)  # the name serves the I-frame encoder below
     intra = MobiclipIntraEncoder(width, height, version, n, device=device)
     inter = MobiclipInterEncoder(width, height, version, n, device=device, partitions=partitions, intra=intra_mode) if t_n > 1 and int(gop) > 1 else None
     slot = max(intra.stream_bound, inter.stream_bound if inter else 0)
     held, rec_all, q_all, ref = [], [], [], None
-    carry = q_dev = None
+    carry = q_dev = muxer = files = None
     try:
+        if container is not None:
+            n_keys = (t_n + int(gop) - 1) // int(gop)
+            muxer = mux.MobiclipMuxer(container, width, height, n, fps_rate=fps[0], fps_scale=fps[1], fps_raw=fps[2], max_key_frames=n_keys, device=device)
+            if file_bytes is None:
+                file_bytes = mux.fixed_bytes(container, n_keys) + t_n * mux.framed_bytes(container, intra.frame_bytes)
+            muxer.begin(n, file_bytes)
         for t in range(t_n):
             pics = frames[:, t].contiguous()
             if target_bytes is not None:
@@ -168,17 +189,26 @@ def encode_clips(frames, quantizer, gop, version, width, height, recon=False, pa
             else:
                 out, sizes, ex = inter.encode(pics, ref, qs[t - 1], qs[t], recon=True, slot_bytes=slot)
             ref = ex["recon"]
-            held.append((out, sizes))
+            if muxer is not None:
+                muxer.append(out, sizes, t % int(gop) == 0)
+                del out  # the frame is in the file: the device need not hold T x N slots
+            else:
+                held.append((out, sizes))
             if quantizers:
                 q_all.append(q_dev if target_bytes is not None else torch.full((n,), qs[t], dtype=torch.uint8, device=frames.device))
             if recon:
                 rec_all.append(ref)
-        torch.cuda.current_stream(frames.device).synchronize()
+        if muxer is not None:
+            files = muxer.finish()  # the one wait
+        else:
+            torch.cuda.current_stream(frames.device).synchronize()
     finally:
         intra.close()
         if inter:
             inter.close()
-    clips = [[] for _ in range(n)]
+        if muxer is not None:
+            muxer.close()
+    clips = files if files is not None else [[] for _ in range(n)]
     for out, sizes in held:
         out, sizes = out.cpu().numpy(), sizes.cpu().numpy()
         for i in range(n):
