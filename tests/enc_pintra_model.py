@@ -5,6 +5,7 @@ the GPU):
   sequences      enc_inter_model's sets and `still`, and two of this mode's own: `cut` (every frame smooth content unrelated to the frame
                  before) and `uncover` (a sharp texture in full- and half-pel motion in which rectangles of macroblocks of one P-frame are
                  replaced by new smooth content: one at column 0 and row 0, one at the right and bottom edges, one interior where there is room)
+  geometry_set   the five clips of `cut` and `uncover` as one batch, for the shapes of enc_model.GEOMETRY_SHAPES
   chain          the host model over a set in mode 0 or 1
   parse_p_stream a P-frame read back with the ORACLE's tables: per macroblock partition code 0 / 1 / 6, vector difference or intra modes,
                  cbp, levels, bits
@@ -146,6 +147,13 @@ def sequence_sets(W, H):
                            np.array([[20, 20, 20, 20], [26, 26, 26, 26], [16, 22, 22, 30]], np.uint8))
         _SETS[(W, H)] = sets
     return _SETS[(W, H)]
+
+
+def geometry_set(W, H):
+    """what the geometry tests run (enc_model.GEOMETRY_SHAPES): the two clips of `cut` and the three of `uncover` as one batch of five ->
+    (frames (5, T, frame), quantizers (5, T))"""
+    sets = sequence_sets(W, H)
+    return np.concatenate([sets[k][0] for k in NEW_SETS]), np.concatenate([sets[k][1] for k in NEW_SETS])
 
 
 def chain(W, H, version, mode, frames, qs, **kw):
@@ -375,14 +383,14 @@ def rounds(qmin, qmax):
     return int(qmax - qmin).bit_length()
 
 
-def fixed(W, H, version, pictures, refs, prev_q, q):
+def fixed(W, H, version, pictures, refs, prev_q, q, threads=1):
     """the intra mode's host model at given quantisers (prev_q as the encoder uses it: clamped to [12, 52])"""
     n = pictures.shape[0]
     pq = np.clip(np.broadcast_to(np.asarray(prev_q, np.int64), (n,)), 12, 52).astype(np.uint8)
-    return host_encode(W, H, version, 1, pictures, refs, pq, np.broadcast_to(np.asarray(q, np.uint8), (n,)))
+    return host_encode(W, H, version, 1, pictures, refs, pq, np.broadcast_to(np.asarray(q, np.uint8), (n,)), threads=threads)
 
 
-def bisect(W, H, version, pictures, refs, prev_q, targets, qmin=12, qmax=52):
+def bisect(W, H, version, pictures, refs, prev_q, targets, qmin=12, qmax=52, threads=1):
     """the rate rule in Python over `fixed`, as enc_rate_model.bisect states it: per round the middle of [lo, hi] is tried; a stream that
     fits its target moves hi down to it, one that does not moves lo above it -> (fixed's dict at q_out, q_out (N,))"""
     n = pictures.shape[0]
@@ -390,7 +398,7 @@ def bisect(W, H, version, pictures, refs, prev_q, targets, qmin=12, qmax=52):
     lo, hi = np.full(n, qmin, np.int64), np.full(n, qmax, np.int64)
     for _ in range(rounds(qmin, qmax)):
         mid = (lo + hi) >> 1
-        fits = fixed(W, H, version, pictures, refs, prev_q, mid)["bytes"].astype(np.int64) <= tg
+        fits = fixed(W, H, version, pictures, refs, prev_q, mid, threads)["bytes"].astype(np.int64) <= tg
         lo, hi = np.where(fits, lo, np.minimum(mid + 1, hi)), np.where(fits, mid, hi)
     assert np.array_equal(lo, hi)
-    return fixed(W, H, version, pictures, refs, prev_q, lo), lo.astype(np.uint8)
+    return fixed(W, H, version, pictures, refs, prev_q, lo, threads), lo.astype(np.uint8)

@@ -51,6 +51,26 @@ def clips(container):
     return sizes, slots, key_flags(sizes.shape[0])
 
 
+# Moflex frames of more than 32 blocks: mobi_mux_append walks a frame's pieces with a grid of at most 32 workgroups, so these are the
+# lengths at which a workgroup takes a second piece (LENS ends at four blocks) -- 32 blocks exactly, one byte more, 33 and a part, 64
+# blocks (every workgroup a second piece), 65 and a part (the first a third) --, with short frames between them that move the next
+# frame's start through the residues mod 16
+LONG_LENS = (32 * B, 1, 32 * B + 1, 17, 33 * B + 17, 1, 64 * B, 17, 65 * B + 3)
+LONG_N = 2
+
+
+@functools.lru_cache(maxsize=None)
+def long_moflex():
+    """a Moflex session of LONG_N clips, clip 0 with LONG_LENS and clip 1 with LONG_LENS backwards, as clips() gives its own: sizes
+    (T, 2) int32, slots (T, 2, slot) uint8 -- random behind each stream's length too --, keys (T,) uint8"""
+    sizes = np.array([LONG_LENS, LONG_LENS[::-1]], np.int32).T.copy()
+    slot = (int(sizes.max()) + 3) & ~3
+    slots = np.random.default_rng(20242).integers(0, 256, size=sizes.shape + (slot,), dtype=np.uint8)
+    for a in (sizes, slots):
+        a.setflags(write=False)
+    return sizes, slots, key_flags(sizes.shape[0])
+
+
 def frames_of(sizes, slots, clip, upto=None):
     T = sizes.shape[0] if upto is None else upto
     return [slots[t, clip, :int(sizes[t, clip])].tobytes() for t in range(T)]

@@ -14,6 +14,8 @@ re-derivation of every decision.  No GPU.
      requires that it does hold for `fullpel` wherever no content enters: all three pictures at 16x16, pictures 1 and 2 at 48x32.)
   6  on `cut`, every P-picture's stream is strictly shorter than mode 0's on the same reference at the same quantiser
   7  header, library and Python table name the same symbols; the stream bound is unchanged; the two modes refuse each other in both orders
+  8  closed loop and parse-back at enc_model.GEOMETRY_SHAPES with `cut` and `uncover` as one batch of five, what the GPU comparison there
+     rests on, and why: one workgroup's statistics and a carry dropped at macroblock 256 differ from the truth in every picture counted
   +  the conditions that make `cut` and `uncover` worth running, asserted on the model's output"""
 import os
 import re
@@ -142,6 +144,133 @@ def test_decisions_are_the_argmin_of_the_stated_costs(W, H, version, ref):
     print(f"{W}x{H} version {version}: {ties} ties of Ji and Jp, {zeroed} inter macroblocks whose predictor the zeroing changed")
     if (W, H) != (16, 16):
         assert zeroed > 0
+
+
+def _logical_bits(data):
+    """a stream's bits in the order they are read: 16-bit little-endian words, most significant bit first"""
+    return np.unpackbits(np.frombuffer(bytes(data), "<u2").byteswap().view(np.uint8))
+
+
+REDERIVE_GEOMETRY = ((32, 80), (1024, 16))  # where the brute-force re-derivation is cheap enough: 10 and 64 macroblocks
+# pictures of the 15 (three P-frame calls of five) that must hold an intra AND an inter macroblock at index >= 256 -- at one column: whose
+# macroblocks 255 and 256 differ in kind --: one below, or at, what the model gives (9, 15 and 2 in both versions)
+BOTH_KINDS_BEHIND_256 = {(272, 256): 8, (1024, 144): 15, (16, 4112): 2}
+
+
+@pytest.mark.parametrize("version", PI.VERSIONS)
+@pytest.mark.parametrize("W,H", E.GEOMETRY_SHAPES)
+def test_geometry_shapes_through_the_oracle(W, H, version, ref):
+    """enc_model.GEOMETRY_SHAPES and the five clips of `cut` and `uncover` as one batch: the oracle decodes I, P, P, P to the reported
+    reconstructions within the streams' bytes; every P-frame reads back to the model's records, code 6 exactly where the flag says, its
+    vectors from predictors whose neighbours do NOT wrap round the picture's edge and in which an intra neighbour counts as zero; and
+    the batch meets what the GPU comparison at these shapes (tests/test_encode_pintra_geometry_gpu.py) rests on.
+
+    The last part is shown to be what makes a device-only mistake visible, on the model's output alone: statistics summed over the first
+    256 macroblocks only (one workgroup of mobi_encpi_finish instead of two) and a stream written with the running sum of the bit lengths
+    restarted at macroblock 256 (a carry dropped between two scan rounds) both differ from the true ones in every picture counted, and the
+    second still ends inside the true stream's length, so that nothing but a byte comparison would see it."""
+    mbw, mbh = W // 16, H // 16
+    nmb = mbw * mbh
+    frames, qs = PI.geometry_set(W, H)
+    n = frames.shape[0]
+    assert n == 5
+    ch = PI.chain(W, H, version, 1, frames, qs, threads=n)
+    at = lambda a, x, y: int(a[y * mbw + x]) if 0 <= x < mbw and y >= 0 else 0
+    for c in range(n):
+        streams = []
+        for t in range(PI.T):
+            nb = int(ch[t]["bytes"][c])
+            assert nb % 2 == 0 and nb <= ch[t]["streams"].shape[1] and not ch[t]["streams"][c, nb:].any()
+            streams.append(ch[t]["streams"][c, :nb])
+        for t, (dec, used, q) in enumerate(M.oracle_chain(W, H, version, streams)):
+            assert np.array_equal(dec, ch[t]["recon"][c]), (c, t)
+            assert q == int(qs[c, t]) and used <= len(streams[t]), (c, t)
+        for t in range(1, PI.T):
+            r, where = ch[t], (c, t)
+            flag = PI.is_intra(r)[c]
+            ps = PI.parse_p_stream(streams[t], W, H, version)
+            assert ps["dq"] == int(qs[c, t]) - int(qs[c, t - 1]), where
+            assert np.array_equal(ps["code"] == PI.CODE_INTRA, flag), where
+            for f in ("lev", "bits", "cbp", "luma_mode", "chroma_mode"):
+                assert np.array_equal(ps["mbs"][f], r["mbs"][c][f]), (where, f)
+            assert ps["end"] == int(r["stats"]["bits"][c]) == ps["hdr_bits"] + int(r["mbs"]["bits"][c].sum()), where
+            assert 8 * len(streams[t]) == (ps["end"] + 16 + 15) // 16 * 16, where
+            dx, dy = np.zeros(nmb, np.int64), np.zeros(nmb, np.int64)
+            pdx, pdy = np.zeros(nmb, np.int64), np.zeros(nmb, np.int64)
+            for i in range(nmb):
+                if flag[i]:  # no vector is sent, and the neighbours take it for zero
+                    assert ps["ddx"][i] == 0 and ps["ddy"][i] == 0
+                    continue
+                x, y = i % mbw, i // mbw
+                pdx[i] = M.med3(at(dx, x - 1, y), at(dx, x, y - 1), at(dx, x + 1, y - 1))
+                pdy[i] = M.med3(at(dy, x - 1, y), at(dy, x, y - 1), at(dy, x + 1, y - 1))
+                dx[i], dy[i] = pdx[i] + ps["ddx"][i], pdy[i] + ps["ddy"][i]
+            mdx, mdy = M.unpack_mv(r["mv"][c])
+            assert np.array_equal(dx, mdx) and np.array_equal(dy, mdy), where
+            mpx, mpy = M.unpack_mv(r["mvp"][c])
+            assert np.array_equal(pdx[~flag], mpx[~flag]) and np.array_equal(pdy[~flag], mpy[~flag]), where
+            assert np.array_equal(ps["code"][~flag], ((dx != pdx) | (dy != pdy))[~flag].astype(np.int64)), where
+            assert int(r["stats"]["mv_bits"][c]) == ps["mv_bits"], where
+            if (W, H) in REDERIVE_GEOMETRY:
+                d = PI.rederive(ref, W, H, version, qs[c, t - 1], qs[c, t], frames[c, t], ch[t - 1]["recon"][c], r["recon"][c])
+                assert np.array_equal(d["intra"], flag) and np.array_equal(d["Jp"], r["jp"][c]), where
+                assert np.array_equal(d["dx"], mdx) and np.array_equal(d["dy"], mdy) and np.array_equal(d["bits"], r["mbs"]["bits"][c]), where
+                assert np.array_equal(d["recon"], r["recon"][c]), where
+                for f, v in d["stats"].items():
+                    assert np.array_equal(np.asarray(v), r["stats"][f][c]), (where, f)
+    # ---- what the GPU comparison rests on ----
+    counted = wide_diagonal = 0
+    for t in range(1, PI.T):
+        r = ch[t]
+        flag, bits, total = PI.is_intra(r), r["mbs"]["bits"].astype(np.int64), r["stats"]["bits"].astype(np.int64)
+        n_intra = r["stats"]["reserved"][:, PI.STAT_INTRA].astype(np.int64)
+        assert np.array_equal(n_intra, flag.sum(1)) and (n_intra > 0).all(), t
+        both = flag.any(1) & ~flag.all(1)
+        if (W, H) in ((1024, 16), (16, 4112)):
+            assert both.any(), t
+        if (W, H) == (1024, 144):  # a diagonal that does not start at column 0 (x_lo = d - mbh + 1 > 0) with both kinds on it
+            k = flag.reshape(n, mbh, mbw)
+            for d in range(mbh, mbw + mbh - 1):
+                xs = np.arange(d - mbh + 1, min(d, mbw - 1) + 1)
+                on = k[:, d - xs, xs]
+                wide_diagonal += int((on.any(1) & ~on.all(1)).sum())
+        if nmb <= 256:
+            print(f"{W}x{H} version {version} picture {t}: intra macroblocks {n_intra.tolist()}, both kinds {both.tolist()}")
+            continue
+        E.geometry_preconditions(bits, total, (W, H, version, "intra mode", t))
+        front, behind = flag[:, :256], flag[:, 256:]
+        assert (front.sum(1) > 0).all(), t  # the first workgroup of mobi_encpi_finish adds to reserved[STAT_INTRA] in every picture
+        mixed = (flag[:, 255] != flag[:, 256]) if mbw == 1 else (behind.any(1) & ~behind.all(1))
+        counted += int(mixed.sum())
+        print(f"{W}x{H} version {version} picture {t}: intra in front of 256 {front.sum(1).tolist()}, behind {behind.sum(1).tolist()}, counted {mixed.tolist()}")
+        # one workgroup's statistics are not the picture's
+        hdr = total - bits.sum(1)
+        assert (hdr + bits[:, :256].sum(1) != total).all(), t
+        cb = np.array([[bin(int(v)).count("1") for v in row] for row in r["mbs"]["cbp"]])
+        assert np.array_equal(cb.sum(1), r["stats"]["coded_blocks"])
+        for c in range(n):
+            if behind[c].any():
+                assert front[c].sum() != n_intra[c]
+            if mixed[c]:
+                assert behind[c].any() and front[c].sum() != n_intra[c], (t, c)
+                assert cb[c, :256].sum() != int(r["stats"]["coded_blocks"][c]), (t, c)
+            # a carry dropped between the scan rounds: macroblocks from 256 on written where a sum restarted at zero puts them
+            start = hdr[c] + np.concatenate([[0], np.cumsum(bits[c])[:-1]])
+            dropped = np.concatenate([start[:256], np.concatenate([[0], np.cumsum(bits[c, 256:])[:-1]])])
+            assert (dropped[256:] != start[256:]).all(), (t, c)
+            true = _logical_bits(r["streams"][c, : r["bytes"][c]])
+            wrong = np.zeros_like(true)
+            wrong[: start[256]] = true[: start[256]]
+            for i in range(256, nmb):
+                wrong[dropped[i]: dropped[i] + bits[c, i]] |= true[start[i]: start[i] + bits[c, i]]
+            assert not np.array_equal(wrong, true), (t, c)
+            assert dropped[-1] + bits[c, -1] <= start[-1] + bits[c, -1] <= len(true), (t, c)  # and it stays inside the stream's own bytes
+    if (W, H) in BOTH_KINDS_BEHIND_256:
+        print(f"{W}x{H} version {version}: {counted} of {3 * n} pictures counted")
+        assert counted >= BOTH_KINDS_BEHIND_256[(W, H)], counted
+    if (W, H) == (1024, 144):
+        print(f"{W}x{H} version {version}: {wide_diagonal} (picture, diagonal) pairs with x_lo > 0 and both kinds")
+        assert wide_diagonal > 0
 
 
 def test_pictures_without_intra_macroblocks_are_mode_0():

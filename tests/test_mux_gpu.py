@@ -9,12 +9,15 @@
   d  round trips at 48x32, both versions: encode_clips(container=) gives files the demuxers split into frames, MobiclipBatch decodes
      them to the recon tensor the same call returned, and apart from the framing the frames are encode_clips(container=None)'s; the same
      with target_bytes=
-  e  the Python refusals"""
+  e  the Python refusals
+  f  Moflex frames of 32 to 66 blocks (mux_model.long_moflex): a workgroup of mobi_mux_append takes a second and a third block
+  g  the round trip at 272x256 with intra=True: slots of the encoders' stream bound, real frames of three and more Moflex blocks"""
 import numpy as np
 import pytest
 import torch
 
 from tests import enc_parts_model as Q
+from tests import enc_pintra_model as PI
 from tests import mux_model as M
 
 pytestmark = pytest.mark.gpu
@@ -188,6 +191,66 @@ def test_round_trip(container, gop, rate):
         got = b.export_tensor("i420")[0]
         torch.cuda.synchronize()
         assert torch.equal(got, recon[:, t]), t
+    b.close()
+
+
+def test_moflex_frames_above_32_blocks():
+    """mux_model.long_moflex: frames of 32 to 66 Moflex blocks, so that a workgroup of mobi_mux_append's grid of 32 takes a second and a
+    third block, each with its own header, the last with the terminator, at a stride of B + 4 in the file"""
+    sizes, slots, keys = M.long_moflex()
+    assert -(-int(sizes.max()) // M.B) > 2 * 32
+    _against_the_model(M.MOFLEX, (sizes, slots, keys, M.capacity_of(M.MOFLEX, sizes, keys), int(keys.sum()), [(0, None)] * M.LONG_N))
+
+
+@pytest.mark.parametrize("rate", (False, True))
+@pytest.mark.parametrize("container", ("moflex", "mods"))
+def test_round_trip_at_272x256_with_intra_macroblocks(container, rate):
+    """test_round_trip at 272 macroblocks with intra=True: the slots are the encoders' stream bound (93 blocks of room a slot, a grid
+    clamped to 32), real frames span three and more Moflex blocks, and the P-frames mix macroblock kinds.  Five clips of five frames
+    from enc_pintra_model.geometry_set in the order 0, 1, 3, 2, 1 under gop 4 (I P P P I): in the `cut` clips every P-frame stands behind
+    a cut, in the `uncover` clips the motion jumps two steps ahead and one back."""
+    import mobiclipdecoder_amd as m
+    from mobiclipdecoder_amd import mux
+    W, H, gop, version = 272, 256, 4, int(mux.CONTAINER_VERSION[container])
+    frames = PI.geometry_set(W, H)[0][:, [0, 1, 3, 2, 1]]
+    n, T = frames.shape[:2]
+    assert (n, T) == (5, 5)
+    dev_frames = _up(frames)
+    kw = dict(quantizer=None, target_bytes=[16000, 6000, 9000, 6000, 12000], carry_bytes=512) if rate else dict(quantizer=[20, 26, 18, 26, 22])
+    q = kw.pop("quantizer")
+    files, recon = m.encode_clips(dev_frames, q, gop, version, W, H, recon=True, container=container, intra=True, **kw)
+    plain, recon_plain = m.encode_clips(dev_frames, q, gop, version, W, H, recon=True, intra=True, **kw)
+    assert torch.equal(recon, recon_plain) and tuple(recon.shape) == (n, T, W * H * 3 // 2)
+    assert len(files) == n and all(isinstance(f, bytes) for f in files)
+    split = [_demux(container, f) for f in files]
+    for c in range(n):
+        assert split[c][0] == plain[c], c
+        if container == "mods":
+            assert split[c][1] == list(range(0, T, gop))
+        assert len(files[c]) == mux.fixed_bytes(container, len(range(0, T, gop))) + sum(mux.framed_bytes(container, len(s)) for s in plain[c])
+    longest = max(len(s) for clip in plain for s in clip)
+    print(container, "rate" if rate else "fixed", [[len(s) for s in clip] for clip in plain])
+    assert longest > 2 * M.B  # three Moflex blocks or more from real content
+    if not rate:  # the model's chain of the P-frames: the same bytes, and macroblocks of both kinds in them
+        qs = np.tile(np.array(q, np.uint8), (n, 1))
+        ch = PI.chain(W, H, version, 1, frames[:, :gop], qs[:, :gop], threads=n)
+        for t in range(gop):
+            assert [plain[c][t] for c in range(n)] == [ch[t]["streams"][c, : ch[t]["bytes"][c]].tobytes() for c in range(n)], t
+        assert all(PI.is_intra(ch[t]).any() and not PI.is_intra(ch[t]).all() for t in range(1, gop))
+    b = m.MobiclipBatch(n, W, H, version)
+    b.set_motion(True)
+    intra_mbs = 0
+    for t in range(T):
+        streams = [split[c][0][t] for c in range(n)]
+        rcs, offs = b.decode(streams, [0] * n)
+        assert rcs == [0] * n, (t, rcs)
+        got = b.export_tensor("i420")[0]
+        mb = b.export_motion("mb")[0] if t % gop else None
+        torch.cuda.synchronize()
+        assert torch.equal(got, recon[:, t]), t
+        if mb is not None:  # the decoder's own count of the intra macroblocks of a P-frame
+            intra_mbs += int((mb[:, 0] == 1).sum())
+    assert intra_mbs > 0
     b.close()
 
 

@@ -9,7 +9,8 @@ compared against in tests/test_mux_gpu.py).
      point of refusal, nothing at or behind a capacity is written
   5  header, library and the binding's table agree; the refusals that need no device
   6  the host model under sanitizers, as a program of its own, with buffers exactly one capacity long
-  7  the clips cover every alignment of a frame's start mod 16 and of a Moflex block boundary mod 4"""
+  7  the clips cover every alignment of a frame's start mod 16 and of a Moflex block boundary mod 4
+  8  Moflex frames of 32 to 66 blocks (mux_model.long_moflex) equal the writer's and read back"""
 import os
 import re
 import subprocess
@@ -79,6 +80,36 @@ def test_moflex_files_read_back():
         assert [bytes(f) for _, f in got] == [f + b"\x00\x00" for f in M.frames_of(sizes, slots, c)]
         st = got[0][0]
         assert (st.chunk_id, st.stream_index, st.fps_rate, st.fps_scale, st.width, st.height) == (1, 0, M.FPS[0], M.FPS[1], M.W, M.H)
+
+
+def _long_case():
+    sizes, slots, keys = M.long_moflex()
+    return sizes, slots, keys, M.capacity_of(M.MOFLEX, sizes, keys), int(keys.sum()), [(0, None)] * M.LONG_N
+
+
+def test_moflex_frames_above_32_blocks():
+    """mux_model.long_moflex: the model equals write_moflex byte for byte and MoLiveDemux reads every frame back; the frames are the ones
+    the GPU comparison needs (a block count of 32, 33, 34, 64 and 66, each started at more than one residue mod 16, some misaligned)"""
+    from mobiclipdecoder_amd.demux import MoLiveDemux
+    case = _long_case()
+    sizes, slots = case[0], case[1]
+    blocks = -(-sizes.astype(np.int64) // M.B)
+    assert sorted(set(blocks[blocks > 1].tolist())) == [32, 33, 34, 64, 66] and sizes.shape[1] == M.LONG_N == 2
+    assert int(sizes.max()) < M.MODS_LONGEST and slots.shape[2] >= int(sizes.max())
+    rc, files, ln, st = M.run_host(M.MOFLEX, *case[:5])
+    assert rc == 0
+    M.check_session(M.MOFLEX, case, files, ln, st)
+    starts = {}
+    for c in range(M.LONG_N):
+        d = MoLiveDemux(files[c, :int(ln[c])].copy())
+        got = [bytes(f) for _, f in d.frames()]
+        d.close()
+        assert got == [f + b"\x00\x00" for f in M.frames_of(sizes, slots, c)]
+        for t, s in enumerate(M.frame_starts(M.MOFLEX, sizes, c)[0]):
+            if sizes[t, c] > M.B:
+                starts.setdefault(int(sizes[t, c]), set()).add(s % 16)
+    print({k: sorted(v) for k, v in starts.items()})
+    assert all(len(v) == 2 for v in starts.values()) and any(s % 4 for v in starts.values() for s in v)
 
 
 def test_mods_files_read_back():
