@@ -18,6 +18,7 @@ from .decoder import (  # noqa: F401
     transform_code,
 )
 from .audio import MobiclipAudio  # noqa: F401
+from .audio_enc import MobiclipAudioEncoder  # noqa: F401
 from .encode import MobiclipIntraEncoder  # noqa: F401
 from .encode_inter import MobiclipInterEncoder, encode_clips  # noqa: F401
 from .mux import MobiclipMuxer  # noqa: F401

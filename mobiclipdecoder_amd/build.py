@@ -17,6 +17,8 @@
   tests/tools/libmobi_encode_rate_host.so  the rate rule (csrc/mobi_encode_rate.h) over those three models' picture functions on the CPU = TEST TOOL (g++)
       (the first three by build_enc_host, over tests/tools/enc_host_pool.h; the encoders' shared host side, csrc/mobi_encode_ctx.h, is part of the product)
   tests/tools/libmobi_mux_host.so  the muxing rule (csrc/mobi_mux.h) on the CPU: begin, append, finish = TEST TOOL (g++)
+  tests/tools/libmobi_mux_audio_host.so  the muxing rule with an audio stream (csrc/mobi_mux.h, include/mobiclip_mux_audio.h) on the CPU = TEST TOOL (g++)
+  tests/tools/libmobi_audio_enc_host.so  the audio encoder's rule (csrc/mobi_audio_enc.h) on the CPU = TEST TOOL (g++)
   tests/tools/abi_caller            plain-C caller of the product's C ABI = TEST TOOL (gcc)
 
 hipcc cross-compiles gfx950 without a GPU.  The built .so files are git-ignored but travel to the
@@ -49,11 +51,13 @@ LIB_ENCPARTSHOST = os.path.join(ROOT, "tests", "tools", "libmobi_encode_parts_ho
 LIB_ENCPINTRAHOST = os.path.join(ROOT, "tests", "tools", "libmobi_encode_pintra_host.so")  # csrc/mobi_encode_pintra.h's whole encoder on the CPU (test tool)
 LIB_ENCRATEHOST = os.path.join(ROOT, "tests", "tools", "libmobi_encode_rate_host.so")  # csrc/mobi_encode_rate.h's bisection over the three models (test tool)
 LIB_MUXHOST = os.path.join(ROOT, "tests", "tools", "libmobi_mux_host.so")  # csrc/mobi_mux.h's begin, append and finish on the CPU (test tool)
+LIB_MUXAUDIOHOST = os.path.join(ROOT, "tests", "tools", "libmobi_mux_audio_host.so")  # csrc/mobi_mux.h's sessions of video and audio frames on the CPU (test tool)
+LIB_AUDIOENCHOST = os.path.join(ROOT, "tests", "tools", "libmobi_audio_enc_host.so")  # csrc/mobi_audio_enc.h's whole encoder on the CPU (test tool)
 ABI_CALLER = os.path.join(ROOT, "tests", "tools", "abi_caller")  # plain-C caller of the product library (test tool)
 
 
 # the sources of libmobiclip_hip.so: *.cpp are host objects (g++), *.hip kernel objects (hipcc --offload-arch=gfx950); linked in this order
-HIP_SOURCES = ("mobi_batch.cpp", "mobi_step_host.cpp", "mobi_step_device.cpp", "mobi_step_groups.cpp", "mobi_replay.cpp", "mobi_pictures.cpp", "mobi_parse.cpp", "mobi_demux.cpp", "mobi_moflex.cpp", "mobi_export.cpp", "mobi_txcode.cpp", "mobi_audio_plan.cpp", "mobi_audio.cpp", "mobi_kernels.hip", "mobi_rgb.hip", "mobi_dparse.hip", "mobi_lsparse.hip", "mobi_gop.hip", "mobi_analysis.hip", "mobi_export.hip", "mobi_txcode.hip", "mobi_export_rgb.hip", "mobi_export_scale.hip", "mobi_export_resample.hip", "mobi_reset.hip", "mobi_idle.hip", "mobi_audio.hip", "mobi_sx.hip", "mobi_motion.hip", "mobi_sink.cpp", "mobi_sink.hip", "mobi_encode.cpp", "mobi_encode.hip", "mobi_encode_inter.cpp", "mobi_encode_inter.hip", "mobi_encode_parts.hip", "mobi_encode_pintra.hip", "mobi_encode_rate.hip", "mobi_mux.cpp", "mobi_mux.hip")
+HIP_SOURCES = ("mobi_batch.cpp", "mobi_step_host.cpp", "mobi_step_device.cpp", "mobi_step_groups.cpp", "mobi_replay.cpp", "mobi_pictures.cpp", "mobi_parse.cpp", "mobi_demux.cpp", "mobi_moflex.cpp", "mobi_export.cpp", "mobi_txcode.cpp", "mobi_audio_plan.cpp", "mobi_audio.cpp", "mobi_kernels.hip", "mobi_rgb.hip", "mobi_dparse.hip", "mobi_lsparse.hip", "mobi_gop.hip", "mobi_analysis.hip", "mobi_export.hip", "mobi_txcode.hip", "mobi_export_rgb.hip", "mobi_export_scale.hip", "mobi_export_resample.hip", "mobi_reset.hip", "mobi_idle.hip", "mobi_audio.hip", "mobi_sx.hip", "mobi_motion.hip", "mobi_sink.cpp", "mobi_sink.hip", "mobi_encode.cpp", "mobi_encode.hip", "mobi_encode_inter.cpp", "mobi_encode_inter.hip", "mobi_encode_parts.hip", "mobi_encode_pintra.hip", "mobi_encode_rate.hip", "mobi_mux.cpp", "mobi_mux.hip", "mobi_mux_audio.hip", "mobi_audio_enc.cpp", "mobi_audio_enc.hip")
 
 
 def hip_objects(profiling=False):
@@ -82,7 +86,7 @@ def header_symbols():
     """every function include/*.h declares (the C ABI)"""
     import re
     names = []
-    for h in ("mobiclip_hip.h", "mobiclip_demux.h", "mobiclip_audio.h", "mobiclip_sx.h", "mobiclip_encode.h", "mobiclip_encode_inter.h", "mobiclip_encode_parts.h", "mobiclip_encode_pintra.h", "mobiclip_encode_rate.h", "mobiclip_mux.h"):
+    for h in ("mobiclip_hip.h", "mobiclip_demux.h", "mobiclip_audio.h", "mobiclip_sx.h", "mobiclip_encode.h", "mobiclip_encode_inter.h", "mobiclip_encode_parts.h", "mobiclip_encode_pintra.h", "mobiclip_encode_rate.h", "mobiclip_mux.h", "mobiclip_mux_audio.h", "mobiclip_audio_enc.h"):
         text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", h)).read(), flags=re.S)
         names += re.findall(r"\b(mobi_\w+)\s*\(", text)
     return sorted(set(names))
@@ -94,7 +98,7 @@ def build_hip(force=False, profiling=False):
     MOBI_DEBUG=9) and the mobi_debug_* test hooks.  The product library has none of them; tools select the other one with MOBI_LIB."""
     srcs = [os.path.join(CSRC, f) for f in HIP_SOURCES]
     deps = srcs + _hdrs(CSRC) + [os.path.join(ROOT, "include", "mobiclip_hip.h"), os.path.join(ROOT, "include", "mobiclip_demux.h"), os.path.join(ROOT, "include", "mobiclip_audio.h"),
-                                  os.path.join(ROOT, "include", "mobiclip_sx.h"), os.path.join(ROOT, "include", "mobiclip_encode.h"), os.path.join(ROOT, "include", "mobiclip_encode_inter.h"), os.path.join(ROOT, "include", "mobiclip_encode_parts.h"), os.path.join(ROOT, "include", "mobiclip_encode_pintra.h"), os.path.join(ROOT, "include", "mobiclip_encode_rate.h"), os.path.join(ROOT, "include", "mobiclip_mux.h"), os.path.abspath(__file__)]
+                                  os.path.join(ROOT, "include", "mobiclip_sx.h"), os.path.join(ROOT, "include", "mobiclip_encode.h"), os.path.join(ROOT, "include", "mobiclip_encode_inter.h"), os.path.join(ROOT, "include", "mobiclip_encode_parts.h"), os.path.join(ROOT, "include", "mobiclip_encode_pintra.h"), os.path.join(ROOT, "include", "mobiclip_encode_rate.h"), os.path.join(ROOT, "include", "mobiclip_mux.h"), os.path.join(ROOT, "include", "mobiclip_mux_audio.h"), os.path.join(ROOT, "include", "mobiclip_audio_enc.h"), os.path.abspath(__file__)]
     lib = LIB_HIP_PROF if profiling else LIB_HIP
     if not force and not _newer(lib, deps):
         return lib
@@ -239,9 +243,26 @@ def build_encratehost(force=False):
 def build_muxhost(force=False):
     """the host model of the muxer: tests/tools/mobi_mux_host.cpp over csrc/mobi_mux.h"""
     src = os.path.join(ROOT, "tests", "tools", "mobi_mux_host.cpp")
-    if force or _newer(LIB_MUXHOST, [src, os.path.join(CSRC, "mobi_mux.h"), os.path.join(ROOT, "include", "mobiclip_mux.h"), os.path.join(ROOT, "include", "mobiclip_hip.h")]):
+    if force or _newer(LIB_MUXHOST, [src, os.path.join(CSRC, "mobi_mux.h"), os.path.join(ROOT, "include", "mobiclip_mux.h"), os.path.join(ROOT, "include", "mobiclip_mux_audio.h"), os.path.join(ROOT, "include", "mobiclip_hip.h")]):
         _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-I" + CSRC, src, "-o", LIB_MUXHOST])
     return LIB_MUXHOST
+
+
+def build_muxaudiohost(force=False):
+    """the host model of the muxer with an audio stream: tests/tools/mobi_mux_audio_host.cpp over csrc/mobi_mux.h"""
+    src = os.path.join(ROOT, "tests", "tools", "mobi_mux_audio_host.cpp")
+    if force or _newer(LIB_MUXAUDIOHOST, [src, os.path.join(CSRC, "mobi_mux.h")] + [os.path.join(ROOT, "include", h) for h in ("mobiclip_mux.h", "mobiclip_mux_audio.h", "mobiclip_hip.h")]):
+        _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-I" + CSRC, src, "-o", LIB_MUXAUDIOHOST])
+    return LIB_MUXAUDIOHOST
+
+
+def build_audioenchost(force=False):
+    """the host model of the audio encoder: tests/tools/mobi_audio_enc_host.cpp over csrc/mobi_audio_enc.h"""
+    src = os.path.join(ROOT, "tests", "tools", "mobi_audio_enc_host.cpp")
+    hdrs = [os.path.join(CSRC, "mobi_audio_enc.h"), os.path.join(CSRC, "mobi_audio.h")] + [os.path.join(ROOT, "include", h) for h in ("mobiclip_audio_enc.h", "mobiclip_audio.h", "mobiclip_hip.h")]
+    if force or _newer(LIB_AUDIOENCHOST, [src] + hdrs):
+        _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-pthread", "-I" + CSRC, src, "-o", LIB_AUDIOENCHOST])
+    return LIB_AUDIOENCHOST
 
 
 def build_caller(force=False):
@@ -252,7 +273,7 @@ def build_caller(force=False):
 
 
 def build_all(force=False):
-    return [build_hip(force), build_hip(force, profiling=True), build_gen(force), build_oracle(force), build_interp(force), build_lshost(force), build_idlehost(force), build_audiohost(force), build_sxhost(force), build_motionhost(force), build_enchost(force), build_encinterhost(force), build_encpartshost(force), build_encpintrahost(force), build_encratehost(force), build_muxhost(force), build_caller(force)]
+    return [build_hip(force), build_hip(force, profiling=True), build_gen(force), build_oracle(force), build_interp(force), build_lshost(force), build_idlehost(force), build_audiohost(force), build_sxhost(force), build_motionhost(force), build_enchost(force), build_encinterhost(force), build_encpartshost(force), build_encpintrahost(force), build_encratehost(force), build_muxhost(force), build_muxaudiohost(force), build_audioenchost(force), build_caller(force)]
 
 
 if __name__ == "__main__":

@@ -9,11 +9,14 @@
 #include "mobi_mux.h"
 
 extern "C" int mobi_launch_mux_begin(const MobiMuxArgs *a, hipStream_t s);
+extern "C" int mobi_launch_mux_begin_audio(const MobiMuxArgs *a, const MobiMuxAudio *au, hipStream_t s);
 extern "C" int mobi_launch_mux_append(const MobiMuxArgs *a, hipStream_t s);
+extern "C" int mobi_launch_mux_append_audio(const MobiMuxArgs *a, hipStream_t s);
 extern "C" int mobi_launch_mux_finish(const MobiMuxArgs *a, hipStream_t s);
 
 struct mobi_mux {
   MobiMuxCfg cfg;
+  MobiMuxAudio audio; // mobi_mux_set_audio; frequency 0: none
   int max_clips, device;
   uint8_t *mem; // the one allocation: states, then key-frame tables, each at a multiple of 256 bytes
   MobiMuxState *state;
@@ -91,14 +94,17 @@ int mobi_mux_begin_async(mobi_mux *m, void *stream, int n, uint8_t *files, size_
   m->n = 0;
   MobiMuxArgs a;
   mux_args(m, n, &a);
-  if (mobi_launch_mux_begin(&a, (hipStream_t)stream) != 0) return MOBI_E_DEVICE;
+  if ((mobi_mux_has_audio(m->cfg, m->audio) ? mobi_launch_mux_begin_audio(&a, &m->audio, (hipStream_t)stream) : mobi_launch_mux_begin(&a, (hipStream_t)stream)) != 0)
+    return MOBI_E_DEVICE;
   m->n = n;
   return MOBI_OK;
 }
 
-int mobi_mux_append_async(mobi_mux *m, void *stream, int n, const uint8_t *slots, size_t slot_pitch, size_t slot_bytes, const int32_t *sizes,
-                          int key_frame) {
+// the append of both streams: stream_index 0 video, 1 audio
+static int mux_append(mobi_mux *m, void *stream, int n, const uint8_t *slots, size_t slot_pitch, size_t slot_bytes, const int32_t *sizes, int key_frame,
+                      uint32_t stream_index) {
   if (!m || !slots || !sizes || !m->n || n < 1 || n > m->n) return MOBI_E_ARG;
+  if (stream_index && !mobi_mux_has_audio(m->cfg, m->audio)) return MOBI_E_ARG;
   if ((uintptr_t)slots % 4 || (uintptr_t)sizes % 4 || slot_pitch % 4 || slot_bytes % 4 || !slot_bytes || slot_pitch < slot_bytes) return MOBI_E_ARG;
   if (slot_bytes > 0x7FFFFFFC) return MOBI_E_ARG; // a length is an int32
   if (hipSetDevice(m->device) != hipSuccess) return MOBI_E_DEVICE;
@@ -109,7 +115,36 @@ int mobi_mux_append_async(mobi_mux *m, void *stream, int n, const uint8_t *slots
   a.slot_bytes = slot_bytes;
   a.sizes = sizes;
   a.key_frame = key_frame != 0;
-  return mobi_launch_mux_append(&a, (hipStream_t)stream) == 0 ? MOBI_OK : MOBI_E_DEVICE;
+  return (stream_index ? mobi_launch_mux_append_audio(&a, (hipStream_t)stream) : mobi_launch_mux_append(&a, (hipStream_t)stream)) == 0 ? MOBI_OK : MOBI_E_DEVICE;
+}
+
+int mobi_mux_append_async(mobi_mux *m, void *stream, int n, const uint8_t *slots, size_t slot_pitch, size_t slot_bytes, const int32_t *sizes,
+                          int key_frame) {
+  return mux_append(m, stream, n, slots, slot_pitch, slot_bytes, sizes, key_frame, 0);
+}
+
+// ---- include/mobiclip_mux_audio.h ----
+int mobi_mux_set_audio(mobi_mux *m, int codec_id, uint32_t frequency, int channels) {
+  if (!m || m->n) return MOBI_E_ARG;
+  if (m->cfg.container != MOBI_MUX_MOFLEX) return MOBI_E_UNSUPPORTED;
+  if (frequency == 0) {
+    m->audio.frequency = m->audio.channels = m->audio.codec = 0;
+    return MOBI_OK;
+  }
+  if (frequency > (1u << 24) || channels < 1 || channels > 8 || codec_id < 0 || codec_id > 2) return MOBI_E_ARG;
+  m->audio.frequency = frequency;
+  m->audio.channels = (uint32_t)channels;
+  m->audio.codec = (uint32_t)codec_id;
+  return MOBI_OK;
+}
+
+size_t mobi_mux_fixed_bytes_audio(int container, int key_frames, int audio) {
+  if ((container != MOBI_MUX_MOFLEX && container != MOBI_MUX_MODS) || key_frames < 0 || (audio && container != MOBI_MUX_MOFLEX)) return 0;
+  return (size_t)mobi_mux_fixed(container, (uint64_t)key_frames, audio != 0);
+}
+
+int mobi_mux_append_audio_async(mobi_mux *m, void *stream, int n, const uint8_t *slots, size_t slot_pitch, size_t slot_bytes, const int32_t *sizes) {
+  return mux_append(m, stream, n, slots, slot_pitch, slot_bytes, sizes, 0, 1);
 }
 
 int mobi_mux_finish_async(mobi_mux *m, void *stream, int n, int64_t *file_bytes_out, int32_t *status_out) {

@@ -1,5 +1,5 @@
 // mobi_mux.h -- the muxing rule (include/mobiclip_mux.h; DESIGN.md "Muxing"), one definition for the kernels (mobi_mux.hip), the entry
-// points (mobi_mux.cpp) and the host model (tests/tools/mobi_mux_host.cpp).  It frames bytes and never looks inside a stream; it
+// points (mobi_mux.cpp) and the host models (tests/tools/mobi_mux_host.cpp, mobi_mux_audio_host.cpp).  It frames bytes and never looks inside a stream; it
 // includes nothing from the encoders.
 //
 // A frame of L bytes is cut into PIECES that are placed independently of each other: piece p of a frame that starts at `pos` finds its
@@ -9,12 +9,17 @@
 //   payload, the byte 0.  Every block but the last is full and takes B + 4 bytes, so block p starts at pos + p (B + 4); the frame takes
 //   L + 4 (blocks - 1) + 8 bytes, blocks = ceil(L / B).
 //   Mods: a piece is a run of at most 4096 bytes at pos + 4 + 4096 p; piece 0 also writes the u32 L << 14 at pos.
+//
+// Audio (include/mobiclip_mux_audio.h; Moflex only): with a frequency set the head carries a MoLiveStreamAudio chunk for stream 1 behind
+// the video chunk and is 38 bytes long; a frame of stream 1 is framed as one of stream 0, the index bits "1 1" in place of "1 0": the
+// byte behind the flag byte has 0x40 set.  With audio off every function below gives what it gave before.
 #ifndef MOBI_MUX_RULE_H
 #define MOBI_MUX_RULE_H
 #include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/mobiclip_mux.h"
+#include "../../include/mobiclip_mux_audio.h"
 
 #if defined(__HIPCC__)
 #define MOBI_MUX_FN __host__ __device__ inline
@@ -24,6 +29,7 @@
 
 enum {
   MOBI_MUX_MOFLEX_HEAD = 30,      // synchro header 14, varbytes 1 and 12, the video chunk 12, varbytes 0 and 0
+  MOBI_MUX_MOFLEX_AUDIO_CHUNK = 8, // varbytes 2 and 6, the audio chunk 6: in front of the terminating varbytes when audio is on
   MOBI_MUX_MOFLEX_BLOCK = 0xF80,  // payload bytes of a full block: 0x1000 - 0x80
   MOBI_MUX_MOFLEX_TAIL = 0x1000,  // FinalizeMoflex
   MOBI_MUX_MODS_HEAD = 0x30,
@@ -37,6 +43,12 @@ struct MobiMuxCfg {
   int32_t container, max_keys;
   uint32_t width, height, fps_rate, fps_scale, fps_raw;
 };
+// the audio stream of a Moflex muxer (mobi_mux_set_audio); it stays out of MobiMuxCfg, so that the kernels of a video-only session
+// take the arguments, and compile to the code, they always did
+struct MobiMuxAudio {
+  uint32_t frequency, channels, codec; // frequency 0: no audio stream
+};
+MOBI_MUX_FN bool mobi_mux_has_audio(const MobiMuxCfg &c, const MobiMuxAudio &au) { return c.container == MOBI_MUX_MOFLEX && au.frequency != 0; }
 
 // a clip's state between the calls, in device memory
 struct MobiMuxState {
@@ -59,20 +71,23 @@ MOBI_MUX_FN uint64_t mobi_mux_framed(int container, uint64_t L) {
 }
 
 // head + tail, or header + index
-MOBI_MUX_FN uint64_t mobi_mux_fixed(int container, uint64_t key_frames) {
-  if (container == MOBI_MUX_MOFLEX) return MOBI_MUX_MOFLEX_HEAD + MOBI_MUX_MOFLEX_TAIL;
+MOBI_MUX_FN uint64_t mobi_mux_fixed(int container, uint64_t key_frames, bool audio = false) {
+  if (container == MOBI_MUX_MOFLEX) return MOBI_MUX_MOFLEX_HEAD + (audio ? MOBI_MUX_MOFLEX_AUDIO_CHUNK : 0) + MOBI_MUX_MOFLEX_TAIL;
   return MOBI_MUX_MODS_HEAD + 8 * key_frames;
 }
 
-MOBI_MUX_FN uint64_t mobi_mux_head_bytes(int container) { return container == MOBI_MUX_MOFLEX ? MOBI_MUX_MOFLEX_HEAD : MOBI_MUX_MODS_HEAD; }
+MOBI_MUX_FN uint64_t mobi_mux_head_bytes(int container, bool audio = false) {
+  if (container != MOBI_MUX_MOFLEX) return MOBI_MUX_MODS_HEAD;
+  return MOBI_MUX_MOFLEX_HEAD + (audio ? MOBI_MUX_MOFLEX_AUDIO_CHUNK : 0);
+}
 
 // what finish adds behind the last frame
 MOBI_MUX_FN uint64_t mobi_mux_tail_bytes(int container, uint32_t keys) { return container == MOBI_MUX_MOFLEX ? (uint64_t)MOBI_MUX_MOFLEX_TAIL : 8 * (uint64_t)keys; }
 
 // begin: the state of a fresh clip; a capacity below the head is refused here
-MOBI_MUX_FN MobiMuxState mobi_mux_begin_state(int container, uint64_t capacity) {
+MOBI_MUX_FN MobiMuxState mobi_mux_begin_state(int container, uint64_t capacity, bool audio = false) {
   MobiMuxState s;
-  s.pos = mobi_mux_head_bytes(container);
+  s.pos = mobi_mux_head_bytes(container, audio);
   s.frames = s.biggest = s.keys = 0;
   s.status = s.pos > capacity ? MOBI_MUX_ST_CAPACITY : 0;
   return s;
@@ -126,7 +141,8 @@ struct MobiMuxPiece {
 };
 MOBI_MUX_FN uint8_t mobi_mux_piece_head(const MobiMuxPiece &q, uint32_t i) { return (uint8_t)(q.head >> (8 * i)); }
 
-MOBI_MUX_FN MobiMuxPiece mobi_mux_piece(int container, uint64_t L, uint32_t p) {
+// stream_index: 0 video, 1 audio (Moflex)
+MOBI_MUX_FN MobiMuxPiece mobi_mux_piece(int container, uint64_t L, uint32_t p, uint32_t stream_index = 0) {
   MobiMuxPiece q;
   if (container == MOBI_MUX_MOFLEX) {
     const uint32_t blocks = mobi_mux_pieces(container, L);
@@ -143,6 +159,7 @@ MOBI_MUX_FN MobiMuxPiece mobi_mux_piece(int container, uint64_t L, uint32_t p) {
       q.head = 1 | (uint64_t)(0x80 | (v >> 8)) << 8 | (uint64_t)(v & 0xFF) << 16;
       q.head_n = 3;
     }
+    q.head |= (uint64_t)(stream_index << 6) << 8; // the index bit behind the unary "1"
     q.term = 1;
   } else {
     q.src = (uint64_t)p * MOBI_MUX_MODS_PIECE;
@@ -187,6 +204,22 @@ MOBI_MUX_FN void mobi_mux_moflex_head(const MobiMuxCfg &c, uint8_t out[MOBI_MUX_
   mobi_mux_put16be(out + 24, c.height);
   out[26] = 1;
   out[27] = 1;
+}
+
+// the head of a file with an audio stream: in front of the terminating varbytes, varbytes 2 and 6 and the MoLiveStreamAudio chunk of
+// stream 1 (stream index, codec id, frequency - 1 as u24be, channels - 1)
+MOBI_MUX_FN void mobi_mux_moflex_head_audio(const MobiMuxCfg &c, const MobiMuxAudio &au, uint8_t out[MOBI_MUX_MOFLEX_HEAD + MOBI_MUX_MOFLEX_AUDIO_CHUNK]) {
+  mobi_mux_moflex_head(c, out);
+  const uint32_t f = au.frequency - 1;
+  out[28] = 2;
+  out[29] = 6;
+  out[30] = 1;
+  out[31] = (uint8_t)au.codec;
+  out[32] = (uint8_t)(f >> 16);
+  out[33] = (uint8_t)(f >> 8);
+  out[34] = (uint8_t)f;
+  out[35] = (uint8_t)(au.channels - 1);
+  out[36] = out[37] = 0;
 }
 
 // the Mods header, known at finish: s.pos is the index offset

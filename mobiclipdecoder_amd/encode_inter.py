@@ -114,7 +114,7 @@ class MobiclipInterEncoder(_Encoder):
 
 
 def encode_clips(frames, quantizer, gop, version, width, height, recon=False, partitions=False, target_bytes=None, carry_bytes=0, qmin=12, qmax=52,
-                 quantizers=False, intra=False, container=None, file_bytes=None, fps=(30, 1, 0x18000000)):
+                 quantizers=False, intra=False, container=None, file_bytes=None, fps=(30, 1, 0x18000000), audio=None, audio_codec="ima", audio_rate=None):
     """frames: an (N, T, width * height * 3 / 2) uint8 torch tensor on a GPU, packed I420 (what a clip sink or export_tensor("i420")
     writes).  Frame 0 and every gop-th frame of every clip go through the intra encoder, the rest through the inter encoder; the
     reconstructions stay on the device and become the next frame's reference.  quantizer: an int in [12, 52] or T of them, one per frame.
@@ -135,7 +135,16 @@ def encode_clips(frames, quantizer, gop, version, width, height, recon=False, pa
     the device behind its encode call (key frames at t % gop == 0), its slots are dropped at once, and the one wait is the muxer's finish,
     which brings only the files' own bytes to the host.  file_bytes: the room of one file (default: head, tail and index plus T frames of
     the size of a raw picture; a clip that needs more raises MobiclipError naming file_bytes).  fps: (fps_rate, fps_scale) for the Moflex
-    stream chunk and the raw fps word of the Mods header."""
+    stream chunk and the raw fps word of the Mods header.
+
+    audio: None, or an (N, C, S_total) int16 tensor on the frames' device, the clips' sound at audio_rate Hz (what MobiclipAudio.decode
+    wrote, planar); needs container="moflex".  The files then carry a second stream (mux.MobiclipMuxer(audio=)): behind video frame t
+    one audio frame of b_t = floor((t + 1) R) - floor(t R) blocks of 256 samples, R = audio_rate * fps_scale / (fps_rate * 256) in exact
+    integer arithmetic, encoded on the GPU (audio_enc.MobiclipAudioEncoder, audio_codec "ima" or "pcm16") from the next blocks of
+    `audio`; nothing is appended where b_t = 0.  `audio` must hold the 256 * floor(T R) samples the T frames take (ValueError); samples
+    behind them are NOT sent: sound is cut to whole blocks at the pace of the pictures.  The default file_bytes grows by the audio
+    frames' framed bytes; there is still one wait.  With recon=True the result ends with one more element, the (N, C, 256 * floor(T R))
+    int16 tensor a decoder returns for the audio frames in order."""
     import torch
     if not type(frames).__module__.startswith("torch") or frames.ndim != 3 or frames.dtype != torch.uint8 or not frames.is_cuda:
         raise ValueError("frames must be an (N, T, frame_bytes) uint8 tensor on a GPU")
@@ -161,18 +170,43 @@ def encode_clips(frames, quantizer, gop, version, width, height, recon=False, pa
             raise ValueError(f"a {container} file carries {mux.CONTAINER_VERSION[container].name} streams, not version {int(version)}")
         if len(fps) != 3:
             raise ValueError("fps must be (fps_rate, fps_scale, fps_raw)")
+    a_blocks = None
+    if audio is not None:
+        if container != "moflex":
+            raise ValueError("audio needs container='moflex': only a moflex file carries an audio stream here")
+        if not isinstance(audio, torch.Tensor) or audio.ndim != 3 or audio.dtype != torch.int16 or audio.device != frames.device or int(audio.shape[0]) != n:
+            raise ValueError(f"audio must be an ({n}, C, S_total) int16 tensor on {frames.device}")
+        if audio_rate is None or isinstance(audio_rate, bool) or int(audio_rate) != audio_rate or not 1 <= int(audio_rate) <= 1 << 24:
+            raise ValueError("audio_rate must be an int in [1, 2**24]")
+        if int(fps[0]) < 1 or int(fps[1]) < 1:
+            raise ValueError("fps_rate and fps_scale must be at least 1 to pace the audio")
+        num, den = int(audio_rate) * int(fps[1]), int(fps[0]) * 256
+        a_blocks = [(t + 1) * num // den - t * num // den for t in range(t_n)]
+        if int(audio.shape[2]) < 256 * sum(a_blocks):
+            raise ValueError(f"audio holds {int(audio.shape[2])} samples per channel; {t_n} frames at {audio_rate} Hz take {256 * sum(a_blocks)}")
+        if not audio.is_contiguous():
+            audio = audio.contiguous()
     intra_mode = bool(intra)  # the name serves the I-frame encoder below
     intra = MobiclipIntraEncoder(width, height, version, n, device=device)
     inter = MobiclipInterEncoder(width, height, version, n, device=device, partitions=partitions, intra=intra_mode) if t_n > 1 and int(gop) > 1 else None
     slot = max(intra.stream_bound, inter.stream_bound if inter else 0)
     held, rec_all, q_all, ref = [], [], [], None
-    carry = q_dev = muxer = files = None
+    carry = q_dev = muxer = files = a_enc = None
+    a_rec, a_at = [], 0
     try:
+        given_file_bytes = file_bytes
         if container is not None:
             n_keys = (t_n + int(gop) - 1) // int(gop)
             muxer = mux.MobiclipMuxer(container, width, height, n, fps_rate=fps[0], fps_scale=fps[1], fps_raw=fps[2], max_key_frames=n_keys, device=device)
             if file_bytes is None:
                 file_bytes = mux.fixed_bytes(container, n_keys) + t_n * mux.framed_bytes(container, intra.frame_bytes)
+            if a_blocks is not None:
+                from .audio_enc import MobiclipAudioEncoder
+                a_enc = MobiclipAudioEncoder(n, int(audio.shape[1]), audio_codec, max(1, max(a_blocks)), device=device)
+                muxer.set_audio(a_enc.codec_id, int(audio_rate), a_enc.n_channels)
+                if given_file_bytes is None:
+                    file_bytes += mux.fixed_bytes(container, n_keys, audio=True) - mux.fixed_bytes(container, n_keys)
+                    file_bytes += sum(mux.framed_bytes(container, a_enc.frame_bytes(b)) for b in a_blocks if b)
             muxer.begin(n, file_bytes)
         for t in range(t_n):
             pics = frames[:, t].contiguous()
@@ -192,6 +226,13 @@ def encode_clips(frames, quantizer, gop, version, width, height, recon=False, pa
             if muxer is not None:
                 muxer.append(out, sizes, t % int(gop) == 0)
                 del out  # the frame is in the file: the device need not hold T x N slots
+                if a_enc is not None and a_blocks[t]:
+                    res_a = a_enc.encode(audio[:, :, 256 * a_at:256 * (a_at + a_blocks[t])], recon=recon)
+                    muxer.append_audio(res_a[0], res_a[1])
+                    a_at += a_blocks[t]
+                    if recon:
+                        a_rec.append(res_a[2]["recon"])
+                    del res_a
             else:
                 held.append((out, sizes))
             if quantizers:
@@ -208,10 +249,14 @@ def encode_clips(frames, quantizer, gop, version, width, height, recon=False, pa
             inter.close()
         if muxer is not None:
             muxer.close()
+        if a_enc is not None:
+            a_enc.close()
     clips = files if files is not None else [[] for _ in range(n)]
     for out, sizes in held:
         out, sizes = out.cpu().numpy(), sizes.cpu().numpy()
         for i in range(n):
             clips[i].append(out[i, :sizes[i]].tobytes())
     res = [clips] + ([torch.stack(rec_all, 1)] if recon else []) + ([torch.stack(q_all, 1)] if quantizers else [])
+    if a_blocks is not None and recon:
+        res.append(torch.cat(a_rec, 2) if a_rec else audio[:, :, :0])
     return tuple(res) if len(res) > 1 else clips

@@ -27,9 +27,17 @@ _SIGS = {
     "mobi_mux_finish_async": (C.c_int, [C.c_void_p, _P, C.c_int, _P, _P]),
 }
 
+# the audio stream; names must match include/mobiclip_mux_audio.h (tests/test_mux_audio_model.py checks header, library and this table)
+_AUDIO_SIGS = {
+    "mobi_mux_set_audio": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_int]),
+    "mobi_mux_fixed_bytes_audio": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "mobi_mux_append_audio_async": (C.c_int, [C.c_void_p, _P, C.c_int, _P, C.c_size_t, C.c_size_t, _P]),
+}
+AUDIO_CODEC_IDS = {"fastaudio": 0, "ima": 1, "pcm16": 2}  # MoLiveStreamAudio.CodecId
+
 
 def _lib():
-    return bind(load_library(), _SIGS)
+    return bind(load_library(), _SIGS, _AUDIO_SIGS)
 
 
 def _container(container):
@@ -43,8 +51,13 @@ def framed_bytes(container, stream_bytes):
     return int(_lib().mobi_mux_framed_bytes(_container(container), int(stream_bytes)))
 
 
-def fixed_bytes(container, key_frames=0):
-    """mobi_mux_fixed_bytes: head plus tail (Moflex), header plus an index of key_frames entries (Mods)"""
+def fixed_bytes(container, key_frames=0, audio=False):
+    """mobi_mux_fixed_bytes: head plus tail (Moflex), header plus an index of key_frames entries (Mods); audio=True
+    (mobi_mux_fixed_bytes_audio, Moflex): with the audio stream's chunk in the head"""
+    if audio:
+        if container != "moflex":
+            raise ValueError("only a moflex file carries an audio stream")
+        return int(_lib().mobi_mux_fixed_bytes_audio(_container(container), int(key_frames), 1))
     return int(_lib().mobi_mux_fixed_bytes(_container(container), int(key_frames)))
 
 
@@ -53,11 +66,12 @@ def status_names(status):
 
 
 class MobiclipMuxer(Handle):
-    """mobi_mux: up to max_clips files of one container ("moflex" or "mods") side by side, video only.  begin(), one append() per frame
-    behind the encode call that made it, finish(); then the object takes the next session."""
+    """mobi_mux: up to max_clips files of one container ("moflex" or "mods") side by side.  begin(), one append() per frame
+    behind the encode call that made it, finish(); then the object takes the next session.  audio=(codec, frequency, channels): the
+    Moflex files carry one audio stream as well (include/mobiclip_mux_audio.h), its frames brought by append_audio()."""
     _destroy = "mobi_mux_destroy"
 
-    def __init__(self, container, width, height, max_clips, fps_rate=30, fps_scale=1, fps_raw=0x18000000, max_key_frames=1024, device=None):
+    def __init__(self, container, width, height, max_clips, fps_rate=30, fps_scale=1, fps_raw=0x18000000, max_key_frames=1024, device=None, audio=None):
         self._h = None
         self._lib = _lib()
         self.container, self.width, self.height, self.max_clips = container, int(width), int(height), int(max_clips)
@@ -68,6 +82,21 @@ class MobiclipMuxer(Handle):
                                             int(max_key_frames), self.device)
         if not self._h:
             raise MobiclipError("mobi_mux_create failed: refused arguments, no usable HIP device, or out of device memory")
+        self.audio = None
+        if audio is not None:
+            self.set_audio(*audio)
+
+    def set_audio(self, codec, frequency, channels):
+        """mobi_mux_set_audio, between sessions: the files of the sessions begun after it carry an audio stream (Moflex only) -- codec
+        "fastaudio", "ima", "pcm16" or the Moflex codec id, frequency in [1, 2**24] Hz, channels in [1, 8]; append_audio() brings its
+        frames.  frequency 0 switches audio off again."""
+        if not self._h:
+            raise MobiclipError("muxer is closed")
+        if codec not in AUDIO_CODEC_IDS and (isinstance(codec, (str, bool)) or int(codec) not in AUDIO_CODEC_IDS.values()):
+            raise ValueError(f"codec must be one of {sorted(AUDIO_CODEC_IDS)} or a Moflex codec id, not {codec!r}")
+        cid = AUDIO_CODEC_IDS.get(codec, codec)
+        check_rc(self._lib.mobi_mux_set_audio(self._h, int(cid), int(frequency), int(channels)))
+        self.audio = (int(cid), int(frequency), int(channels)) if int(frequency) else None
 
     def _stream(self, stream):
         import torch
@@ -91,9 +120,19 @@ class MobiclipMuxer(Handle):
         self._files, self._n = files, n
         return files
 
+    def append_audio(self, slots, sizes, stream=None):
+        """One audio frame for every clip, as stream index 1: slots (n, slot_bytes) uint8 and sizes (n,) int32, the tensors
+        MobiclipAudioEncoder.encode returned, read on the device behind that call.  Needs audio=(codec, frequency, channels)."""
+        if self._h and self.audio is None:
+            raise MobiclipError("append_audio on a muxer without an audio stream (audio=, set_audio)")
+        self._append(slots, sizes, False, stream, True)
+
     def append(self, slots, sizes, key_frame, stream=None):
         """One frame for every clip: slots (n, slot_bytes) uint8 and sizes (n,) int32, the tensors an encoder call returned with slot_bytes
         given, read on the device behind that call.  key_frame: whether the frame is one, for every clip (Mods' index)."""
+        self._append(slots, sizes, key_frame, stream, False)
+
+    def _append(self, slots, sizes, key_frame, stream, audio):
         import torch
         dev, s = self._stream(stream)
         if self._files is None:
@@ -104,7 +143,10 @@ class MobiclipMuxer(Handle):
         if slots.ndim != 2 or tuple(sizes.shape) != (self._n,) or int(slots.shape[0]) != self._n:
             raise ValueError(f"slots must be ({self._n}, slot_bytes) and sizes ({self._n},)")
         slot = int(slots.shape[1])
-        check_rc(self._lib.mobi_mux_append_async(self._h, s.cuda_stream, self._n, slots.data_ptr(), slot, slot, sizes.data_ptr(), int(bool(key_frame))))
+        if audio:
+            check_rc(self._lib.mobi_mux_append_audio_async(self._h, s.cuda_stream, self._n, slots.data_ptr(), slot, slot, sizes.data_ptr()))
+        else:
+            check_rc(self._lib.mobi_mux_append_async(self._h, s.cuda_stream, self._n, slots.data_ptr(), slot, slot, sizes.data_ptr(), int(bool(key_frame))))
         if s != torch.cuda.current_stream(dev):
             slots.record_stream(s)
             sizes.record_stream(s)
